@@ -210,6 +210,7 @@ def make_thermo(args, dyc, d, st, nth):
                 "tridiag_frac_of_hbm_peak": round(b_tri / 1e9 / t_tri / (HBM_PEAK_GBS * args.gpus), 4),
                 "ms_per_dynamics_step_amortised": round(1e3 * (t_adv + t_tri) / nth, 3),
                 "note": "INSIDE the headline metric (one call per %d dynamics steps); this breakdown is one more call timed after the run" % nth}
+    info.fields = dict(T=T, S=S, **{"tracer%d" % m: t for m, t in enumerate(tr)})   # what --dump-outputs writes next to the state
     return thermo, info
 
 
@@ -704,6 +705,38 @@ def cpu_baseline(args, full_size=False):
 PMC_PASS_TIMEOUT = 40   # s; a pass that works takes about 4 s, one whose rocprofv3 hangs at start-up never ends
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20   # --dump-outputs: at most this much in all (< 64 MB)
+DUMP_SEED = 20251015
+STAGGER = {"u": "u", "uh": "u", "uhtr": "u", "v": "v", "vh": "v", "vhtr": "v"}   # everything else sits at h points
+
+
+def dump_outputs(dirname, d, fields, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs DIR: the computational domain of every field in `fields` (name -> float64 tensor with the context's
+    padded layout d.shape3() / d.shape2()) as DIR/<name>.npy, float64.  A field whose domain holds more than its share of
+    `budget` is written as a fixed sample of that share: the same seeded positions (sorted flat indices of the domain, k then j
+    then i) in every run, so two builds of the project can be compared value for value.  Returns {name: shape written}."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    cap = max(budget // (8 * len(fields)), 1)
+    written = {}
+    for name, t in fields.items():
+        st = STAGGER.get(name, "h")
+        i0 = d.ioff - (1 if st == "u" else 0); i1 = d.ioff + d.ni         # symmetric memory: the u (v) faces start one column (row) early
+        j0 = d.joff - (1 if st == "v" else 0); j1 = d.joff + d.nj
+        dom = t[..., j0:j1, i0:i1]
+        if dom.numel() <= cap:
+            a = dom.cpu().numpy()
+        else:
+            n, nij, ni = dom.numel(), (j1 - j0) * (i1 - i0), i1 - i0
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+            flat = (idx // nij) * (t.shape[-2] * t.shape[-1]) + (j0 + idx % nij // ni) * t.shape[-1] + (i0 + idx % ni)
+            a = t.reshape(-1)[torch.from_numpy(flat).to(t.device)].cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def run_group(cmd, cwd, env, timeout):
     """Run `cmd` in a process group of its own; on timeout the whole group is killed (rocprofv3's child -- this script again --
     would otherwise live on and share the GPU with the legs that follow).  Returns (exit code or None on timeout, stderr)."""
@@ -805,7 +838,12 @@ def main():
     ap.add_argument("--transport", choices=["rccl", "threads"], default="rccl",
                     help="threads: run the --gpus N ranks as host threads on one GPU and check the layout against N = 1 (not a performance run)")
     ap.add_argument("--tracers", type=int, default=2, help="passive PPM tracers next to T and S in the thermodynamic step; -1 = dynamics only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the prognostic state and the tracers as the last timed step left them (rank 0's tile) "
+                         "to DIR/<name>.npy, float64, at most 60 MiB in all (a fixed seeded sample of each field's computational domain); dumps/ is ignored by git")
     args = ap.parse_args()
+    if args.dump_outputs and args.transport == "threads":
+        raise SystemExit("bench.py: --dump-outputs is for the real run, not --transport threads")
     if args.bthalo is None:
         args.bthalo = 12 if args.gpus > 1 else 0
 
@@ -1016,6 +1054,10 @@ def run_rank(args, env):
     barrier()
     elapsed = env.max(time.perf_counter() - t0, dyc.device)
     ph.mark("timed_region")
+    dumped = None
+    if getattr(args, "dump_outputs", None) and rank == 0:   # before anything below steps the model again
+        dumped = dump_outputs(args.dump_outputs, d, dict(st, **(thermo_info.fields if thermo_info is not None else {})))
+        ph.mark("dump_outputs")
     restart_checksums = {n: "%016X" % (dyc.field_chksum(st[n]) % 2 ** 64) for n in RESTART_FIELDS}   # (collective: summed over the tiles)
     restart_checksums["dtbt"] = repr(dyc.barotropic_dtbt())
     dom = prof_report(dyc)
@@ -1082,6 +1124,9 @@ def run_rank(args, env):
                    "tile": [d.ni, d.nj, d.nk], "halo": d.halo, "BTHALO": args.bthalo},
         "roofline": roofline, "restart_checksums": restart_checksums,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped, "dtype": "float64",
+                                 "sampled_with_seed": DUMP_SEED}
     th = thermo_info() if thermo_info is not None else None
     if th is not None:
         out["thermo"] = th
