@@ -1776,7 +1776,8 @@ extern "C" int mom6x_ALE_regrid_zstar(mom6x_ctx *c, const mom6x_regrid_zstar_par
   if (rc) return rc;
   const dim3 b(64, 4, 1);
   if (d.nk <= COLS_NK_BOUND) {   // the layer counts the on-chip column kernel is built for
-#define RZC(NKT) KLAUNCH_LDS(c, "k_regrid_zstar", (k_regrid_zstar_cols<NKT>), dim3((unsigned)((nxa(d.ni + 2, -1) + 63) / 64), (unsigned)(d.nj + 2), 1), dim3(64, 1, 1), \
+    // (the profile label carries the template argument, so that a test can see which instantiation ran)
+#define RZC(NKT) KLAUNCH_LDS(c, "k_regrid_zstar_cols<" #NKT ">", (k_regrid_zstar_cols<NKT>), dim3((unsigned)((nxa(d.ni + 2, -1) + 63) / 64), (unsigned)(d.nj + 2), 1), dim3(64, 1, 1), \
                 (size_t)(NK_OF(NKT) + 1) * 64 * sizeof(double), d, c->G, *p, c->GV.Z_to_H, (const double *)c->regrid_res, h, h_new, dzRegrid, c->flag)
     COLS_NK_DISPATCH(d.nk, RZC);
 #undef RZC

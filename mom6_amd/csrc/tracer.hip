@@ -1090,7 +1090,8 @@ static int tridiag(mom6x_ctx *c, const double *hold, const double *ea, const dou
     // LDS -- 7 words per cell-layer instead of 10 (3.6 -> 3.1 ms per thermodynamic step at 1440 x 1080 x 75).  The instantiation with
     // a BOUND on the layer count serves 75 layers too: with the layer count itself the compiler schedules the fully unrolled,
     // branch-free column into 512 registers + 138 spilled; the uniform tests on the layer index keep its loads where they are.
-#define TDC2(NKT) KLAUNCH_LDS(c, "k_tridiag_cols", (k_tridiag_cols<NKT, true>), gc, bc, (size_t)NK_OF(NKT) * 64 * sizeof(double), d, c->G, hold, ea, eb, T, S, \
+    // (the profile label carries the template argument, so that a test can see which instantiation ran)
+#define TDC2(NKT) KLAUNCH_LDS(c, "k_tridiag_cols<" #NKT ">", (k_tridiag_cols<NKT, true>), gc, bc, (size_t)NK_OF(NKT) * 64 * sizeof(double), d, c->G, hold, ea, eb, T, S, \
                 c->GV.H_subroundoff, vertdiff, sfc_flux, btm_flux, flux_scale, is, ie, js, je)
     if (S) {
       if (d.nk <= 52) TDC2(-52); else if (d.nk <= 66) TDC2(-66); else TDC2(-COLS_NK_BOUND);
@@ -1098,7 +1099,7 @@ static int tridiag(mom6x_ctx *c, const double *hold, const double *ea, const dou
       return MOM6X_OK;
     }
 #undef TDC2
-#define TDC(NKT) KLAUNCH_LDS(c, "k_tridiag_cols", (k_tridiag_cols<NKT, false>), gc, bc, (size_t)0, d, c->G, hold, ea, eb, T, (double *)nullptr, \
+#define TDC(NKT) KLAUNCH_LDS(c, "k_tridiag_cols<" #NKT ">", (k_tridiag_cols<NKT, false>), gc, bc, (size_t)0, d, c->G, hold, ea, eb, T, (double *)nullptr, \
                 c->GV.H_subroundoff, vertdiff, sfc_flux, btm_flux, flux_scale, is, ie, js, je)
     COLS_NK_DISPATCH(d.nk, TDC);
 #undef TDC

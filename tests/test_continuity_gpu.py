@@ -27,9 +27,10 @@ def massflux_path(request, monkeypatch):
     return request.param
 
 
-def _run_case(orc, cfg, first_direction, mode, cs_mod=None, thin=0.0, u_scale=1.0, bt_pert=0.05, ties=False, stats=False):
+def _run_case(orc, cfg, first_direction, mode, cs_mod=None, thin=0.0, u_scale=1.0, bt_pert=0.05, ties=False, stats=False, launches=None):
+    """launches: a dict that receives the device call's kernel launches (mom6x_prof_report)."""
     import torch
-    from mom6_amd.dycore import Dycore, BTContDev
+    from mom6_amd.dycore import Dycore, BTContDev, prof_enable, prof_report
     gg, d, M = cfg
     GV = abi.vgrid_default()
     CS = abi.continuity_params_default(d.nk, GV.Angstrom_H)
@@ -83,8 +84,12 @@ def _run_case(orc, cfg, first_direction, mode, cs_mod=None, thin=0.0, u_scale=1.
     torch.cuda.synchronize()
     if stats:
         dyc.continuity_stats(1)
+    if launches is not None:
+        prof_enable(dyc, True)
     dyc.continuity_PPM(ud, vd, hd, out_g["h"], out_g["uh"], out_g["vh"], dt, **kw_g)
     dyc.sync()
+    if launches is not None:
+        launches.update(prof_report(dyc)); prof_enable(dyc, False)
     counts = dyc.continuity_stats(0) if stats else None
 
     sl = {"h": H.interior(d, "h"), "uh": H.interior(d, "u"), "vh": H.interior(d, "v"),
@@ -140,11 +145,14 @@ def test_continuity_tied_quotients(orc, mode, cfg):
     _run_case(orc, getattr(H, cfg)(nk=6), 0, mode, ties=True)
 
 
-@pytest.mark.parametrize("nk", [20, 40, 48, 50, 63, 75, 90])
+@pytest.mark.parametrize("nk", [20, 32, 33, 40, 48, 50, 63, 64, 65, 75, 80, 81, 90, 128, 130])
 @pytest.mark.parametrize("mode", ["full", "bt_cont", "adjust"])
 def test_continuity_many_layers(orc, nk, mode):
     # every layer lane carries ceil(nk/16) layers: the 2-, 3-, 4-, 5- and 8-slot instantiations, in the three shapes of a step's
-    # launches (the 3-, 4- and 5-slot kernels have an instantiation compiled for each: struct Sw<SPEC>)
+    # launches (the 3-, 4- and 5-slot kernels have an instantiation compiled for each: struct Sw<SPEC>); 32 / 64 / 80 / 128 fill
+    # the 2- / 4- / 5- / 8-slot kernels exactly and 33 / 65 / 81 are their first overflows.  130: deeper than the wave-owned and
+    # the LDS kernels carry -- every path, whatever order was asked for, runs the thread-per-column kernels in the REFERENCE order
+    # (abi.default_sum_order; tests/test_layer_counts_gpu.py checks that the tree orders are refused there)
     _run_case(orc, H.benchmark_small(nk=nk), 1, mode, thin=0.1)
 
 

@@ -49,11 +49,17 @@ def hv_params(mods, dt=1200.0):
 @pytest.mark.parametrize("cfg", ["island_basin", "benchmark_small", "channel"])
 @pytest.mark.parametrize("flags", sorted(FLAGS))
 def test_horizontal_viscosity(orc, cfg, flags):
-    import torch
-    from mom6_amd.dycore import Dycore
     gg, d, M = getattr(H, cfg)()
     if cfg == "island_basin":
         M = H.partial_faces(d, M)
+    horizontal_viscosity_case(orc, (gg, d, M), flags)
+
+
+def horizontal_viscosity_case(orc, cfg, flags):
+    """The body of test_horizontal_viscosity on any grid; returns the launches (mom6x_prof_report) of the call."""
+    import torch
+    from mom6_amd.dycore import Dycore, prof_enable, prof_report
+    gg, d, M = cfg
     GV = abi.vgrid_default()
     P = hv_params(FLAGS[flags])
     h, u, v = synth.make_state(d, M, thin_frac=0.15)
@@ -65,10 +71,12 @@ def test_horizontal_viscosity(orc, cfg, flags):
     ud, vd, hd = dyc.to_dev(u), dyc.to_dev(v), dyc.to_dev(h)
     du, dv = torch.zeros_like(ud), torch.zeros_like(vd)
     torch.cuda.synchronize()
+    prof_enable(dyc, True)
     dyc.horizontal_viscosity(ud, vd, hd, du, dv)
     dyc.sync()
-    H.assert_bitwise(du.cpu().numpy(), o_du, "diffu", H.interior(d, "u"))
-    H.assert_bitwise(dv.cpu().numpy(), o_dv, "diffv", H.interior(d, "v"))
+    rep = prof_report(dyc); prof_enable(dyc, False)
+    H.assert_bitwise(du.cpu().numpy(), o_du, "diffu", H.interior(d, "u"), signed_zero_ok=False)
+    H.assert_bitwise(dv.cpu().numpy(), o_dv, "diffv", H.interior(d, "v"), signed_zero_ok=False)
     assert np.isfinite(o_du).all() and np.abs(o_du).max() > 0 and np.abs(o_dv).max() > 0
     if "leith" in flags:   # the Leith terms are felt: the same call without them gives another answer
         P0 = hv_params({k: v for k, v in FLAGS[flags].items() if "Leith" not in k and "leith" not in k.lower()})
@@ -76,6 +84,7 @@ def test_horizontal_viscosity(orc, cfg, flags):
         orc.horizontal_viscosity(d, M, GV, P0, orc.hor_visc_init(d, M, P0), u, v, h, r_du, r_dv)
         assert not np.array_equal(r_du, o_du)
     dyc.close()
+    return rep
 
 
 def test_hor_visc_init_rejects_noslip_biharmonic():

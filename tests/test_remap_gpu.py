@@ -250,9 +250,14 @@ def test_ALE_regrid_zstar_then_remap(orc, cfg, mods):
     """A whole ALE step for the z* coordinate on the device: ALE_regrid (new grid and interface displacements), then the
     remapping of two tracers and the velocities onto it -- every array bit for bit against the oracle.  (benchmark_75: nk = 75 is
     the layer count of the on-chip column kernel k_regrid_zstar_cols.)"""
+    regrid_zstar_remap_case(orc, H.benchmark_small(nk=75, ni=70, nj=12) if cfg == "benchmark_75" else getattr(H, cfg)(nk=10), mods)
+
+
+def regrid_zstar_remap_case(orc, cfg, mods):
+    """The body of test_ALE_regrid_zstar_then_remap on any grid; returns the launches (mom6x_prof_report) of the regrid."""
     import torch
-    from mom6_amd.dycore import Dycore
-    gg, d, M = H.benchmark_small(nk=75, ni=70, nj=12) if cfg == "benchmark_75" else getattr(H, cfg)(nk=10)
+    from mom6_amd.dycore import Dycore, prof_enable, prof_report
+    gg, d, M = cfg
     GV = abi.vgrid_default()
     h, u, v = synth.make_state(d, M, thin_frac=0.2)
     depth = float(M[G["bathyT"]].max())
@@ -261,23 +266,39 @@ def test_ALE_regrid_zstar_then_remap(orc, cfg, mods):
     CS = abi.remapping_params_default(abi.REMAP_PPM_H4, GV.H_subroundoff, om4_remap_via_sub_cells=1, boundary_extrapolation=0)
     hn_o = np.zeros_like(h); dz_o = np.zeros((d.nk + 1,) + d.shape2())
     orc.ALE_regrid_zstar(d, M, GV, RP, cr, h, hn_o, dz_o)
-    T = np.ascontiguousarray(10.0 + 5.0 * synth.smooth_field(d, 70, nk=d.nk, ox=0.5, oy=0.5)); To = T.copy()
-    orc.ALE_remap_tracers(d, M, CS, h, hn_o, [To])
+    trs = [np.ascontiguousarray(10.0 + 5.0 * synth.smooth_field(d, 70 + m, nk=d.nk, ox=0.5, oy=0.5)) for m in range(2)]
+    tro = [t.copy() for t in trs]
+    orc.ALE_remap_tracers(d, M, CS, h, hn_o, tro)
+    hu_o, hv_o, hu_n, hv_n = (np.full_like(h, 1.0e-3) for _ in range(4))
+    orc.ALE_remap_set_h_vel(d, M, h, hu_o, hv_o); orc.ALE_remap_set_h_vel(d, M, hn_o, hu_n, hv_n)
+    uo, vo = u.copy(), v.copy()
+    orc.ALE_remap_velocities(d, M, CS, hu_o, hv_o, hu_n, hv_n, uo, vo)
 
     dyc = Dycore(d, M, GV)
     hd = dyc.to_dev(h)
     hn_g = torch.zeros_like(hd); dz_g = torch.zeros((d.nk + 1,) + d.shape2(), dtype=torch.float64, device=dyc.device)
-    Tg = dyc.to_dev(T)
+    trg = [dyc.to_dev(t) for t in trs]
+    ud, vd = dyc.to_dev(u), dyc.to_dev(v)
+    g = [dyc.to_dev(a) for a in (hu_o, hv_o, hu_n, hv_n)]
     torch.cuda.synchronize()
+    prof_enable(dyc, True)
     dyc.ALE_regrid_zstar(RP, cr, hd, hn_g, dz_g)
-    dyc.ALE_remap_tracers(CS, hd, hn_g, [Tg])
+    rep = prof_report(dyc); prof_enable(dyc, False)
+    dyc.ALE_remap_tracers(CS, hd, hn_g, trg)
+    dyc.ALE_remap_velocities(CS, g[0], g[1], g[2], g[3], ud, vd)
     dyc.sync()
     sl1 = H.interior(d, "h", 1)
-    H.assert_bitwise(hn_g.cpu().numpy(), hn_o, "h_new", sl1)
-    H.assert_bitwise(dz_g.cpu().numpy(), dz_o, "dzRegrid", sl1)
-    H.assert_bitwise(Tg.cpu().numpy(), To, "T", H.interior(d, "h"))
-    assert np.abs(dz_o).max() > 1.0 and np.abs(To - T).max() > 1e-3
+    H.assert_bitwise(hn_g.cpu().numpy(), hn_o, "h_new", sl1, signed_zero_ok=False)
+    H.assert_bitwise(dz_g.cpu().numpy(), dz_o, "dzRegrid", sl1, signed_zero_ok=False)
+    for m in range(2):
+        H.assert_bitwise(trg[m].cpu().numpy(), tro[m], f"tracer {m}", H.interior(d, "h"), signed_zero_ok=False)
+    H.assert_bitwise(ud.cpu().numpy(), uo, "u", H.interior(d, "u"), signed_zero_ok=False)
+    H.assert_bitwise(vd.cpu().numpy(), vo, "v", H.interior(d, "v"), signed_zero_ok=False)
+    assert np.abs(dz_o).max() > 1.0 and np.abs(tro[0] - trs[0]).max() > 1e-3
+    su = (Ellipsis,) + tuple(H.interior(d, "u"))
+    assert np.abs(uo - u)[su].max() > 1e-6
     dyc.close()
+    return rep
 
 
 @pytest.mark.parametrize("cfg", ["island_basin", "benchmark_small"])

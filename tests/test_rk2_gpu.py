@@ -16,8 +16,9 @@ G = abi.G
 
 @pytest.fixture(autouse=True)
 def _both_sum_orders(sums):
-    """Every whole-step case runs twice: with the device's default order of the mass-flux column sums (TREE16, held to the
-    oracle's restatement of that tree) and with MOM6X_SUMS=exact, i.e. the REFERENCE order of MOM_continuity_PPM.F90
+    """Every whole-step case runs three times: with the device's default order of the mass-flux column sums (TREE16_FMA: the
+    16-lane tree with fused multiply-adds at fixed sites), with the un-fused tree (MOM6X_SUMS=tree) -- each held to the oracle's
+    restatement of the same arithmetic -- and with MOM6X_SUMS=exact, i.e. the REFERENCE order of MOM_continuity_PPM.F90
     :1093-1242, :1293-1316 on both sides -- the device bit for bit against the sequential-k oracle (tests/conftest.py)."""
     return sums
 
@@ -263,7 +264,8 @@ def test_rk2_75_layers_on_chip_columns(orc, ni, nj, nk):
     run(orc, H.benchmark_small(nk=nk, ni=ni, nj=nj), nsteps=2, bt_mod=dict(strong_drag=1), rk2_mod=dict(visc_rem_dt_bug=0), per_stage=True)
 
 
-@pytest.mark.parametrize("ni,nj,nk", [(70, 10, 75), (24, 40, 75), (70, 10, 50), (24, 40, 63), (40, 12, 76), (24, 12, 33)])
+@pytest.mark.parametrize("ni,nj,nk", [(70, 10, 75), (24, 40, 75), (70, 10, 50), (24, 40, 63), (40, 12, 76), (24, 12, 33), (40, 12, 52),
+                                      (40, 12, 53), (40, 12, 66), (40, 12, 67), (40, 12, 77)])
 @pytest.mark.parametrize("shear", [True, False])
 def test_rk2_75_layers_one_kernel_vertical_viscosity(orc, ni, nj, nk, shear):
     """Without Rayleigh drag (and without the direct-stress and KV_ML_INVZ2 options) the three vertvisc_coef calls of a step and the
@@ -271,8 +273,10 @@ def test_rk2_75_layers_one_kernel_vertical_viscosity(orc, ni, nj, nk, shear):
     Thomas sweeps top-down from there; MODE 1 with the remnant only for :602-610).  Two steps against the oracle, which calls
     vertvisc_coef, vertvisc and vertvisc_remnant one after the other: bit for bit, with and without visc%Kv_shear, with the remnant
     in the solve's sweep and (VISC_REM_TIMESTEP_BUG = False) in a kernel of its own after it -- and the kernel did run.  75 layers is
-    the instantiation of the headline; every other count up to COLS_NK_BOUND = 76 runs the instantiation with 76 slots and a uniform
-    test on the layer index (mom6x_dev.h), here 33, 50, 63 and 76 layers -- also the 3-, 4- and 5-slot mass-flux kernels."""
+    the instantiation of the headline; every other count up to COLS_NK_BOUND = 76 runs an instantiation with a bound of 52, 66 or 76
+    slots and a uniform test on the layer index (mom6x_dev.h COLS_NK_DISPATCH), here 33, 50, 52, 53, 63, 66, 67 and 76 layers: both
+    sides of every bound -- also the 3-, 4- and 5-slot mass-flux kernels.  77 layers, the first count beyond the bound: the same
+    step through the kernels that walk the column in HBM, and k_vertvisc_coef_cols did NOT run."""
     for rk2_mod in (None, dict(visc_rem_dt_bug=0)):
         run(orc, H.benchmark_small(nk=nk, ni=ni, nj=nj), nsteps=2, bt_mod=dict(strong_drag=1), rk2_mod=rk2_mod, dev_vv=dict(), ray=False, shear=shear)
     import os
@@ -299,7 +303,11 @@ def test_rk2_75_layers_one_kernel_vertical_viscosity(orc, ni, nj, nk, shear):
         dyc.step_MOM_dyn_split_RK2(sg["u"], sg["v"], sg["h"], sg["uh"], sg["vh"], sg["uhtr"], sg["vhtr"], sg["eta_av"], tx, ty, inp["dt"], calc_dtbt=True)
         dyc.sync()
         rep = prof_report(dyc); prof_enable(dyc, False)
-        assert rep.get("k_vertvisc_coef_cols<0>", (0, 0))[0] == 3 and rep.get("k_vertvisc_coef_cols<1>", (0, 0))[0] == 3, sorted(rep)
+        if nk <= 76:
+            assert rep.get("k_vertvisc_coef_cols<0>", (0, 0))[0] == 3 and rep.get("k_vertvisc_coef_cols<1>", (0, 0))[0] == 3, sorted(rep)
+        else:
+            assert not any(k.startswith("k_vertvisc_coef_cols") for k in rep), sorted(rep)
+            assert rep.get("k_vertvisc_coef<0>", (0, 0))[0] == 3 and rep.get("k_vertvisc_coef<1>", (0, 0))[0] == 3, sorted(rep)
         dyc.close()
 
 

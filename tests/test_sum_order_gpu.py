@@ -1,16 +1,20 @@
-"""The device's DEFAULT order of the mass-flux column sums (mom6x_continuity_params.sum_order = MOM6X_SUM_TREE16, the wave-owned
-kernel of continuity_wave.hip) against the oracle run in the REFERENCE's order (sequential in k: zonal/meridional_flux_adjust
-MOM_continuity_PPM.F90:1093-1242, set_zonal/merid_BT_cont :1246-1409 with the duL / duR recurrences :1293-1316).
+"""The device's DEFAULT order of the mass-flux column sums (mom6x_continuity_params.sum_order = MOM6X_SUM_TREE16_FMA, the wave-owned
+kernel of continuity_wave.hip: the 16-lane tree of the column sums with fused multiply-adds at fixed sites, abi.default_sum_order)
+and the same tree un-fused (MOM6X_SUM_TREE16, MOM6X_SUMS=tree) against the oracle run in the REFERENCE's order (sequential in k:
+zonal/meridional_flux_adjust MOM_continuity_PPM.F90:1093-1242, set_zonal/merid_BT_cont :1246-1409 with the duL / duR recurrences
+:1293-1316).
 
-The two orders are different floating-point programs, so this is a TOLERANCE test, the only one on the path: the whole
+The orders are different floating-point programs, so this is a TOLERANCE test, the only one on the path: the whole
 split-RK2 step with every callee on the device (vertvisc_coef, horizontal_viscosity), device and oracle stepped side by side,
 the difference of every prognostic and restart field measured after every step as a fraction of the field's range.
-Stated bound: 1e-11 of range per field after 10 steps at nk = 75 (BOUND below; the observed numbers are printed and, on the
-GPU box, written to gpurun_out/sum_order_drift.json -- README.md / DESIGN.md section 2 quote them).  Independent of the
-order: sum_k uh = uhbt to ETA_TOLERANCE (the Newton solve's own stopping rule :1178) and the basin's volume to round-off.
+Stated bound: 1e-11 of range per field after 10 steps at nk = 75 (BOUND below), for both tree orders on every case; the observed
+numbers are printed and recorded by _report in sum_order_drift.json under "<order>:<case>" (profiles/ keeps a
+copy; README.md / DESIGN.md section 2 quote them).  Independent of the order: sum_k uh = uhbt to ETA_TOLERANCE (the Newton
+solve's own stopping rule :1178) and the basin's volume to round-off.
 
-The same file holds the opposite check for the exact mode: device REFERENCE order vs oracle REFERENCE order over the same 10
-steps is bit-identical (zeros of opposite sign not tolerated)."""
+The same file holds the opposite checks for matching arithmetics: device REFERENCE order vs oracle REFERENCE order, and device
+TREE16_FMA vs the oracle's restatement of the same fused sites, over the same 10 steps are bit-identical (zeros of opposite sign
+not tolerated).  tests/test_headline_oracle_gpu.py makes the three comparisons once more on the benchmark's own 1440 x 1080 x 75."""
 import json
 import os
 
@@ -25,7 +29,7 @@ from tests.test_rk2_gpu import STAG, STATE
 pytestmark = pytest.mark.gpu
 G = abi.G
 
-BOUND = 1.0e-11           # of max |field|, after the last step; observed (gpurun_out/sum_order_drift.json, copied to profiles/): <= 3.3e-12
+BOUND = 1.0e-11           # of max |field|, after the last step; observed: profiles/r07_sum_order_drift.json
 AUX = ["CAu_pred", "CAv_pred", "diffu", "diffv", "visc_rem_u", "visc_rem_v", "u_av", "v_av", "h_av", "eta", "uhbt", "vhbt"]
 
 
@@ -108,7 +112,7 @@ def _budgets(p):
     return float(err.max())
 
 
-def _report(name, rows, extra=None):
+def _report(name, rows, extra=None, bound=BOUND):
     worst = {n: max(r[n] for r in rows) for n in rows[0]}
     line = f"[sum-order drift] {name}: after {len(rows)} steps max over fields {max(rows[-1].values()):.2e} of range; per step " + \
            " ".join(f"{max(r.values()):.1e}" for r in rows)
@@ -122,40 +126,56 @@ def _report(name, rows, extra=None):
         except Exception:
             doc = {}
         doc[name] = dict(per_step_max_over_fields=[max(r.values()) for r in rows], last_step_per_field=rows[-1], worst_per_field=worst,
-                         bound=BOUND, **(extra or {}))
+                         bound=bound, **(extra or {}))
         json.dump(doc, open(path, "w"), indent=1, sort_keys=True)
 
 
-@pytest.mark.parametrize("case,nsteps", [("benchmark_small_75", 10), ("island_basin_75", 10), ("benchmark_small_75_pow", 10),
-                                         ("island_basin_75_pow", 10)])
-def test_default_device_order_stays_within_the_stated_bound_of_the_reference_order(orc, case, nsteps):
-    """..._pow: the same ten steps on btstep's DEFAULT drag path (BT_STRONG_DRAG = False: bt_rem = av_rem**(1/nstep), the one
-    expression of the path where the device's pow and libm's may differ in the last bit), so that the stated bound covers the
-    configuration the benchmark runs: sum order + pow together, against the REFERENCE-order oracle with libm's pow."""
-    pow_path = case.endswith("_pow")
-    cfg = dict(benchmark_small_75=lambda: H.benchmark_small(nk=75), island_basin_75=lambda: H.island_basin(nk=75))[case.replace("_pow", "")]()
-    p = _pair(orc, cfg, abi.SUM_TREE16, abi.SUM_REFERENCE, strong_drag=0 if pow_path else 1)
+def _device_order(order, monkeypatch):
+    """"default": what the device runs when nobody asks (abi.default_sum_order with MOM6X_SUMS unset) -- asserted to be
+    TREE16_FMA, so that a later change of the default cannot leave these cases testing another arithmetic; "tree": the
+    un-fused tree (MOM6X_SUMS=tree)."""
+    if order == "tree":
+        return abi.SUM_TREE16
+    monkeypatch.delenv("MOM6X_SUMS", raising=False)
+    o = abi.default_sum_order(75)
+    assert o == abi.SUM_TREE16_FMA, o
+    return o
+
+
+def _drift_run(orc, cfg, dev_order, name, nsteps, strong_drag=1):
+    p = _pair(orc, cfg, dev_order, abi.SUM_REFERENCE, strong_drag=strong_drag)
     rows = []
     for n in range(nsteps):
         p["step"](n)
         rows.append(_drift(p))
     eta_err = _budgets(p)
-    _report(case, rows, dict(sum_k_uh_minus_uhbt_as_eta_change=eta_err, tol_eta=p["cont"].tol_eta))
+    _report(name, rows, dict(sum_k_uh_minus_uhbt_as_eta_change=eta_err, tol_eta=p["cont"].tol_eta))
     bad = {n: v for n, v in rows[-1].items() if v > BOUND}
     assert not bad, bad
     p["dyc"].close()
 
 
-def test_default_device_order_on_config2_grid_one_step(orc):
-    """BASELINE.json configs[2]'s 360 x 180 x 75 grid, one step: the same bound."""
-    p = _pair(orc, H.benchmark_360(), abi.SUM_TREE16, abi.SUM_REFERENCE)
-    p["step"](0)
-    rows = [_drift(p)]
-    eta_err = _budgets(p)
-    _report("benchmark_360x180x75", rows, dict(sum_k_uh_minus_uhbt_as_eta_change=eta_err, tol_eta=p["cont"].tol_eta))
-    bad = {n: v for n, v in rows[-1].items() if v > BOUND}
-    assert not bad, bad
-    p["dyc"].close()
+ORDER_TAG = {abi.SUM_TREE16_FMA: "fma", abi.SUM_TREE16: "tree"}
+
+
+@pytest.mark.parametrize("order", ["default", "tree"])
+@pytest.mark.parametrize("case,nsteps", [("benchmark_small_75", 10), ("island_basin_75", 10), ("benchmark_small_75_pow", 10),
+                                         ("island_basin_75_pow", 10)])
+def test_default_device_order_stays_within_the_stated_bound_of_the_reference_order(orc, case, nsteps, order, monkeypatch):
+    """..._pow: the same ten steps on btstep's DEFAULT drag path (BT_STRONG_DRAG = False: bt_rem = av_rem**(1/nstep), the one
+    expression of the path where the device's pow and libm's may differ in the last bit), so that the stated bound covers the
+    configuration the benchmark runs: sum order + pow together, against the REFERENCE-order oracle with libm's pow."""
+    dev_order = _device_order(order, monkeypatch)
+    pow_path = case.endswith("_pow")
+    cfg = dict(benchmark_small_75=lambda: H.benchmark_small(nk=75), island_basin_75=lambda: H.island_basin(nk=75))[case.replace("_pow", "")]()
+    _drift_run(orc, cfg, dev_order, f"{ORDER_TAG[dev_order]}:{case}", nsteps, strong_drag=0 if pow_path else 1)
+
+
+@pytest.mark.parametrize("order", ["default", "tree"])
+def test_default_device_order_on_config2_grid_ten_steps(orc, order, monkeypatch):
+    """BASELINE.json configs[2]'s 360 x 180 x 75 grid, ten steps: the same bound."""
+    dev_order = _device_order(order, monkeypatch)
+    _drift_run(orc, H.benchmark_360(), dev_order, f"{ORDER_TAG[dev_order]}:benchmark_360x180x75", 10)
 
 
 def test_reference_order_on_the_device_is_bit_identical_over_ten_steps(orc):
@@ -170,26 +190,17 @@ def test_reference_order_on_the_device_is_bit_identical_over_ten_steps(orc):
     p["dyc"].close()
 
 
-def test_fused_multiply_add_arithmetic_over_ten_steps(orc):
-    """sum_order = MOM6X_SUM_TREE16_FMA (opt-in: the tree's sums and fused multiply-adds at fixed sites of the flux and the PPM
-    edge formulas, include/mom6x.h): ten steps at nk = 75 with every callee on the device (a) equal the oracle's restatement of the
-    same sites in every bit, and (b) stay within the stated bound of the REFERENCE-order, un-fused oracle -- the reference's own
-    arithmetic.  The observed drift goes to gpurun_out/sum_order_drift.json under "fma_benchmark_small_75"."""
-    cfg = H.benchmark_small(nk=75)
+@pytest.mark.parametrize("case", ["benchmark_small_75", "island_basin_75"])
+def test_fused_multiply_add_arithmetic_over_ten_steps(orc, case):
+    """sum_order = MOM6X_SUM_TREE16_FMA (the default: the tree's sums and fused multiply-adds at fixed sites of the flux and the
+    PPM edge formulas, include/mom6x.h): ten steps at nk = 75 with every callee on the device equal the oracle's restatement of
+    the same sites in every bit.  (Its distance from the REFERENCE-order, un-fused oracle -- the reference's own arithmetic --
+    is the "default" half of the drift cases above.)"""
+    cfg = dict(benchmark_small_75=lambda: H.benchmark_small(nk=75), island_basin_75=lambda: H.island_basin(nk=75))[case]()
     p = _pair(orc, cfg, abi.SUM_TREE16_FMA, abi.SUM_TREE16_FMA)
     for n in range(10):
         p["step"](n)
     for n, a, b in _fields(p):
         H.assert_bitwise(a, b, n, H.interior(p["d"], STAG[n]), signed_zero_ok=False)
     _budgets(p)
-    p["dyc"].close()
-    p = _pair(orc, cfg, abi.SUM_TREE16_FMA, abi.SUM_REFERENCE, strong_drag=0)
-    rows = []
-    for n in range(10):
-        p["step"](n)
-        rows.append(_drift(p))
-    eta_err = _budgets(p)
-    _report("fma_benchmark_small_75_pow", rows, dict(sum_k_uh_minus_uhbt_as_eta_change=eta_err, tol_eta=p["cont"].tol_eta))
-    bad = {n: v for n, v in rows[-1].items() if v > BOUND}
-    assert not bad, bad
     p["dyc"].close()

@@ -110,9 +110,15 @@ def test_advect_more_tracers_than_one_pass_carries(orc, cfg):
 def test_tridiagonal_solvers(orc, cfg):
     """(benchmark_75: nk = 75 is the layer count of the on-chip column kernel k_tridiag_cols; 70 columns per row = one full and
     one ragged wavefront)"""
+    tridiagonal_case(orc, H.benchmark_small(nk=75, ni=70, nj=10) if cfg == "benchmark_75" else getattr(H, cfg)())
+
+
+def tridiagonal_case(orc, cfg):
+    """triDiagTS (T and S paired in one sweep), the single-field triDiagTS, triDiagTS_Eulerian, tracer_vertdiff (+ fluxes) and
+    tracer_vertdiff_Eulerian on the device == the oracle, bit for bit.  Returns the launches (mom6x_prof_report) of the solves."""
     import torch
-    from mom6_amd.dycore import Dycore
-    gg, d, M = H.benchmark_small(nk=75, ni=70, nj=10) if cfg == "benchmark_75" else getattr(H, cfg)()
+    from mom6_amd.dycore import Dycore, prof_enable, prof_report
+    gg, d, M = cfg
     GV = abi.vgrid_default()
     nk = d.nk
     h, _, _ = synth.make_state(d, M, thin_frac=0.05)
@@ -133,18 +139,24 @@ def test_tridiagonal_solvers(orc, cfg):
     g = {k: dyc.to_dev(T) for k in o}
     S2 = dyc.to_dev(T)
     sd, bd = dyc.to_dev(sfc), dyc.to_dev(btm)
+    g["ts1"] = dyc.to_dev(T); o["ts1"] = o["ts"]
     torch.cuda.synchronize()
+    prof_enable(dyc, True)
     dyc.triDiagTS(hd, ead, ebd, g["ts"], S2)
+    dyc.triDiagTS(hd, ead, ebd, g["ts1"])
     dyc.triDiagTS_Eulerian(hd, entd, g["tse"])
     dyc.tracer_vertdiff(hd, ead, ebd, dt, g["vd"], sd, bd, True)
     dyc.tracer_vertdiff_Eulerian(hd, entd, dt, g["vde"])
     dyc.sync()
+    rep = prof_report(dyc); prof_enable(dyc, False)
     sl = H.interior(d, "h")
     for k in o:
-        H.assert_bitwise(g[k].cpu().numpy(), o[k], k, sl)
-    H.assert_bitwise(S2.cpu().numpy(), o["ts"], "S", sl)
+        H.assert_bitwise(g[k].cpu().numpy(), o[k], k, sl, signed_zero_ok=False)
+    H.assert_bitwise(S2.cpu().numpy(), o["ts"], "S", sl, signed_zero_ok=False)
     np.testing.assert_array_equal(o["ts"], o["tse"])
+    assert np.abs(o["vd"] - T).max() > 1e-3
     dyc.close()
+    return rep
 
 
 @pytest.mark.parametrize("cfg", ["double_gyre", "benchmark_small", "benchmark_75"])
@@ -154,9 +166,13 @@ def test_tracer_vertdiff_with_sinking(orc, cfg, reservoir):
     distances (all three branches of :134-146: the synthetic thin layers are thinner than the sinking distance, the thick ones not),
     the solve with the sinking flux on the lower diagonal, and -- with btm_reservoir -- the unlimited form that collects what leaves
     the bottom layer.  Device == oracle, bit for bit."""
+    vertdiff_sinking_case(orc, H.benchmark_small(nk=75, ni=70, nj=10) if cfg == "benchmark_75" else getattr(H, cfg)(), reservoir)
+
+
+def vertdiff_sinking_case(orc, cfg, reservoir):
     import torch
     from mom6_amd.dycore import Dycore
-    gg, d, M = H.benchmark_small(nk=75, ni=70, nj=10) if cfg == "benchmark_75" else getattr(H, cfg)()
+    gg, d, M = cfg
     GV = abi.vgrid_default()
     nk = d.nk
     h, _, _ = synth.make_state(d, M, thin_frac=0.15)
@@ -187,9 +203,9 @@ def test_tracer_vertdiff_with_sinking(orc, cfg, reservoir):
     dyc.sync()
     sl = H.interior(d, "h")
     for k in o:
-        H.assert_bitwise(g[k].cpu().numpy(), o[k], "sink:" + k, sl)
+        H.assert_bitwise(g[k].cpu().numpy(), o[k], "sink:" + k, sl, signed_zero_ok=False)
     if reservoir:
-        H.assert_bitwise(res_g.cpu().numpy(), res_o, "sink:btm_reservoir", sl)
-        H.assert_bitwise(res_ge.cpu().numpy(), res_oe, "sink:btm_reservoir (Eulerian)", sl)
+        H.assert_bitwise(res_g.cpu().numpy(), res_o, "sink:btm_reservoir", sl, signed_zero_ok=False)
+        H.assert_bitwise(res_ge.cpu().numpy(), res_oe, "sink:btm_reservoir (Eulerian)", sl, signed_zero_ok=False)
         assert (res_o[sl] - (0.1 + 0.05 * synth.smooth_field(d, 84, ox=0.5, oy=0.5))[sl]).max() > 0.0
     dyc.close()
