@@ -19,6 +19,12 @@ total time in the last warm-up step (k_mass_flux_lds: PPM reconstruction + zonal
 Newton flux adjustment + BT_cont fits) -- timed live with HIP events on the compute stream inside the
 timed region; `cpu_baseline` is the oracle (plain-C port of the reference algorithm, OpenMP over the loops the
 reference threads, all host cores) timed on a bounded 360x180x75 tile of the same workload and scaled by the cell count.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line (with the figures
+the warm-up and timed steps give for free: the per-kernel table of the last warm-up step, `roofline` with its traffic cited
+from profiles/, the restart checksums).  Everything that costs work of its own after the timed region -- the in-run
+rocprofv3 counter passes, the Newton statistics step, the thermodynamic breakdown, `hbm_step`, the ALE / diagnostics /
+comm_model / configs[4] legs, `box_calibration` and `cpu_baseline` -- runs with --full only.
 """
 import argparse
 import json
@@ -776,7 +782,7 @@ def measure_traffic_inrun(kernel, args):
     key = lambda n: (re.match(r"\w+(<\d+)?", n.replace(" ", "")) or [n])[0]
     tmp = tempfile.mkdtemp(prefix="mom6x_pmc_")
     env = dict(os.environ, MOM6X_BENCH_NO_PMC="1", TMPDIR="/tmp")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-config4",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-config4",
            "--no-comm-model", "--tracers", "-1", "--ni", str(args.ni), "--nj", str(args.nj), "--nk", str(args.nk)]
     try:
         for tag, ctr in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE")):
@@ -841,6 +847,10 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the prognostic state and the tracers as the last timed step left them (rank 0's tile) "
                          "to DIR/<name>.npy, float64, at most 60 MiB in all (a fixed seeded sample of each field's computational domain); dumps/ is ignored by git")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the rocprofv3 counter passes of roofline.traffic, "
+                         "the Newton statistics, the thermodynamic breakdown, hbm_step, the ALE / diagnostics / comm_model / configs[4] legs, "
+                         "box_calibration and cpu_baseline (the --no-* options switch parts of it off)")
     args = ap.parse_args()
     if args.dump_outputs and args.transport == "threads":
         raise SystemExit("bench.py: --dump-outputs is for the real run, not --transport threads")
@@ -1064,8 +1074,10 @@ def run_rank(args, env):
     prof_enable(dyc, False)
     dyc.lib.mom6x_prof_filter(dyc.ctx, None)
     n_thermo = args.steps // nth if thermo is not None else 0
-    # the Newton statistics of the mass-flux kernel: ONE more step after the timed region with the collecting variant of the kernel
-    dyc.continuity_stats(1); step(); nw_evals, nw_solves, nw_redos = dyc.continuity_stats(0)
+    newton = None
+    if args.full:
+        # the Newton statistics of the mass-flux kernel: ONE more step after the timed region with the collecting variant of the kernel
+        dyc.continuity_stats(1); step(); newton = dyc.continuity_stats(0)
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = (args.steps * args.dt / 86400.0) / elapsed
@@ -1078,8 +1090,8 @@ def run_rank(args, env):
     n_dom = sum(v[0] for v in dom.values()); ms_dom = sum(v[1] for v in dom.values())
     roofline = None
     traffic, traffic_src, measured_live = None, None, None
-    traffic_why = None
-    if args.gpus == 1 and rank == 0 and not args.no_pmc:
+    traffic_why = None if args.full else "the in-run counter passes run with --full only"
+    if args.full and args.gpus == 1 and rank == 0 and not args.no_pmc:
         measured_live, traffic_why = measure_traffic_inrun(dom_name, args)
         ph.mark("pmc_passes")
     if measured_live is not None:
@@ -1114,7 +1126,6 @@ def run_rank(args, env):
                                f"{nsub} barotropic sub-steps per step",
                    "thermo_steps_in_timed_region": n_thermo,
                    "state": "seeded smooth fields (SURVEY.md 8d): |u|, |v| <= %.2g m/s per layer, thicknesses perturbed by 1 %%" % float(os.environ.get("MOM6X_BENCH_UMAX", "0.5")),
-                   "newton_evals_per_solve": round(nw_evals / max(nw_solves, 1), 3), "newton_solves_repeated_with_exact_limits": nw_redos,
                    "sum_order": {0: "REFERENCE (sequential in k, bit-identical to the Fortran loop nest)",
                                  1: "TREE16 (column sums of the mass-flux kernels as a 16-lane tree; MOM6X_SUMS=exact: the reference's k order)",
                                  2: "TREE16_FMA (column sums of the mass-flux kernels as a 16-lane tree, fused multiply-adds at fixed sites that the "
@@ -1127,24 +1138,28 @@ def run_rank(args, env):
     if dumped is not None:
         out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped, "dtype": "float64",
                                  "sampled_with_seed": DUMP_SEED}
-    th = thermo_info() if thermo_info is not None else None
-    if th is not None:
-        out["thermo"] = th
-    th_bytes = (th["advect_algorithmic_GB"] + th["tridiag_algorithmic_GB"]) * 1e9 / nth if th else 0.0   # amortised per dynamics step
-    tot_bytes = bytes_step + th_bytes
-    measured, measured_src = (measured_live[1], measured_live[2]) if measured_live is not None else \
-        (pmc_step_traffic() if args.gpus == 1 and (args.ni, args.nj, args.nk) == (1440, 1080, 75) else (None, None))
-    if measured_live is None and measured_src:
-        measured_src += " sha256:" + sha256_of(os.path.join(ROOT, measured_src))
-    out["hbm_step"] = {
-        "algorithmic_GB_per_step": round(tot_bytes / 1e9, 2), "dynamics_GB": round(bytes_step / 1e9, 2), "thermo_GB_amortised": round(th_bytes / 1e9, 2),
-        "achieved_GBps": round(tot_bytes / 1e9 / (ms_per_step * 1e-3), 1),
-        "frac_of_peak": round(tot_bytes / 1e9 / (ms_per_step * 1e-3) / (HBM_PEAK_GBS * args.gpus), 4),
-        "model": "SURVEY.md 8(d), un-fused: 1616 B x N3 + 570 B x N2 x sub-steps, + 192 B x N3 for vertvisc_coef x3 + 40 B x N3 for horizontal_viscosity"
-                 " (+ the thermodynamic step's words / 4)",
-        "fused_away": FUSED_WORDS,
-        "measured_FETCH_plus_WRITE_GB_per_step": measured, "measured_source": measured_src}
-    if args.tracers >= 0 and args.gpus == 1 and not getattr(args, "skip_legs", False):
+    if newton is not None:
+        nw_evals, nw_solves, nw_redos = newton
+        out["config"].update(newton_evals_per_solve=round(nw_evals / max(nw_solves, 1), 3), newton_solves_repeated_with_exact_limits=nw_redos)
+    if args.full:
+        th = thermo_info() if thermo_info is not None else None
+        if th is not None:
+            out["thermo"] = th
+        th_bytes = (th["advect_algorithmic_GB"] + th["tridiag_algorithmic_GB"]) * 1e9 / nth if th else 0.0   # amortised per dynamics step
+        tot_bytes = bytes_step + th_bytes
+        measured, measured_src = (measured_live[1], measured_live[2]) if measured_live is not None else \
+            (pmc_step_traffic() if args.gpus == 1 and (args.ni, args.nj, args.nk) == (1440, 1080, 75) else (None, None))
+        if measured_live is None and measured_src:
+            measured_src += " sha256:" + sha256_of(os.path.join(ROOT, measured_src))
+        out["hbm_step"] = {
+            "algorithmic_GB_per_step": round(tot_bytes / 1e9, 2), "dynamics_GB": round(bytes_step / 1e9, 2), "thermo_GB_amortised": round(th_bytes / 1e9, 2),
+            "achieved_GBps": round(tot_bytes / 1e9 / (ms_per_step * 1e-3), 1),
+            "frac_of_peak": round(tot_bytes / 1e9 / (ms_per_step * 1e-3) / (HBM_PEAK_GBS * args.gpus), 4),
+            "model": "SURVEY.md 8(d), un-fused: 1616 B x N3 + 570 B x N2 x sub-steps, + 192 B x N3 for vertvisc_coef x3 + 40 B x N3 for horizontal_viscosity"
+                     " (+ the thermodynamic step's words / 4)",
+            "fused_away": FUSED_WORDS,
+            "measured_FETCH_plus_WRITE_GB_per_step": measured, "measured_source": measured_src}
+    if args.full and args.tracers >= 0 and args.gpus == 1 and not getattr(args, "skip_legs", False):
         # the legs reported next to the headline are measured on one GPU; the scaling runs (N > 1) keep to the headline path
         out["ale_remap_leg"] = ale_remap_leg(args, dyc, d, st, barrier, dist)
         out["diag_leg"] = diag_leg(args, dyc, d, st, barrier, dist)
@@ -1160,10 +1175,11 @@ def run_rank(args, env):
             out["config4_tile_leg"] = ale_cycle(args, local_rank)[1]
             ph.mark("config4_tile_leg")
     if rank == 0:
-        try:
-            out["box_calibration"] = box_calibration(torch.device("cuda", local_rank))
-        except Exception as e:   # noqa: BLE001  (a calibration that fails must not cost the line)
-            out["box_calibration"] = {"error": str(e)[:120]}
+        if args.full:
+            try:
+                out["box_calibration"] = box_calibration(torch.device("cuda", local_rank))
+            except Exception as e:   # noqa: BLE001  (a calibration that fails must not cost the line)
+                out["box_calibration"] = {"error": str(e)[:120]}
         tot = sum(v[1] for v in full.values())
         out["kernel_ms_per_step"] = {k: round(v[1], 3) for k, v in sorted(full.items(), key=lambda kv: -kv[1][1])[:12]}
         out["kernel_sum_ms"] = round(tot, 2)
@@ -1172,7 +1188,7 @@ def run_rank(args, env):
                 if cnt == 0:
                     continue
                 print(f"{k:28s} n={cnt:5d} total={ms:9.3f} ms avg={ms / cnt * 1e3:9.1f} us ({100 * ms / tot:5.1f}%)", file=sys.stderr)
-        if not args.no_cpu_baseline and args.gpus == 1:   # (rank 0 at N = 1 only)
+        if args.full and not args.no_cpu_baseline and args.gpus == 1:   # (rank 0 at N = 1 only)
             ph.mark("other")
             out["cpu_baseline"] = cpu_baseline(args)
             if not args.no_cpu_full_size and not os.environ.get("MOM6X_BENCH_NO_CPU_FULL"):

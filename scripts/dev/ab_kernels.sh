@@ -10,7 +10,7 @@ for fl in "$@"; do
   MOM6X_ARCH="${a:-gfx950}" MOM6X_CFLAGS="$fl" python -m mom6_amd.build > /dev/null 2>$OUT/ab_build.err || { echo BUILD FAILED; tail -5 $OUT/ab_build.err; continue; }
   for rep in 1 2; do
     D=/tmp/abk_$$_$rep; rm -rf $D
-    (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $D -o ab -- python $ROOT/bench.py --steps ${AB_STEPS:-6} --warmup 2 --no-config4 --no-cpu-baseline --no-comm-model ${AB_BENCH_ARGS} > $D.log 2>&1)
+    (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $D -o ab -- python $ROOT/bench.py --full --steps ${AB_STEPS:-6} --warmup 2 --no-config4 --no-cpu-baseline --no-comm-model ${AB_BENCH_ARGS} > $D.log 2>&1)
     python - "$D" "$PAT" <<'PY'
 import csv, glob, re, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True)

@@ -45,7 +45,7 @@ def main():
             idle[hw] = 0
     t = threading.Thread(target=loop); t.start()
     env = dict(os.environ, MOM6X_BENCH_NO_PMC="1")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "60", "--warmup", "5", "--no-config4", "--no-cpu-baseline", "--no-comm-model"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "60", "--warmup", "5", "--no-config4", "--no-cpu-baseline", "--no-comm-model"],
                        capture_output=True, text=True, env=env)
     stop[0] = True; t.join()
     import json
