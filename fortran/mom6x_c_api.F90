@@ -11,6 +11,7 @@ module mom6x_c_api
   public :: mom6x_dims, mom6x_vgrid, mom6x_continuity_params, mom6x_BT_cont, mom6x_barotropic_params
   public :: mom6x_coriolis_params, mom6x_pgf_params, mom6x_eos_params, mom6x_rk2_params, mom6x_rk2_hooks
   public :: mom6x_PressureForce_set_tv, mom6x_vertvisc_params, mom6x_vertvisc_init, mom6x_vertvisc_set_visc, mom6x_vertvisc_coef
+  public :: mom6x_set_visc_params, mom6x_set_visc_init, mom6x_set_viscous_BBL
   public :: mom6x_hor_visc_params, mom6x_hor_visc_init, mom6x_horizontal_viscosity, mom6x_vertvisc_set_direct_stress
   public :: mom6x_remapping_params, mom6x_ALE_remap_tracers, mom6x_ALE_remap_set_h_vel, mom6x_ALE_remap_velocities
   public :: mom6x_ALE_remap_velocities_conserve_ke, mom6x_ALE_remap_velocities_from_h, mom6x_comm_overlap_btstep
@@ -98,6 +99,14 @@ module mom6x_c_api
     real(c_double) :: Kv, Kvml_invZ2, Hmix, Hbbl, harm_BL_val, Kv_extra_bbl
     integer(c_int) :: harmonic_visc, bottomdraglaw, answer_date
   end type mom6x_vertvisc_params
+
+  type, bind(C) :: mom6x_set_visc_params   !< set_visc_CS (MOM_set_viscosity.F90:46-133), the members set_viscous_BBL reads
+    integer(c_int) :: bottomdraglaw
+    real(c_double) :: cdrag, drag_bg_vel, Hbbl, dz_bbl, BBL_thick_min, Kv_BBL_min
+    integer(c_int) :: linear_drag, BBL_use_EOS, BBL_use_tidal_bg, body_force_drag, correct_BBL_bounds, RiNo_mix, channel_drag
+    real(c_double) :: Rad_Earth, L_to_Z, L_to_H
+    integer(c_int) :: nkml, open_bcs, ice_shelf, SpV_avg
+  end type mom6x_set_visc_params
 
   type, bind(C) :: mom6x_hor_visc_params   !< hor_visc_CS (MOM_hor_visc.F90:36-259), the members the device path reads
     integer(c_int) :: Laplacian, biharmonic
@@ -315,6 +324,16 @@ module mom6x_c_api
     integer(c_int) function mom6x_vertvisc_init(ctx, p) bind(C, name="mom6x_vertvisc_init")
       import :: c_ptr, c_int, mom6x_vertvisc_params
       type(c_ptr), value :: ctx ; type(mom6x_vertvisc_params), intent(in) :: p
+    end function
+    integer(c_int) function mom6x_set_visc_init(ctx, p, eos, tideamp) bind(C, name="mom6x_set_visc_init")
+      import :: c_ptr, c_int, mom6x_set_visc_params
+      type(c_ptr), value :: ctx ; type(mom6x_set_visc_params), intent(in) :: p
+      type(c_ptr), value :: eos, tideamp   ! c_loc(an eos_params) or c_null_ptr; device pointer or c_null_ptr
+    end function
+    integer(c_int) function mom6x_set_viscous_BBL(ctx, u, v, h, T, S, p_surf, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, &
+        Ray_u, Ray_v) bind(C, name="mom6x_set_viscous_BBL")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, u, v, h, T, S, p_surf, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Ray_u, Ray_v
     end function
     integer(c_int) function mom6x_vertvisc_set_visc(ctx, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Kv_shear, Ray_u, Ray_v) &
         bind(C, name="mom6x_vertvisc_set_visc")

@@ -350,7 +350,8 @@ int  mom6x_abi_version(void);
 int  mom6x_device_count(void);
 /* sizeof() of the public structs (0 dims, 1 vgrid, 2 continuity_params, 3 BT_cont, 4 barotropic_params,
  * 5 coriolis_params, 6 pgf_params, 7 rk2_params, 8 rk2_hooks, 9 eos_params, 10 vertvisc_params, 11 hor_visc_params,
- * 12 remapping_params, 13 regrid_zstar_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
+ * 12 remapping_params, 13 regrid_zstar_params, 14 chksum_result, 15 sum_output_params, 16 energy_sums, 17 regrid_rho_params,
+ * 18 set_visc_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
 int  mom6x_struct_size(int which);
 
 /* Create a context for one tile on HIP device `device`.  `metrics_host` is a
@@ -628,8 +629,8 @@ int mom6x_vertvisc_set_coef(mom6x_ctx *ctx, const double *a_u, const double *a_v
 int mom6x_vertvisc_init(mom6x_ctx *ctx, const mom6x_vertvisc_params *p);
 /* The members of vertvisc_type (MOM_variables.F90) that vertvisc_coef / vertvisc read: visc%Kv_bbl_u/v and
  * visc%bbl_thick_u/v (2-D; required with BOTTOMDRAGLAW), visc%Kv_shear (3-D, nk+1 interfaces at h points,
- * nullable), visc%Ray_u/v (3-D, nullable).  Device arrays owned by the caller (set_viscous_BBL and the
- * shear-mixing schemes stay on the host).                                                            */
+ * nullable), visc%Ray_u/v (3-D, nullable).  Device arrays owned by the caller: mom6x_set_viscous_BBL below
+ * fills the first four (and Ray_u/v) on the device; the shear-mixing schemes stay on the host.       */
 int mom6x_vertvisc_set_visc(mom6x_ctx *ctx, const double *Kv_bbl_u, const double *Kv_bbl_v, const double *bbl_thick_u,
                             const double *bbl_thick_v, const double *Kv_shear, const double *Ray_u, const double *Ray_v);
 /* vertvisc_coef(u, v, h, dz, forces, visc, tv, dt, G, GV, US, CS, OBC, VarMix) :1357, with dz = H_to_Z*h
@@ -647,6 +648,47 @@ int mom6x_vertvisc(mom6x_ctx *ctx, double *u, double *v, const double *taux, con
 int mom6x_vertvisc_set_direct_stress(mom6x_ctx *ctx, double Hmix_stress, const double *h);
 /* vertvisc_remnant(visc, visc_rem_u, visc_rem_v, dt, G, GV, US, CS)  :1229                   */
 int mom6x_vertvisc_remnant(mom6x_ctx *ctx, double *visc_rem_u, double *visc_rem_v, double dt);
+
+/* ------------------------------------------------------------------------- */
+/* MOM_set_viscosity: set_viscous_BBL                                          */
+/* set_visc_CS (src/parameterizations/vertical/MOM_set_viscosity.F90:46-133; set_visc_init :2876-3204): the members the
+ * non-channel, Boussinesq path of set_viscous_BBL (:135-1115) reads.  CHANNEL_DRAG (find_L_open_*, :878-1018), open
+ * boundaries, ice shelves, a bulk mixed layer (nkml > 0) and the non-Boussinesq tv%SpV_avg forms are refused.      */
+typedef struct mom6x_set_visc_params {
+  int    bottomdraglaw;      /* BOTTOMDRAGLAW (T, :2941); F: mom6x_set_viscous_BBL returns at once (:323)             */
+  double cdrag;              /* CDRAG (0.003, :3025)                                                                 */
+  double drag_bg_vel;        /* DRAG_BG_VEL (0 m s-1, :3047) [L T-1]; 1e30 with BBL_USE_TIDAL_BG (:3045)             */
+  double Hbbl;               /* CS%Hbbl = dz_bbl*(Z_to_m*m_to_H) (:3140) [H]                                         */
+  double dz_bbl;             /* HBBL (required, :3018) [Z]                                                           */
+  double BBL_thick_min;      /* BBL_THICK_MIN (0, :3068) [Z]                                                         */
+  double Kv_BBL_min;         /* KV_BBL_MIN (KV, :3094) [H Z T-1]                                                     */
+  int    linear_drag;        /* LINEAR_DRAG (F, :2957)                                                               */
+  int    BBL_use_EOS;        /* BBL_USE_EOS (USE_EOS, :3060); used only with an EOS (use_BBL_EOS, :340)              */
+  int    BBL_use_tidal_bg;   /* BBL_USE_TIDAL_BG (F, :3029): u2_bg from the tideamp field of mom6x_set_visc_init     */
+  int    body_force_drag;    /* DRAG_AS_BODY_FORCE (F, :2947): needs visc%Ray_u/v                                    */
+  int    correct_BBL_bounds; /* CORRECT_BBL_BOUNDS (F, :3100)                                                        */
+  int    RiNo_mix;           /* CS%RiNo_mix = kappa_shear_is_used (F, :2970)                                         */
+  int    channel_drag;       /* CHANNEL_DRAG (F, :2953): must be 0                                                   */
+  double Rad_Earth;          /* G%Rad_Earth_L (6.378e6 m) [L]: BBL_thick_max = Rad_Earth*L_to_Z (:348)               */
+  double L_to_Z;             /* US%L_to_Z (1): GV%g_Earth_Z_T2 = L_to_Z**2*g_Earth (MOM_verticalGrid.F90:178)        */
+  double L_to_H;             /* US%L_to_m*GV%m_to_H (1): cdrag_sqrt_H, cdrag_L_to_H (:344-347)                       */
+  int    nkml;               /* GV%nkml (0): must be 0                                                               */
+  int    open_bcs;           /* CS%OBC associated (0): must be 0                                                     */
+  int    ice_shelf;          /* an ice shelf (0): must be 0                                                          */
+  int    SpV_avg;            /* tv%SpV_avg allocated (0, non-Boussinesq): must be 0                                  */
+} mom6x_set_visc_params;
+/* set_visc_init :2876: keeps the parameters.  eos: tv%eqn_of_state (NULL: none; use_BBL_EOS = eos && BBL_use_EOS, :340);
+ * without it the density walk uses GV%Rlay as given to mom6x_PressureForce_init.  tideamp: CS%tideamp (:3175-3179), a
+ * 2-D h-point DEVICE array [Z T-1] with a valid halo of one (required with BBL_USE_TIDAL_BG, kept).                    */
+int mom6x_set_visc_init(mom6x_ctx *ctx, const mom6x_set_visc_params *p, const mom6x_eos_params *eos, const double *tideamp);
+/* set_viscous_BBL(u, v, h, tv, visc, G, GV, US, CS, pbv) :135 on the context's stream, dz = H_to_Z*h.  u, v, h, T, S and
+ * tv%p_surf (nullable) need a valid halo of one.  Writes visc%bbl_thick_u/v and visc%Kv_bbl_u/v (nullable) at the unmasked
+ * faces I = isc-1..iec, j = jsc..jec and i = isc..iec, J = jsc-1..jec (:450-460), the range vertvisc_coef reads; masked
+ * faces and all other points are left as they are.  visc%Ray_u/v (3-D, nullable; required with DRAG_AS_BODY_FORCE) are
+ * zeroed everywhere first (:442-443), as the reference does whenever they are allocated.  T, S: required with use_BBL_EOS. */
+int mom6x_set_viscous_BBL(mom6x_ctx *ctx, const double *u, const double *v, const double *h, const double *T, const double *S,
+                          const double *p_surf, double *Kv_bbl_u, double *Kv_bbl_v, double *bbl_thick_u, double *bbl_thick_v,
+                          double *Ray_u, double *Ray_v);
 
 /* ------------------------------------------------------------------------- */
 /* MOM_dynamics_split_RK2                                                      */

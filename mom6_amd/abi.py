@@ -207,6 +207,30 @@ def vertvisc_params_default(Kv=1.0e-4, Hmix=20.0, Hbbl=10.0):
     return p
 
 
+class SetViscParams(C.Structure):
+    """mom6x_set_visc_params; the set_visc_CS members of set_viscous_BBL (MOM_set_viscosity.F90:46-133)."""
+    _fields_ = [("bottomdraglaw", C.c_int), ("cdrag", C.c_double), ("drag_bg_vel", C.c_double), ("Hbbl", C.c_double),
+                ("dz_bbl", C.c_double), ("BBL_thick_min", C.c_double), ("Kv_BBL_min", C.c_double), ("linear_drag", C.c_int),
+                ("BBL_use_EOS", C.c_int), ("BBL_use_tidal_bg", C.c_int), ("body_force_drag", C.c_int),
+                ("correct_BBL_bounds", C.c_int), ("RiNo_mix", C.c_int), ("channel_drag", C.c_int), ("Rad_Earth", C.c_double),
+                ("L_to_Z", C.c_double), ("L_to_H", C.c_double), ("nkml", C.c_int), ("open_bcs", C.c_int), ("ice_shelf", C.c_int),
+                ("SpV_avg", C.c_int)]
+
+
+def set_visc_params_default(HBBL=10.0, Kv=1.0e-4, BBL_use_EOS=True):
+    """set_visc_init :2876-3204 defaults (Boussinesq, unscaled units); HBBL and KV have none in MOM6 (fail_if_missing), and
+    BBL_USE_EOS defaults to USE_EOS (:3060)."""
+    p = SetViscParams()
+    p.bottomdraglaw = 1; p.cdrag = 0.003; p.drag_bg_vel = 0.0
+    p.dz_bbl = HBBL; p.Hbbl = HBBL          # CS%Hbbl = CS%dz_bbl * (US%Z_to_m * GV%m_to_H) (:3140)
+    p.BBL_thick_min = 0.0; p.Kv_BBL_min = Kv
+    p.linear_drag = 0; p.BBL_use_EOS = int(BBL_use_EOS); p.BBL_use_tidal_bg = 0; p.body_force_drag = 0
+    p.correct_BBL_bounds = 0; p.RiNo_mix = 0; p.channel_drag = 0
+    p.Rad_Earth = 6.378e6; p.L_to_Z = 1.0; p.L_to_H = 1.0
+    p.nkml = 0; p.open_bcs = 0; p.ice_shelf = 0; p.SpV_avg = 0
+    return p
+
+
 class HorViscParams(C.Structure):
     """mom6x_hor_visc_params; hor_visc_CS (MOM_hor_visc.F90:36-259)."""
     _fields_ = [("Laplacian", C.c_int), ("biharmonic", C.c_int), ("Kh", C.c_double), ("Kh_bg_min", C.c_double),

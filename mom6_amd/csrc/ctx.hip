@@ -136,6 +136,7 @@ extern "C" int mom6x_struct_size(int which) {
     case 15: return (int)sizeof(mom6x_sum_output_params);
     case 16: return (int)sizeof(mom6x_energy_sums);
     case 17: return (int)sizeof(mom6x_regrid_rho_params);
+    case 18: return (int)sizeof(mom6x_set_visc_params);
     default: return -1;
   }
 }

@@ -1386,29 +1386,7 @@ k_pgf_main_eos(Dm d, const double *__restrict__ G, const double *__restrict__ h,
       } else {
         const double T_int = 0.5 * (T_prev + T0), S_int = 0.5 * (S_prev + S0);
         double dR_dT, dR_dS;
-        if (FORM == MOM6X_EOS_LINEAR) { dR_dT = E.dRho_dT; dR_dS = E.dRho_dS; }
-        else if (FORM == MOM6X_EOS_UNESCO) unesco::density_derivs(T_int, S_int, press, dR_dT, dR_dS);
-        else if (FORM == MOM6X_EOS_ROQUET_RHO) roquet::roquet_density_derivs(T_int, S_int, press, &dR_dT, &dR_dS);
-        else if (FORM == MOM6X_EOS_JACKETT06) jackett::jackett_density_derivs(T_int, S_int, press, &dR_dT, &dR_dS);
-        else if (FORM == MOM6X_EOS_ROQUET_SPV) roquet::roquet_spv_density_derivs(T_int, S_int, press, &dR_dT, &dR_dS);
-        else {
-          typedef WC<FORM> W;
-          double al0, p0, lambda;
-          wright_coefs<FORM>(T_int, S_int, al0, p0, lambda);
-          if (FORM == MOM6X_EOS_WRIGHT) {   // calculate_density_derivs_elem_buggy_Wright, MOM_EOS_Wright.F90:208-222
-            double I_denom2 = 1.0 / (lambda + al0 * (press + p0));
-            I_denom2 = I_denom2 * I_denom2;
-            dR_dT = I_denom2 * (lambda * (W::b1 + T_int * (2.0 * W::b2 + 3.0 * W::b3 * T_int) + W::b5 * S_int) -
-                                (press + p0) * ((press + p0) * W::a1 + (W::c1 + T_int * (W::c2 * 2.0 + W::c3 * 3.0 * T_int) + W::c5 * S_int)));
-            dR_dS = I_denom2 * (lambda * (W::b4 + W::b5 * T_int) - (press + p0) * ((press + p0) * W::a2 + (W::c4 + W::c5 * T_int)));
-          } else {                          // calculate_density_derivs_elem_Wright_full / _red, MOM_EOS_Wright_full.F90:192-200
-            const double den = (lambda + al0 * (press + p0));
-            const double I_denom2 = 1.0 / (den * den);
-            dR_dT = I_denom2 * (lambda * (W::b1 + (T_int * (2.0 * W::b2 + 3.0 * W::b3 * T_int) + W::b5 * S_int)) -
-                                (press + p0) * ((press + p0) * W::a1 + (W::c1 + (T_int * (W::c2 * 2.0 + W::c3 * 3.0 * T_int) + W::c5 * S_int))));
-            dR_dS = I_denom2 * (lambda * (W::b4 + W::b5 * T_int) - (press + p0) * ((press + p0) * W::a2 + (W::c4 + W::c5 * T_int)));
-          }
-        }
+        eos_density_derivs<FORM>(E, T_int, S_int, press, dR_dT, dR_dS);
         pb = pb + G_Rho0 * ((zt0 - e_bot) * Ihtot) * (dR_dT * (T0 - T_prev) + dR_dS * (S0 - S_prev));
       }
       pbce[c] = pb;

@@ -583,4 +583,34 @@ __device__ __forceinline__ double eos_density(int form, double Rho_T0_S0, double
   if (form == MOM6X_EOS_WRIGHT_REDUCED) return wright_density<MOM6X_EOS_WRIGHT_REDUCED>(T, S, p);
   return wright_density<MOM6X_EOS_WRIGHT>(T, S, p);
 }
+
+// calculate_density_derivs(T, S, pressure, dR_dT, dR_dS, EOS) of every form on the device (MOM_EOS.F90 calculate_density_derivs ->
+// the form's calculate_density_derivs_elem): the pressure force's pbce (dyn_kernels.hip) and set_viscous_BBL (set_visc.hip).
+// E needs only dRho_dT / dRho_dS (EOS_LINEAR, MOM_EOS_linear.F90:136-148).
+template <int FORM, class EOS>
+__device__ __forceinline__ void eos_density_derivs(const EOS &E, double T, double S, double press, double &dR_dT, double &dR_dS) {
+  if (FORM == MOM6X_EOS_LINEAR) { dR_dT = E.dRho_dT; dR_dS = E.dRho_dS; }
+  else if (FORM == MOM6X_EOS_UNESCO) unesco::density_derivs(T, S, press, dR_dT, dR_dS);
+  else if (FORM == MOM6X_EOS_ROQUET_RHO) roquet::roquet_density_derivs(T, S, press, &dR_dT, &dR_dS);
+  else if (FORM == MOM6X_EOS_JACKETT06) jackett::jackett_density_derivs(T, S, press, &dR_dT, &dR_dS);
+  else if (FORM == MOM6X_EOS_ROQUET_SPV) roquet::roquet_spv_density_derivs(T, S, press, &dR_dT, &dR_dS);
+  else {
+    typedef WC<FORM> W;
+    double al0, p0, lambda;
+    wright_coefs<FORM>(T, S, al0, p0, lambda);
+    if (FORM == MOM6X_EOS_WRIGHT) {   // calculate_density_derivs_elem_buggy_Wright, MOM_EOS_Wright.F90:208-222
+      double I_denom2 = 1.0 / (lambda + al0 * (press + p0));
+      I_denom2 = I_denom2 * I_denom2;
+      dR_dT = I_denom2 * (lambda * (W::b1 + T * (2.0 * W::b2 + 3.0 * W::b3 * T) + W::b5 * S) -
+                          (press + p0) * ((press + p0) * W::a1 + (W::c1 + T * (W::c2 * 2.0 + W::c3 * 3.0 * T) + W::c5 * S)));
+      dR_dS = I_denom2 * (lambda * (W::b4 + W::b5 * T) - (press + p0) * ((press + p0) * W::a2 + (W::c4 + W::c5 * T)));
+    } else {                          // calculate_density_derivs_elem_Wright_full / _red, MOM_EOS_Wright_full.F90:192-200
+      const double den = (lambda + al0 * (press + p0));
+      const double I_denom2 = 1.0 / (den * den);
+      dR_dT = I_denom2 * (lambda * (W::b1 + (T * (2.0 * W::b2 + 3.0 * W::b3 * T) + W::b5 * S)) -
+                          (press + p0) * ((press + p0) * W::a1 + (W::c1 + (T * (W::c2 * 2.0 + W::c3 * 3.0 * T) + W::c5 * S))));
+      dR_dS = I_denom2 * (lambda * (W::b4 + W::b5 * T) - (press + p0) * ((press + p0) * W::a2 + (W::c4 + W::c5 * T)));
+    }
+  }
+}
 }  // namespace

@@ -120,6 +120,8 @@ struct mom6x_ctx {
   unsigned long long *cont_stats;   // device: Newton statistics of the wave-owned mass-flux kernel (mom6x_continuity_stats), or null
   bool cont_h_unused;       // the caller of continuity_PPM does not look at the new thicknesses (RK2.F90:646: hp is overwritten at :781
                             // before anybody reads it): the convergence of the second direction is not computed
+  // set_visc.hip: set_visc_CS of set_viscous_BBL, tv%eqn_of_state when use_BBL_EOS, CS%tideamp (caller-owned device array)
+  mom6x_set_visc_params sv; bool sv_init = false; bool sv_use_eos = false; mom6x_eos_params sv_eos; const double *sv_tideamp = nullptr;
 };
 void comm_free(mom6x_ctx *c);                                         // halo.hip
 void halo_start(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n);   // start_group_pass

@@ -271,6 +271,20 @@ class Dycore:
         self._visc = (Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Kv_shear, Ray_u, Ray_v)
         check(self.lib, self.lib.mom6x_vertvisc_set_visc(self.ctx, *[_ptr(a) for a in self._visc]))
 
+    # -- MOM_set_viscosity -------------------------------------------------------------------
+    def set_visc_init(self, params, eos=None, tideamp=None):
+        """set_visc_init (MOM_set_viscosity.F90:2876); eos: tv%eqn_of_state (None: the GV%Rlay walk); tideamp: CS%tideamp."""
+        self.sv_params = params
+        self._sv = (eos, tideamp)
+        check(self.lib, self.lib.mom6x_set_visc_init(self.ctx, C.byref(params), C.byref(eos) if eos is not None else None, _ptr(tideamp)))
+
+    def set_viscous_BBL(self, u, v, h, T=None, S=None, p_surf=None, Kv_bbl_u=None, Kv_bbl_v=None, bbl_thick_u=None, bbl_thick_v=None,
+                        Ray_u=None, Ray_v=None):
+        """set_viscous_BBL (MOM_set_viscosity.F90:135) into the caller's visc%Kv_bbl_u/v, bbl_thick_u/v (and Ray_u/v)."""
+        check(self.lib, self.lib.mom6x_set_viscous_BBL(self.ctx, _ptr(u), _ptr(v), _ptr(h), _ptr(T), _ptr(S), _ptr(p_surf),
+                                                       _ptr(Kv_bbl_u), _ptr(Kv_bbl_v), _ptr(bbl_thick_u), _ptr(bbl_thick_v),
+                                                       _ptr(Ray_u), _ptr(Ray_v)))
+
     def vertvisc_field(self, name):
         """CS%a_u / a_v / h_u / h_v of the device vertvisc_CS as a torch view."""
         which = ["a_u", "a_v", "h_u", "h_v"].index(name)
