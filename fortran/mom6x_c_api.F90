@@ -12,6 +12,7 @@ module mom6x_c_api
   public :: mom6x_coriolis_params, mom6x_pgf_params, mom6x_eos_params, mom6x_rk2_params, mom6x_rk2_hooks
   public :: mom6x_PressureForce_set_tv, mom6x_vertvisc_params, mom6x_vertvisc_init, mom6x_vertvisc_set_visc, mom6x_vertvisc_coef
   public :: mom6x_set_visc_params, mom6x_set_visc_init, mom6x_set_viscous_BBL
+  public :: mom6x_thickness_diffuse_params, mom6x_thickness_diffuse_init, mom6x_thickness_diffuse
   public :: mom6x_hor_visc_params, mom6x_hor_visc_init, mom6x_horizontal_viscosity, mom6x_vertvisc_set_direct_stress
   public :: mom6x_remapping_params, mom6x_ALE_remap_tracers, mom6x_ALE_remap_set_h_vel, mom6x_ALE_remap_velocities
   public :: mom6x_ALE_remap_velocities_conserve_ke, mom6x_ALE_remap_velocities_from_h, mom6x_comm_overlap_btstep
@@ -107,6 +108,15 @@ module mom6x_c_api
     real(c_double) :: Rad_Earth, L_to_Z, L_to_H
     integer(c_int) :: nkml, open_bcs, ice_shelf, SpV_avg
   end type mom6x_set_visc_params
+
+  type, bind(C) :: mom6x_thickness_diffuse_params   !< thickness_diffuse_CS (MOM_thickness_diffuse.F90:41-128), the members thickness_diffuse reads
+    integer(c_int) :: thickness_diffuse
+    real(c_double) :: Khth
+    integer(c_int) :: read_khth
+    real(c_double) :: Khth_Min, Khth_Max, max_Khth_CFL, slope_max, kappa_smooth, Z_to_L, Z_to_H_fill, Kh_eta_bg, Kh_eta_vel
+    integer(c_int) :: use_FGNV_streamfn, use_stanley_gm, detangle_interfaces, use_GME, use_variable_mixing, use_MEKE
+    integer(c_int) :: use_Kh_in_MEKE, GMwork, skeb_use_gm, nkml, open_bcs, non_Boussinesq
+  end type mom6x_thickness_diffuse_params
 
   type, bind(C) :: mom6x_hor_visc_params   !< hor_visc_CS (MOM_hor_visc.F90:36-259), the members the device path reads
     integer(c_int) :: Laplacian, biharmonic
@@ -334,6 +344,17 @@ module mom6x_c_api
         Ray_u, Ray_v) bind(C, name="mom6x_set_viscous_BBL")
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx, u, v, h, T, S, p_surf, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Ray_u, Ray_v
+    end function
+    integer(c_int) function mom6x_thickness_diffuse_init(ctx, p, eos, khth2d) bind(C, name="mom6x_thickness_diffuse_init")
+      import :: c_ptr, c_int, mom6x_thickness_diffuse_params
+      type(c_ptr), value :: ctx ; type(mom6x_thickness_diffuse_params), intent(in) :: p
+      type(c_ptr), value :: eos, khth2d   ! c_loc(an eos_params) or c_null_ptr; device pointer or c_null_ptr
+    end function
+    integer(c_int) function mom6x_thickness_diffuse(ctx, h, uhtr, vhtr, T, S, p_surf, slope_x, slope_y, dt, uhGM, vhGM) &
+        bind(C, name="mom6x_thickness_diffuse")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, h, uhtr, vhtr, T, S, p_surf, slope_x, slope_y, uhGM, vhGM
+      real(c_double), value :: dt
     end function
     integer(c_int) function mom6x_vertvisc_set_visc(ctx, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Kv_shear, Ray_u, Ray_v) &
         bind(C, name="mom6x_vertvisc_set_visc")

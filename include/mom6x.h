@@ -351,7 +351,7 @@ int  mom6x_device_count(void);
 /* sizeof() of the public structs (0 dims, 1 vgrid, 2 continuity_params, 3 BT_cont, 4 barotropic_params,
  * 5 coriolis_params, 6 pgf_params, 7 rk2_params, 8 rk2_hooks, 9 eos_params, 10 vertvisc_params, 11 hor_visc_params,
  * 12 remapping_params, 13 regrid_zstar_params, 14 chksum_result, 15 sum_output_params, 16 energy_sums, 17 regrid_rho_params,
- * 18 set_visc_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
+ * 18 set_visc_params, 19 thickness_diffuse_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
 int  mom6x_struct_size(int which);
 
 /* Create a context for one tile on HIP device `device`.  `metrics_host` is a
@@ -691,7 +691,54 @@ int mom6x_set_viscous_BBL(mom6x_ctx *ctx, const double *u, const double *v, cons
                           double *Ray_u, double *Ray_v);
 
 /* ------------------------------------------------------------------------- */
-/* MOM_dynamics_split_RK2                                                      */
+/* MOM_thickness_diffuse: thickness_diffuse                                    */
+/* thickness_diffuse_CS (src/parameterizations/lateral/MOM_thickness_diffuse.F90:41-128; thickness_diffuse_init :2175-2500):
+ * the members thickness_diffuse (:134-630) and thickness_diffuse_full (:635-1671) read on a Boussinesq grid with the plain
+ * (Gent-McWilliams) streamfunction.  The members marked "must be 0" are refused with MOM6X_EUNSUPPORTED.                  */
+typedef struct mom6x_thickness_diffuse_params {
+  int    thickness_diffuse;   /* THICKNESSDIFFUSE (F, :2207); F: mom6x_thickness_diffuse returns at once (:195)            */
+  double Khth;                /* KHTH (0, :2210) [L2 T-1]; 0 without khth2d: returns at once (:196)                         */
+  int    read_khth;           /* READ_KHTH (F, :2213): CS%khth2d is the khth2d of the init call; with KHTH > 0 an error (:2218) */
+  double Khth_Min;            /* KHTH_MIN (0, :2242) [L2 T-1]                                                               */
+  double Khth_Max;            /* KHTH_MAX (0, :2256) [L2 T-1]; used when > 0 (:291)                                         */
+  double max_Khth_CFL;        /* KHTH_MAX_CFL (0.8, :2259); must be > 0 (:2291 and :404 leave KH_v unset otherwise)         */
+  double slope_max;           /* KHTH_SLOPE_MAX (0.01, :2302) [Z L-1]                                                       */
+  double kappa_smooth;        /* KD_SMOOTH (1e-6 m2 s-1, :2305) [H Z T-1]                                                   */
+  double Z_to_L;              /* US%Z_to_L (1): mag_grad2 (:1037)                                                           */
+  double Z_to_H_fill;         /* US%Z_to_m*GV%m_to_H (1) of vert_fill_TS (MOM_isopycnal_slopes.F90:655) [H Z-1]             */
+  double Kh_eta_bg;           /* KH_ETA_CONST (0, :2266): must be 0                                                         */
+  double Kh_eta_vel;          /* KH_ETA_VEL_SCALE (0, :2272): must be 0                                                     */
+  int    use_FGNV_streamfn;   /* KHTH_USE_FGNV_STREAMFUNCTION (F, :2309): must be 0                                         */
+  int    use_stanley_gm;      /* USE_STANLEY_GM (F, :2327): must be 0                                                       */
+  int    detangle_interfaces; /* DETANGLE_INTERFACES (F, :2292): must be 0                                                  */
+  int    use_GME;             /* USE_GME (F, :2397): must be 0                                                              */
+  int    use_variable_mixing; /* VarMix%use_variable_mixing (Visbeck, resolution / depth scaling, khth_struct, QG Leith; :210): must be 0 */
+  int    use_MEKE;            /* MEKE%Kh or MEKE%GM_src allocated (USE_MEKE, :2386; :262, :846): must be 0                  */
+  int    use_Kh_in_MEKE;      /* USE_KH_IN_MEKE (F, :2388): must be 0                                                       */
+  int    GMwork;              /* the GMwork diagnostic (CS%GMwork allocated: find_work, :847): must be 0                    */
+  int    skeb_use_gm;         /* STOCH%skeb_use_gm (:509): must be 0                                                        */
+  int    nkml;                /* GV%nkml (0; nk_linear, :839): must be 0                                                    */
+  int    open_bcs;            /* open boundaries (G%OBCmaskCu/v differ from mask2dCu/v): must be 0                          */
+  int    non_Boussinesq;      /* tv%SpV_avg allocated or GV%semi_Boussinesq: must be 0                                      */
+} mom6x_thickness_diffuse_params;
+/* thickness_diffuse_init :2175: keeps the parameters and allocates the work arrays (seven 3-D arrays with an EOS, three
+ * without).  eos: tv%eqn_of_state (NULL: layers of constant density, :1085-1094).  khth2d: CS%khth2d (:2235), a 2-D h-point
+ * DEVICE array [L2 T-1] with a valid halo of one, owned by the caller and kept (required with READ_KHTH, else NULL).         */
+int mom6x_thickness_diffuse_init(mom6x_ctx *ctx, const mom6x_thickness_diffuse_params *p, const mom6x_eos_params *eos,
+                                 const double *khth2d);
+/* thickness_diffuse(h, uhtr, vhtr, tv, dt, G, GV, US, MEKE, VarMix, CDp, CS, STOCH) :134 on the context's stream, without a
+ * host synchronisation or an allocation.  h, T, S, tv%p_surf (nullable) and khth2d need a valid halo of one; T, S are
+ * required with an EOS.  slope_x, slope_y: VarMix%slope_x/y with use_stored_slopes, two nullable 3-D interface arrays of
+ * nk+1 planes [Z L-1] that come together.  uhGM, vhGM: CDp%uhGM / vhGM, two nullable 3-D outputs that receive uhD, vhD
+ * (:604, :608) and come together.  uhtr and uhGM are written at I = isc-1..iec, j = jsc..jec, vhtr and vhGM at i = isc..iec,
+ * J = jsc-1..jec, h on the computational domain only; all other points are left as they are.  Faces are not masked by the
+ * routine: a closed face gives a zero flux because G%dy_Cu / G%dx_Cv is zero there.  The caller still owes pass_var(h).     */
+int mom6x_thickness_diffuse(mom6x_ctx *ctx, double *h, double *uhtr, double *vhtr, const double *T, const double *S,
+                            const double *p_surf, const double *slope_x, const double *slope_y, double dt, double *uhGM,
+                            double *vhGM);
+
+/* ------------------------------------------------------------------------- */
+/* MOM_dynamics_split_RK2                                                    */
 
 /* Host callbacks for the callees of step_MOM_dyn_split_RK2 that are NOT on the ported hot path
  * (SURVEY.md 8f).  All array arguments are DEVICE pointers.  A NULL callback means "keep what the

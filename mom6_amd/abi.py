@@ -231,6 +231,34 @@ def set_visc_params_default(HBBL=10.0, Kv=1.0e-4, BBL_use_EOS=True):
     return p
 
 
+class ThicknessDiffuseParams(C.Structure):
+    """mom6x_thickness_diffuse_params; the thickness_diffuse_CS members of thickness_diffuse (MOM_thickness_diffuse.F90:41-128)."""
+    _fields_ = [("thickness_diffuse", C.c_int), ("Khth", C.c_double), ("read_khth", C.c_int), ("Khth_Min", C.c_double),
+                ("Khth_Max", C.c_double), ("max_Khth_CFL", C.c_double), ("slope_max", C.c_double), ("kappa_smooth", C.c_double),
+                ("Z_to_L", C.c_double), ("Z_to_H_fill", C.c_double), ("Kh_eta_bg", C.c_double), ("Kh_eta_vel", C.c_double),
+                ("use_FGNV_streamfn", C.c_int), ("use_stanley_gm", C.c_int), ("detangle_interfaces", C.c_int), ("use_GME", C.c_int),
+                ("use_variable_mixing", C.c_int), ("use_MEKE", C.c_int), ("use_Kh_in_MEKE", C.c_int), ("GMwork", C.c_int),
+                ("skeb_use_gm", C.c_int), ("nkml", C.c_int), ("open_bcs", C.c_int), ("non_Boussinesq", C.c_int)]
+
+
+THICKNESS_DIFFUSE_MUST_BE_0 = ("use_FGNV_streamfn", "use_stanley_gm", "detangle_interfaces", "Kh_eta_bg", "Kh_eta_vel", "use_GME",
+                               "use_variable_mixing", "use_MEKE", "use_Kh_in_MEKE", "GMwork", "skeb_use_gm", "nkml", "open_bcs",
+                               "non_Boussinesq")
+
+
+def thickness_diffuse_params_default(KHTH=600.0):
+    """thickness_diffuse_init :2207-2401 defaults (Boussinesq, unscaled units) with THICKNESSDIFFUSE = True; KHTH defaults to 0 in
+    MOM6, which switches the routine off (:196)."""
+    p = ThicknessDiffuseParams()
+    p.thickness_diffuse = 1; p.Khth = KHTH; p.read_khth = 0
+    p.Khth_Min = 0.0; p.Khth_Max = 0.0; p.max_Khth_CFL = 0.8
+    p.slope_max = 0.01; p.kappa_smooth = 1.0e-6
+    p.Z_to_L = 1.0; p.Z_to_H_fill = 1.0
+    for n in THICKNESS_DIFFUSE_MUST_BE_0:
+        setattr(p, n, 0)
+    return p
+
+
 class HorViscParams(C.Structure):
     """mom6x_hor_visc_params; hor_visc_CS (MOM_hor_visc.F90:36-259)."""
     _fields_ = [("Laplacian", C.c_int), ("biharmonic", C.c_int), ("Kh", C.c_double), ("Kh_bg_min", C.c_double),

@@ -137,6 +137,7 @@ extern "C" int mom6x_struct_size(int which) {
     case 16: return (int)sizeof(mom6x_energy_sums);
     case 17: return (int)sizeof(mom6x_regrid_rho_params);
     case 18: return (int)sizeof(mom6x_set_visc_params);
+    case 19: return (int)sizeof(mom6x_thickness_diffuse_params);
     default: return -1;
   }
 }
@@ -214,6 +215,7 @@ extern "C" int mom6x_ctx_destroy(mom6x_ctx *c) {
   (void)hipFree(c->Rlay); (void)hipFree(c->g_prime); (void)hipFree(c->retry); (void)hipFree(c->cont_stats);
   hor_visc_free(c);
   diag_sums_free(c);
+  thickness_diffuse_free(c);
   (void)hipFree(c->regrid_res); (void)hipFree(c->regrid_vec); (void)hipFree(c->remap_src); (void)hipFree(c->remap_hvel);
   (void)hipFree(c->vv_a_u); (void)hipFree(c->vv_a_v); (void)hipFree(c->vv_h_u); (void)hipFree(c->vv_h_v);
   (void)hipFree(c->G); (void)hipFree(c->hL); (void)hipFree(c->hR); (void)hipFree(c->flag);

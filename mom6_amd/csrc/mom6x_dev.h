@@ -122,7 +122,12 @@ struct mom6x_ctx {
                             // before anybody reads it): the convergence of the second direction is not computed
   // set_visc.hip: set_visc_CS of set_viscous_BBL, tv%eqn_of_state when use_BBL_EOS, CS%tideamp (caller-owned device array)
   mom6x_set_visc_params sv; bool sv_init = false; bool sv_use_eos = false; mom6x_eos_params sv_eos; const double *sv_tideamp = nullptr;
+  // thickness_diffuse.hip: thickness_diffuse_CS, tv%eqn_of_state, CS%khth2d (caller-owned device array) and the work arrays of
+  // mom6x_thickness_diffuse_init: td_work = [uhD | vhD | h_avail_rsum] and, with an EOS, [h_frac | pres | T_f | S_f], nk levels each
+  mom6x_thickness_diffuse_params td; bool td_init = false; bool td_use_eos = false; mom6x_eos_params td_eos;
+  const double *td_khth2d = nullptr; double *td_work = nullptr;
 };
+void thickness_diffuse_free(mom6x_ctx *c);                            // thickness_diffuse.hip
 void comm_free(mom6x_ctx *c);                                         // halo.hip
 void halo_start(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n);   // start_group_pass
 void halo_complete(mom6x_ctx *c);                                     // complete_group_pass

@@ -1,0 +1,342 @@
+// thickness_diffuse.hip -- isopycnal height diffusion (the Gent-McWilliams closure) on gfx950.
+//
+//   thickness_diffuse       <- MOM_thickness_diffuse.F90:134-630: the diffusivities :224-233, :240-250, :291-325, :343-353, :392-429,
+//                              the update of uhtr, vhtr and h :600-615
+//   thickness_diffuse_full  <- :635-1671 without the FGNV streamfunction: the column pass :864-882, the face pass :916-1213 /
+//                              :1231-1530, layer 1 :1533-1535
+//   find_eta                <- MOM_interface_heights.F90:91-97 (Boussinesq), vert_fill_TS <- MOM_isopycnal_slopes.F90:612-700
+//
+// Three launches.  k_td_cols: one lane per cell of the domain widened by one, top-down: h_avail_rsum, h_frac, pres and the
+// tridiagonal solve of vert_fill_TS (any layer count: the solve's c1 goes through a work array).  k_td_faces: one lane per face,
+// both directions in one launch (blockIdx.z), ONE bottom-up walk -- without the FGNV solver the two K = nz..2 loops of a face row
+// carry only uhtot -- that forms e from h as it climbs (find_eta's own order), h_avail pointwise, writes uhD | vhD and adds them
+// to uhtr | vhtr.  k_td_update: h.  MAX and MIN are the reference compiler's: the first argument on a tie (zeros of either sign).
+#include "mom6x_dev.h"
+#include "eos_dev.h"
+
+namespace {
+
+// the scalars of :818-824 and vert_fill_TS :649-659, formed once on the host in the reference's order
+struct TdK {
+  double dt, I4dt, I_slope_max2, h_neglect, h_neglect2, dz_neglect, H_to_Z, Z_to_H, Angstrom_H, gH, Z_to_L, int_slope;
+  double Khth, Khth_Min, Khth_Max, qCFL, kap_dt_x2, h0;
+  double dRho_dT, dRho_dS;
+};
+
+__device__ __forceinline__ double fmax1(double a, double b) { return (b > a) ? b : a; }   // MAX(a, b)
+__device__ __forceinline__ double fmin1(double a, double b) { return (b < a) ? b : a; }   // MIN(a, b)
+
+// The column pass :864-882 on cells is-1..ie+1, js-1..je+1 and, with Tf, vert_fill_TS(halo_here=1, larger_h_denom=.true.).
+// rsum[k], pres[k]: h_avail_rsum and pres at the interface ABOVE layer k.  Lanes start at i = -IAL (whole lines per wavefront).
+__global__ void __launch_bounds__(256)
+k_td_cols(Dm d, const double *__restrict__ G, TdK K, const double *__restrict__ h, const double *__restrict__ T,
+          const double *__restrict__ S, const double *__restrict__ p_surf, double *__restrict__ rsum, double *__restrict__ hfrac,
+          double *__restrict__ pres, double *Tf, double *Sf, double *c1) {
+  const int i = -IAL + blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = -1 + blockIdx.y * blockDim.y + threadIdx.y;
+  if (i < -1 || i > d.ni || j > d.nj) return;
+  const size_t x = ix2(d, i, j), slab = (size_t)d.slab;
+  const int nz = d.nk;
+  const double Ia = K.I4dt * gm(G, d, MOM6X_G_areaT)[x];
+  double rs = 0.0, pr = p_surf ? p_surf[x] : 0.0;
+  for (int k = 0; k < nz; ++k) {
+    const size_t o = (size_t)k * slab + x;
+    const double hk = h[o];
+    const double ha = fmax1(Ia * (hk - K.Angstrom_H), 0.0);
+    rsum[o] = rs;
+    if (pres) pres[o] = pr;
+    const double rn = k ? rs + ha : ha;
+    if (hfrac) hfrac[o] = k ? ((ha > 0.0) ? ha / rn : 0.0) : 1.0;
+    pr = pr + K.gH * hk;
+    rs = rn;
+  }
+  if (!Tf) return;
+  // vert_fill_TS :668-697, kap_dt_x2 > 0
+  double hk = h[x], hn = h[slab + x];
+  double ent = K.kap_dt_x2 / ((hk + hn) + K.h0);
+  double h_tr = hk + K.h_neglect;
+  double b1 = 1.0 / (h_tr + ent);
+  double d1 = b1 * h_tr;
+  double Tp = (b1 * h_tr) * T[x], Sp = (b1 * h_tr) * S[x];
+  Tf[x] = Tp; Sf[x] = Sp;
+  for (int k = 1; k < nz - 1; ++k) {
+    const size_t o = (size_t)k * slab + x;
+    hk = hn; hn = h[o + slab];
+    const double entn = K.kap_dt_x2 / ((hk + hn) + K.h0);
+    h_tr = hk + K.h_neglect;
+    c1[o] = ent * b1;
+    const double t = h_tr + d1 * ent;
+    b1 = 1.0 / (t + entn);
+    d1 = b1 * t;
+    Tp = b1 * (h_tr * T[o] + ent * Tp);
+    Sp = b1 * (h_tr * S[o] + ent * Sp);
+    Tf[o] = Tp; Sf[o] = Sp;
+    ent = entn;
+  }
+  {
+    const size_t o = (size_t)(nz - 1) * slab + x;
+    c1[o] = ent * b1;
+    h_tr = hn + K.h_neglect;
+    b1 = 1.0 / (h_tr + d1 * ent);
+    Tp = b1 * (h_tr * T[o] + ent * Tp);
+    Sp = b1 * (h_tr * S[o] + ent * Sp);
+    Tf[o] = Tp; Sf[o] = Sp;
+  }
+  for (int k = nz - 2; k >= 0; --k) {
+    const size_t o = (size_t)k * slab + x;
+    const double c = c1[o + slab];
+    Tp = Tf[o] + c * Tp;
+    Sp = Sf[o] + c * Sp;
+    Tf[o] = Tp; Sf[o] = Sp;
+  }
+}
+
+// MODE 0: layers of constant density (:1085-1094); 1: an EOS of form FORM, slopes from the filled T, S; 2: an EOS with stored
+// slopes (no density derivative, calc_derivatives :924); 3: constant density with stored slopes.
+// blockIdx.z: 0 u faces (I = -1..ni-1, j = 0..nj-1), 1 v faces (i = 0..ni-1, J = -1..nj-1).
+template <int FORM, int MODE>
+__global__ void __launch_bounds__(256)
+k_td_faces(Dm d, const double *__restrict__ G, TdK K, const double *__restrict__ h, double *__restrict__ uhtr,
+           double *__restrict__ vhtr, const double *__restrict__ khth2d, const double *__restrict__ slope_x,
+           const double *__restrict__ slope_y, const double *__restrict__ rsum, const double *__restrict__ hfrac,
+           const double *__restrict__ pres, const double *__restrict__ Tf, const double *__restrict__ Sf,
+           double *__restrict__ uhD, double *__restrict__ vhD) {
+  constexpr bool EOS = (MODE == 1 || MODE == 2);
+  const int dir = blockIdx.z;
+  const int i = -IAL + blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = -1 + blockIdx.y * blockDim.y + threadIdx.y;
+  if (i > d.ni - 1 || j > d.nj - 1) return;
+  if (dir == 0 ? (i < -1 || j < 0) : (i < 0)) return;
+  const size_t x = ix2(d, i, j), st = dir ? (size_t)d.pitch : 1, y = x + st, slab = (size_t)d.slab;
+  const int nz = d.nk;
+  double *htr = dir ? vhtr : uhtr, *hD = dir ? vhD : uhD;
+  const double *slope = dir ? slope_y : slope_x;
+
+  // KH_u_CFL, Khth_loc_u, KH_u(:,:,1) (:224-233, :240-250, :291-305) and their v twins
+  const double Idx = gm(G, d, dir ? MOM6X_G_IdxCv : MOM6X_G_IdxCu)[x], Idy = gm(G, d, dir ? MOM6X_G_IdyCv : MOM6X_G_IdyCu)[x];
+  const double KH_CFL = K.qCFL / (K.dt * ((Idx * Idx) + (Idy * Idy)));
+  double Kh_loc = khth2d ? 0.5 * (khth2d[x] + khth2d[y]) : K.Khth;
+  if (K.Khth_Max > 0) Kh_loc = fmax1(K.Khth_Min, fmin1(Kh_loc, K.Khth_Max));
+  else Kh_loc = fmax1(K.Khth_Min, Kh_loc);
+  const double KHlen = fmin1(KH_CFL, Kh_loc) * gm(G, d, dir ? MOM6X_G_dx_Cv : MOM6X_G_dy_Cu)[x];
+  const double Igrad = dir ? Idy : Idx;
+  const double mask = gm(G, d, dir ? MOM6X_G_mask2dCv : MOM6X_G_mask2dCu)[x];   // OBCmaskCu/v without open boundaries
+  const double *aT = gm(G, d, MOM6X_G_areaT), *bT = gm(G, d, MOM6X_G_bathyT);
+  const double IaL = K.I4dt * aT[x], IaR = K.I4dt * aT[y];
+  const double ebL = -(bT[x] + 0.0), ebR = -(bT[y] + 0.0);   // find_eta :91, dZ_ref = 0
+
+  double elL = ebL, elR = ebR;   // e(:,K+1)
+  double uhtot = 0.0;
+  size_t o = (size_t)(nz - 1) * slab;
+  double hLk = h[o + x], hRk = h[o + y];
+  double TLk = 0.0, TRk = 0.0, SLk = 0.0, SRk = 0.0;
+  if constexpr (MODE == 1) { TLk = Tf[o + x]; TRk = Tf[o + y]; SLk = Sf[o + x]; SRk = Sf[o + y]; }
+  for (int k = nz - 1; k >= 1; --k, o -= slab) {
+    const size_t om = o - slab;
+    const double eL = elL + hLk * K.H_to_Z, eR = elR + hRk * K.H_to_Z;   // e(:,K), find_eta :96
+    const double hLm = h[om + x], hRm = h[om + y];
+    double TLm = 0.0, TRm = 0.0, SLm = 0.0, SRm = 0.0;
+    double Slope, ratio = 0.0, Sfn_unlim;
+    if constexpr (EOS) {
+      if constexpr (MODE == 1) {
+        TLm = Tf[om + x]; TRm = Tf[om + y]; SLm = Sf[om + x]; SRm = Sf[om + y];
+        const double pres_u = 0.5 * (pres[o + x] + pres[o + y]);
+        const double T_u = 0.25 * ((TLk + TRk) + (TLm + TRm));
+        const double S_u = 0.25 * ((SLk + SRk) + (SLm + SRm));
+        double dR_dT, dR_dS;
+        eos_density_derivs<FORM>(K, T_u, S_u, pres_u, dR_dT, dR_dS);
+        const double drdiA = dR_dT * (TRm - TLm) + dR_dS * (SRm - SLm);
+        const double drdiB = dR_dT * (TRk - TLk) + dR_dS * (SRk - SLk);
+        const double drdkL = (dR_dT * (TLk - TLm) + dR_dS * (SLk - SLm));
+        const double drdkR = (dR_dT * (TRk - TRm) + dR_dS * (SRk - SRm));
+        const double hg2L = hLm * hLk + K.h_neglect2, hg2R = hRm * hRk + K.h_neglect2;
+        const double haL = 0.5 * (hLm + hLk) + K.h_neglect, haR = 0.5 * (hRm + hRk) + K.h_neglect;
+        const double dzaL = haL * K.H_to_Z, dzaR = haR * K.H_to_Z;
+        const double wtL = hg2L * (haR * dzaR), wtR = hg2R * (haL * dzaL);
+        const double drdz = ((wtL * drdkL) + (wtR * drdkR)) / ((dzaL * wtL) + (dzaR * wtR));
+        const double hg2A = hLm * hRm + K.h_neglect2, hg2B = hLk * hRk + K.h_neglect2;
+        const double haA = 0.5 * (hLm + hRm) + K.h_neglect, haB = 0.5 * (hLk + hRk) + K.h_neglect;
+        const double wtA = hg2A * haB, wtB = hg2B * haA;
+        const double drdx = ((wtA * drdiA + wtB * drdiB) / (wtA + wtB) - drdz * (eL - eR)) * Igrad;
+        const double zx = K.Z_to_L * drdx;
+        const double mag_grad2 = zx * zx + drdz * drdz;
+        if (mag_grad2 > 0.0) {
+          Slope = drdx / sqrt(mag_grad2);
+          ratio = Slope * Slope * K.I_slope_max2;
+        } else {
+          Slope = 0.0;
+          ratio = 1.0e20;
+        }
+      } else {
+        Slope = slope[o + x];
+        ratio = Slope * Slope * K.I_slope_max2;
+      }
+      // :1049-1051 with int_slope_u = 0 (kept: it decides the sign of a zero slope)
+      Slope = (1.0 - K.int_slope) * Slope + K.int_slope * ((eR - eL) * Igrad);
+      ratio = (1.0 - K.int_slope) * ratio;
+      Sfn_unlim = -(KHlen)*Slope;
+      // no dense water upslope from below the bottom of the receiving side (:1067-1083)
+      if (Sfn_unlim > 0.0) {
+        if (eL < ebR) Sfn_unlim = 0.0;
+        else if (ebR > elL) Sfn_unlim = Sfn_unlim * ((eL - ebR) / ((eL - elL) + K.dz_neglect));
+      } else {
+        if (eR < ebL) Sfn_unlim = 0.0;
+        else if (ebL > elR) Sfn_unlim = Sfn_unlim * ((eR - ebL) / ((eR - elR) + K.dz_neglect));
+      }
+    } else {
+      if constexpr (MODE == 3) Slope = slope[o + x];
+      else Slope = ((eR - eL) * Igrad) * mask;
+      Sfn_unlim = -(KHlen)*Slope;
+    }
+
+    // the second K loop (:1125-1190)
+    const double haL_ = fmax1(IaL * (hLk - K.Angstrom_H), 0.0), haR_ = fmax1(IaR * (hRk - K.Angstrom_H), 0.0);
+    double Sfn_est;
+    if constexpr (EOS) {
+      const double Sfn_safe = (uhtot <= 0.0) ? uhtot * (1.0 - hfrac[o + x]) : uhtot * (1.0 - hfrac[o + y]);
+      Sfn_est = (K.Z_to_H * Sfn_unlim + ratio * Sfn_safe) / (1.0 + ratio);
+    } else {
+      Sfn_est = K.Z_to_H * Sfn_unlim;
+    }
+    const double Sfn_in_H = fmin1(fmax1(Sfn_est, -rsum[o + x]), rsum[o + y]);
+    const double D = fmax1(fmin1((Sfn_in_H - uhtot), haL_), -haR_);
+    uhtot = uhtot + D;
+    hD[o + x] = D;
+    htr[o + x] = htr[o + x] + D * K.dt;
+    elL = eL; elR = eR; hLk = hLm; hRk = hRm;
+    TLk = TLm; TRk = TRm; SLk = SLm; SRk = SRm;
+  }
+  // layer 1 (:1534-1535)
+  const double D = -uhtot;
+  hD[x] = D;
+  htr[x] = htr[x] + D * K.dt;
+}
+
+// h(i,j,k) -= dt*IareaT*div(uhD, vhD) with the floor at Angstrom_H (:610-614)
+__global__ void __launch_bounds__(256)
+k_td_update(Dm d, const double *__restrict__ G, double dt, double Angstrom_H, double *__restrict__ h,
+            const double *__restrict__ uhD, const double *__restrict__ vhD) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = blockIdx.y * blockDim.y + threadIdx.y;
+  if (i >= d.ni || j >= d.nj) return;
+  const size_t x = ix3(d, i, j, blockIdx.z), p = (size_t)d.pitch;
+  double hn = h[x] - dt * gm(G, d, MOM6X_G_IareaT)[ix2(d, i, j)] * ((uhD[x] - uhD[x - 1]) + (vhD[x] - vhD[x - p]));
+  if (hn < Angstrom_H) hn = Angstrom_H;
+  h[x] = hn;
+}
+
+}  // namespace
+
+void thickness_diffuse_free(mom6x_ctx *c) {
+  (void)hipFree(c->td_work);
+  c->td_work = nullptr;
+}
+
+extern "C" int mom6x_thickness_diffuse_init(mom6x_ctx *c, const mom6x_thickness_diffuse_params *p, const mom6x_eos_params *eos,
+                                            const double *khth2d) {
+  REQUIRE(c && p, MOM6X_EINVAL, "mom6x_thickness_diffuse_init: null argument");
+#define TD_REFUSE(cond, what) REQUIRE(!(cond), MOM6X_EUNSUPPORTED, "thickness_diffuse_init: " what " is not on the device")
+  TD_REFUSE(p->use_FGNV_streamfn, "KHTH_USE_FGNV_STREAMFUNCTION");
+  TD_REFUSE(p->use_stanley_gm, "USE_STANLEY_GM");
+  TD_REFUSE(p->detangle_interfaces, "DETANGLE_INTERFACES");
+  TD_REFUSE(p->Kh_eta_bg > 0.0, "KH_ETA_CONST > 0");
+  TD_REFUSE(p->Kh_eta_vel > 0.0, "KH_ETA_VEL_SCALE > 0");
+  TD_REFUSE(p->use_GME, "USE_GME");
+  TD_REFUSE(p->use_variable_mixing, "variable mixing (VarMix%use_variable_mixing)");
+  TD_REFUSE(p->use_MEKE, "MEKE (MEKE%Kh, MEKE%GM_src)");
+  TD_REFUSE(p->use_Kh_in_MEKE, "USE_KH_IN_MEKE");
+  TD_REFUSE(p->GMwork, "the GMwork diagnostic (find_work)");
+  TD_REFUSE(p->skeb_use_gm, "SKEB (STOCH%skeb_use_gm)");
+  TD_REFUSE(p->nkml != 0, "a bulk mixed layer (GV%nkml > 0)");
+  TD_REFUSE(p->open_bcs, "open boundary conditions");
+  TD_REFUSE(p->non_Boussinesq || !c->GV.Boussinesq, "non-Boussinesq mode (tv%SpV_avg, semi_Boussinesq)");
+#undef TD_REFUSE
+  REQUIRE(p->max_Khth_CFL > 0.0, MOM6X_EINVAL, "thickness_diffuse_init: KHTH_MAX_CFL <= 0 leaves KH_v unset in the reference");
+  REQUIRE(!(p->read_khth && p->Khth > 0.0), MOM6X_EINVAL,
+          "thickness_diffuse_init: KHTH > 0 is not compatible with READ_KHTH = TRUE. ");
+  REQUIRE((p->read_khth != 0) == (khth2d != nullptr), MOM6X_EINVAL, "thickness_diffuse_init: khth2d comes with READ_KHTH");
+  REQUIRE(p->slope_max > 0.0, MOM6X_EINVAL, "thickness_diffuse_init: KHTH_SLOPE_MAX must be positive");
+  REQUIRE(!eos || (eos->form >= MOM6X_EOS_LINEAR && eos->form <= MOM6X_EOS_ROQUET_SPV), MOM6X_EINVAL,
+          "thickness_diffuse_init: unknown EQN_OF_STATE form");
+  REQUIRE(!eos || c->d.nk >= 2, MOM6X_EINVAL, "thickness_diffuse_init: vert_fill_TS needs two layers");
+  HIPCHK(hipSetDevice(c->device));
+  c->td = *p;
+  c->td_use_eos = eos != nullptr;
+  if (eos) c->td_eos = *eos;
+  c->td_khth2d = khth2d;
+  c->td_init = false;
+  thickness_diffuse_free(c);
+  if (p->thickness_diffuse && (p->Khth > 0.0 || p->read_khth)) {
+    const size_t n = (size_t)(eos ? 7 : 3) * c->d.nk * c->d.slab * sizeof(double);
+    HIPCHK(hipMalloc(&c->td_work, n));
+    HIPCHK(hipMemsetAsync(c->td_work, work_fill_byte(), n, c->stream));
+  }
+  c->td_init = true;
+  return MOM6X_OK;
+}
+
+extern "C" int mom6x_thickness_diffuse(mom6x_ctx *c, double *h, double *uhtr, double *vhtr, const double *T, const double *S,
+                                       const double *p_surf, const double *slope_x, const double *slope_y, double dt,
+                                       double *uhGM, double *vhGM) {
+  REQUIRE(c && c->td_init, MOM6X_EINVAL, "MOM_thickness_diffuse: Module must be initialized before it is used.");
+  const mom6x_thickness_diffuse_params &P = c->td;
+  if (!P.thickness_diffuse || !(P.Khth > 0.0 || P.read_khth)) return MOM6X_OK;   // :195-197
+  REQUIRE(h && uhtr && vhtr, MOM6X_EINVAL, "thickness_diffuse: null array");
+  REQUIRE(dt > 0.0, MOM6X_EINVAL, "thickness_diffuse: dt must be positive");
+  REQUIRE((slope_x != nullptr) == (slope_y != nullptr), MOM6X_EINVAL, "thickness_diffuse: slope_x and slope_y come together");
+  REQUIRE((uhGM != nullptr) == (vhGM != nullptr), MOM6X_EINVAL, "thickness_diffuse: uhGM and vhGM come together");
+  const bool use_eos = c->td_use_eos, stored = slope_x != nullptr;
+  REQUIRE(!use_eos || stored || (T && S), MOM6X_EINVAL, "thickness_diffuse: an equation of state needs tv%T and tv%S");
+  HIPCHK(hipSetDevice(c->device));
+  const Dm d = c->d;
+  const mom6x_vgrid &GV = c->GV;
+  TdK K;
+  K.dt = dt;
+  K.I4dt = 0.25 / dt;                                          // :818
+  K.I_slope_max2 = 1.0 / (P.slope_max * P.slope_max);          // :819
+  K.h_neglect = GV.H_subroundoff; K.h_neglect2 = K.h_neglect * K.h_neglect; K.dz_neglect = GV.dZ_subroundoff;   // :821-822
+  K.H_to_Z = GV.H_to_Z; K.Z_to_H = GV.Z_to_H; K.Angstrom_H = GV.Angstrom_H;
+  K.gH = GV.g_Earth * GV.H_to_RZ;                              // :872
+  K.Z_to_L = P.Z_to_L; K.int_slope = 0.0;                      // :472-474
+  K.Khth = P.Khth; K.Khth_Min = P.Khth_Min; K.Khth_Max = P.Khth_Max;
+  K.qCFL = 0.25 * P.max_Khth_CFL;                              // :226
+  K.kap_dt_x2 = (2.0 * (P.kappa_smooth * dt)) * P.Z_to_H_fill;  // MOM_isopycnal_slopes.F90:655
+  K.h0 = 1.0e-16 * sqrt(0.5 * K.kap_dt_x2);                    // :658
+  K.dRho_dT = c->td_eos.dRho_dT; K.dRho_dS = c->td_eos.dRho_dS;
+  const size_t n3 = (size_t)d.nk * d.slab;
+  double *W = c->td_work;
+  double *uD = uhGM ? uhGM : W, *vD = vhGM ? vhGM : W + n3, *rsum = W + 2 * n3;
+  double *hfrac = use_eos ? W + 3 * n3 : nullptr;
+  const bool derivs = use_eos && !stored;                      // calc_derivatives :924-925
+  double *pres = derivs ? W + 4 * n3 : nullptr;
+  const bool fill = derivs && K.kap_dt_x2 > 0.0;               // else T_f = T_in (MOM_isopycnal_slopes.F90:661-665): read in place
+  double *Tf = fill ? W + 5 * n3 : nullptr, *Sf = fill ? W + 6 * n3 : nullptr;
+  const dim3 b(64, 4, 1);
+  KLAUNCH(c, "k_td_cols", k_td_cols, grid3(d.ni + 1 + IAL, d.nj + 2, 1, b), b, d, c->G, K, h, T, S, p_surf, rsum, hfrac, pres, Tf,
+          Sf, W);   // (c1 lives in the uhD work array until the face pass)
+  const double *Tr = fill ? Tf : T, *Sr = fill ? Sf : S;
+  const dim3 g = grid3(d.ni + IAL, d.nj + 1, 2, b);
+#define TDF(F, M)                                                                                                            \
+  KLAUNCH(c, "k_td_faces<" #F "," #M ">", (k_td_faces<F, M>), g, b, d, c->G, K, h, uhtr, vhtr, c->td_khth2d, slope_x, slope_y, \
+          rsum, hfrac, pres, Tr, Sr, uD, vD)
+  if (!use_eos) {
+    if (stored) TDF(0, 3); else TDF(0, 0);
+  } else if (stored) {
+    TDF(0, 2);
+  } else {
+    switch (c->td_eos.form) {
+      case MOM6X_EOS_LINEAR: TDF(1, 1); break;
+      case MOM6X_EOS_WRIGHT: TDF(2, 1); break;
+      case MOM6X_EOS_WRIGHT_FULL: TDF(3, 1); break;
+      case MOM6X_EOS_WRIGHT_REDUCED: TDF(4, 1); break;
+      case MOM6X_EOS_UNESCO: TDF(5, 1); break;
+      case MOM6X_EOS_ROQUET_RHO: TDF(6, 1); break;
+      case MOM6X_EOS_JACKETT06: TDF(7, 1); break;
+      default: TDF(8, 1); break;
+    }
+  }
+#undef TDF
+  KLAUNCH(c, "k_td_update", k_td_update, grid3(d.ni, d.nj, d.nk, b), b, d, c->G, dt, GV.Angstrom_H, h, uD, vD);
+  HIPCHK(hipGetLastError());
+  return MOM6X_OK;
+}

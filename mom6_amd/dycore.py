@@ -285,6 +285,20 @@ class Dycore:
                                                        _ptr(Kv_bbl_u), _ptr(Kv_bbl_v), _ptr(bbl_thick_u), _ptr(bbl_thick_v),
                                                        _ptr(Ray_u), _ptr(Ray_v)))
 
+    # -- MOM_thickness_diffuse -----------------------------------------------------------------
+    def thickness_diffuse_init(self, params, eos=None, khth2d=None):
+        """thickness_diffuse_init (MOM_thickness_diffuse.F90:2175); eos: tv%eqn_of_state (None: layers of constant density);
+        khth2d: CS%khth2d with READ_KHTH."""
+        self.td_params = params
+        self._td = (eos, khth2d)
+        check(self.lib, self.lib.mom6x_thickness_diffuse_init(self.ctx, C.byref(params), C.byref(eos) if eos is not None else None,
+                                                              _ptr(khth2d)))
+
+    def thickness_diffuse(self, h, uhtr, vhtr, dt, T=None, S=None, p_surf=None, slope_x=None, slope_y=None, uhGM=None, vhGM=None):
+        """thickness_diffuse (MOM_thickness_diffuse.F90:134): h, uhtr, vhtr in place; uhGM, vhGM receive uhD, vhD."""
+        check(self.lib, self.lib.mom6x_thickness_diffuse(self.ctx, _ptr(h), _ptr(uhtr), _ptr(vhtr), _ptr(T), _ptr(S), _ptr(p_surf),
+                                                         _ptr(slope_x), _ptr(slope_y), C.c_double(dt), _ptr(uhGM), _ptr(vhGM)))
+
     def vertvisc_field(self, name):
         """CS%a_u / a_v / h_u / h_v of the device vertvisc_CS as a torch view."""
         which = ["a_u", "a_v", "h_u", "h_v"].index(name)
