@@ -925,8 +925,6 @@ k_layer_accel(Dm d, const double *__restrict__ G, const double *__restrict__ wor
   }
 }
 
-inline dim3 blk2() { return dim3(64, 4, 1); }
-
 }  // namespace
 
 void bt_defer_layer_accel(mom6x_ctx *c, bool on) { if (c->bts) c->bts->la_defer = on; }

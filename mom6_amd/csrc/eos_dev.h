@@ -585,7 +585,7 @@ __device__ __forceinline__ double eos_density(int form, double Rho_T0_S0, double
 }
 
 // calculate_density_derivs(T, S, pressure, dR_dT, dR_dS, EOS) of every form on the device (MOM_EOS.F90 calculate_density_derivs ->
-// the form's calculate_density_derivs_elem): the pressure force's pbce (dyn_kernels.hip) and set_viscous_BBL (set_visc.hip).
+// the form's calculate_density_derivs_elem): the pressure force's pbce (pressure_force.hip) and set_viscous_BBL (set_visc.hip).
 // E needs only dRho_dT / dRho_dS (EOS_LINEAR, MOM_EOS_linear.F90:136-148).
 template <int FORM, class EOS>
 __device__ __forceinline__ void eos_density_derivs(const EOS &E, double T, double S, double press, double &dR_dT, double &dR_dS) {

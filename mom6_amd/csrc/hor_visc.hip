@@ -26,7 +26,6 @@ enum HV {
 
 namespace {
 
-inline dim3 blk2() { return dim3(64, 4, 1); }
 #define MG(n) gm(G, d, MOM6X_G_##n)
 #define PLN(n) (P + (size_t)(n) * slab)
 
@@ -704,7 +703,7 @@ k_hv_fused(Dm d, const double *__restrict__ G, const double *__restrict__ P, mom
   constexpr int HT_LDW = HT_X + 2, HT_LDN = (HT_Y + 2) * HT_LDW;
   // Work-groups go to the eight XCDs round robin: with xcd_order XCD n walks a CONTIGUOUS run of tiles (x fastest), so that the
   // 128-byte lines two neighbouring tiles share (a tile row is 32 doubles at an offset of 28 n - 3: three lines for 224 useful
-  // bytes) meet in ONE L2 instead of being fetched by two (as k_corad_lds, dyn_kernels.hip)
+  // bytes) meet in ONE L2 instead of being fetched by two (as k_corad_lds, coriolis_adv.hip)
   int bid = (int)blockIdx.x;
   const int nb = gx * gy * gz;
   if (xcd_order) { const int per = (nb + 7) / 8; bid = (bid % 8) * per + bid / 8; }

@@ -158,15 +158,12 @@ int ctx_scratch(mom6x_ctx *c, int slot, int nlev, double **out);
 int work_fill_byte();   // 0, or 0xFF with MOM6X_POISON_WORK=1 (ctx.hip): the initial contents of work arrays   // ctx.hip
 void hor_visc_free(mom6x_ctx *c);                                  // hor_visc.hip
 void diag_sums_free(mom6x_ctx *c);                                 // diag_sums.hip
-// dyn_kernels.hip: vertvisc_coef looking at u (mode 0), mask*(u + dtx*u_bc) (1) or mask*(u + dtx*(u_bc + u_abt)) (2)
 int CorAdCalc_bc(mom6x_ctx *c, const double *u, const double *v, const double *h, const double *uh, const double *vh, double *CAu,
                  double *CAv, const double *PFu, const double *PFv, const double *diffu, const double *diffv, double *u_bc,
-                 double *v_bc, double *uhtr, double *vhtr, double dt_tr);   // dyn_kernels.hip
-int vertvisc_coef_upd(mom6x_ctx *c, int mode, const double *u, const double *v, const double *u_bc, const double *v_bc,
-                      const double *u_abt, const double *v_abt, double dtx, const double *h, double dt, double *u_out, double *v_out);
+                 double *v_bc, double *uhtr, double *vhtr, double dt_tr);   // coriolis_adv.hip
 // btstep_layer_accel (MOM_barotropic.F90:3432-3504) evaluated by the CONSUMER of accel_layer_u / _v instead of being written to
 // HBM and read back: what a face column needs of the barotropic solver's 2-D results (barotropic.hip keeps them in its work block
-// until the next btstep).  mode 3 of vertvisc_coef_upd = mode 2 with u_abt formed from these.
+// until the next btstep).
 struct LayerAccelSrc {
   const double *pbce;      // 3-D
   const double *e_anom;    // 2-D, h points
@@ -175,13 +172,6 @@ struct LayerAccelSrc {
   const double *a2d;       // u_accel_bt | v_accel_bt (2-D)
   double underflow;        // accel_underflow = vel_underflow / dt
 };
-bool vertvisc_coef_solve_usable(mom6x_ctx *c);                           // dyn_kernels.hip: k_vertvisc_coef_cols exists for this configuration
-int vertvisc_coef_solve_la(mom6x_ctx *c, const double *u_in, const double *v_in, const double *u_bc, const double *v_bc,
-                           const LayerAccelSrc &LAu, const LayerAccelSrc &LAv, double dtx, const double *h, double dt_coef,
-                           double *u, double *v, const double *taux, const double *tauy, double dt, double *taux_bot, double *tauy_bot,
-                           double *vr_u, double *vr_v, bool keep_coef);
-int vertvisc_coef_remnant(mom6x_ctx *c, const double *u_in, const double *v_in, const double *u_bc, const double *v_bc, double dtx,
-                          const double *h, double dt_coef, double *vr_u, double *vr_v, double dt, bool keep_coef);
 int bt_mass_source_from(mom6x_ctx *c, const double *eta_h, const double *eta, int set_cor);   // bt_mass_source with the column sum given
 int set_dtbt_eta(mom6x_ctx *c, const double *pbce, const double *eta);      // barotropic.hip: set_dtbt(pbce, eta=eta) RK2.F90:667
 void bt_defer_btcalc(mom6x_ctx *c, bool on);                            // barotropic.hip: btcalc's fractions formed by btstep's column pass while on
@@ -189,10 +179,19 @@ int bt_frhat_materialize(mom6x_ctx *c);                                 // write
 void bt_defer_layer_accel(mom6x_ctx *c, bool on);                       // barotropic.hip: btstep skips k_layer_accel while on
 bool bt_layer_accel_src(mom6x_ctx *c, LayerAccelSrc *u, LayerAccelSrc *v);   // false if no deferred result is pending
 int bt_layer_accel_materialize(mom6x_ctx *c, double *accel_layer_u, double *accel_layer_v);
-int vertvisc_coef_upd_la(mom6x_ctx *c, const double *u, const double *v, const double *u_bc, const double *v_bc,
-                         const LayerAccelSrc &LAu, const LayerAccelSrc &LAv, double dtx, const double *h, double dt, double *u_out,
-                         double *v_out);
-// dyn_kernels.hip: [u = mask*(u_in + dtx*(u_bc + u_abt));] vertvisc(u, v, dt); [vertvisc_remnant(vr_u, vr_v, dt)] in one sweep
+// vert_friction.hip, for the RK2 step.  Which kernels serve a call (one per direction with the column on chip, vertvisc_coef + the
+// fused solve, or the fused solve alone in a context without device coefficients) is decided there.
+// :591-610: vertvisc_coef on mask*(u + dt*u_bc), then vertvisc_remnant(vr_u, vr_v, dt)
+int vertvisc_stage_remnant(mom6x_ctx *c, const double *u, const double *v, const double *u_bc, const double *v_bc, const double *h,
+                           double dt, double *vr_u, double *vr_v);
+// :681-767 / :957-1022: u = mask*(u_in + dt*(u_bc + u_abt)), u_abt from the arrays or, if given, from the LayerAccelSrc pair; vertvisc_coef
+// on it; vertvisc(u, v, dt); [vertvisc_remnant(vr_u, vr_v, dt)].  keep_coef: CS%a_u, CS%h_u must hold these coefficients afterwards
+int vertvisc_stage_solve(mom6x_ctx *c, const double *u_in, const double *v_in, const double *u_bc, const double *v_bc,
+                         const double *u_abt, const double *v_abt, const LayerAccelSrc *LAu, const LayerAccelSrc *LAv, double dt,
+                         const double *h, double *u, double *v, const double *taux, const double *tauy, double *taux_bot, double *tauy_bot,
+                         double *vr_u, double *vr_v, bool keep_coef);
+// [u = mask*(u_in + dtx*(u_bc + u_abt));] vertvisc(u, v, dt); [vertvisc_remnant(vr_u, vr_v, dt)] in one sweep, with the coefficients
+// the context holds (the step's host-callback arms, which call back between the pieces)
 int vertvisc_fused(mom6x_ctx *c, const double *u_in, const double *v_in, const double *u_bc, const double *v_bc,
                    const double *u_abt, const double *v_abt, double dtx, double *u, double *v, const double *taux,
                    const double *tauy, double dt, double *taux_bot, double *tauy_bot, double *vr_u, double *vr_v);
@@ -213,6 +212,8 @@ inline int nxa(int nx, int I0) { return (I0 < 0) ? nx + IAL + I0 : nx; }
 inline dim3 grid3(int nx, int ny, int nz, dim3 b) {
   return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y, (nz + b.z - 1) / b.z);
 }
+inline dim3 blk2() { return dim3(64, 4, 1); }   // the work-group of the i-parallel kernels: a wavefront along i, four rows
+inline dim3 gridk(int nx, int ny, int nk, dim3 b) { return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y, nchunks(nk)); }
 
 // The kernels that keep a whole column on chip (registers + LDS: k_vertvisc_coef_cols, k_vertvisc_cols, k_vertvisc_remnant_cols,
 // k_tridiag_cols, k_btcalc_cols, k_regrid_zstar_cols) unroll the column at compile time.  Their template argument NKT is the layer

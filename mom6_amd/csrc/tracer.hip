@@ -37,8 +37,6 @@ struct FluxList { double *f[MAXTR]; };
 
 namespace {
 
-inline dim3 blk2() { return dim3(64, 4, 1); }
-
 __device__ __forceinline__ double dmax3(double a, double b, double c) { return dmax(dmax(a, b), c); }
 __device__ __forceinline__ double dmin3(double a, double b, double c) { return dmin(dmin(a, b), c); }
 
@@ -990,7 +988,7 @@ extern "C" int mom6x_advect_tracer(mom6x_ctx *c, const double *h_end, const doub
   return MOM6X_OK;
 }
 
-// k_tridiag with the whole column on chip (the technique of k_vertvisc_cols, dyn_kernels.hip): c1 and the un-substituted T in
+// k_tridiag with the whole column on chip (the technique of k_vertvisc_cols, vert_friction.hip): c1 and the un-substituted T in
 // registers, the un-substituted S of triDiagTS in LDS, one wavefront per work-group, inputs fetched TD_G layers ahead into a
 // double buffer.  4 (5) words read and 1 (2) written per cell-layer instead of 9 (13); the same operations in the same order.
 template <int NKT, bool TWO>   // (NKT: mom6x_dev.h NK_OF / NK_EXACT -- the layer count itself, or a bound on it)
