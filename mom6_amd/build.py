@@ -28,7 +28,7 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 # from: continuity_wave.hip face_column).
 PER_FILE = {"continuity_wave.hip": ["-ffinite-math-only"],
             # barotropic.hip: the scheduler's max-ILP strategy takes 4-5 % off k_bt_col (1.41 -> 1.35 ms per launch, four launches per step)
-            # and leaves the sub-cycle's kernels where they are; on the other files it is neutral or loses (tracer.hip: +13 % on
+            # and leaves the sub-cycle's kernels where they are; on the other files it is neutral or loses (tracer_advect.hip: +13 % on
             # k_ta_x_tile).  profiles/r06_ab_sched_all.txt
             "barotropic.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 

@@ -157,7 +157,7 @@ extern "C" int mom6x_dims_init(mom6x_dims *d, int ni, int nj, int nk, int halo) 
 
 void bt_state_free(mom6x_ctx *ctx);   // barotropic.hip
 void rk2_state_free(mom6x_ctx *ctx);  // dyn_split_RK2.hip
-void ta_state_free(mom6x_ctx *ctx);   // tracer.hip
+void ta_state_free(mom6x_ctx *ctx);   // tracer_advect.hip
 
 extern "C" int mom6x_ctx_create(mom6x_ctx **out, const mom6x_dims *dims, int device,
                                 const double *metrics_host, const mom6x_vgrid *GV,

@@ -1,4 +1,4 @@
-/* The three-operation division by 3 and by 6 of mom6_amd/csrc/tracer.hip (div_by<C>): q = RN(x RN(1/c)), r = x - c q exact in a fused
+/* The three-operation division by 3 and by 6 of mom6_amd/csrc/tracer_advect.hip (div_by<C>): q = RN(x RN(1/c)), r = x - c q exact in a fused
  * multiply-add, RN(q + r RN(1/c)), sign from the numerator -- against the division, bit for bit, on random values of every exponent,
  * on patterns around 1, 2, 4/3 and 8/3 of every binade, and on the subnormals, where it must FAIL only when the quotient is subnormal
  * (the kernel sends every |x| < 2^-1000 through the division).  Usage: div_by_check <millions of random values>; prints

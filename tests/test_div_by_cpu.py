@@ -1,4 +1,4 @@
-"""The three-operation division by 3 and 6 of the tracer kernels (mom6_amd/csrc/tracer.hip `div_by<C>`: Markstein's correction of
+"""The three-operation division by 3 and 6 of the tracer kernels (mom6_amd/csrc/tracer_advect.hip `div_by<C>`: Markstein's correction of
 x * RN(1/c) with one exact remainder) equals the division bit for bit wherever the kernel uses it (|x| >= 2**-1000, zeros included) --
 checked here on the host with the same operations (C `fma`), tens of millions of values of every exponent plus the patterns that
 break naive x * (1/3): tests/native/div_by_check.c.  The device side is held to the oracle, which divides, by tests/test_tracer_gpu.py."""
