@@ -23,6 +23,7 @@ program check_abi
   type(mom6x_regrid_rho_params) :: rr
   type(mom6x_set_visc_params) :: sv
   type(mom6x_thickness_diffuse_params) :: td
+  type(mom6x_tracer_hor_diff_params) :: thd
   integer :: nbad, rc
   nbad = 0
   call chk(0, int(c_sizeof(d)), "mom6x_dims")
@@ -45,6 +46,7 @@ program check_abi
   call chk(17, int(c_sizeof(rr)), "mom6x_regrid_rho_params")
   call chk(18, int(c_sizeof(sv)), "mom6x_set_visc_params")
   call chk(19, int(c_sizeof(td)), "mom6x_thickness_diffuse_params")
+  call chk(20, int(c_sizeof(thd)), "mom6x_tracer_hor_diff_params")
   if (mom6x_abi_version() /= MOM6X_ABI_BUILT_FOR) then
     print '(a,i0,a,i0)', "ABI version: library ", mom6x_abi_version(), ", fortran/mom6x_c_api.F90 ", MOM6X_ABI_BUILT_FOR ; nbad = nbad + 1
   endif

@@ -13,6 +13,7 @@ module mom6x_c_api
   public :: mom6x_PressureForce_set_tv, mom6x_vertvisc_params, mom6x_vertvisc_init, mom6x_vertvisc_set_visc, mom6x_vertvisc_coef
   public :: mom6x_set_visc_params, mom6x_set_visc_init, mom6x_set_viscous_BBL
   public :: mom6x_thickness_diffuse_params, mom6x_thickness_diffuse_init, mom6x_thickness_diffuse
+  public :: mom6x_tracer_hor_diff_params, mom6x_tracer_hor_diff_init, mom6x_tracer_hordiff, mom6x_tracer_hordiff_tile
   public :: mom6x_hor_visc_params, mom6x_hor_visc_init, mom6x_horizontal_viscosity, mom6x_vertvisc_set_direct_stress
   public :: mom6x_remapping_params, mom6x_ALE_remap_tracers, mom6x_ALE_remap_set_h_vel, mom6x_ALE_remap_velocities
   public :: mom6x_ALE_remap_velocities_conserve_ke, mom6x_ALE_remap_velocities_from_h, mom6x_comm_overlap_btstep
@@ -117,6 +118,15 @@ module mom6x_c_api
     integer(c_int) :: use_FGNV_streamfn, use_stanley_gm, detangle_interfaces, use_GME, use_variable_mixing, use_MEKE
     integer(c_int) :: use_Kh_in_MEKE, GMwork, skeb_use_gm, nkml, open_bcs, non_Boussinesq
   end type mom6x_thickness_diffuse_params
+
+  type, bind(C) :: mom6x_tracer_hor_diff_params   !< tracer_hor_diff_CS (MOM_tracer_hor_diff.F90:41-97) and the VarMix / MEKE switches tracer_hordiff reads
+    real(c_double) :: KhTr, KhTr_Slope_Cff, KhTr_min, KhTr_max, KhTr_passivity_coeff, KhTr_passivity_min
+    integer(c_int) :: check_diffusive_CFL
+    real(c_double) :: max_diff_CFL
+    integer(c_int) :: use_variable_mixing, Resoln_scaled_KhTr, use_MEKE_Kh
+    real(c_double) :: MEKE_KhTr_fac
+    integer(c_int) :: use_neutral_diffusion, use_hor_bnd_diffusion, Diffuse_ML_interior, offline, open_bcs
+  end type mom6x_tracer_hor_diff_params
 
   type, bind(C) :: mom6x_hor_visc_params   !< hor_visc_CS (MOM_hor_visc.F90:36-259), the members the device path reads
     integer(c_int) :: Laplacian, biharmonic
@@ -355,6 +365,25 @@ module mom6x_c_api
       import :: c_ptr, c_int, c_double
       type(c_ptr), value :: ctx, h, uhtr, vhtr, T, S, p_surf, slope_x, slope_y, uhGM, vhGM
       real(c_double), value :: dt
+    end function
+    !> tracer_hor_diff_init (MOM_tracer_hor_diff.F90:1630)
+    integer(c_int) function mom6x_tracer_hor_diff_init(ctx, p) bind(C, name="mom6x_tracer_hor_diff_init")
+      import :: c_ptr, c_int, mom6x_tracer_hor_diff_params
+      type(c_ptr), value :: ctx ; type(mom6x_tracer_hor_diff_params), intent(in) :: p
+    end function
+    !> tracer_hordiff (MOM_tracer_hor_diff.F90:119); tracers, df_x, df_y: c_loc of host arrays of ntr device pointers (df_x, df_y
+    !! or their entries may be c_null_ptr); conc_underflow: c_loc of ntr host values or c_null_ptr; num_itts_out: c_loc(an integer)
+    integer(c_int) function mom6x_tracer_hordiff(ctx, h, dt, tracers, conc_underflow, ntr, L2u, SN_u, L2v, SN_v, Res_fn_h, Rd_dx_h, &
+        MEKE_Kh, df_x, df_y, khdt_x_out, khdt_y_out, cfl_out, num_itts_out) bind(C, name="mom6x_tracer_hordiff")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, h, tracers, conc_underflow, L2u, SN_u, L2v, SN_v, Res_fn_h, Rd_dx_h, MEKE_Kh, df_x, df_y
+      type(c_ptr), value :: khdt_x_out, khdt_y_out, cfl_out, num_itts_out
+      real(c_double), value :: dt
+      integer(c_int), value :: ntr
+    end function
+    integer(c_int) function mom6x_tracer_hordiff_tile(tx, ty, max_tracers) bind(C, name="mom6x_tracer_hordiff_tile")
+      import :: c_int
+      integer(c_int), intent(out) :: tx, ty, max_tracers
     end function
     integer(c_int) function mom6x_vertvisc_set_visc(ctx, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Kv_shear, Ray_u, Ray_v) &
         bind(C, name="mom6x_vertvisc_set_visc")

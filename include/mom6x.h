@@ -351,7 +351,7 @@ int  mom6x_device_count(void);
 /* sizeof() of the public structs (0 dims, 1 vgrid, 2 continuity_params, 3 BT_cont, 4 barotropic_params,
  * 5 coriolis_params, 6 pgf_params, 7 rk2_params, 8 rk2_hooks, 9 eos_params, 10 vertvisc_params, 11 hor_visc_params,
  * 12 remapping_params, 13 regrid_zstar_params, 14 chksum_result, 15 sum_output_params, 16 energy_sums, 17 regrid_rho_params,
- * 18 set_visc_params, 19 thickness_diffuse_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
+ * 18 set_visc_params, 19 thickness_diffuse_params, 20 tracer_hor_diff_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
 int  mom6x_struct_size(int which);
 
 /* Create a context for one tile on HIP device `device`.  `metrics_host` is a
@@ -736,6 +736,56 @@ int mom6x_thickness_diffuse_init(mom6x_ctx *ctx, const mom6x_thickness_diffuse_p
 int mom6x_thickness_diffuse(mom6x_ctx *ctx, double *h, double *uhtr, double *vhtr, const double *T, const double *S,
                             const double *p_surf, const double *slope_x, const double *slope_y, double dt, double *uhGM,
                             double *vhGM);
+
+/* ------------------------------------------------------------------------- */
+/* MOM_tracer_hor_diff: tracer_hordiff                                        */
+/* tracer_hor_diff_CS (src/tracer/MOM_tracer_hor_diff.F90:41-97; tracer_hor_diff_init :1630-1779) and the switches of VarMix and
+ * MEKE that tracer_hordiff (:119-699) reads on its along-layer path (:541-612).  The members marked "must be 0" are refused
+ * with MOM6X_EUNSUPPORTED.                                                                                                   */
+typedef struct mom6x_tracer_hor_diff_params {
+  double KhTr;                 /* KHTR (0, :1659) [L2 T-1]; <= 0 without variable mixing: mom6x_tracer_hordiff returns at once (:199) */
+  double KhTr_Slope_Cff;       /* KHTR_SLOPE_CFF (0, :1666): the Eady term, with variable mixing, when > 0 (:225, :242)              */
+  double KhTr_min;             /* KHTR_MIN (0, :1671) [L2 T-1]                                                                       */
+  double KhTr_max;             /* KHTR_MAX (0, :1681) [L2 T-1]; used when > 0 (:245)                                                 */
+  double KhTr_passivity_coeff; /* KHTR_PASSIVITY_COEFF (0, :1684); used with variable mixing when > 0 (:249)                         */
+  double KhTr_passivity_min;   /* KHTR_PASSIVITY_MIN (0.5, :1690)                                                                    */
+  int    check_diffusive_CFL;  /* CHECK_DIFFUSIVE_CFL (F, :1697): the iteration count from the cell CFL (:371-384), one stream
+                                  synchronisation and one all-reduce per call                                                        */
+  double max_diff_CFL;         /* MAX_TR_DIFFUSION_CFL (-1, :1702): when > 0 limits khdt_x, khdt_y (:322-357) and, without
+                                  CHECK_DIFFUSIVE_CFL, gives the iteration count (:386)                                              */
+  int    use_variable_mixing;  /* VarMix%use_variable_mixing (:222): the branch :238-281                                             */
+  int    Resoln_scaled_KhTr;   /* VarMix%Resoln_scaled_KhTr (RESOLN_SCALED_KHTR): Res_fn_h scales the diffusivity (:246, :282-294).
+                                  The reference reads it only with variable mixing; here the branch :282-294 runs as written when
+                                  it is set without                                                                                  */
+  int    use_MEKE_Kh;          /* MEKE%Kh is allocated (:243): the MEKE term, with variable mixing                                   */
+  double MEKE_KhTr_fac;        /* MEKE%KhTr_fac (MEKE_KHTR_FAC, 0)                                                                   */
+  int    use_neutral_diffusion; /* USE_NEUTRAL_DIFFUSION (F, :1738): must be 0                                                       */
+  int    use_hor_bnd_diffusion; /* USE_HORIZONTAL_BOUNDARY_DIFFUSION (F, :1742): must be 0                                           */
+  int    Diffuse_ML_interior;  /* DIFFUSE_ML_TO_INTERIOR (F, :1694; tracer_epipycnal_ML_diff needs a bulk mixed layer): must be 0    */
+  int    offline;              /* do_online_flag = .false. with read_khdt_x, read_khdt_y (:359-369): must be 0                       */
+  int    open_bcs;             /* open boundary conditions: must be 0                                                                */
+} mom6x_tracer_hor_diff_params;
+/* tracer_hor_diff_init(Time, G, GV, US, param_file, diag, EOS, diabatic_CSp, CS) :1630: keeps the parameters and allocates the
+ * work arrays (three 2-D planes and the copies of the tile edges for eight tracers).                                           */
+int mom6x_tracer_hor_diff_init(mom6x_ctx *ctx, const mom6x_tracer_hor_diff_params *p);
+/* tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv) :119 on the context's stream.  tracers: the registry, a HOST
+ * array of ntr 3-D device arrays, updated in place on the computational domain; each iteration starts with the context's group
+ * pass of all of them (:545), so their halos are filled on return from the values before the last iteration.  h is read one
+ * point into the halo and never passed: the caller owes that halo.  conc_underflow: ntr HOST values (Reg%Tr(m)%conc_underflow,
+ * :605) or NULL for none.  L2u, SN_u, L2v, SN_v, Res_fn_h, Rd_dx_h (VarMix) and MEKE_Kh (MEKE%Kh): 2-D device planes owned by
+ * the caller, h-point ones valid one point into the halo; NULL when absent, and a term that is switched on without its plane is
+ * an error that names the field.  df_x, df_y: NULL or HOST arrays of ntr nullable 3-D device arrays (Reg%Tr(m)%df_x / df_y,
+ * :581-588) that receive the fluxes summed over the iterations at I = isc-1..iec, j = jsc..jec | i = isc..iec, J = jsc-1..jec;
+ * other points keep what they held.  khdt_x_out, khdt_y_out (2-D, the same face ranges), cfl_out (2-D, the computational domain,
+ * written with CHECK_DIFFUSIVE_CFL only) and num_itts_out are optional outputs.  Without CHECK_DIFFUSIVE_CFL the call neither
+ * synchronises nor allocates.  With no tracers, or KHTR <= 0 without variable mixing, nothing is written (:199).
+ * Not carried: the 2-D flux diagnostics df2d_x / df2d_y, the Kh_u / Kh_v / Kh_h diagnostics, DEBUG checksums.                   */
+int mom6x_tracer_hordiff(mom6x_ctx *ctx, const double *h, double dt, double *const *tracers, const double *conc_underflow, int ntr,
+                         const double *L2u, const double *SN_u, const double *L2v, const double *SN_v, const double *Res_fn_h,
+                         const double *Rd_dx_h, const double *MEKE_Kh, double *const *df_x, double *const *df_y, double *khdt_x_out,
+                         double *khdt_y_out, double *cfl_out, int *num_itts_out);
+/* The extents of the iteration kernel's tile (columns, rows) and the number of tracers it carries per launch.                   */
+int mom6x_tracer_hordiff_tile(int *tx, int *ty, int *max_tracers);
 
 /* ------------------------------------------------------------------------- */
 /* MOM_dynamics_split_RK2                                                    */

@@ -259,6 +259,33 @@ def thickness_diffuse_params_default(KHTH=600.0):
     return p
 
 
+class TracerHorDiffParams(C.Structure):
+    """mom6x_tracer_hor_diff_params; tracer_hor_diff_CS (MOM_tracer_hor_diff.F90:41-97) and the VarMix / MEKE switches of tracer_hordiff."""
+    _fields_ = [("KhTr", C.c_double), ("KhTr_Slope_Cff", C.c_double), ("KhTr_min", C.c_double), ("KhTr_max", C.c_double),
+                ("KhTr_passivity_coeff", C.c_double), ("KhTr_passivity_min", C.c_double), ("check_diffusive_CFL", C.c_int),
+                ("max_diff_CFL", C.c_double), ("use_variable_mixing", C.c_int), ("Resoln_scaled_KhTr", C.c_int),
+                ("use_MEKE_Kh", C.c_int), ("MEKE_KhTr_fac", C.c_double), ("use_neutral_diffusion", C.c_int),
+                ("use_hor_bnd_diffusion", C.c_int), ("Diffuse_ML_interior", C.c_int), ("offline", C.c_int), ("open_bcs", C.c_int)]
+
+
+TRACER_HOR_DIFF_MUST_BE_0 = ("use_neutral_diffusion", "use_hor_bnd_diffusion", "Diffuse_ML_interior", "offline", "open_bcs")
+
+
+def tracer_hor_diff_params_default(KHTR=0.0, **kw):
+    """tracer_hor_diff_init :1659-1707 defaults (unscaled units), no variable mixing, no MEKE; KHTR defaults to 0 in MOM6, which
+    switches the routine off (:199)."""
+    p = TracerHorDiffParams()
+    p.KhTr = KHTR; p.KhTr_Slope_Cff = 0.0; p.KhTr_min = 0.0; p.KhTr_max = 0.0
+    p.KhTr_passivity_coeff = 0.0; p.KhTr_passivity_min = 0.5
+    p.check_diffusive_CFL = 0; p.max_diff_CFL = -1.0
+    p.use_variable_mixing = 0; p.Resoln_scaled_KhTr = 0; p.use_MEKE_Kh = 0; p.MEKE_KhTr_fac = 0.0
+    for n in TRACER_HOR_DIFF_MUST_BE_0:
+        setattr(p, n, 0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 class HorViscParams(C.Structure):
     """mom6x_hor_visc_params; hor_visc_CS (MOM_hor_visc.F90:36-259)."""
     _fields_ = [("Laplacian", C.c_int), ("biharmonic", C.c_int), ("Kh", C.c_double), ("Kh_bg_min", C.c_double),

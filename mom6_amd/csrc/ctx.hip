@@ -138,6 +138,7 @@ extern "C" int mom6x_struct_size(int which) {
     case 17: return (int)sizeof(mom6x_regrid_rho_params);
     case 18: return (int)sizeof(mom6x_set_visc_params);
     case 19: return (int)sizeof(mom6x_thickness_diffuse_params);
+    case 20: return (int)sizeof(mom6x_tracer_hor_diff_params);
     default: return -1;
   }
 }
@@ -216,6 +217,7 @@ extern "C" int mom6x_ctx_destroy(mom6x_ctx *c) {
   hor_visc_free(c);
   diag_sums_free(c);
   thickness_diffuse_free(c);
+  tracer_hor_diff_free(c);
   (void)hipFree(c->regrid_res); (void)hipFree(c->regrid_vec); (void)hipFree(c->remap_src); (void)hipFree(c->remap_hvel);
   (void)hipFree(c->vv_a_u); (void)hipFree(c->vv_a_v); (void)hipFree(c->vv_h_u); (void)hipFree(c->vv_h_v);
   (void)hipFree(c->G); (void)hipFree(c->hL); (void)hipFree(c->hR); (void)hipFree(c->flag);

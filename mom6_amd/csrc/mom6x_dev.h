@@ -126,8 +126,10 @@ struct mom6x_ctx {
   // mom6x_thickness_diffuse_init: td_work = [uhD | vhD | h_avail_rsum] and, with an EOS, [h_frac | pres | T_f | S_f], nk levels each
   mom6x_thickness_diffuse_params td; bool td_init = false; bool td_use_eos = false; mom6x_eos_params td_eos;
   const double *td_khth2d = nullptr; double *td_work = nullptr;
+  void *thd = nullptr;      // tracer_hor_diff.hip: tracer_hor_diff_CS and the work arrays of mom6x_tracer_hor_diff_init (ThdState)
 };
 void thickness_diffuse_free(mom6x_ctx *c);                            // thickness_diffuse.hip
+void tracer_hor_diff_free(mom6x_ctx *c);                              // tracer_hor_diff.hip
 void comm_free(mom6x_ctx *c);                                         // halo.hip
 void halo_start(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n);   // start_group_pass
 void halo_complete(mom6x_ctx *c);                                     // complete_group_pass

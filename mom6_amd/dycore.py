@@ -299,6 +299,38 @@ class Dycore:
         check(self.lib, self.lib.mom6x_thickness_diffuse(self.ctx, _ptr(h), _ptr(uhtr), _ptr(vhtr), _ptr(T), _ptr(S), _ptr(p_surf),
                                                          _ptr(slope_x), _ptr(slope_y), C.c_double(dt), _ptr(uhGM), _ptr(vhGM)))
 
+    # -- MOM_tracer_hor_diff -------------------------------------------------------------------
+    def tracer_hor_diff_init(self, params):
+        """tracer_hor_diff_init (MOM_tracer_hor_diff.F90:1630)."""
+        self.thd_params = params
+        check(self.lib, self.lib.mom6x_tracer_hor_diff_init(self.ctx, C.byref(params)))
+
+    def tracer_hordiff(self, h, dt, tracers, MEKE_Kh=None, L2u=None, SN_u=None, L2v=None, SN_v=None, Res_fn_h=None, Rd_dx_h=None,
+                       conc_underflow=None, df_x=None, df_y=None, khdt_x=None, khdt_y=None, CFL=None):
+        """tracer_hordiff(h, dt, MEKE, VarMix, ..., Reg) (MOM_tracer_hor_diff.F90:119): `tracers` is the registry as a list of 3-D
+        fields, updated in place; MEKE_Kh is MEKE%Kh, L2u .. Rd_dx_h the members of VarMix; conc_underflow, df_x, df_y are lists
+        with one entry per tracer (entries of df_x, df_y may be None).  Returns num_itts."""
+        n = len(tracers)
+        ptrs = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in tracers])
+        uf = (C.c_double * n)(*conc_underflow) if conc_underflow is not None and n else None
+
+        def plist(fs):
+            if fs is None or n == 0:
+                return None
+            assert len(fs) == n
+            return (C.c_void_p * n)(*[(f.data_ptr() if f is not None else None) for f in fs])
+        itts = C.c_int(0)
+        check(self.lib, self.lib.mom6x_tracer_hordiff(self.ctx, _ptr(h), C.c_double(dt), ptrs, uf, n, _ptr(L2u), _ptr(SN_u), _ptr(L2v),
+                                                      _ptr(SN_v), _ptr(Res_fn_h), _ptr(Rd_dx_h), _ptr(MEKE_Kh), plist(df_x), plist(df_y),
+                                                      _ptr(khdt_x), _ptr(khdt_y), _ptr(CFL), C.byref(itts)))
+        return itts.value
+
+    def tracer_hordiff_tile(self):
+        """(columns, rows, tracers per launch) of the iteration kernel's tile."""
+        tx, ty, mt = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self.lib, self.lib.mom6x_tracer_hordiff_tile(C.byref(tx), C.byref(ty), C.byref(mt)))
+        return tx.value, ty.value, mt.value
+
     def vertvisc_field(self, name):
         """CS%a_u / a_v / h_u / h_v of the device vertvisc_CS as a torch view."""
         which = ["a_u", "a_v", "h_u", "h_v"].index(name)
