@@ -14,6 +14,7 @@ module mom6x_c_api
   public :: mom6x_set_visc_params, mom6x_set_visc_init, mom6x_set_viscous_BBL
   public :: mom6x_thickness_diffuse_params, mom6x_thickness_diffuse_init, mom6x_thickness_diffuse
   public :: mom6x_tracer_hor_diff_params, mom6x_tracer_hor_diff_init, mom6x_tracer_hordiff, mom6x_tracer_hordiff_tile
+  public :: mom6x_varmix_params, mom6x_varmix_init, mom6x_calc_slope_functions
   public :: mom6x_hor_visc_params, mom6x_hor_visc_init, mom6x_horizontal_viscosity, mom6x_vertvisc_set_direct_stress
   public :: mom6x_remapping_params, mom6x_ALE_remap_tracers, mom6x_ALE_remap_set_h_vel, mom6x_ALE_remap_velocities
   public :: mom6x_ALE_remap_velocities_conserve_ke, mom6x_ALE_remap_velocities_from_h, mom6x_comm_overlap_btstep
@@ -127,6 +128,14 @@ module mom6x_c_api
     real(c_double) :: MEKE_KhTr_fac
     integer(c_int) :: use_neutral_diffusion, use_hor_bnd_diffusion, Diffuse_ML_interior, offline, open_bcs
   end type mom6x_tracer_hor_diff_params
+
+  type, bind(C) :: mom6x_varmix_params   !< VarMix_CS (MOM_lateral_mixing_coeffs.F90:38-215), the members calc_slope_functions reads
+    integer(c_int) :: calculate_Eady_growth_rate, use_stored_slopes, use_simpler_Eady_growth_rate, full_depth_Eady_growth_rate
+    real(c_double) :: kappa_smooth, Visbeck_S_max, Visbeck_L_scale, Eady_GR_D_scale, cropping_distance
+    integer(c_int) :: VarMix_Ktop
+    real(c_double) :: h_min_N2, max_depth, H_to_Z, Z_to_L, L_to_m, H_to_RZ, Z_to_H_fill, Angstrom_Z, g_Earth, Rho0
+    integer(c_int) :: use_stanley_iso, open_bcs, non_Boussinesq, debug
+  end type mom6x_varmix_params
 
   type, bind(C) :: mom6x_hor_visc_params   !< hor_visc_CS (MOM_hor_visc.F90:36-259), the members the device path reads
     integer(c_int) :: Laplacian, biharmonic
@@ -384,6 +393,20 @@ module mom6x_c_api
     integer(c_int) function mom6x_tracer_hordiff_tile(tx, ty, max_tracers) bind(C, name="mom6x_tracer_hordiff_tile")
       import :: c_int
       integer(c_int), intent(out) :: tx, ty, max_tracers
+    end function
+    !> VarMix_init (MOM_lateral_mixing_coeffs.F90:1445) for calc_slope_functions; eos: c_loc(an eos_params) or c_null_ptr; Rlay,
+    !! g_prime: c_loc of GV%Rlay, GV%g_prime (host); L2u, L2v: device planes or c_null_ptr
+    integer(c_int) function mom6x_varmix_init(ctx, p, eos, Rlay, g_prime, L2u, L2v) bind(C, name="mom6x_varmix_init")
+      import :: c_ptr, c_int, mom6x_varmix_params
+      type(c_ptr), value :: ctx ; type(mom6x_varmix_params), intent(in) :: p
+      type(c_ptr), value :: eos, Rlay, g_prime, L2u, L2v
+    end function
+    !> calc_slope_functions (MOM_lateral_mixing_coeffs.F90:686); every array is a device pointer, the diagnostics may be c_null_ptr
+    integer(c_int) function mom6x_calc_slope_functions(ctx, h, T, S, p_surf, dt, SN_u, SN_v, slope_x, slope_y, N2_u, N2_v, dzu, dzv, &
+        dzSxN, dzSyN, S2_u, S2_v) bind(C, name="mom6x_calc_slope_functions")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, h, T, S, p_surf, SN_u, SN_v, slope_x, slope_y, N2_u, N2_v, dzu, dzv, dzSxN, dzSyN, S2_u, S2_v
+      real(c_double), value :: dt
     end function
     integer(c_int) function mom6x_vertvisc_set_visc(ctx, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Kv_shear, Ray_u, Ray_v) &
         bind(C, name="mom6x_vertvisc_set_visc")

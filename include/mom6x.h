@@ -351,7 +351,7 @@ int  mom6x_device_count(void);
 /* sizeof() of the public structs (0 dims, 1 vgrid, 2 continuity_params, 3 BT_cont, 4 barotropic_params,
  * 5 coriolis_params, 6 pgf_params, 7 rk2_params, 8 rk2_hooks, 9 eos_params, 10 vertvisc_params, 11 hor_visc_params,
  * 12 remapping_params, 13 regrid_zstar_params, 14 chksum_result, 15 sum_output_params, 16 energy_sums, 17 regrid_rho_params,
- * 18 set_visc_params, 19 thickness_diffuse_params, 20 tracer_hor_diff_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
+ * 18 set_visc_params, 19 thickness_diffuse_params, 20 tracer_hor_diff_params, 21 varmix_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
 int  mom6x_struct_size(int which);
 
 /* Create a context for one tile on HIP device `device`.  `metrics_host` is a
@@ -786,6 +786,67 @@ int mom6x_tracer_hordiff(mom6x_ctx *ctx, const double *h, double dt, double *con
                          double *khdt_y_out, double *cfl_out, int *num_itts_out);
 /* The extents of the iteration kernel's tile (columns, rows) and the number of tracers it carries per launch.                   */
 int mom6x_tracer_hordiff_tile(int *tx, int *ty, int *max_tracers);
+
+/* ------------------------------------------------------------------------- */
+/* MOM_lateral_mixing_coeffs: calc_slope_functions                            */
+/* VarMix_CS (src/parameterizations/lateral/MOM_lateral_mixing_coeffs.F90:38-215; VarMix_init :1445-2054): the members that
+ * calc_slope_functions (:686-738) and its callees read: calc_isoneutral_slopes (src/core/MOM_isopycnal_slopes.F90:31-608),
+ * calc_Eady_growth_rate_2D (:962-1112), calc_Visbeck_coeffs_old (:743-959, without open boundaries) and
+ * calc_slope_functions_using_just_e (:1116-1275), on a Boussinesq grid.  The members marked "must be 0" are refused with
+ * MOM6X_EUNSUPPORTED.                                                                                                      */
+typedef struct mom6x_varmix_params {
+  int    calculate_Eady_growth_rate;   /* CS%calculate_Eady_growth_rate (:1604); 0: mom6x_calc_slope_functions writes nothing (:708) */
+  int    use_stored_slopes;            /* USE_STORED_SLOPES (F, :1589)                                                              */
+  int    use_simpler_Eady_growth_rate; /* USE_SIMPLER_EADY_GROWTH_RATE (F, :1718); needs use_stored_slopes (:1722)                  */
+  int    full_depth_Eady_growth_rate;  /* FULL_DEPTH_EADY_GROWTH_RATE (F when Boussinesq, :1743)                                    */
+  double kappa_smooth;                 /* KD_SMOOTH (1e-6 m2 s-1, :1704) [H Z T-1]                                                  */
+  double Visbeck_S_max;                /* VISBECK_MAX_SLOPE (0, :1689) [Z L-1]; the limiter acts when its square is > 0 (:882)      */
+  double Visbeck_L_scale;              /* VISBECK_L_SCALE (0, :1755) [L], or when negative a nondimensional factor on the face areas */
+  double Eady_GR_D_scale;              /* EADY_GROWTH_RATE_D_SCALE (0, :1725) [Z]; <= 0: 64*max_depth (:991)                        */
+  double cropping_distance;            /* EADY_GROWTH_RATE_CROPPING_DISTANCE (0, :1729) [Z]; negative: no cropping (:993)           */
+  int    VarMix_Ktop;                  /* VARMIX_KTOP (2, :1734); must be >= 2 (layer k-1 is read, :1203)                           */
+  double h_min_N2;                     /* MIN_DZ_FOR_SLOPE_N2 (1 m, :1738) [H]                                                      */
+  double max_depth;                    /* GV%max_depth [Z] (:991)                                                                   */
+  double H_to_Z;                       /* GV%H_to_Z (1): find_eta, dzaL / dzaR                                                      */
+  double Z_to_L;                       /* US%Z_to_L (1): mag_grad2 (MOM_isopycnal_slopes.F90:390)                                   */
+  double L_to_m;                       /* US%L_to_m (1): L2u, L2v with a negative VISBECK_L_SCALE (:1764)                           */
+  double H_to_RZ;                      /* GV%H_to_RZ (Rho0): pres (MOM_isopycnal_slopes.F90:245)                                    */
+  double Z_to_H_fill;                  /* US%Z_to_m*GV%m_to_H (1) of vert_fill_TS (MOM_isopycnal_slopes.F90:655) [H Z-1]            */
+  double Angstrom_Z;                   /* GV%Angstrom_Z (1e-10 m) [Z]: dZ_cutoff (:1160)                                            */
+  double g_Earth;                      /* GV%g_Earth [L2 Z-1 T-2]                                                                   */
+  double Rho0;                         /* GV%Rho0 [R]: G_Rho0 (MOM_isopycnal_slopes.F90:173)                                        */
+  int    use_stanley_iso;              /* USE_STANLEY_ISO (F, :1614): must be 0                                                     */
+  int    open_bcs;                     /* open boundaries (OBC associated; G%OBCmaskCu/v differ from mask2dCu/v): must be 0         */
+  int    non_Boussinesq;               /* tv%SpV_avg allocated or GV%semi_Boussinesq: must be 0                                     */
+  int    debug;                        /* DEBUG (F): the checksums of :948-957, :995-999, :1107-1110: must be 0                     */
+} mom6x_varmix_params;
+/* VarMix_init :1445 for the members above: checks them (use_simpler_Eady_growth_rate without use_stored_slopes is the reference's
+ * own fatal error, :1722), keeps them and allocates every work array calc_slope_functions will need.  The context's halo must be
+ * at least two wide.  eos: tv%eqn_of_state (NULL: layers of constant density, slopes from GV%Rlay).  Rlay, g_prime: GV%Rlay,
+ * GV%g_prime, HOST arrays of nk values, copied.  L2u, L2v: nullable 2-D DEVICE planes that receive CS%L2u, CS%L2v (:1759-1772):
+ * Visbeck_L_scale**2 at every point of the array or, when the scale is negative, (L_to_m*Visbeck_L_scale)**2 * areaCu | areaCv at
+ * I = isc-1..iec, j = jsc..jec | i = isc..iec, J = jsc-1..jec and zero elsewhere.                                                 */
+int mom6x_varmix_init(mom6x_ctx *ctx, const mom6x_varmix_params *p, const mom6x_eos_params *eos, const double *Rlay,
+                      const double *g_prime, double *L2u, double *L2v);
+/* calc_slope_functions(h, tv, dt, G, GV, US, CS, OBC) :686 on the context's stream, without an exchange, a host synchronisation
+ * or an allocation.  h, T, S and tv%p_surf (nullable) need TWO valid halo points (find_eta(halo_size=2), vert_fill_TS(halo+1));
+ * T, S are required with an EOS.  SN_u, SN_v: CS%SN_u, CS%SN_v, 2-D planes.  slope_x, slope_y: CS%slope_x, CS%slope_y, the 3-D
+ * interface arrays of nk+1 planes that mom6x_thickness_diffuse takes; required with use_stored_slopes (both branches that call
+ * calc_isoneutral_slopes), not touched otherwise.  Nullable diagnostics, each of nk+1 planes unless noted: N2_u, N2_v (the
+ * use_stored_slopes branch posts them; filled in both slope branches), dzu, dzv, dzSxN, dzSyN (use_simpler_Eady_growth_rate),
+ * S2_u, S2_v (2-D planes, calc_Visbeck_coeffs_old :944-945).
+ * What is written, everything else keeps its value:
+ *   calc_isoneutral_slopes(halo=1): slope_x, N2_u, dzu, dzSxN at I = isc-2..iec+1, j = jsc-1..jec+1 and slope_y, N2_v, dzv, dzSyN
+ *     at i = isc-1..iec+1, J = jsc-2..jec+1, interfaces 2..nk; planes 1 and nk+1 of N2 and dz* are zeroed there, those of the
+ *     slopes are not touched;
+ *   use_simpler_Eady_growth_rate: SN_u and SN_v on isc-1..iec+1 x jsc-1..jec+1 (:1002-1005, :1045, :1088, :1094, :1101);
+ *   use_stored_slopes alone: SN_u, SN_v zeroed at every point of the array (:798-799), then set at I = isc-1..iec, j = jsc..jec |
+ *     i = isc..iec, J = jsc-1..jec, as are S2_u, S2_v;
+ *   neither: SN_u, SN_v at I = isc-1..iec, j = jsc..jec | i = isc..iec, J = jsc-1..jec.
+ * With calculate_Eady_growth_rate = 0 nothing is written.                                                                       */
+int mom6x_calc_slope_functions(mom6x_ctx *ctx, const double *h, const double *T, const double *S, const double *p_surf, double dt,
+                               double *SN_u, double *SN_v, double *slope_x, double *slope_y, double *N2_u, double *N2_v,
+                               double *dzu, double *dzv, double *dzSxN, double *dzSyN, double *S2_u, double *S2_v);
 
 /* ------------------------------------------------------------------------- */
 /* MOM_dynamics_split_RK2                                                    */

@@ -286,6 +286,41 @@ def tracer_hor_diff_params_default(KHTR=0.0, **kw):
     return p
 
 
+class VarMixParams(C.Structure):
+    """mom6x_varmix_params; the VarMix_CS members of calc_slope_functions (MOM_lateral_mixing_coeffs.F90:38-215)."""
+    _fields_ = [("calculate_Eady_growth_rate", C.c_int), ("use_stored_slopes", C.c_int), ("use_simpler_Eady_growth_rate", C.c_int),
+                ("full_depth_Eady_growth_rate", C.c_int), ("kappa_smooth", C.c_double), ("Visbeck_S_max", C.c_double),
+                ("Visbeck_L_scale", C.c_double), ("Eady_GR_D_scale", C.c_double), ("cropping_distance", C.c_double),
+                ("VarMix_Ktop", C.c_int), ("h_min_N2", C.c_double), ("max_depth", C.c_double), ("H_to_Z", C.c_double),
+                ("Z_to_L", C.c_double), ("L_to_m", C.c_double), ("H_to_RZ", C.c_double), ("Z_to_H_fill", C.c_double),
+                ("Angstrom_Z", C.c_double), ("g_Earth", C.c_double), ("Rho0", C.c_double), ("use_stanley_iso", C.c_int),
+                ("open_bcs", C.c_int), ("non_Boussinesq", C.c_int), ("debug", C.c_int)]
+
+
+VARMIX_MUST_BE_0 = ("use_stanley_iso", "open_bcs", "non_Boussinesq", "debug")
+
+
+def varmix_params_default(GV=None, max_depth=4000.0, **kw):
+    """VarMix_init :1589-1758 defaults (Boussinesq, unscaled units) with the Eady growth rate wanted (KHTR_SLOPE_CFF or
+    KHTH_SLOPE_CFF > 0, or MEKE, :1604): USE_STORED_SLOPES and USE_SIMPLER_EADY_GROWTH_RATE off, KD_SMOOTH = 1e-6,
+    VISBECK_MAX_SLOPE = 0, VISBECK_L_SCALE = 0, EADY_GROWTH_RATE_D_SCALE = 0, EADY_GROWTH_RATE_CROPPING_DISTANCE = 0,
+    VARMIX_KTOP = 2, MIN_DZ_FOR_SLOPE_N2 = 1 m, FULL_DEPTH_EADY_GROWTH_RATE off; the unit factors from GV; MAXIMUM_DEPTH has no
+    default in MOM6."""
+    GV = GV if GV is not None else vgrid_default()
+    p = VarMixParams()
+    p.calculate_Eady_growth_rate = 1; p.use_stored_slopes = 0; p.use_simpler_Eady_growth_rate = 0
+    p.full_depth_Eady_growth_rate = 0
+    p.kappa_smooth = 1.0e-6; p.Visbeck_S_max = 0.0; p.Visbeck_L_scale = 0.0; p.Eady_GR_D_scale = 0.0; p.cropping_distance = 0.0
+    p.VarMix_Ktop = 2; p.h_min_N2 = 1.0 * GV.Z_to_H; p.max_depth = max_depth
+    p.H_to_Z = GV.H_to_Z; p.Z_to_L = 1.0; p.L_to_m = 1.0; p.H_to_RZ = GV.H_to_RZ; p.Z_to_H_fill = 1.0
+    p.Angstrom_Z = GV.Angstrom_H * GV.H_to_Z; p.g_Earth = GV.g_Earth; p.Rho0 = GV.Rho0
+    for n in VARMIX_MUST_BE_0:
+        setattr(p, n, 0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 class HorViscParams(C.Structure):
     """mom6x_hor_visc_params; hor_visc_CS (MOM_hor_visc.F90:36-259)."""
     _fields_ = [("Laplacian", C.c_int), ("biharmonic", C.c_int), ("Kh", C.c_double), ("Kh_bg_min", C.c_double),

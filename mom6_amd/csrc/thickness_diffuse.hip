@@ -13,6 +13,7 @@
 // to uhtr | vhtr.  k_td_update: h.  MAX and MIN are the reference compiler's: the first argument on a tie (zeros of either sign).
 #include "mom6x_dev.h"
 #include "eos_dev.h"
+#include "vert_fill_dev.h"
 
 namespace {
 
@@ -52,43 +53,7 @@ k_td_cols(Dm d, const double *__restrict__ G, TdK K, const double *__restrict__ 
   }
   if (!Tf) return;
   // vert_fill_TS :668-697, kap_dt_x2 > 0
-  double hk = h[x], hn = h[slab + x];
-  double ent = K.kap_dt_x2 / ((hk + hn) + K.h0);
-  double h_tr = hk + K.h_neglect;
-  double b1 = 1.0 / (h_tr + ent);
-  double d1 = b1 * h_tr;
-  double Tp = (b1 * h_tr) * T[x], Sp = (b1 * h_tr) * S[x];
-  Tf[x] = Tp; Sf[x] = Sp;
-  for (int k = 1; k < nz - 1; ++k) {
-    const size_t o = (size_t)k * slab + x;
-    hk = hn; hn = h[o + slab];
-    const double entn = K.kap_dt_x2 / ((hk + hn) + K.h0);
-    h_tr = hk + K.h_neglect;
-    c1[o] = ent * b1;
-    const double t = h_tr + d1 * ent;
-    b1 = 1.0 / (t + entn);
-    d1 = b1 * t;
-    Tp = b1 * (h_tr * T[o] + ent * Tp);
-    Sp = b1 * (h_tr * S[o] + ent * Sp);
-    Tf[o] = Tp; Sf[o] = Sp;
-    ent = entn;
-  }
-  {
-    const size_t o = (size_t)(nz - 1) * slab + x;
-    c1[o] = ent * b1;
-    h_tr = hn + K.h_neglect;
-    b1 = 1.0 / (h_tr + d1 * ent);
-    Tp = b1 * (h_tr * T[o] + ent * Tp);
-    Sp = b1 * (h_tr * S[o] + ent * Sp);
-    Tf[o] = Tp; Sf[o] = Sp;
-  }
-  for (int k = nz - 2; k >= 0; --k) {
-    const size_t o = (size_t)k * slab + x;
-    const double c = c1[o + slab];
-    Tp = Tf[o] + c * Tp;
-    Sp = Sf[o] + c * Sp;
-    Tf[o] = Tp; Sf[o] = Sp;
-  }
+  vert_fill_TS_col(h, T, S, Tf, Sf, c1, x, slab, nz, K.kap_dt_x2, K.h0, K.h_neglect);
 }
 
 // MODE 0: layers of constant density (:1085-1094); 1: an EOS of form FORM, slopes from the filled T, S; 2: an EOS with stored

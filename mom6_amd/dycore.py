@@ -331,6 +331,27 @@ class Dycore:
         check(self.lib, self.lib.mom6x_tracer_hordiff_tile(C.byref(tx), C.byref(ty), C.byref(mt)))
         return tx.value, ty.value, mt.value
 
+    # -- MOM_lateral_mixing_coeffs -------------------------------------------------------------
+    def varmix_init(self, params, eos=None, Rlay=None, g_prime=None, L2u=None, L2v=None):
+        """VarMix_init (MOM_lateral_mixing_coeffs.F90:1445) for calc_slope_functions; eos: tv%eqn_of_state (None: layers of constant
+        density); Rlay, g_prime: GV%Rlay, GV%g_prime (host arrays of nk values); L2u, L2v: device planes that receive CS%L2u, CS%L2v."""
+        self.varmix_params = params
+        hp = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        Rlay, g_prime = hp(Rlay), hp(g_prime)
+        assert all(a is None or a.size == self.dims.nk for a in (Rlay, g_prime))
+        cp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(self.lib, self.lib.mom6x_varmix_init(self.ctx, C.byref(params), C.byref(eos) if eos is not None else None, cp(Rlay),
+                                                   cp(g_prime), _ptr(L2u), _ptr(L2v)))
+
+    def calc_slope_functions(self, h, dt, SN_u, SN_v, T=None, S=None, p_surf=None, slope_x=None, slope_y=None, N2_u=None, N2_v=None,
+                             dzu=None, dzv=None, dzSxN=None, dzSyN=None, S2_u=None, S2_v=None):
+        """calc_slope_functions (MOM_lateral_mixing_coeffs.F90:686): fills CS%SN_u, CS%SN_v and, with stored slopes, CS%slope_x,
+        CS%slope_y; the remaining arguments are the diagnostics the reference posts."""
+        check(self.lib, self.lib.mom6x_calc_slope_functions(self.ctx, _ptr(h), _ptr(T), _ptr(S), _ptr(p_surf), C.c_double(dt),
+                                                            _ptr(SN_u), _ptr(SN_v), _ptr(slope_x), _ptr(slope_y), _ptr(N2_u),
+                                                            _ptr(N2_v), _ptr(dzu), _ptr(dzv), _ptr(dzSxN), _ptr(dzSyN), _ptr(S2_u),
+                                                            _ptr(S2_v)))
+
     def vertvisc_field(self, name):
         """CS%a_u / a_v / h_u / h_v of the device vertvisc_CS as a torch view."""
         which = ["a_u", "a_v", "h_u", "h_v"].index(name)

@@ -1,0 +1,275 @@
+"""mom6x_calc_slope_functions on the device (mom6_amd/csrc/lateral_mixing_coeffs.hip) against the restatement tests/varmix_ref.py,
+bit for bit and on whole arrays (every output starts as NaN, so the points the reference leaves alone are checked too): every case
+of the list and EOS form on coasts, narrowed faces and vanished layers; layer counts around the edges of the column pass; L2u, L2v
+of the init call; refused settings and error paths; 2 x 1 and 1 x 2 tile cuts; and the chain into mom6x_thickness_diffuse and
+mom6x_tracer_hordiff with device pointers handed on."""
+import functools
+
+import numpy as np
+import pytest
+
+from mom6_amd import abi
+from tests import helpers as H
+from tests import varmix_ref as R
+from tests.test_thickness_diffuse_gpu import _bits
+from tests.test_varmix_cpu import GRIDS, REQUIRED, STAG, TILES, cut2
+
+pytestmark = pytest.mark.gpu
+G = abi.G
+
+
+def _device(d, M, GV, P, inp, dt, eos=None, give_ps=False, give_diag=False, fill=np.nan):
+    """One mom6x_varmix_init and one mom6x_calc_slope_functions call on inputs that live on the host; every output starts as
+    `fill`."""
+    import torch
+    from mom6_amd.dycore import Dycore
+    dy = Dycore(d, M, GV)
+    try:
+        t = {n: dy.to_dev(a) for n, a in inp.items()}
+        out = {n: dy.to_dev(a) for n, a in R.outputs(d, P, give_diag, fill).items()}
+        Rlay, gp = abi.layer_densities(d.nk, Rho0=GV.Rho0, g_Earth=GV.g_Earth)
+        dy.varmix_init(P, eos, Rlay, gp)
+        torch.cuda.synchronize()
+        dy.calc_slope_functions(t["h"], dt, T=t["T"], S=t["S"], p_surf=t["p_surf"] if give_ps else None, **out)
+        dy.sync()
+        for n in ("h", "T", "S", "p_surf"):
+            _bits(t[n].cpu().numpy(), inp[n], n + " is only read")
+        return {n: a.cpu().numpy() for n, a in out.items()}
+    finally:
+        dy.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _want(grid, nk, name, form, Ktop=None):
+    """The restatement's result of a case on a grid, computed once and shared by the tests below (read only)."""
+    from oracle import orc
+    orc.build()
+    d, M = GRIDS[grid](nk)
+    GV = abi.vgrid_default()
+    P, eos, ps, dg, dt, opts = R.case(name, GV, form=form, nk=nk)
+    if Ktop is not None:
+        P.VarMix_Ktop = Ktop
+    inp = R.inputs(d, M, GV, **opts)
+    want, counts = R.run(d, M, GV, P, inp, dt, eos=eos, give_ps=ps, give_diag=dg, orc=orc)
+    return d, M, GV, P, eos, ps, dg, dt, inp, want, counts
+
+
+def _both(grid, nk, name, form, tot=None, Ktop=None):
+    d, M, GV, P, eos, ps, dg, dt, inp, want, counts = _want(grid, nk, name, form, Ktop)
+    got = _device(d, M, GV, P, inp, dt, eos=eos, give_ps=ps, give_diag=dg)
+    assert set(got) == set(want)
+    for n in want:
+        _bits(got[n], want[n], f"{grid}/{nk}/{name}/{form}:{n}")
+    if tot is not None:
+        for k, v in counts.items():
+            tot[k] += v
+    return d, P, got
+
+
+GROUPS = {"eady": ("eady", "eady_diag", "eady_nocrop", "eady_noeos"),
+          "visbeck": ("visbeck", "visbeck_diag", "visbeck_neg", "visbeck_noeos"),
+          "just_e": ("just_e", "just_e_full")}
+GROUP_REQUIRED = {"eady": ("mag_grad2_zero", "Dscale_full", "Dscale_partial", "Dscale_zero", "crop_top_0", "crop_top_mid", "crop_top_1",
+                           "crop_bot_0", "crop_bot_mid", "crop_bot_1"),
+                  "visbeck": ("mag_grad2_zero", "N2_clipped", "S2max_applied", "S2max_idle"),
+                  "just_e": ("H_cutoff_mask", "bathy_cutoff", "denom_bathy", "denom_dztot")}
+assert set(sum(GROUPS.values(), ())) == set(R.CASES) and set(sum(GROUP_REQUIRED.values(), ())) == set(REQUIRED)
+
+
+@pytest.mark.parametrize("group", list(GROUPS))
+@pytest.mark.parametrize("grid", list(GRIDS))
+def test_parity_with_the_restatement(grid, group):
+    """Every case of the branch (each of the eight EOS forms where the list says so; with and without p_surf; every diagnostic
+    pointer given and none) at 8 and 75 layers, whole arrays bit for bit: slope_x, slope_y, N2 and dz* keep the NaN they started
+    with outside the ranges of calc_isoneutral_slopes(halo=1) and in planes 1 and nk+1 of the slopes, SN_u and SN_v outside the
+    ranges of their branch.  The branches of the CPU test are counted again over what ran here."""
+    tot = dict.fromkeys(R.BRANCHES, 0)
+    for nk in (8, 75):
+        for name, form in R.case_list():
+            if name not in GROUPS[group]:
+                continue
+            d, P, got = _both(grid, nk, name, form, tot)
+            face = {s: np.zeros(d.shape2(), bool) for s in "uv"}
+            for s in "uv":
+                face[s][H.interior(d, s)] = True
+                assert np.isfinite(got["SN_" + s][face[s]]).all()
+            if group == "visbeck":
+                assert all((got["SN_" + s][~face[s]] == 0.0).all() for s in "uv")          # :798-799
+            if group == "just_e":
+                assert all(np.isnan(got["SN_" + s][~face[s]]).all() for s in "uv")
+            if "slope_x" in got:
+                for s in ("slope_x", "slope_y"):
+                    assert np.isnan(got[s][0]).all() and np.isnan(got[s][d.nk]).all()
+                    assert np.isfinite(got[s][1:d.nk][:, face[dict(x="u", y="v")[s[-1]]]]).all()
+            if "N2_u" in got:
+                box = R._A(d, got["N2_u"], (-2, d.ni, -1, d.nj))
+                assert (box[0] == 0.0).all() and (box[d.nk] == 0.0).all() and np.isfinite(box).all()
+    print(f"{grid}/{group}: branch counts {tot}")
+    for k in GROUP_REQUIRED[group]:
+        assert tot[k] > 0, (k, tot)
+
+
+@pytest.mark.parametrize("nk", [1, 2, 3, 4, 76, 77, 120])
+def test_layer_counts(nk):
+    """The kernels take the layer count at run time and keep no column on chip: one path.  The column pass has its own edges at
+    nk = 2 (vert_fill_TS without interior layers) and 3; the counts around the on-chip solvers' bound (76) and beyond are run all
+    the same.  VARMIX_KTOP = 2 and = nk.  One layer: no EOS only (vert_fill_TS reads layer 2)."""
+    names = ("eady", "visbeck", "eady_noeos", "visbeck_noeos", "just_e") if nk > 1 else ("eady_noeos", "visbeck_noeos", "just_e")
+    for name in names:
+        _both("benchmark_small", nk, name, abi.WRIGHT)
+    if nk > 2:
+        _both("benchmark_small", nk, "just_e_full", None, Ktop=nk)
+
+
+@pytest.mark.parametrize("L_scale", [3.0e4, -0.25])
+def test_L2_planes_of_the_init_call(L_scale):
+    import torch
+    from mom6_amd.dycore import Dycore
+    d, M = GRIDS["partial_faces"](8)
+    GV = abi.vgrid_default()
+    P = abi.varmix_params_default(GV, Visbeck_L_scale=L_scale, L_to_m=2.0)
+    want = R.varmix_L2(d, M, P)
+    assert (want[0] != 0.0).any() and (L_scale > 0 or (want[0] == 0.0).any())
+    dy = Dycore(d, M, GV)
+    try:
+        got = [dy.to_dev(np.full(d.shape2(), np.nan)) for _ in range(2)]
+        torch.cuda.synchronize()
+        dy.varmix_init(P, None, *abi.layer_densities(d.nk), L2u=got[0], L2v=got[1])
+        dy.sync()
+        for g, w, n in zip(got, want, ("L2u", "L2v")):
+            _bits(g.cpu().numpy(), w, n)
+    finally:
+        dy.close()
+
+
+def test_off_and_refused_settings():
+    """Each `must be 0` member raises at init with a message naming the setting, as do USE_SIMPLER_EADY_GROWTH_RATE without
+    USE_STORED_SLOPES (the reference's own fatal error) and VARMIX_KTOP < 2; a missing slope_x in the two branches that compute
+    slopes and an EOS without T, S are refused at the call; calculate_Eady_growth_rate = 0 writes nothing."""
+    import torch
+    from mom6_amd.dycore import Dycore
+    d, M = GRIDS["benchmark_small"](8)
+    GV = abi.vgrid_default()
+    inp = R.inputs(d, M, GV)
+    Rlay, gp = abi.layer_densities(d.nk)
+    eos = abi.eos_params_default()
+    dy = Dycore(d, M, GV)
+    try:
+        t = {n: dy.to_dev(a) for n, a in inp.items()}
+        words = dict(use_stanley_iso="STANLEY", open_bcs="open boundary", non_Boussinesq="Boussinesq", debug="DEBUG")
+        assert set(words) == set(abi.VARMIX_MUST_BE_0)
+        for member, word in words.items():
+            with pytest.raises(Exception, match=word):
+                dy.varmix_init(abi.varmix_params_default(GV, **{member: 1}), eos, Rlay, gp)
+        with pytest.raises(Exception, match="USE_STORED_SLOPES must also be True"):
+            dy.varmix_init(abi.varmix_params_default(GV, use_simpler_Eady_growth_rate=1), eos, Rlay, gp)
+        for ktop in (1, 0):
+            with pytest.raises(Exception, match="VARMIX_KTOP"):
+                dy.varmix_init(abi.varmix_params_default(GV, VarMix_Ktop=ktop), eos, Rlay, gp)
+        with pytest.raises(Exception, match="Rlay"):
+            dy.varmix_init(abi.varmix_params_default(GV), None)
+        full = lambda P: {n: dy.to_dev(a) for n, a in R.outputs(d, P, True).items()}   # noqa: E731
+        for mods in (R.EADY, R.VISB):
+            P = abi.varmix_params_default(GV, **mods)
+            dy.varmix_init(P, eos, Rlay, gp)
+            out = full(P)
+            torch.cuda.synchronize()
+            with pytest.raises(Exception, match="slope_x"):
+                dy.calc_slope_functions(t["h"], 900.0, out["SN_u"], out["SN_v"], T=t["T"], S=t["S"], slope_y=out["slope_y"])
+            with pytest.raises(Exception, match="tv%T"):
+                dy.calc_slope_functions(t["h"], 900.0, out["SN_u"], out["SN_v"], slope_x=out["slope_x"], slope_y=out["slope_y"])
+        P = abi.varmix_params_default(GV, calculate_Eady_growth_rate=0, **R.VISB)
+        dy.varmix_init(P, eos, Rlay, gp)
+        out = full(P)
+        torch.cuda.synchronize()
+        dy.calc_slope_functions(t["h"], 900.0, T=t["T"], S=t["S"], p_surf=t["p_surf"], **out)
+        dy.sync()
+        assert all(bool(torch.isnan(a).all()) for a in out.values())
+    finally:
+        dy.close()
+
+
+@pytest.mark.parametrize("layout,pe", TILES)
+@pytest.mark.parametrize("name", ["eady_diag", "visbeck_diag", "just_e"])
+def test_tile_cuts(name, layout, pe):
+    """Each tile of a 2 x 1 and of a 1 x 2 layout, called on its cut of the inputs with the halos of h, T, S filled (two points are
+    read): whole arrays bit for bit against the restatement on the same tile -- the y cut puts open water on the rows jsc-1 and
+    jec+1, the x cut on the columns isc-1 and iec+1, which on the closed grids are land -- and its own faces, the west and south
+    edge faces (I = isc-1, J = jsc-1) included, equal to the one-tile result of the device."""
+    from oracle import orc
+    orc.build()
+    GV = abi.vgrid_default()
+    d, M, _, P, eos, ps, dg, dt, inp, _, _ = _want("benchmark_small", 8, name, abi.WRIGHT)
+    one = _one_tile_device(name)
+    dt_, Mt = H.benchmark_small(nk=8, layout=layout, pe=pe)[1:]
+    tin = R.inputs(dt_, Mt, GV, **R.CASES[name][5])
+    want, _ = R.run(dt_, Mt, GV, P, tin, dt, eos=eos, give_ps=ps, give_diag=dg, orc=orc)
+    tile = _device(dt_, Mt, GV, P, tin, dt, eos=eos, give_ps=ps, give_diag=dg)
+    for n in want:
+        _bits(tile[n], want[n], f"tile {layout} {pe} {name}:{n} against the restatement")
+        slt, slg = cut2(d, dt_, STAG[n])
+        _bits(tile[n][..., slt[0], slt[1]], one[n][..., slg[0], slg[1]], f"tile {layout} {pe} {name}:{n} against one tile")
+    if layout == (1, 2) and pe == (0, 1):
+        assert (tile["SN_v"][dt_.joff - 1, dt_.ioff:dt_.ioff + dt_.ni] > 0.0).sum() > 10
+
+
+@functools.lru_cache(maxsize=None)
+def _one_tile_device(name):
+    d, M, GV, P, eos, ps, dg, dt, inp, _, _ = _want("benchmark_small", 8, name, abi.WRIGHT)
+    return _device(d, M, GV, P, inp, dt, eos=eos, give_ps=ps, give_diag=dg)
+
+
+def test_chain_into_thickness_diffuse_and_tracer_hordiff(orc):
+    """benchmark_small x 8, WRIGHT, stored slopes: one mom6x_calc_slope_functions call fills slope_x, slope_y, SN_u, SN_v and the
+    init call L2u, L2v; the same device arrays go straight into mom6x_thickness_diffuse (stored slopes) and into
+    mom6x_tracer_hordiff (KHTR_SLOPE_CFF > 0), nothing passing through the host in between.  Compared with tests/thickdiff_ref.py
+    and tests/hordiff_ref.py fed the restatement's slopes and planes, bit for bit."""
+    import torch
+    from mom6_amd.dycore import Dycore
+    from tests import hordiff_ref, thickdiff_ref
+    d, M = GRIDS["benchmark_small"](8)
+    GV = abi.vgrid_default()
+    eos = abi.eos_params_default(abi.WRIGHT)
+    inp = thickdiff_ref.inputs(d, M, GV)
+    dt = 3600.0
+    Pv = abi.varmix_params_default(GV, Visbeck_L_scale=3.0e4, **R.VISB)
+    Ptd = abi.thickness_diffuse_params_default()
+    Pth = abi.tracer_hor_diff_params_default(KHTR=500.0, use_variable_mixing=1, KhTr_Slope_Cff=1.0)
+    Rlay, gp = abi.layer_densities(d.nk)
+    # the restatements
+    z2, z3 = (lambda: np.zeros(d.shape2())), (lambda: np.zeros(d.shape3(d.nk + 1)))
+    w = dict(SN_u=z2(), SN_v=z2(), slope_x=z3(), slope_y=z3())
+    R.calc_slope_functions(d, M, GV, Pv, inp["h"], dt, w["SN_u"], w["SN_v"], T=inp["T"], S=inp["S"], eos=eos, Rlay=Rlay, g_prime=gp,
+                           slope_x=w["slope_x"], slope_y=w["slope_y"], orc=orc)
+    w["L2u"], w["L2v"] = R.varmix_L2(d, M, Pv)
+    assert w["SN_u"].max() > 0 and np.abs(w["slope_x"]).max() > 0
+    wtd = dict(h=inp["h"].copy(), uhtr=inp["uhtr"].copy(), vhtr=inp["vhtr"].copy())
+    thickdiff_ref.thickness_diffuse(d, M, GV, Ptd, wtd["h"], wtd["uhtr"], wtd["vhtr"], dt, T=inp["T"], S=inp["S"], eos=eos,
+                                    slope_x=w["slope_x"], slope_y=w["slope_y"], orc=orc)
+    wtr = [inp["T"].copy(), inp["S"].copy()]
+    planes = {n: w[n] for n in ("L2u", "SN_u", "L2v", "SN_v")}
+    nw = hordiff_ref.tracer_hordiff(d, M, GV, Pth, wtd["h"], dt, wtr, planes=planes)
+    assert not np.array_equal(wtd["h"], inp["h"]) and not np.array_equal(wtr[0], inp["T"])
+    # the device, one context, pointers handed on
+    dy = Dycore(d, M, GV)
+    try:
+        t = {n: dy.to_dev(a) for n, a in inp.items()}
+        g = dict(SN_u=dy.zeros2(), SN_v=dy.zeros2(), slope_x=dy.zeros3(d.nk + 1), slope_y=dy.zeros3(d.nk + 1), L2u=dy.zeros2(),
+                 L2v=dy.zeros2())
+        dy.varmix_init(Pv, eos, Rlay, gp, L2u=g["L2u"], L2v=g["L2v"])
+        dy.thickness_diffuse_init(Ptd, eos)
+        dy.tracer_hor_diff_init(Pth)
+        torch.cuda.synchronize()
+        dy.calc_slope_functions(t["h"], dt, g["SN_u"], g["SN_v"], T=t["T"], S=t["S"], slope_x=g["slope_x"], slope_y=g["slope_y"])
+        dy.thickness_diffuse(t["h"], t["uhtr"], t["vhtr"], dt, T=t["T"], S=t["S"], slope_x=g["slope_x"], slope_y=g["slope_y"])
+        ng = dy.tracer_hordiff(t["h"], dt, [t["T"], t["S"]], L2u=g["L2u"], SN_u=g["SN_u"], L2v=g["L2v"], SN_v=g["SN_v"])
+        dy.sync()
+        for n in w:
+            _bits(g[n].cpu().numpy(), w[n], "chain: " + n)
+        for n in wtd:
+            _bits(t[n].cpu().numpy(), wtd[n], "chain: thickness_diffuse " + n)
+        assert ng == nw
+        for n, a in zip("TS", wtr):
+            _bits(t[n].cpu().numpy(), a, "chain: tracer_hordiff " + n)
+    finally:
+        dy.close()
