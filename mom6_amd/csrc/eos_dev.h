@@ -613,4 +613,21 @@ __device__ __forceinline__ void eos_density_derivs(const EOS &E, double T, doubl
     }
   }
 }
+
+// The kernels templated on the EOS form (set_visc.hip, thickness_diffuse.hip, lateral_mixing_coeffs.hip): CALL(F) with F the
+// literal 1..8 of `form`, so that CALL can put #F into the label it gives KLAUNCH.  An init call holds `form` to eos_form_known.
+inline bool eos_form_known(const mom6x_eos_params *e) { return e->form >= MOM6X_EOS_LINEAR && e->form <= MOM6X_EOS_ROQUET_SPV; }
+#define EOS_FORM_DISPATCH(form, CALL)                   \
+  do {                                                  \
+    switch (form) {                                     \
+      case MOM6X_EOS_LINEAR: CALL(1); break;            \
+      case MOM6X_EOS_WRIGHT: CALL(2); break;            \
+      case MOM6X_EOS_WRIGHT_FULL: CALL(3); break;       \
+      case MOM6X_EOS_WRIGHT_REDUCED: CALL(4); break;    \
+      case MOM6X_EOS_UNESCO: CALL(5); break;            \
+      case MOM6X_EOS_ROQUET_RHO: CALL(6); break;        \
+      case MOM6X_EOS_JACKETT06: CALL(7); break;         \
+      default: CALL(8); break;                          \
+    }                                                   \
+  } while (0)
 }  // namespace

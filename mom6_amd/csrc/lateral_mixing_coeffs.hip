@@ -13,10 +13,12 @@
 // carries vint_SN and sum_dz of calc_Eady_growth_rate_2D along (the reference's summation order), so dzu, dzSxN and N2 only go to
 // memory when a diagnostic asks for them.  k_vm_eady_combine: the four-neighbour combination from the un-combined planes.
 // k_vm_visbeck: the sums of calc_Visbeck_coeffs_old, h4_u | h4_v formed from h as the walk goes.  k_vm_just_e: the third branch in
-// one launch, the neighbours' E_x | E_y recomputed from e.  MAX and MIN are the reference compiler's: the first argument on a tie.
+// one launch, the neighbours' E_x | E_y recomputed from e.  MAX and MIN are fmax1 and fmin1 of mom6x_dev.h, the reference
+// compiler's.  The density gradients (isoneutral_grads) and the vert_fill_TS solve come from isopycnal_slopes_dev.h, which
+// thickness_diffuse.hip shares; the lane of a face from face_lane (mom6x_dev.h), the EOS form's kernel from EOS_FORM_DISPATCH.
 #include "mom6x_dev.h"
 #include "eos_dev.h"
-#include "vert_fill_dev.h"
+#include "isopycnal_slopes_dev.h"
 
 namespace {
 
@@ -35,9 +37,6 @@ struct VmState {
   double *Rlay, *g_prime;   // device copies (nk)
   double *work;             // [e (nk+1) | pres, T_f, S_f, c1 (nk each, with an EOS) | N2_u, N2_v (nk+1 each, Visbeck) | SN raw u, v (2 planes, Eady)]
 };
-
-__device__ __forceinline__ double fmax1(double a, double b) { return (b > a) ? b : a; }   // MAX(a, b)
-__device__ __forceinline__ double fmin1(double a, double b) { return (b < a) ? b : a; }   // MIN(a, b)
 
 // find_eta(halo_size=2) :91-97, pres (MOM_isopycnal_slopes.F90:231-247) and vert_fill_TS(halo+1) on cells isc-2..iec+2,
 // jsc-2..jec+2.  e[K], pres[K]: at the interface ABOVE layer K (e has nk+1 planes).  Lanes start at i = -IAL.
@@ -69,7 +68,7 @@ k_vm_cols(Dm d, const double *__restrict__ G, VmK K, const double *__restrict__ 
 }
 
 // calc_isoneutral_slopes(halo=1) and, with BR == 1, the vertical sums of calc_Eady_growth_rate_2D.  FORM 0: no EOS (GV%Rlay).
-// blockIdx.z: 0 u faces (I = -2..ni, j = -1..nj), 1 v faces (i = -1..ni, J = -2..nj).
+// The faces of face_lane<1>: one wider than the other face kernels'.
 template <int FORM, int BR>
 __global__ void __launch_bounds__(256)
 k_vm_faces(Dm d, const double *__restrict__ G, VmK K, const double *__restrict__ h, const double *__restrict__ e,
@@ -77,12 +76,10 @@ k_vm_faces(Dm d, const double *__restrict__ G, VmK K, const double *__restrict__
            const double *__restrict__ Rlay, double *__restrict__ slope_x, double *__restrict__ slope_y, VmDiag D,
            double *__restrict__ raw_u, double *__restrict__ raw_v) {
   constexpr bool EOS = FORM != 0;
-  const int dir = blockIdx.z;
-  const int i = -IAL + blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = -2 + blockIdx.y * blockDim.y + threadIdx.y;
-  if (i > d.ni || j > d.nj) return;
-  if (dir == 0 ? (i < -2 || j < -1) : (i < -1)) return;
-  const size_t x = ix2(d, i, j), st = dir ? (size_t)d.pitch : 1, y = x + st, slab = (size_t)d.slab;
+  const FaceLane f = face_lane<1>(d);
+  if (!f.in) return;
+  const int dir = f.dir;
+  const size_t x = f.x, y = f.y, slab = (size_t)d.slab;
   const int nz = d.nk;
   double *slope = dir ? slope_y : slope_x;
   double *N2 = D.N2[dir], *dzo = D.dz[dir], *dzs = D.dzSN[dir];
@@ -102,38 +99,21 @@ k_vm_faces(Dm d, const double *__restrict__ G, VmK K, const double *__restrict__
   for (int k = 1; k < nz; ++k, o += slab) {       // K = 2..nz; layers k-1 (A, m) and k (B, k)
     const double hLk = h[o + x], hRk = h[o + y];
     const double eL = e[o + x], eR = e[o + y];
-    double drdiA = 0.0, drdiB = 0.0, drdkL, drdkR;
-    double TLk = 0.0, TRk = 0.0, SLk = 0.0, SRk = 0.0;
+    // g.drdkL, g.drdkR go IN without an EOS (FORM 0, from GV%Rlay) and come OUT with one; T, S and pres_u are then not read
+    double TLk = 0.0, TRk = 0.0, SLk = 0.0, SRk = 0.0, pres_u = 0.0;
+    IsoGrad g;
     if constexpr (EOS) {
       TLk = Tf[o + x]; TRk = Tf[o + y]; SLk = Sf[o + x]; SRk = Sf[o + y];
-      const double pres_u = 0.5 * (pres[o + x] + pres[o + y]);
-      const double T_u = 0.25 * ((TLk + TRk) + (TLm + TRm));
-      const double S_u = 0.25 * ((SLk + SRk) + (SLm + SRm));
-      double dR_dT, dR_dS;
-      eos_density_derivs<FORM>(K, T_u, S_u, pres_u, dR_dT, dR_dS);
-      drdiA = dR_dT * (TRm - TLm) + dR_dS * (SRm - SLm);
-      drdiB = dR_dT * (TRk - TLk) + dR_dS * (SRk - SLk);
-      drdkL = (dR_dT * (TLk - TLm) + dR_dS * (SLk - SLm));
-      drdkR = (dR_dT * (TRk - TRm) + dR_dS * (SRk - SRm));
+      pres_u = 0.5 * (pres[o + x] + pres[o + y]);
     } else {
-      drdkL = Rlay[k] - Rlay[k - 1]; drdkR = drdkL;
+      g.drdkL = Rlay[k] - Rlay[k - 1]; g.drdkR = g.drdkL;
     }
-    const double hg2A = hLm * hRm + K.h_neglect2, hg2B = hLk * hRk + K.h_neglect2;
-    const double hg2L = hLm * hLk + K.h_neglect2, hg2R = hRm * hRk + K.h_neglect2;
-    const double haA = 0.5 * (hLm + hRm) + K.h_neglect, haB = 0.5 * (hLk + hRk) + K.h_neglect;
-    const double haL = 0.5 * (hLm + hLk) + K.h_neglect, haR = 0.5 * (hRm + hRk) + K.h_neglect;
-    const double dzaL = haL * K.H_to_Z, dzaR = haR * K.H_to_Z;
-    const double dzu = 0.5 * (dzaL + dzaR);
-    const double wtA = hg2A * haB, wtB = hg2B * haA;
-    const double wtL = hg2L * (haR * dzaR), wtR = hg2R * (haL * dzaL);
-    const double drdz = ((wtL * drdkL) + (wtR * drdkR)) / ((dzaL * wtL) + (dzaR * wtR));
-    if (N2) N2[o + x] = K.G_Rho0 * drdz * mask;
+    isoneutral_grads<FORM>(K, hLm, hRm, hLk, hRk, TLm, TRm, TLk, TRk, SLm, SRm, SLk, SRk, pres_u, eL, eR, Igrad, g);
+    const double dzu = 0.5 * (g.dzaL + g.dzaR);
+    if (N2) N2[o + x] = K.G_Rho0 * g.drdz * mask;
     double sl;
     if constexpr (EOS) {
-      const double drdx = ((wtA * drdiA + wtB * drdiB) / (wtA + wtB) - drdz * (eL - eR)) * Igrad;
-      const double zx = K.Z_to_L * drdx;
-      const double mag_grad2 = zx * zx + drdz * drdz;
-      sl = (mag_grad2 > 0.0) ? drdx / sqrt(mag_grad2) : 0.0;
+      sl = (g.mag_grad2 > 0.0) ? g.drdx / sqrt(g.mag_grad2) : 0.0;
     } else {
       sl = (eR - eL) * Igrad;
     }
@@ -142,7 +122,7 @@ k_vm_faces(Dm d, const double *__restrict__ G, VmK K, const double *__restrict__
     bool want_dzSN = dzs != nullptr;
     if constexpr (BR == 1) want_dzSN = true;
     if (want_dzSN) {
-      const double dzSN = sqrt(K.G_Rho0 * fmax1(0.0, (wtL * (dzaL * drdkL)) + (wtR * (dzaR * drdkR))) / (wtL + wtR)) * fabs(sl) * mask;
+      const double dzSN = sqrt(K.G_Rho0 * fmax1(0.0, (g.wtL * (g.dzaL * g.drdkL)) + (g.wtR * (g.dzaR * g.drdkR))) / (g.wtL + g.wtR)) * fabs(sl) * mask;
       if (dzs) dzs[o + x] = dzSN;
       if constexpr (BR == 1) {                    // :1014-1041 | :1057-1085
         double dnew = sum_dz + dzu;
@@ -164,7 +144,7 @@ k_vm_faces(Dm d, const double *__restrict__ G, VmK K, const double *__restrict__
   }
   if constexpr (BR == 1) {
     // :1045-1046 at I = -1..ni-1, j = -1..nj | :1088 at i = -1..ni, J = -1..nj-1
-    const bool in = dir ? (j >= -1 && j <= d.nj - 1) : (i >= -1 && i <= d.ni - 1);
+    const bool in = dir ? (f.j >= -1 && f.j <= d.nj - 1) : (f.i >= -1 && f.i <= d.ni - 1);
     if (in) (dir ? raw_v : raw_u)[x] = mask * (vint_SN / sum_dz);
   }
 }
@@ -200,17 +180,15 @@ k_vm_eady_combine(Dm d, const double *__restrict__ ru, const double *__restrict_
 // u: NW, SE, NE, SW (:879-880); v: SE, NW, NE, SW (:922-923).  Each has its two cells at f and f + ot.
 #define VM_NBR_FACES const size_t f1 = x, f2 = x + st - ot, f3 = x + st, f4 = x - ot
 
-// calc_Visbeck_coeffs_old :856-940.  blockIdx.z: 0 u faces (I = -1..ni-1, j = 0..nj-1), 1 v faces (i = 0..ni-1, J = -1..nj-1).
+// calc_Visbeck_coeffs_old :856-940 on the faces of face_lane<0>.
 __global__ void __launch_bounds__(256)
 k_vm_visbeck(Dm d, const double *__restrict__ G, VmK K, const double *__restrict__ h, const double *__restrict__ slope_x,
              const double *__restrict__ slope_y, const double *__restrict__ N2_u, const double *__restrict__ N2_v,
              double *__restrict__ SN_u, double *__restrict__ SN_v, double *__restrict__ S2_u, double *__restrict__ S2_v) {
-  const int dir = blockIdx.z;
-  const int i = -IAL + blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = -1 + blockIdx.y * blockDim.y + threadIdx.y;
-  if (i > d.ni - 1 || j > d.nj - 1) return;
-  if (dir == 0 ? (i < -1 || j < 0) : (i < 0)) return;
-  const size_t p = (size_t)d.pitch, st = dir ? p : 1, ot = dir ? 1 : p, x = ix2(d, i, j), y = x + st, slab = (size_t)d.slab;
+  const FaceLane f = face_lane<0>(d);
+  if (!f.in) return;
+  const int dir = f.dir;
+  const size_t st = f.st, ot = f.ot, x = f.x, y = f.y, slab = (size_t)d.slab;
   const int nz = d.nk;
   VM_NBR_FACES;
   const double *so = dir ? slope_y : slope_x, *sn = dir ? slope_x : slope_y, *N2 = dir ? N2_v : N2_u;
@@ -253,12 +231,10 @@ k_vm_visbeck(Dm d, const double *__restrict__ G, VmK K, const double *__restrict
 __global__ void __launch_bounds__(256)
 k_vm_just_e(Dm d, const double *__restrict__ G, VmK K, const double *__restrict__ h, const double *__restrict__ e,
             const double *__restrict__ g_prime, double *__restrict__ SN_u, double *__restrict__ SN_v) {
-  const int dir = blockIdx.z;
-  const int i = -IAL + blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = -1 + blockIdx.y * blockDim.y + threadIdx.y;
-  if (i > d.ni - 1 || j > d.nj - 1) return;
-  if (dir == 0 ? (i < -1 || j < 0) : (i < 0)) return;
-  const size_t p = (size_t)d.pitch, st = dir ? p : 1, ot = dir ? 1 : p, x = ix2(d, i, j), y = x + st, slab = (size_t)d.slab;
+  const FaceLane f = face_lane<0>(d);
+  if (!f.in) return;
+  const int dir = f.dir;
+  const size_t st = f.st, ot = f.ot, x = f.x, y = f.y, slab = (size_t)d.slab;
   const int nz = d.nk;
   VM_NBR_FACES;
   const double Io = gm(G, d, dir ? MOM6X_G_IdyCv : MOM6X_G_IdxCu)[x];
@@ -329,17 +305,14 @@ void varmix_free(mom6x_ctx *c) {
 extern "C" int mom6x_varmix_init(mom6x_ctx *c, const mom6x_varmix_params *p, const mom6x_eos_params *eos, const double *Rlay,
                                  const double *g_prime, double *L2u, double *L2v) {
   REQUIRE(c && p, MOM6X_EINVAL, "mom6x_varmix_init: null argument");
-#define VM_REFUSE(cond, what) REQUIRE(!(cond), MOM6X_EUNSUPPORTED, "VarMix_init: " what " is not on the device")
-  VM_REFUSE(p->use_stanley_iso, "USE_STANLEY_ISO");
-  VM_REFUSE(p->open_bcs, "open boundary conditions (OBC)");
-  VM_REFUSE(p->non_Boussinesq || !c->GV.Boussinesq, "non-Boussinesq mode (tv%SpV_avg, semi_Boussinesq)");
-  VM_REFUSE(p->debug, "DEBUG (the checksums of calc_slope_functions)");
-#undef VM_REFUSE
+  REFUSE(p->use_stanley_iso, "VarMix_init", "USE_STANLEY_ISO");
+  REFUSE(p->open_bcs, "VarMix_init", "open boundary conditions (OBC)");
+  REFUSE(p->non_Boussinesq || !c->GV.Boussinesq, "VarMix_init", "non-Boussinesq mode (tv%SpV_avg, semi_Boussinesq)");
+  REFUSE(p->debug, "VarMix_init", "DEBUG (the checksums of calc_slope_functions)");
   REQUIRE(!p->use_simpler_Eady_growth_rate || p->use_stored_slopes, MOM6X_EINVAL,
           "MOM_lateral_mixing_coeffs.F90, VarMix_init:When USE_SIMPLER_EADY_GROWTH_RATE=True, USE_STORED_SLOPES must also be True.");
   REQUIRE(p->VarMix_Ktop >= 2, MOM6X_EINVAL, "VarMix_init: VARMIX_KTOP must be at least 2");
-  REQUIRE(!eos || (eos->form >= MOM6X_EOS_LINEAR && eos->form <= MOM6X_EOS_ROQUET_SPV), MOM6X_EINVAL,
-          "VarMix_init: unknown EQN_OF_STATE form");
+  REQUIRE(!eos || eos_form_known(eos), MOM6X_EINVAL, "VarMix_init: unknown EQN_OF_STATE form");
   const bool slopes = p->calculate_Eady_growth_rate && p->use_stored_slopes;
   REQUIRE(!p->calculate_Eady_growth_rate || c->d.halo >= 2, MOM6X_EINVAL, "VarMix_init: calc_slope_functions needs a halo of two");
   REQUIRE(!p->calculate_Eady_growth_rate || (slopes && eos) || (Rlay && g_prime), MOM6X_EINVAL,
@@ -456,16 +429,7 @@ extern "C" int mom6x_calc_slope_functions(mom6x_ctx *c, const double *h, const d
                  D, raw_u, raw_v);                                                                                          \
   } while (0)
   if (!use_eos) VMF(0);
-  else switch (s->eos.form) {
-    case MOM6X_EOS_LINEAR: VMF(1); break;
-    case MOM6X_EOS_WRIGHT: VMF(2); break;
-    case MOM6X_EOS_WRIGHT_FULL: VMF(3); break;
-    case MOM6X_EOS_WRIGHT_REDUCED: VMF(4); break;
-    case MOM6X_EOS_UNESCO: VMF(5); break;
-    case MOM6X_EOS_ROQUET_RHO: VMF(6); break;
-    case MOM6X_EOS_JACKETT06: VMF(7); break;
-    default: VMF(8); break;
-  }
+  else EOS_FORM_DISPATCH(s->eos.form, VMF);
 #undef VMF
   if (simpler) {
     KLAUNCH(c, "k_vm_eady_combine", k_vm_eady_combine, grid3(d.ni + 1 + IAL, d.nj + 2, 1, b), b, d, raw_u, raw_v, SN_u, SN_v);

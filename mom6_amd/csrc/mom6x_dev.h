@@ -29,8 +29,13 @@ __device__ __forceinline__ const double *gm(const double *G, const Dm &d, int m)
   return G + (size_t)m * (size_t)d.slab;
 }
 
+// Two families of MAX and MIN.  They differ only on a tie, where dmax / dmin return the SECOND argument and fmax1 / fmin1 the
+// FIRST, as the reference's compiler evaluates MAX(a, b) and MIN(a, b): between +0 and -0 that decides the sign of the zero.
+// Every call site keeps the family it was held to the reference with; do not convert one into the other.
 __device__ __forceinline__ double dmax(double a, double b) { return (a > b) ? a : b; }
 __device__ __forceinline__ double dmin(double a, double b) { return (a < b) ? a : b; }
+__device__ __forceinline__ double fmax1(double a, double b) { return (b > a) ? b : a; }
+__device__ __forceinline__ double fmin1(double a, double b) { return (b < a) ? b : a; }
 __device__ __forceinline__ double dsign(double a, double b) { return (b >= 0.0) ? fabs(a) : -fabs(a); }
 
 // ---------------------------------------------------------------------------------------------
@@ -48,6 +53,8 @@ void mom6x_set_error(const char *fmt, ...);
   do {                                            \
     if (!(cond)) { mom6x_set_error("%s", msg); return code; } \
   } while (0)
+// an option of the reference that the device path of an init call (`who`) does not have
+#define REFUSE(cond, who, what) REQUIRE(!(cond), MOM6X_EUNSUPPORTED, who ": " what " is not on the device")
 
 // ---------------------------------------------------------------------------------------------
 // The context (opaque to C callers).
@@ -212,6 +219,23 @@ inline int nchunks(int nk) { return (nk + KCHUNK - 1) / KCHUNK; }
 #define IAL 16
 #define I_BASE(I0) (((I0) < 0) ? -IAL : (I0))
 inline int nxa(int nx, int I0) { return (I0 < 0) ? nx + IAL + I0 : nx; }
+
+// The lane of a kernel that serves the faces of both directions in one launch (blockIdx.z): one lane per face, lanes along i from
+// i = -IAL, rows from j = -1 - W.  dir 0: u faces I = -1..ni-1, j = 0..nj-1; dir 1: v faces i = 0..ni-1, J = -1..nj-1; with W = 1
+// every range is one face wider at either end (I = -2..ni, j = -1..nj | i = -1..ni, J = -2..nj).  x: the face and its own cell,
+// y = x + st: the cell on its far side, ot: the stride across the face's direction.  A lane outside the ranges (!in) returns.
+struct FaceLane { int dir, i, j; size_t x, y, st, ot; bool in; };
+template <int W>
+__device__ __forceinline__ FaceLane face_lane(const Dm &d) {
+  FaceLane f;
+  f.dir = blockIdx.z;
+  f.i = -IAL + blockIdx.x * blockDim.x + threadIdx.x;
+  f.j = -1 - W + blockIdx.y * blockDim.y + threadIdx.y;
+  f.in = f.i <= d.ni - 1 + W && f.j <= d.nj - 1 + W && (f.dir == 0 ? (f.i >= -1 - W && f.j >= -W) : (f.i >= -W));
+  f.st = f.dir ? (size_t)d.pitch : 1; f.ot = f.dir ? 1 : (size_t)d.pitch;
+  f.x = ix2(d, f.i, f.j); f.y = f.x + f.st;
+  return f;
+}
 
 inline dim3 grid3(int nx, int ny, int nz, dim3 b) {
   return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y, (nz + b.z - 1) / b.z);

@@ -10,10 +10,12 @@
 // tridiagonal solve of vert_fill_TS (any layer count: the solve's c1 goes through a work array).  k_td_faces: one lane per face,
 // both directions in one launch (blockIdx.z), ONE bottom-up walk -- without the FGNV solver the two K = nz..2 loops of a face row
 // carry only uhtot -- that forms e from h as it climbs (find_eta's own order), h_avail pointwise, writes uhD | vhD and adds them
-// to uhtr | vhtr.  k_td_update: h.  MAX and MIN are the reference compiler's: the first argument on a tie (zeros of either sign).
+// to uhtr | vhtr.  k_td_update: h.  MAX and MIN are fmax1 and fmin1 of mom6x_dev.h, the reference compiler's.  The density
+// gradients of MODE 1 (isoneutral_grads) and the vert_fill_TS solve come from isopycnal_slopes_dev.h, which
+// lateral_mixing_coeffs.hip shares; the lane of a face from face_lane (mom6x_dev.h), the EOS form's kernel from EOS_FORM_DISPATCH.
 #include "mom6x_dev.h"
 #include "eos_dev.h"
-#include "vert_fill_dev.h"
+#include "isopycnal_slopes_dev.h"
 
 namespace {
 
@@ -23,9 +25,6 @@ struct TdK {
   double Khth, Khth_Min, Khth_Max, qCFL, kap_dt_x2, h0;
   double dRho_dT, dRho_dS;
 };
-
-__device__ __forceinline__ double fmax1(double a, double b) { return (b > a) ? b : a; }   // MAX(a, b)
-__device__ __forceinline__ double fmin1(double a, double b) { return (b < a) ? b : a; }   // MIN(a, b)
 
 // The column pass :864-882 on cells is-1..ie+1, js-1..je+1 and, with Tf, vert_fill_TS(halo_here=1, larger_h_denom=.true.).
 // rsum[k], pres[k]: h_avail_rsum and pres at the interface ABOVE layer k.  Lanes start at i = -IAL (whole lines per wavefront).
@@ -58,7 +57,6 @@ k_td_cols(Dm d, const double *__restrict__ G, TdK K, const double *__restrict__ 
 
 // MODE 0: layers of constant density (:1085-1094); 1: an EOS of form FORM, slopes from the filled T, S; 2: an EOS with stored
 // slopes (no density derivative, calc_derivatives :924); 3: constant density with stored slopes.
-// blockIdx.z: 0 u faces (I = -1..ni-1, j = 0..nj-1), 1 v faces (i = 0..ni-1, J = -1..nj-1).
 template <int FORM, int MODE>
 __global__ void __launch_bounds__(256)
 k_td_faces(Dm d, const double *__restrict__ G, TdK K, const double *__restrict__ h, double *__restrict__ uhtr,
@@ -67,12 +65,10 @@ k_td_faces(Dm d, const double *__restrict__ G, TdK K, const double *__restrict__
            const double *__restrict__ pres, const double *__restrict__ Tf, const double *__restrict__ Sf,
            double *__restrict__ uhD, double *__restrict__ vhD) {
   constexpr bool EOS = (MODE == 1 || MODE == 2);
-  const int dir = blockIdx.z;
-  const int i = -IAL + blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = -1 + blockIdx.y * blockDim.y + threadIdx.y;
-  if (i > d.ni - 1 || j > d.nj - 1) return;
-  if (dir == 0 ? (i < -1 || j < 0) : (i < 0)) return;
-  const size_t x = ix2(d, i, j), st = dir ? (size_t)d.pitch : 1, y = x + st, slab = (size_t)d.slab;
+  const FaceLane f = face_lane<0>(d);
+  if (!f.in) return;
+  const int dir = f.dir;
+  const size_t x = f.x, y = f.y, slab = (size_t)d.slab;
   const int nz = d.nk;
   double *htr = dir ? vhtr : uhtr, *hD = dir ? vhD : uhD;
   const double *slope = dir ? slope_y : slope_x;
@@ -105,28 +101,11 @@ k_td_faces(Dm d, const double *__restrict__ G, TdK K, const double *__restrict__
     if constexpr (EOS) {
       if constexpr (MODE == 1) {
         TLm = Tf[om + x]; TRm = Tf[om + y]; SLm = Sf[om + x]; SRm = Sf[om + y];
-        const double pres_u = 0.5 * (pres[o + x] + pres[o + y]);
-        const double T_u = 0.25 * ((TLk + TRk) + (TLm + TRm));
-        const double S_u = 0.25 * ((SLk + SRk) + (SLm + SRm));
-        double dR_dT, dR_dS;
-        eos_density_derivs<FORM>(K, T_u, S_u, pres_u, dR_dT, dR_dS);
-        const double drdiA = dR_dT * (TRm - TLm) + dR_dS * (SRm - SLm);
-        const double drdiB = dR_dT * (TRk - TLk) + dR_dS * (SRk - SLk);
-        const double drdkL = (dR_dT * (TLk - TLm) + dR_dS * (SLk - SLm));
-        const double drdkR = (dR_dT * (TRk - TRm) + dR_dS * (SRk - SRm));
-        const double hg2L = hLm * hLk + K.h_neglect2, hg2R = hRm * hRk + K.h_neglect2;
-        const double haL = 0.5 * (hLm + hLk) + K.h_neglect, haR = 0.5 * (hRm + hRk) + K.h_neglect;
-        const double dzaL = haL * K.H_to_Z, dzaR = haR * K.H_to_Z;
-        const double wtL = hg2L * (haR * dzaR), wtR = hg2R * (haL * dzaL);
-        const double drdz = ((wtL * drdkL) + (wtR * drdkR)) / ((dzaL * wtL) + (dzaR * wtR));
-        const double hg2A = hLm * hRm + K.h_neglect2, hg2B = hLk * hRk + K.h_neglect2;
-        const double haA = 0.5 * (hLm + hRm) + K.h_neglect, haB = 0.5 * (hLk + hRk) + K.h_neglect;
-        const double wtA = hg2A * haB, wtB = hg2B * haA;
-        const double drdx = ((wtA * drdiA + wtB * drdiB) / (wtA + wtB) - drdz * (eL - eR)) * Igrad;
-        const double zx = K.Z_to_L * drdx;
-        const double mag_grad2 = zx * zx + drdz * drdz;
-        if (mag_grad2 > 0.0) {
-          Slope = drdx / sqrt(mag_grad2);
+        IsoGrad g;
+        isoneutral_grads<FORM>(K, hLm, hRm, hLk, hRk, TLm, TRm, TLk, TRk, SLm, SRm, SLk, SRk, 0.5 * (pres[o + x] + pres[o + y]),
+                               eL, eR, Igrad, g);
+        if (g.mag_grad2 > 0.0) {
+          Slope = g.drdx / sqrt(g.mag_grad2);
           ratio = Slope * Slope * K.I_slope_max2;
         } else {
           Slope = 0.0;
@@ -200,29 +179,26 @@ void thickness_diffuse_free(mom6x_ctx *c) {
 extern "C" int mom6x_thickness_diffuse_init(mom6x_ctx *c, const mom6x_thickness_diffuse_params *p, const mom6x_eos_params *eos,
                                             const double *khth2d) {
   REQUIRE(c && p, MOM6X_EINVAL, "mom6x_thickness_diffuse_init: null argument");
-#define TD_REFUSE(cond, what) REQUIRE(!(cond), MOM6X_EUNSUPPORTED, "thickness_diffuse_init: " what " is not on the device")
-  TD_REFUSE(p->use_FGNV_streamfn, "KHTH_USE_FGNV_STREAMFUNCTION");
-  TD_REFUSE(p->use_stanley_gm, "USE_STANLEY_GM");
-  TD_REFUSE(p->detangle_interfaces, "DETANGLE_INTERFACES");
-  TD_REFUSE(p->Kh_eta_bg > 0.0, "KH_ETA_CONST > 0");
-  TD_REFUSE(p->Kh_eta_vel > 0.0, "KH_ETA_VEL_SCALE > 0");
-  TD_REFUSE(p->use_GME, "USE_GME");
-  TD_REFUSE(p->use_variable_mixing, "variable mixing (VarMix%use_variable_mixing)");
-  TD_REFUSE(p->use_MEKE, "MEKE (MEKE%Kh, MEKE%GM_src)");
-  TD_REFUSE(p->use_Kh_in_MEKE, "USE_KH_IN_MEKE");
-  TD_REFUSE(p->GMwork, "the GMwork diagnostic (find_work)");
-  TD_REFUSE(p->skeb_use_gm, "SKEB (STOCH%skeb_use_gm)");
-  TD_REFUSE(p->nkml != 0, "a bulk mixed layer (GV%nkml > 0)");
-  TD_REFUSE(p->open_bcs, "open boundary conditions");
-  TD_REFUSE(p->non_Boussinesq || !c->GV.Boussinesq, "non-Boussinesq mode (tv%SpV_avg, semi_Boussinesq)");
-#undef TD_REFUSE
+  REFUSE(p->use_FGNV_streamfn, "thickness_diffuse_init", "KHTH_USE_FGNV_STREAMFUNCTION");
+  REFUSE(p->use_stanley_gm, "thickness_diffuse_init", "USE_STANLEY_GM");
+  REFUSE(p->detangle_interfaces, "thickness_diffuse_init", "DETANGLE_INTERFACES");
+  REFUSE(p->Kh_eta_bg > 0.0, "thickness_diffuse_init", "KH_ETA_CONST > 0");
+  REFUSE(p->Kh_eta_vel > 0.0, "thickness_diffuse_init", "KH_ETA_VEL_SCALE > 0");
+  REFUSE(p->use_GME, "thickness_diffuse_init", "USE_GME");
+  REFUSE(p->use_variable_mixing, "thickness_diffuse_init", "variable mixing (VarMix%use_variable_mixing)");
+  REFUSE(p->use_MEKE, "thickness_diffuse_init", "MEKE (MEKE%Kh, MEKE%GM_src)");
+  REFUSE(p->use_Kh_in_MEKE, "thickness_diffuse_init", "USE_KH_IN_MEKE");
+  REFUSE(p->GMwork, "thickness_diffuse_init", "the GMwork diagnostic (find_work)");
+  REFUSE(p->skeb_use_gm, "thickness_diffuse_init", "SKEB (STOCH%skeb_use_gm)");
+  REFUSE(p->nkml != 0, "thickness_diffuse_init", "a bulk mixed layer (GV%nkml > 0)");
+  REFUSE(p->open_bcs, "thickness_diffuse_init", "open boundary conditions");
+  REFUSE(p->non_Boussinesq || !c->GV.Boussinesq, "thickness_diffuse_init", "non-Boussinesq mode (tv%SpV_avg, semi_Boussinesq)");
   REQUIRE(p->max_Khth_CFL > 0.0, MOM6X_EINVAL, "thickness_diffuse_init: KHTH_MAX_CFL <= 0 leaves KH_v unset in the reference");
   REQUIRE(!(p->read_khth && p->Khth > 0.0), MOM6X_EINVAL,
           "thickness_diffuse_init: KHTH > 0 is not compatible with READ_KHTH = TRUE. ");
   REQUIRE((p->read_khth != 0) == (khth2d != nullptr), MOM6X_EINVAL, "thickness_diffuse_init: khth2d comes with READ_KHTH");
   REQUIRE(p->slope_max > 0.0, MOM6X_EINVAL, "thickness_diffuse_init: KHTH_SLOPE_MAX must be positive");
-  REQUIRE(!eos || (eos->form >= MOM6X_EOS_LINEAR && eos->form <= MOM6X_EOS_ROQUET_SPV), MOM6X_EINVAL,
-          "thickness_diffuse_init: unknown EQN_OF_STATE form");
+  REQUIRE(!eos || eos_form_known(eos), MOM6X_EINVAL, "thickness_diffuse_init: unknown EQN_OF_STATE form");
   REQUIRE(!eos || c->d.nk >= 2, MOM6X_EINVAL, "thickness_diffuse_init: vert_fill_TS needs two layers");
   HIPCHK(hipSetDevice(c->device));
   c->td = *p;
@@ -289,16 +265,9 @@ extern "C" int mom6x_thickness_diffuse(mom6x_ctx *c, double *h, double *uhtr, do
   } else if (stored) {
     TDF(0, 2);
   } else {
-    switch (c->td_eos.form) {
-      case MOM6X_EOS_LINEAR: TDF(1, 1); break;
-      case MOM6X_EOS_WRIGHT: TDF(2, 1); break;
-      case MOM6X_EOS_WRIGHT_FULL: TDF(3, 1); break;
-      case MOM6X_EOS_WRIGHT_REDUCED: TDF(4, 1); break;
-      case MOM6X_EOS_UNESCO: TDF(5, 1); break;
-      case MOM6X_EOS_ROQUET_RHO: TDF(6, 1); break;
-      case MOM6X_EOS_JACKETT06: TDF(7, 1); break;
-      default: TDF(8, 1); break;
-    }
+#define TDF_1(F) TDF(F, 1)
+    EOS_FORM_DISPATCH(c->td_eos.form, TDF_1);
+#undef TDF_1
   }
 #undef TDF
   KLAUNCH(c, "k_td_update", k_td_update, grid3(d.ni, d.nj, d.nk, b), b, d, c->G, dt, GV.Angstrom_H, h, uD, vD);

@@ -4,15 +4,16 @@
 //                            :237-357, the iteration count :371-390, the zeroing of df_x, df_y :392-402, the iteration :544-612
 //   tracer_hor_diff_init  <- :1630-1779
 //
-// The 2-D part is two small launches: k_thd_khdt (both face directions, blockIdx.z) and, with CHECK_DIFFUSIVE_CFL, k_thd_cfl (the
-// cell CFL and its maximum).  The iteration is k_thd_tile: the coefficients do not depend on the tracer, so h, khdt_x, khdt_y and
-// IareaT are read once for up to eight tracers.  The update is in place and every dTr of a layer is formed from the values BEFORE
-// the iteration, so a work item may only read what its own work-group will overwrite.  A work-group owns HD_TX consecutive columns
-// of a segment of HD_TY rows of one layer and walks the segment along j, one thread per column: the row below is the thread's own
-// old value, kept in a register; the row above has not been written yet; the neighbours in i go through LDS.  What lies beyond the
-// tile (one column on either side of every row, one row below and one above the segment) belongs to another work-group, which may
-// have overwritten it already: it comes from the copies k_thd_save_x and k_thd_save_y made before the pass (tracer_advect.hip's
-// k_ta_save_x/y, for a five-point stencil).  h is only read and needs no copy.
+// The 2-D part is two small launches: k_thd_khdt (both face directions, blockIdx.z; MAX and MIN are fmax1 and fmin1 of
+// mom6x_dev.h, the reference compiler's) and, with CHECK_DIFFUSIVE_CFL, k_thd_cfl (the cell CFL and its maximum).  The iteration is
+// k_thd_tile: the coefficients do not depend on the tracer, so h, khdt_x, khdt_y and IareaT are read once for up to eight tracers.
+// The update is in place and every dTr of a layer is formed from the values BEFORE the iteration, so a work item may only read what
+// its own work-group will overwrite.  A work-group owns HD_TX consecutive columns of a segment of HD_TY rows of one layer and walks
+// the segment along j, one thread per column: the row below is the thread's own old value, kept in a register; the row above has
+// not been written yet; the neighbours in i go through LDS.  What lies beyond the tile (one column on either side of every row,
+// one row below and one above the segment) belongs to another work-group, which may have overwritten it already: it comes from
+// the copies k_thd_save_x and k_thd_save_y made before the pass (tracer_advect.hip's k_ta_save_x/y, for a five-point stencil).
+// h is only read and needs no copy.
 #include "mom6x_dev.h"
 #include <cmath>
 #include <cfloat>
@@ -26,15 +27,12 @@ constexpr int HD_MAXT = 8;     // tracers per launch
 
 namespace {
 
-__device__ __forceinline__ double fmax1(double a, double b) { return (b > a) ? b : a; }   // MAX(a, b)
-__device__ __forceinline__ double fmin1(double a, double b) { return (b < a) ? b : a; }   // MIN(a, b)
-
 struct ThdK {       // tracer_hor_diff_CS and the switches of :221-227
   double dt, KhTr, KhTr_Slope_Cff, KhTr_min, KhTr_max, passivity_coeff, passivity_min, KhTr_fac, max_diff_CFL;
   int use_VarMix, Resoln_scaled, use_Eady, use_MEKE;
 };
 
-// khdt_x at I = -1..ni-1, j = 0..nj-1 (blockIdx.z = 0) and khdt_y at i = 0..ni-1, J = -1..nj-1 (1), :237-357
+// khdt_x at the u faces and khdt_y at the v faces, :237-357.  The lane: face_lane<0> (mom6x_dev.h) written out, as measured faster.
 __global__ void __launch_bounds__(256)
 k_thd_khdt(Dm d, const double *__restrict__ G, ThdK K, const double *__restrict__ L2u, const double *__restrict__ SN_u,
            const double *__restrict__ L2v, const double *__restrict__ SN_v, const double *__restrict__ Res_fn_h,
@@ -259,13 +257,11 @@ extern "C" int mom6x_tracer_hordiff_tile(int *tx, int *ty, int *max_tracers) {
 
 extern "C" int mom6x_tracer_hor_diff_init(mom6x_ctx *c, const mom6x_tracer_hor_diff_params *p) {
   REQUIRE(c && p, MOM6X_EINVAL, "mom6x_tracer_hor_diff_init: null argument");
-#define THD_REFUSE(cond, what) REQUIRE(!(cond), MOM6X_EUNSUPPORTED, "tracer_hor_diff_init: " what " is not on the device")
-  THD_REFUSE(p->use_neutral_diffusion, "USE_NEUTRAL_DIFFUSION");
-  THD_REFUSE(p->use_hor_bnd_diffusion, "USE_HORIZONTAL_BOUNDARY_DIFFUSION");
-  THD_REFUSE(p->Diffuse_ML_interior, "DIFFUSE_ML_TO_INTERIOR (tracer_epipycnal_ML_diff)");
-  THD_REFUSE(p->offline, "offline tracer transport (do_online_flag = .false., read_khdt_x, read_khdt_y)");
-  THD_REFUSE(p->open_bcs, "open boundary conditions");
-#undef THD_REFUSE
+  REFUSE(p->use_neutral_diffusion, "tracer_hor_diff_init", "USE_NEUTRAL_DIFFUSION");
+  REFUSE(p->use_hor_bnd_diffusion, "tracer_hor_diff_init", "USE_HORIZONTAL_BOUNDARY_DIFFUSION");
+  REFUSE(p->Diffuse_ML_interior, "tracer_hor_diff_init", "DIFFUSE_ML_TO_INTERIOR (tracer_epipycnal_ML_diff)");
+  REFUSE(p->offline, "tracer_hor_diff_init", "offline tracer transport (do_online_flag = .false., read_khdt_x, read_khdt_y)");
+  REFUSE(p->open_bcs, "tracer_hor_diff_init", "open boundary conditions");
   REQUIRE(c->d.halo >= 1, MOM6X_EINVAL, "tracer_hor_diff_init: the stencil needs a halo of one");
   HIPCHK(hipSetDevice(c->device));
   tracer_hor_diff_free(c);

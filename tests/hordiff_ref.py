@@ -12,6 +12,7 @@ import math
 import numpy as np
 
 from mom6_amd import abi
+from tests.ref_common import _faces, _max, _min
 
 G = abi.G
 EPSILON = 2.0 ** -52
@@ -19,24 +20,6 @@ BRANCHES = ("itts_1", "itts_ge3_check", "itts_from_max", "clamp_x_on", "clamp_x_
             "pass_floor", "pass_slope", "meke_nonzero", "eady_nonzero", "closed_face_wet", "vanished_next_thick", "underflow_flushed",
             "underflow_kept")
 PLANES = ("L2u", "SN_u", "L2v", "SN_v", "Res_fn_h", "Rd_dx_h", "MEKE_Kh")
-
-
-def _max(a, b):
-    """Fortran MAX(a, b): a on a tie."""
-    return np.where(b > a, b, a)
-
-
-def _min(a, b):
-    """Fortran MIN(a, b): a on a tie."""
-    return np.where(b < a, b, a)
-
-
-def _faces(d, dir):
-    """Row and column ranges of the faces (u: I = isc-1..iec, j = jsc..jec; v: i = isc..iec, J = jsc-1..jec) and the offset of
-    the cell on the far side."""
-    if dir == 0:
-        return (d.joff, d.joff + d.nj), (d.ioff - 1, d.ioff + d.ni), (0, 1)
-    return (d.joff - 1, d.joff + d.nj), (d.ioff, d.ioff + d.ni), (1, 0)
 
 
 def group_pass(d, a):

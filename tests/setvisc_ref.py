@@ -9,6 +9,7 @@ a test can show the branches it claims to cover were reached."""
 import numpy as np
 
 from mom6_amd import abi
+from tests.ref_common import _faces
 
 G = abi.G
 BRANCHES = ("vanished_skip", "frac_used", "layer1_eos", "layer1_rlay", "thick_min", "correct_bounds", "RiNo_cap", "body_force",
@@ -16,16 +17,8 @@ BRANCHES = ("vanished_skip", "frac_used", "layer1_eos", "layer1_rlay", "thick_mi
 
 
 def _min(a, b):
-    """Fortran MIN(a, b) of two reals."""
+    """Fortran MIN(a, b) of two reals, b on a tie: dmin on the device (set_visc.hip), not the _min of tests/ref_common.py."""
     return np.where(a < b, a, b)
-
-
-def _faces(d, dir):
-    """Row and column slices of the faces :450-460 (u: I = isc-1..iec, j = jsc..jec; v: i = isc..iec, J = jsc-1..jec) and the
-    offset of the cell on the far side of each face."""
-    if dir == 0:
-        return (d.joff, d.joff + d.nj), (d.ioff - 1, d.ioff + d.ni), (0, 1)
-    return (d.joff - 1, d.joff + d.nj), (d.ioff, d.ioff + d.ni), (1, 0)
 
 
 def set_viscous_BBL(d, M, GV, P, u, v, h, T=None, S=None, p_surf=None, eos=None, tideamp=None, Rlay=None, Kv_bbl_u=None,

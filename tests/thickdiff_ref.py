@@ -1,11 +1,11 @@
 """The checker of mom6x_thickness_diffuse: a numpy restatement of thickness_diffuse and thickness_diffuse_full
 (src/parameterizations/lateral/MOM_thickness_diffuse.F90:134-630, :635-1671) on a Boussinesq grid without the FGNV
 streamfunction, with find_eta (src/core/MOM_interface_heights.F90:91-97) and vert_fill_TS
-(src/core/MOM_isopycnal_slopes.F90:612-700), written from the Fortran operation for operation (x**2 as x*x, nothing reordered)
-and vectorised over the faces of one direction with a loop over K.  Arrays are in the pitched tile layout of include/mom6x.h
-([k, j + joff, i + ioff]).  Density derivatives come from the oracle's EOS only (oracle/orc.py eos_density_derivs), one point
-at a time.  MAX and MIN return their first argument on a tie, as the reference's compiler evaluates them, which decides the
-sign of a zero.  `counts` records how often each branch fired.
+(src/core/MOM_isopycnal_slopes.F90:612-700, larger_h_denom = .true.; both from tests/ref_common.py), written from the
+Fortran operation for operation (x**2 as x*x, nothing reordered) and vectorised over the faces of one direction with a loop
+over K.  Arrays are in the pitched tile layout of include/mom6x.h ([k, j + joff, i + ioff]).  Density derivatives come from the
+oracle's EOS only (oracle/orc.py eos_density_derivs), one point at a time.  MAX and MIN return their first argument on a tie,
+as the reference's compiler evaluates them, which decides the sign of a zero.  `counts` records how often each branch fired.
 
 The Fortran routine itself cannot be compiled into oracle/_ref: the recipe under oracle/ is fixed and does not build it.  A
 restatement and a kernel written by one person can share a misreading, so tests/test_thickness_diffuse_cpu.py first holds this
@@ -13,76 +13,12 @@ module to facts that do not come from it (closed forms, exact column sums, bound
 import numpy as np
 
 from mom6_amd import abi
+from tests.ref_common import _derivs, _faces, _max, _min, find_eta, pressure_column, vert_fill_TS
 
 G = abi.G
 BRANCHES = ("bottom_zero_pos", "bottom_zero_neg", "bottom_scale_pos", "bottom_scale_neg", "mag_grad2_zero", "rsum_clip_lo",
             "rsum_clip_hi", "havail_clip_hi", "havail_clip_lo", "uhtot_le0", "uhtot_gt0", "hfrac_zero", "KH_cfl", "KH_max",
             "kap_zero", "angstrom_floor")
-
-
-def _max(a, b):
-    """Fortran MAX(a, b): a on a tie."""
-    return np.where(b > a, b, a)
-
-
-def _min(a, b):
-    """Fortran MIN(a, b): a on a tie."""
-    return np.where(b < a, b, a)
-
-
-def _faces(d, dir):
-    """Row and column ranges of the faces (u: I = isc-1..iec, j = jsc..jec; v: i = isc..iec, J = jsc-1..jec) and the offset of
-    the cell on the far side."""
-    if dir == 0:
-        return (d.joff, d.joff + d.nj), (d.ioff - 1, d.ioff + d.ni), (0, 1)
-    return (d.joff - 1, d.joff + d.nj), (d.ioff, d.ioff + d.ni), (1, 0)
-
-
-def _derivs(orc, eos, T, S, p):
-    a, b = np.empty(T.shape), np.empty(T.shape)
-    fa, fb = a.reshape(-1), b.reshape(-1)
-    f = orc.eos_density_derivs
-    for n, (t, s, q) in enumerate(zip(T.reshape(-1).tolist(), S.reshape(-1).tolist(), p.reshape(-1).tolist())):
-        fa[n], fb[n] = f(eos, t, s, q)
-    return a, b
-
-
-def vert_fill_TS(h, T_in, S_in, kappa_dt, GV, Z_to_H_fill, counts=None):
-    """vert_fill_TS(..., larger_h_denom=.true.) on every column of the arrays."""
-    nz = h.shape[0]
-    h_neglect = GV.H_subroundoff
-    kap_dt_x2 = (2.0 * kappa_dt) * Z_to_H_fill                    # :655
-    h0 = 1.0e-16 * np.sqrt(0.5 * kap_dt_x2)                       # :658
-    if kap_dt_x2 <= 0.0:                                          # :661-665
-        if counts is not None:
-            counts["kap_zero"] += 1
-        return T_in.copy(), S_in.copy()
-    T_f, S_f = np.empty_like(T_in), np.empty_like(S_in)
-    c1 = np.zeros_like(h)
-    ent = kap_dt_x2 / ((h[0] + h[1]) + h0)
-    h_tr = h[0] + h_neglect
-    b1 = 1.0 / (h_tr + ent)
-    d1 = b1 * h_tr
-    T_f[0] = (b1 * h_tr) * T_in[0]
-    S_f[0] = (b1 * h_tr) * S_in[0]
-    for k in range(1, nz - 1):
-        entn = kap_dt_x2 / ((h[k] + h[k + 1]) + h0)
-        h_tr = h[k] + h_neglect
-        c1[k] = ent * b1
-        b1 = 1.0 / ((h_tr + d1 * ent) + entn)
-        d1 = b1 * (h_tr + d1 * ent)
-        T_f[k] = b1 * (h_tr * T_in[k] + ent * T_f[k - 1])
-        S_f[k] = b1 * (h_tr * S_in[k] + ent * S_f[k - 1])
-        ent = entn
-    c1[nz - 1] = ent * b1
-    h_tr = h[nz - 1] + h_neglect
-    b1 = 1.0 / (h_tr + d1 * ent)
-    T_f[nz - 1] = b1 * (h_tr * T_in[nz - 1] + ent * T_f[nz - 2])
-    S_f[nz - 1] = b1 * (h_tr * S_in[nz - 1] + ent * S_f[nz - 2])
-    for k in range(nz - 2, -1, -1):
-        T_f[k] = T_f[k] + c1[k + 1] * T_f[k + 1]
-        S_f[k] = S_f[k] + c1[k + 1] * S_f[k + 1]
-    return T_f, S_f
 
 
 def thickness_diffuse(d, M, GV, P, h, uhtr, vhtr, dt, T=None, S=None, p_surf=None, eos=None, khth2d=None, slope_x=None,
@@ -108,31 +44,22 @@ def thickness_diffuse(d, M, GV, P, h, uhtr, vhtr, dt, T=None, S=None, p_surf=Non
     int_slope = 0.0                                              # :472-474
     aT = M[G["areaT"]]
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        # find_eta, Boussinesq (MOM_interface_heights.F90:91-97)
-        e = np.empty((nz + 1,) + h.shape[1:])
-        e[nz] = -(M[G["bathyT"]] + 0.0)
-        for k in range(nz - 1, -1, -1):
-            e[k] = e[k + 1] + h[k] * GV.H_to_Z
+        e = find_eta(d, M, h, GV.H_to_Z)
         if calc_derivatives:                                     # :850-853
-            Tf, Sf = vert_fill_TS(h, T, S, P.kappa_smooth * dt, GV, P.Z_to_H_fill, counts)
+            Tf, Sf = vert_fill_TS(h, T, S, P.kappa_smooth * dt, GV, P.Z_to_H_fill, True, counts)
         # the column pass :864-882
         h_avail = np.empty_like(h)
         h_frac = np.empty_like(h)
         rsum = np.empty_like(e)
-        pres = np.empty_like(e)
+        pres = pressure_column(h, p_surf, GV.g_Earth * GV.H_to_RZ)
         rsum[0] = 0.0
-        pres[0] = 0.0
-        if p_surf is not None:
-            pres[0] = p_surf
         h_avail[0] = _max(I4dt * aT * (h[0] - GV.Angstrom_H), 0.0)
         rsum[1] = h_avail[0]
         h_frac[0] = 1.0
-        pres[1] = pres[0] + (GV.g_Earth * GV.H_to_RZ) * h[0]
         for k in range(1, nz):
             h_avail[k] = _max(I4dt * aT * (h[k] - GV.Angstrom_H), 0.0)
             rsum[k + 1] = rsum[k] + h_avail[k]
             h_frac[k] = np.where(h_avail[k] > 0.0, h_avail[k] / rsum[k + 1], 0.0)
-            pres[k + 1] = pres[k] + (GV.g_Earth * GV.H_to_RZ) * h[k]
         counts["hfrac_zero"] += int((h_avail[1:][(slice(None),) + d.sl(0, d.ni - 1, 0, d.nj - 1)] <= 0.0).sum())
 
         hD = [np.zeros_like(h), np.zeros_like(h)]

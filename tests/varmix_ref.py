@@ -6,74 +6,21 @@ calc_Eady_growth_rate_2D (:962-1112), calc_Visbeck_coeffs_old (:743-959) and cal
 of the L2u, L2v of VarMix_init (:1759-1772).  Written from the Fortran operation for operation (x**2 as x*x, x**4 as (x*x)*(x*x),
 nothing reordered), independent of the HIP, vectorised over the faces of one direction with a loop over K.  Arrays are in the
 pitched tile layout of include/mom6x.h ([k, j + joff, i + ioff]); local indices are zero based (isc = 0, iec = ni-1).  Density
-derivatives come from the oracle's EOS only, one point at a time, as in tests/thickdiff_ref.py.  MAX and MIN return their first
-argument on a tie.  `counts` records how often each branch fired.
+derivatives come from the oracle's EOS only, one point at a time.  MAX and MIN return their first argument on a tie.  These,
+find_eta, the pressure column and vert_fill_TS come from tests/ref_common.py; the slope arithmetic is this module's own.
+`counts` records how often each branch fired.
 
 The Fortran routines cannot be compiled into oracle/_ref (the recipe under oracle/ is fixed and does not build them), so
 tests/test_varmix_cpu.py first holds this module to facts that do not come from it."""
 import numpy as np
 
 from mom6_amd import abi
-from tests.thickdiff_ref import _derivs, _max, _min
+from tests.ref_common import _A, _derivs, _max, _min, find_eta, pressure_column, vert_fill_TS
 
 G = abi.G
 BRANCHES = ("mag_grad2_zero", "kap_zero", "dzSN_clip", "N2_clipped", "S2max_applied", "S2max_idle", "Hu_le0", "Dscale_full",
             "Dscale_partial", "Dscale_zero", "crop_top_0", "crop_top_mid", "crop_top_1", "crop_bot_0", "crop_bot_mid", "crop_bot_1",
             "H_cutoff_mask", "bathy_cutoff", "denom_bathy", "denom_dztot")
-
-
-def _A(d, a, rng, di=0, dj=0):
-    """The part of `a` on local inclusive ranges rng = (i0, i1, j0, j1), shifted by (di, dj)."""
-    i0, i1, j0, j1 = rng
-    return a[(Ellipsis,) + d.sl(i0 + di, i1 + di, j0 + dj, j1 + dj)]
-
-
-def find_eta(d, M, h, H_to_Z):
-    """find_eta, Boussinesq, dZ_ref = 0 (:91-97), on every column of the array."""
-    nz = d.nk
-    e = np.empty((nz + 1,) + h.shape[1:])
-    e[nz] = -(M[G["bathyT"]] + 0.0)
-    for k in range(nz - 1, -1, -1):
-        e[k] = e[k + 1] + h[k] * H_to_Z
-    return e
-
-
-def vert_fill_TS(h, T_in, S_in, kappa_dt, GV, Z_to_H_fill, counts=None):
-    """vert_fill_TS without larger_h_denom on every column of the arrays."""
-    nz = h.shape[0]
-    h_neglect = GV.H_subroundoff
-    kap_dt_x2 = (2.0 * kappa_dt) * Z_to_H_fill                    # :655
-    h0 = h_neglect                                                # :656
-    if kap_dt_x2 <= 0.0:                                          # :661-665
-        if counts is not None:
-            counts["kap_zero"] += 1
-        return T_in.copy(), S_in.copy()
-    T_f, S_f = np.empty_like(T_in), np.empty_like(S_in)
-    ent = np.zeros((nz + 1,) + h.shape[1:])
-    c1 = np.zeros_like(h)
-    ent[1] = kap_dt_x2 / ((h[0] + h[1]) + h0)                     # :670-675
-    h_tr = h[0] + h_neglect
-    b1 = 1.0 / (h_tr + ent[1])
-    d1 = b1 * h_tr
-    T_f[0] = (b1 * h_tr) * T_in[0]
-    S_f[0] = (b1 * h_tr) * S_in[0]
-    for k in range(1, nz - 1):                                    # :677-685
-        ent[k + 1] = kap_dt_x2 / ((h[k] + h[k + 1]) + h0)
-        h_tr = h[k] + h_neglect
-        c1[k] = ent[k] * b1
-        b1 = 1.0 / ((h_tr + d1 * ent[k]) + ent[k + 1])
-        d1 = b1 * (h_tr + d1 * ent[k])
-        T_f[k] = b1 * (h_tr * T_in[k] + ent[k] * T_f[k - 1])
-        S_f[k] = b1 * (h_tr * S_in[k] + ent[k] * S_f[k - 1])
-    c1[nz - 1] = ent[nz - 1] * b1                                 # :687-691
-    h_tr = h[nz - 1] + h_neglect
-    b1 = 1.0 / (h_tr + d1 * ent[nz - 1])
-    T_f[nz - 1] = b1 * (h_tr * T_in[nz - 1] + ent[nz - 1] * T_f[nz - 2])
-    S_f[nz - 1] = b1 * (h_tr * S_in[nz - 1] + ent[nz - 1] * S_f[nz - 2])
-    for k in range(nz - 2, -1, -1):                               # :693-696
-        T_f[k] = T_f[k] + c1[k + 1] * T_f[k + 1]
-        S_f[k] = S_f[k] + c1[k + 1] * S_f[k + 1]
-    return T_f, S_f
 
 
 def calc_isoneutral_slopes(d, M, GV, P, h, e, dt_kappa_smooth, out, T=None, S=None, p_surf=None, eos=None, Rlay=None, counts=None,
@@ -89,13 +36,8 @@ def calc_isoneutral_slopes(d, M, GV, P, h, e, dt_kappa_smooth, out, T=None, S=No
     if use_EOS:
         if orc is None:
             from oracle import orc
-        Tf, Sf = vert_fill_TS(h, T, S, dt_kappa_smooth, GV, P.Z_to_H_fill, counts)     # :213
-        pres = np.empty((nz + 1,) + h.shape[1:])                                        # :231-247
-        pres[0] = 0.0
-        if p_surf is not None:
-            pres[0] = p_surf
-        for k in range(nz):
-            pres[k + 1] = pres[k] + P.g_Earth * P.H_to_RZ * h[k]
+        Tf, Sf = vert_fill_TS(h, T, S, dt_kappa_smooth, GV, P.Z_to_H_fill, False, counts)   # :213
+        pres = pressure_column(h, p_surf, P.g_Earth * P.H_to_RZ)                        # :231-247
     for dir in (0, 1):
         rng = (is_ - 1, ie, js, je) if dir == 0 else (is_, ie, js - 1, je)
         far = dict(di=1, dj=0) if dir == 0 else dict(di=0, dj=1)
