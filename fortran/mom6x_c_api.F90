@@ -15,6 +15,7 @@ module mom6x_c_api
   public :: mom6x_thickness_diffuse_params, mom6x_thickness_diffuse_init, mom6x_thickness_diffuse
   public :: mom6x_tracer_hor_diff_params, mom6x_tracer_hor_diff_init, mom6x_tracer_hordiff, mom6x_tracer_hordiff_tile
   public :: mom6x_varmix_params, mom6x_varmix_init, mom6x_calc_slope_functions
+  public :: mom6x_mixedlayer_restrat_params, mom6x_mixedlayer_restrat_init, mom6x_mixedlayer_restrat, mom6x_mixedlayer_restrat_mu
   public :: mom6x_hor_visc_params, mom6x_hor_visc_init, mom6x_horizontal_viscosity, mom6x_vertvisc_set_direct_stress
   public :: mom6x_remapping_params, mom6x_ALE_remap_tracers, mom6x_ALE_remap_set_h_vel, mom6x_ALE_remap_velocities
   public :: mom6x_ALE_remap_velocities_conserve_ke, mom6x_ALE_remap_velocities_from_h, mom6x_comm_overlap_btstep
@@ -136,6 +137,13 @@ module mom6x_c_api
     real(c_double) :: h_min_N2, max_depth, H_to_Z, Z_to_L, L_to_m, H_to_RZ, Z_to_H_fill, Angstrom_Z, g_Earth, Rho0
     integer(c_int) :: use_stanley_iso, open_bcs, non_Boussinesq, debug
   end type mom6x_varmix_params
+
+  type, bind(C) :: mom6x_mixedlayer_restrat_params   !< mixedlayer_restrat_CS (MOM_mixed_layer_restrat.F90:37-140), the members of the OM4 path
+    real(c_double) :: ml_restrat_coef, ml_restrat_coef2, front_length
+    integer(c_int) :: MLE_use_PBL_MLD
+    real(c_double) :: MLE_MLD_decay_time, MLE_MLD_decay_time2, MLE_density_diff, MLE_tail_dh, MLE_MLD_stretch, vonKar, ustar_min
+    integer(c_int) :: use_Bodner, nkml, use_Stanley_ML, non_Boussinesq, open_bcs, debug
+  end type mom6x_mixedlayer_restrat_params
 
   type, bind(C) :: mom6x_hor_visc_params   !< hor_visc_CS (MOM_hor_visc.F90:36-259), the members the device path reads
     integer(c_int) :: Laplacian, biharmonic
@@ -407,6 +415,27 @@ module mom6x_c_api
       import :: c_ptr, c_int, c_double
       type(c_ptr), value :: ctx, h, T, S, p_surf, SN_u, SN_v, slope_x, slope_y, N2_u, N2_v, dzu, dzv, dzSxN, dzSyN, S2_u, S2_v
       real(c_double), value :: dt
+    end function
+    !> mixedlayer_restrat_init (MOM_mixed_layer_restrat.F90:1617) for the OM4 path; eos: c_loc(an eos_params), required
+    integer(c_int) function mom6x_mixedlayer_restrat_init(ctx, p, eos) bind(C, name="mom6x_mixedlayer_restrat_init")
+      import :: c_ptr, c_int, mom6x_mixedlayer_restrat_params
+      type(c_ptr), value :: ctx ; type(mom6x_mixedlayer_restrat_params), intent(in) :: p
+      type(c_ptr), value :: eos
+    end function
+    !> mixedlayer_restrat (MOM_mixed_layer_restrat.F90:149); every array is a device pointer; h_MLD, Rd_dx_h, mle_fl, the filtered
+    !! planes and the diagnostics from uhml on may be c_null_ptr where include/mom6x.h says so
+    integer(c_int) function mom6x_mixedlayer_restrat(ctx, h, uhtr, vhtr, T, S, ustar, dt, h_MLD, Rd_dx_h, mle_fl, MLD_filtered, &
+        MLD_filtered_slow, uhml, vhml, utimescale, vtimescale, uDml, vDml, MLD_fast_out, MLD_slow_out, Rml_av_fast_out) &
+        bind(C, name="mom6x_mixedlayer_restrat")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, h, uhtr, vhtr, T, S, ustar, h_MLD, Rd_dx_h, mle_fl, MLD_filtered, MLD_filtered_slow, uhml, vhml
+      type(c_ptr), value :: utimescale, vtimescale, uDml, vDml, MLD_fast_out, MLD_slow_out, Rml_av_fast_out
+      real(c_double), value :: dt
+    end function
+    !> the device's mu(sigma, dh) (MOM_mixed_layer_restrat.F90:717) at n device values: a test hook
+    integer(c_int) function mom6x_mixedlayer_restrat_mu(ctx, sigma, dh, out, n) bind(C, name="mom6x_mixedlayer_restrat_mu")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, sigma, dh, out ; integer(c_int), value :: n
     end function
     integer(c_int) function mom6x_vertvisc_set_visc(ctx, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Kv_shear, Ray_u, Ray_v) &
         bind(C, name="mom6x_vertvisc_set_visc")

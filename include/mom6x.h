@@ -351,7 +351,8 @@ int  mom6x_device_count(void);
 /* sizeof() of the public structs (0 dims, 1 vgrid, 2 continuity_params, 3 BT_cont, 4 barotropic_params,
  * 5 coriolis_params, 6 pgf_params, 7 rk2_params, 8 rk2_hooks, 9 eos_params, 10 vertvisc_params, 11 hor_visc_params,
  * 12 remapping_params, 13 regrid_zstar_params, 14 chksum_result, 15 sum_output_params, 16 energy_sums, 17 regrid_rho_params,
- * 18 set_visc_params, 19 thickness_diffuse_params, 20 tracer_hor_diff_params, 21 varmix_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
+ * 18 set_visc_params, 19 thickness_diffuse_params, 20 tracer_hor_diff_params, 21 varmix_params,
+ * 22 mixedlayer_restrat_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
 int  mom6x_struct_size(int which);
 
 /* Create a context for one tile on HIP device `device`.  `metrics_host` is a
@@ -847,6 +848,60 @@ int mom6x_varmix_init(mom6x_ctx *ctx, const mom6x_varmix_params *p, const mom6x_
 int mom6x_calc_slope_functions(mom6x_ctx *ctx, const double *h, const double *T, const double *S, const double *p_surf, double dt,
                                double *SN_u, double *SN_v, double *slope_x, double *slope_y, double *N2_u, double *N2_v,
                                double *dzu, double *dzv, double *dzSxN, double *dzSyN, double *S2_u, double *S2_v);
+
+/* ------------------------------------------------------------------------- */
+/* MOM_mixed_layer_restrat: mixedlayer_restrat (Fox-Kemper, the OM4 path)     */
+/* mixedlayer_restrat_CS (src/parameterizations/lateral/MOM_mixed_layer_restrat.F90:37-140; mixedlayer_restrat_init :1617-1958):
+ * the members that mixedlayer_restrat_OM4 (:189-714), detect_mld (:1504-1571) and mu (:717-751) read on a Boussinesq grid in
+ * general coordinates.  GV%Angstrom_H, GV%H_subroundoff, GV%H_to_Z, GV%Z_to_H, GV%g_Earth and GV%Rho0 are the context's
+ * (mom6x_vgrid).  The members marked "must be 0" are refused with MOM6X_EUNSUPPORTED.                                          */
+typedef struct mom6x_mixedlayer_restrat_params {
+  double ml_restrat_coef;      /* FOX_KEMPER_ML_RESTRAT_COEF (0, :1786): scales the fast timescale (:510)                        */
+  double ml_restrat_coef2;     /* FOX_KEMPER_ML_RESTRAT_COEF2 (0, :1812): scales the slow timescale (:525)                       */
+  double front_length;         /* MLE_FRONT_LENGTH (0, :1815) [L]; > 0: the resolution upscaling with this length (:355-359);
+                                  0 with an mle_fl plane: MLE_FRONT_LENGTH_FROM_FILE (:360-363); otherwise no upscaling          */
+  int    MLE_use_PBL_MLD;      /* MLE_USE_PBL_MLD (F, :1844): MLD_fast = MLE_MLD_stretch*h_MLD (:304) when MLE_density_diff <= 0  */
+  double MLE_MLD_decay_time;   /* MLE_MLD_DECAY_TIME (0, :1849) [T]; > 0: the running mean of :317-325 on MLD_filtered           */
+  double MLE_MLD_decay_time2;  /* MLE_MLD_DECAY_TIME2 (0, :1854) [T]; > 0: the slow running mean of :335-343                     */
+  double MLE_density_diff;     /* MLE_DENSITY_DIFF (0.03 kg m-3, :1860; not read with MLE_USE_PBL_MLD) [R]; > 0: detect_mld      */
+  double MLE_tail_dh;          /* MLE_TAIL_DH (0, :1865): the extension of the stream function below the mixed layer (mu :739)    */
+  double MLE_MLD_stretch;      /* MLE_MLD_STRETCH (1, :1869)                                                                     */
+  double vonKar;               /* VON_KARMAN_CONST (0.41, :1806)                                                                 */
+  double ustar_min;            /* RESTRAT_USTAR_MIN as :1882-1887 leave it in CS%ustar_min [H T-1]                               */
+  int    use_Bodner;           /* MLE%USE_BODNER23 (mixedlayer_restrat_Bodner): must be 0                                        */
+  int    nkml;                 /* GV%nkml (mixedlayer_restrat_BML): must be 0                                                    */
+  int    use_Stanley_ML;       /* USE_STANLEY_ML (F, :1796): must be 0                                                           */
+  int    non_Boussinesq;       /* not GV%Boussinesq, or semi-Boussinesq (calculate_spec_vol :427-471, tau_mag in find_ustar): must be 0 */
+  int    open_bcs;             /* open boundaries (G%OBCmaskCu/v differ from mask2dCu/v): must be 0                              */
+  int    debug;                /* DEBUG (F, :1671): the checksums of :313-334, :473-479: must be 0                               */
+} mom6x_mixedlayer_restrat_params;
+/* mixedlayer_restrat_init :1617 for the members above: checks them, keeps them and allocates every work array the step needs
+ * (four 2-D planes and uhml, vhml).  eos: tv%eqn_of_state, required (the reference's fatal error, :288).  MOM6X_EINVAL when
+ * MLE_density_diff <= 0 without MLE_use_PBL_MLD (:306).                                                                         */
+int mom6x_mixedlayer_restrat_init(mom6x_ctx *ctx, const mom6x_mixedlayer_restrat_params *p, const mom6x_eos_params *eos);
+/* mixedlayer_restrat(h, uhtr, vhtr, tv, forces, dt, MLD, h_MLD, bflux, VarMix, G, GV, US, CS) :149 on the context's stream, without
+ * an exchange, a host synchronisation or an allocation.  h, uhtr, vhtr are updated in place; T, S are tv%T, tv%S; ustar is
+ * forces%ustar [Z T-1] (the device forms GV%Z_to_H*ustar as find_ustar(H_T_units=.true.) does, MOM_forcing_type.F90:1271).
+ * h_MLD: the boundary-layer scheme's mixed-layer thickness [H], required with MLE_use_PBL_MLD when MLE_density_diff <= 0.
+ * Rd_dx_h: VarMix%Rd_dx_h, required whenever the resolution upscaling is on.  mle_fl: nullable plane of the frontal length [L]
+ * (with front_length == 0 it is the MLE_FRONT_LENGTH_FROM_FILE arm; the host keeps time_interp_external, its halo pass and the
+ * sign check :364-371).  MLD_filtered, MLD_filtered_slow: CS%MLD_filtered, CS%MLD_filtered_slow (the restart fields
+ * MLD_MLE_filtered and MLD_MLE_filtered_slow), the caller's resident planes, each required when its decay time is > 0 and
+ * updated in place on isc-1..iec+1 x jsc-1..jec+1.  The remaining arguments are nullable diagnostics as the reference posts them:
+ * uhml, vhml (3-D), utimescale, vtimescale (the value the reference stores, the slow one: :572, :662), uDml, vDml (after the
+ * limiter), MLD_fast_out (id_BLD), MLD_slow_out (id_MLD), Rml_av_fast_out (id_Rml), the last three on isc-1..iec+1 x jsc-1..jec+1.
+ * h, T, S, ustar, h_MLD, Rd_dx_h, mle_fl and the two filtered planes need ONE valid halo point.
+ * Written: uhtr, uhml, utimescale, uDml at I = isc-1..iec, j = jsc..jec; vhtr, vhml, vtimescale, vDml at i = isc..iec,
+ * J = jsc-1..jec (uhtr, vhtr keep their bits at a face whose uDml + uDml_slow is zero, :531); h on the computational domain.
+ * Every other point keeps its value, and the caller still owes pass_var(h).
+ * Not carried: the id_uml / id_vml diagnostics, DEBUG checksums, diag_update_remap_grids.                                        */
+int mom6x_mixedlayer_restrat(mom6x_ctx *ctx, double *h, double *uhtr, double *vhtr, const double *T, const double *S,
+                             const double *ustar, double dt, const double *h_MLD, const double *Rd_dx_h, const double *mle_fl,
+                             double *MLD_filtered, double *MLD_filtered_slow, double *uhml, double *vhml, double *utimescale,
+                             double *vtimescale, double *uDml, double *vDml, double *MLD_fast_out, double *MLD_slow_out,
+                             double *Rml_av_fast_out);
+/* A test hook: the device's mu(sigma, dh) (:717) at n values; sigma, dh and out are DEVICE arrays of n.                          */
+int mom6x_mixedlayer_restrat_mu(mom6x_ctx *ctx, const double *sigma, const double *dh, double *out, int n);
 
 /* ------------------------------------------------------------------------- */
 /* MOM_dynamics_split_RK2                                                    */

@@ -321,6 +321,36 @@ def varmix_params_default(GV=None, max_depth=4000.0, **kw):
     return p
 
 
+class MixedLayerRestratParams(C.Structure):
+    """mom6x_mixedlayer_restrat_params; the mixedlayer_restrat_CS members of mixedlayer_restrat_OM4 (MOM_mixed_layer_restrat.F90:37-140)."""
+    _fields_ = [("ml_restrat_coef", C.c_double), ("ml_restrat_coef2", C.c_double), ("front_length", C.c_double),
+                ("MLE_use_PBL_MLD", C.c_int), ("MLE_MLD_decay_time", C.c_double), ("MLE_MLD_decay_time2", C.c_double),
+                ("MLE_density_diff", C.c_double), ("MLE_tail_dh", C.c_double), ("MLE_MLD_stretch", C.c_double), ("vonKar", C.c_double),
+                ("ustar_min", C.c_double), ("use_Bodner", C.c_int), ("nkml", C.c_int), ("use_Stanley_ML", C.c_int),
+                ("non_Boussinesq", C.c_int), ("open_bcs", C.c_int), ("debug", C.c_int)]
+
+
+MIXEDLAYER_RESTRAT_MUST_BE_0 = ("use_Bodner", "nkml", "use_Stanley_ML", "non_Boussinesq", "open_bcs", "debug")
+
+
+def mixedlayer_restrat_params_default(GV=None, omega=7.2921e-5, **kw):
+    """mixedlayer_restrat_init :1784-1887 defaults (Boussinesq, unscaled units, NKML = 0): FOX_KEMPER_ML_RESTRAT_COEF and COEF2 = 0
+    (the routine then moves nothing), MLE_FRONT_LENGTH = 0, MLE_USE_PBL_MLD off, both decay times 0, MLE_DENSITY_DIFF = 0.03 kg m-3,
+    MLE_TAIL_DH = 0, MLE_MLD_STRETCH = 1, VON_KARMAN_CONST = 0.41, RESTRAT_USTAR_MIN = 2e-4*OMEGA*(Angstrom_Z + dZ_subroundoff)
+    in thickness units (:1882-1887)."""
+    GV = GV if GV is not None else vgrid_default()
+    p = MixedLayerRestratParams()
+    p.ml_restrat_coef = 0.0; p.ml_restrat_coef2 = 0.0; p.front_length = 0.0; p.MLE_use_PBL_MLD = 0
+    p.MLE_MLD_decay_time = 0.0; p.MLE_MLD_decay_time2 = 0.0; p.MLE_density_diff = 0.03; p.MLE_tail_dh = 0.0
+    p.MLE_MLD_stretch = 1.0; p.vonKar = 0.41
+    p.ustar_min = (2.0e-4 * omega * (GV.Angstrom_H * GV.H_to_Z + GV.dZ_subroundoff)) * GV.Z_to_H
+    for n in MIXEDLAYER_RESTRAT_MUST_BE_0:
+        setattr(p, n, 0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 class HorViscParams(C.Structure):
     """mom6x_hor_visc_params; hor_visc_CS (MOM_hor_visc.F90:36-259)."""
     _fields_ = [("Laplacian", C.c_int), ("biharmonic", C.c_int), ("Kh", C.c_double), ("Kh_bg_min", C.c_double),

@@ -140,6 +140,7 @@ extern "C" int mom6x_struct_size(int which) {
     case 19: return (int)sizeof(mom6x_thickness_diffuse_params);
     case 20: return (int)sizeof(mom6x_tracer_hor_diff_params);
     case 21: return (int)sizeof(mom6x_varmix_params);
+    case 22: return (int)sizeof(mom6x_mixedlayer_restrat_params);
     default: return -1;
   }
 }
@@ -220,6 +221,7 @@ extern "C" int mom6x_ctx_destroy(mom6x_ctx *c) {
   thickness_diffuse_free(c);
   tracer_hor_diff_free(c);
   varmix_free(c);
+  mixedlayer_restrat_free(c);
   (void)hipFree(c->regrid_res); (void)hipFree(c->regrid_vec); (void)hipFree(c->remap_src); (void)hipFree(c->remap_hvel);
   (void)hipFree(c->vv_a_u); (void)hipFree(c->vv_a_v); (void)hipFree(c->vv_h_u); (void)hipFree(c->vv_h_v);
   (void)hipFree(c->G); (void)hipFree(c->hL); (void)hipFree(c->hR); (void)hipFree(c->flag);

@@ -135,10 +135,12 @@ struct mom6x_ctx {
   const double *td_khth2d = nullptr; double *td_work = nullptr;
   void *thd = nullptr;      // tracer_hor_diff.hip: tracer_hor_diff_CS and the work arrays of mom6x_tracer_hor_diff_init (ThdState)
   void *vm = nullptr;       // lateral_mixing_coeffs.hip: VarMix_CS and the work arrays of mom6x_varmix_init (VmState)
+  void *mle = nullptr;      // mixed_layer_restrat.hip: mixedlayer_restrat_CS and the work arrays of mom6x_mixedlayer_restrat_init (MleState)
 };
 void thickness_diffuse_free(mom6x_ctx *c);                            // thickness_diffuse.hip
 void tracer_hor_diff_free(mom6x_ctx *c);                              // tracer_hor_diff.hip
 void varmix_free(mom6x_ctx *c);                                       // lateral_mixing_coeffs.hip
+void mixedlayer_restrat_free(mom6x_ctx *c);                           // mixed_layer_restrat.hip
 void comm_free(mom6x_ctx *c);                                         // halo.hip
 void halo_start(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n);   // start_group_pass
 void halo_complete(mom6x_ctx *c);                                     // complete_group_pass

@@ -352,6 +352,36 @@ class Dycore:
                                                             _ptr(N2_v), _ptr(dzu), _ptr(dzv), _ptr(dzSxN), _ptr(dzSyN), _ptr(S2_u),
                                                             _ptr(S2_v)))
 
+    # -- MOM_mixed_layer_restrat ---------------------------------------------------------------
+    def mixedlayer_restrat_init(self, params, eos):
+        """mixedlayer_restrat_init (MOM_mixed_layer_restrat.F90:1617) for the OM4 path; eos: tv%eqn_of_state (required)."""
+        self.mle_params = params
+        self._mle_eos = eos
+        check(self.lib, self.lib.mom6x_mixedlayer_restrat_init(self.ctx, C.byref(params), C.byref(eos) if eos is not None else None))
+
+    def mixedlayer_restrat(self, h, uhtr, vhtr, T, S, ustar, dt, h_MLD=None, Rd_dx_h=None, mle_fl=None, MLD_filtered=None,
+                           MLD_filtered_slow=None, uhml=None, vhml=None, utimescale=None, vtimescale=None, uDml=None, vDml=None,
+                           MLD_fast=None, MLD_slow=None, Rml_av_fast=None):
+        """mixedlayer_restrat (MOM_mixed_layer_restrat.F90:149): h, uhtr, vhtr and the two filtered planes in place; ustar is
+        forces%ustar; the arguments from uhml on are the diagnostics the reference posts."""
+        # the kernels index whole planes and whole 3-D arrays: a smaller buffer would be read and written past its end
+        n2 = self.dims.slab
+        for a in (ustar, h_MLD, Rd_dx_h, mle_fl, MLD_filtered, MLD_filtered_slow, utimescale, vtimescale, uDml, vDml, MLD_fast, MLD_slow,
+                  Rml_av_fast):
+            assert a is None or a.numel() == n2, "need a 2-D plane of the tile"
+        for a in (h, uhtr, vhtr, T, S, uhml, vhml):
+            assert a is None or a.numel() == n2 * self.dims.nk, "need a 3-D array of the tile"
+        check(self.lib, self.lib.mom6x_mixedlayer_restrat(
+            self.ctx, _ptr(h), _ptr(uhtr), _ptr(vhtr), _ptr(T), _ptr(S), _ptr(ustar), C.c_double(dt), _ptr(h_MLD), _ptr(Rd_dx_h),
+            _ptr(mle_fl), _ptr(MLD_filtered), _ptr(MLD_filtered_slow), _ptr(uhml), _ptr(vhml), _ptr(utimescale), _ptr(vtimescale),
+            _ptr(uDml), _ptr(vDml), _ptr(MLD_fast), _ptr(MLD_slow), _ptr(Rml_av_fast)))
+
+    def mixedlayer_restrat_mu(self, sigma, dh, out):
+        """The device's mu(sigma, dh) (MOM_mixed_layer_restrat.F90:717) at the values of two 1-D device arrays: a test hook."""
+        n = sigma.numel()
+        assert dh.numel() == n and out.numel() == n
+        check(self.lib, self.lib.mom6x_mixedlayer_restrat_mu(self.ctx, _ptr(sigma), _ptr(dh), _ptr(out), C.c_int(n)))
+
     def vertvisc_field(self, name):
         """CS%a_u / a_v / h_u / h_v of the device vertvisc_CS as a torch view."""
         which = ["a_u", "a_v", "h_u", "h_v"].index(name)
