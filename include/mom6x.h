@@ -346,6 +346,9 @@ typedef struct mom6x_ctx mom6x_ctx;
 
 const char *mom6x_last_error(void);
 int  mom6x_abi_version(void);
+/* The work-group (lanes along i, rows) of the kernels that give each cell or face of a plane a lane, and the i of their first lane
+ * (a cache line before the first own point).  For tests that place a grid's edges where a launch extent rounds up to another block. */
+int  mom6x_lane_launch_shape(int *bx, int *by, int *i_first);
 /* hipGetDeviceCount: lets a host with one process per GPU pick its device as (local rank) mod (count).  < 0 on error. */
 int  mom6x_device_count(void);
 /* sizeof() of the public structs (0 dims, 1 vgrid, 2 continuity_params, 3 BT_cont, 4 barotropic_params,

@@ -598,3 +598,12 @@ def check(lib, rc):
     if rc != MOM6X_OK:
         msg = lib.mom6x_last_error()
         raise Mom6xError(f"mom6x error {rc}: {msg.decode() if msg else ''}")
+
+
+def lane_launch_shape(lib=None):
+    """(lanes along i, rows, i of the first lane) of the work-groups of the one-lane-per-face kernels: mom6x_lane_launch_shape.
+    Needs the library, not a GPU."""
+    lib = lib or load_library()
+    bx, by, i0 = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(lib, lib.mom6x_lane_launch_shape(C.byref(bx), C.byref(by), C.byref(i0)))
+    return bx.value, by.value, i0.value

@@ -109,6 +109,15 @@ void mom6x_set_error(const char *fmt, ...) {
 
 extern "C" const char *mom6x_last_error(void) { return g_err; }
 extern "C" int mom6x_abi_version(void) { return MOM6X_ABI_VERSION; }
+
+// the work-group and the first lane of the one-lane-per-face kernels (mom6x_dev.h), for tests that place a grid's edges around them
+extern "C" int mom6x_lane_launch_shape(int *bx, int *by, int *i_first) {
+  if (bx) *bx = LANE_BX;
+  if (by) *by = LANE_BY;
+  if (i_first) *i_first = -IAL;
+  return MOM6X_OK;
+}
+
 extern "C" int mom6x_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) { mom6x_set_error("mom6x_device_count: hipGetDeviceCount failed"); return -1; }

@@ -347,7 +347,7 @@ extern "C" int mom6x_varmix_init(mom6x_ctx *c, const mom6x_varmix_params *p, con
     double L2;
     if (p->Visbeck_L_scale < 0) { const double t = p->L_to_m * p->Visbeck_L_scale; L2 = t * t; }
     else L2 = p->Visbeck_L_scale * p->Visbeck_L_scale;
-    const dim3 b(64, 4, 1);
+    const dim3 b = blk2();
     KLAUNCH(c, "k_vm_L2", k_vm_L2, grid3(d.pitch, nrows, 1, b), b, d, c->G, L2, p->Visbeck_L_scale < 0 ? 1 : 0, nrows, L2u, L2v);
     HIPCHK(hipGetLastError());
   }
@@ -399,7 +399,7 @@ extern "C" int mom6x_calc_slope_functions(mom6x_ctx *c, const double *h, const d
   if (slopes && s->use_eos) { pres = W; Tf = W + n3; Sf = W + 2 * n3; c1 = W + 3 * n3; W += 4 * n3; }
   const bool fill = use_eos && K.kap_dt_x2 > 0.0;               // else T_f = T_in (:661-665): read in place
   REQUIRE(!fill || nz >= 2, MOM6X_EINVAL, "calc_slope_functions: vert_fill_TS needs two layers");
-  const dim3 b(64, 4, 1);
+  const dim3 b = blk2();
   KLAUNCH(c, "k_vm_cols", k_vm_cols, grid3(d.ni + 2 + IAL, d.nj + 4, 1, b), b, d, c->G, K, h, T, S, p_surf, e, use_eos ? pres : nullptr,
           fill ? Tf : nullptr, Sf, c1);
   if (!slopes) {

@@ -354,7 +354,7 @@ extern "C" int mom6x_mixedlayer_restrat(mom6x_ctx *c, double *h, double *uhtr, d
   double *htot_f = W, *htot_s = W + n2, *Rml_f = W + 2 * n2, *Rml_s = W + 3 * n2;
   if (!uhml) uhml = W + 4 * n2;
   if (!vhml) vhml = W + 4 * n2 + n3;
-  const dim3 b(64, 4, 1);
+  const dim3 b = blk2();
 #define MLC(F)                                                                                                                   \
   KLAUNCH(c, "k_mle_cols<" #F ">", (k_mle_cols<F>), grid3(d.ni + 1 + IAL, d.nj + 2, 1, b), b, d, K, h, T, S, h_MLD, MLD_filtered, \
           MLD_filtered_slow, htot_f, htot_s, Rml_f, Rml_s, MLD_fast_out, MLD_slow_out, Rml_av_fast_out)

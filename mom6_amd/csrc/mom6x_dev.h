@@ -219,6 +219,10 @@ inline int nchunks(int nk) { return (nk + KCHUNK - 1) / KCHUNK; }
 // whole cache lines instead of sharing its first and last line with the neighbouring block (which usually runs
 // on another XCD, i.e. behind another L2).  Lanes below I0 exit.  nxa() is the matching grid extent.
 #define IAL 16
+// The work-group of those kernels and of the other i-parallel ones (blk2()): a wavefront along i, LANE_BY rows.  With IAL it fixes
+// where a launch extent rounds up to another block; mom6x_lane_launch_shape() hands the three to the tests that sit on those edges.
+#define LANE_BX 64
+#define LANE_BY 4
 #define I_BASE(I0) (((I0) < 0) ? -IAL : (I0))
 inline int nxa(int nx, int I0) { return (I0 < 0) ? nx + IAL + I0 : nx; }
 
@@ -242,7 +246,7 @@ __device__ __forceinline__ FaceLane face_lane(const Dm &d) {
 inline dim3 grid3(int nx, int ny, int nz, dim3 b) {
   return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y, (nz + b.z - 1) / b.z);
 }
-inline dim3 blk2() { return dim3(64, 4, 1); }   // the work-group of the i-parallel kernels: a wavefront along i, four rows
+inline dim3 blk2() { return dim3(LANE_BX, LANE_BY, 1); }   // the work-group of the i-parallel kernels: a wavefront along i, four rows
 inline dim3 gridk(int nx, int ny, int nk, dim3 b) { return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y, nchunks(nk)); }
 
 // The kernels that keep a whole column on chip (registers + LDS: k_vertvisc_coef_cols, k_vertvisc_cols, k_vertvisc_remnant_cols,

@@ -288,7 +288,7 @@ extern "C" int mom6x_set_viscous_BBL(mom6x_ctx *c, const double *u, const double
     HIPCHK(hipMemsetAsync(Ray_u, 0, (size_t)d.nk * d.slab * sizeof(double), c->stream));
     HIPCHK(hipMemsetAsync(Ray_v, 0, (size_t)d.nk * d.slab * sizeof(double), c->stream));
   }
-  const dim3 b(64, 4, 1), g = grid3(d.ni + IAL, d.nj + 1, 2, dim3(64, 4, 1));
+  const dim3 b = blk2(), g = grid3(d.ni + IAL, d.nj + 1, 2, b);
 #define SVB(F)                                                                                                              \
   KLAUNCH(c, "k_set_viscous_BBL<" #F ">", k_set_viscous_BBL<F>, g, b, d, c->G, K, u, v, h, T, S, p_surf, c->sv_tideamp,      \
           c->Rlay, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Ray_u, Ray_v)

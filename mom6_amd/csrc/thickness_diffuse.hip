@@ -252,7 +252,7 @@ extern "C" int mom6x_thickness_diffuse(mom6x_ctx *c, double *h, double *uhtr, do
   double *pres = derivs ? W + 4 * n3 : nullptr;
   const bool fill = derivs && K.kap_dt_x2 > 0.0;               // else T_f = T_in (MOM_isopycnal_slopes.F90:661-665): read in place
   double *Tf = fill ? W + 5 * n3 : nullptr, *Sf = fill ? W + 6 * n3 : nullptr;
-  const dim3 b(64, 4, 1);
+  const dim3 b = blk2();
   KLAUNCH(c, "k_td_cols", k_td_cols, grid3(d.ni + 1 + IAL, d.nj + 2, 1, b), b, d, c->G, K, h, T, S, p_surf, rsum, hfrac, pres, Tf,
           Sf, W);   // (c1 lives in the uhD work array until the face pass)
   const double *Tr = fill ? Tf : T, *Sr = fill ? Sf : S;

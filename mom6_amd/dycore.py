@@ -331,6 +331,11 @@ class Dycore:
         check(self.lib, self.lib.mom6x_tracer_hordiff_tile(C.byref(tx), C.byref(ty), C.byref(mt)))
         return tx.value, ty.value, mt.value
 
+    def lane_launch_shape(self):
+        """(lanes along i, rows, i of the first lane) of the work-groups of the one-lane-per-face kernels (set_viscous_BBL,
+        thickness_diffuse, calc_slope_functions, mixedlayer_restrat)."""
+        return abi.lane_launch_shape(self.lib)
+
     # -- MOM_lateral_mixing_coeffs -------------------------------------------------------------
     def varmix_init(self, params, eos=None, Rlay=None, g_prime=None, L2u=None, L2v=None):
         """VarMix_init (MOM_lateral_mixing_coeffs.F90:1445) for calc_slope_functions; eos: tv%eqn_of_state (None: layers of constant

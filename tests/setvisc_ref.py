@@ -255,7 +255,8 @@ def set_viscous_BBL(d, M, GV, P, u, v, h, T=None, S=None, p_surf=None, eos=None,
 
 def inputs(d, M, GV, seed=5, strat=1.0, vanish=True, u_max=0.3):
     """u, v, h, T, S (a stratification scaled by `strat`), p_surf and tideamp on a tile; with `vanish` the two bottom layers of a
-    band of columns are Angstrom thin (vanished layers in the near-bottom walk)."""
+    band of rows are Angstrom thin (vanished layers in the near-bottom walk).  The band is laid in global coordinates, like every
+    other field here, so that a tile of any layout sees its part of the one-tile state."""
     from mom6_amd import synth
     h, u, v = synth.make_state(d, M, seed=20250808 + seed, u_max=u_max, h_pert=0.01)
     T = np.zeros_like(h); S = np.zeros_like(h)
@@ -263,8 +264,9 @@ def inputs(d, M, GV, seed=5, strat=1.0, vanish=True, u_max=0.3):
         T[k] = 10.0 + strat * (10.0 - 15.0 * k / max(d.nk - 1, 1) + 0.8 * synth.smooth_field(d, seed + k, ox=0.5, oy=0.5))
         S[k] = 34.5 + strat * (1.0 * k / max(d.nk - 1, 1) - 0.5 + 0.2 * synth.smooth_field(d, seed + 100 + k, ox=0.5, oy=0.5))
     if vanish and d.nk > 2:
-        band = np.zeros(d.shape2(), bool)
-        band[d.sl(-1, d.ni, d.nj // 3, d.nj // 2)] = True
+        ig = np.arange(d.pitch) - d.ioff + d.i_glob0
+        jg = np.arange(d.shape2()[0]) - d.joff + d.j_glob0
+        band = ((jg >= d.nj_glob // 3) & (jg <= d.nj_glob // 2))[:, None] & ((ig >= -1) & (ig <= d.ni_glob))[None, :]
         for k in (d.nk - 2, d.nk - 1):
             h[k] = np.where(band, GV.Angstrom_H, h[k])
     p_surf = 1.0e4 * (1.0 + 0.2 * synth.smooth_field(d, seed + 300, ox=0.5, oy=0.5))

@@ -279,7 +279,7 @@ STAG = dict(h="h", uhtr="u", vhtr="v", uhml="u", vhml="v", utimescale="u", vtime
 
 @pytest.mark.parametrize("name", ["both_filters", "front_plane"])
 def test_tile_cuts(name, orc):
-    """Each tile of a 2 x 1 and of a 1 x 2 layout, on its cut of the inputs with the filtered planes cut from the one-tile state
+    """Each tile of a 2 x 1, of a 1 x 2 and of a 2 x 2 layout, on its cut of the inputs with the filtered planes cut from the one-tile state
     (one halo point is read), gives its own points of the one-tile result; the filtered planes and the h-point diagnostics also one
     point into the halo."""
     GV = abi.vgrid_default()

@@ -1,8 +1,8 @@
 """mom6x_mixedlayer_restrat on the device (mom6_amd/csrc/mixed_layer_restrat.hip) against the restatement tests/mle_ref.py, bit for
 bit and on whole arrays with no tolerated signed zero (every diagnostic starts as NaN, so the points the reference leaves alone are
 checked too): every case with MLE_TAIL_DH = 0 on coasts, narrowed faces, vanished layers and an equator; every EOS form; layer
-counts; a -0 planted in uhtr; consecutive calls that carry the filtered planes, also into a fresh context; 2 x 1 and 1 x 2 tile
-cuts; the device's mu; refused settings and error paths; the chain from mom6x_thickness_diffuse on device pointers.  The one case
+counts; a -0 planted in uhtr; consecutive calls that carry the filtered planes, also into a fresh context; 2 x 1, 1 x 2 and 2 x 2
+tile cuts; the device's mu; refused settings and error paths; the chain from mom6x_thickness_diffuse on device pointers.  The one case
 with MLE_TAIL_DH > 0 evaluates a pow and is held to the project's bound for its other pow site (tests/test_barotropic_gpu.py)."""
 import functools
 
@@ -25,12 +25,15 @@ def _call(dy, t, P, dt, given, dg):
                           MLD_filtered_slow=t["MLD_filtered_slow"], **{n: t[n] for n in given}, **dg)
 
 
-def _device(d, M, GV, P, inp, dt, eos, given, give_diag, fill=np.nan, ncalls=1):
+def _device(d, M, GV, P, inp, dt, eos, given, give_diag, fill=np.nan, ncalls=1, dy=None):
     """One mom6x_mixedlayer_restrat_init and `ncalls` mom6x_mixedlayer_restrat calls on inputs that live on the host; every
-    diagnostic starts as `fill`.  Returns the state and the diagnostics of the last call."""
+    diagnostic starts as `fill`.  Returns the state and the diagnostics of the last call.  In a context of its own, or in the
+    caller's `dy`, which is then left open."""
     import torch
     from mom6_amd.dycore import Dycore
-    dy = Dycore(d, M, GV)
+    own = dy is None
+    if own:
+        dy = Dycore(d, M, GV)
     try:
         t = {n: dy.to_dev(a) for n, a in inp.items()}
         dg = {n: dy.to_dev(a) for n, a in R.outputs(d, give_diag, fill).items()}
@@ -45,7 +48,8 @@ def _device(d, M, GV, P, inp, dt, eos, given, give_diag, fill=np.nan, ncalls=1):
         out.update({n: a.cpu().numpy() for n, a in dg.items()})
         return out
     finally:
-        dy.close()
+        if own:
+            dy.close()
 
 
 @functools.lru_cache(maxsize=None)
@@ -176,7 +180,7 @@ def _one_tile_device(name):
 
 @pytest.mark.parametrize("layout,pe", TILES)
 def test_tile_cuts(layout, pe, orc):
-    """Each tile of a 2 x 1 and of a 1 x 2 layout, called on its cut of the inputs with the filtered planes cut from the one-tile
+    """Each tile of a 2 x 1, of a 1 x 2 and of a 2 x 2 layout, called on its cut of the inputs with the filtered planes cut from the one-tile
     state: whole arrays bit for bit against the restatement on the same tile, and its own points equal to the one-tile result of
     the device, the filtered planes and the h-point diagnostics one point into the halo."""
     name = "both_filters"

@@ -162,3 +162,26 @@ def test_unit_scaling_by_2_to_the_11():
             got, _ = R.run(d, M2, GV2, P2, in2, eos=eos, Rlay=Rlay * Rr, give_ps=ps, give_ray=ray, fill=0.0)
             for n in ref:
                 _bits(got[n] * un[n.rsplit("_", 1)[0]], ref[n], f"{name}.{dim}:{n}")
+
+
+def test_tile_cuts():
+    """Each tile of a 2 x 1 and of a 2 x 2 layout, on its cut of the inputs (one halo point is read), gives its own faces of the
+    one-tile result.  The 2 x 2 cut puts open water in the halo corner that set_v_at_u and set_u_at_v read (v(i+1, J-1) of a u
+    face), which on the closed grids is land."""
+    from tests.test_thickness_diffuse_cpu import CUT_TILES, cut
+    GV = abi.vgrid_default()
+    d, M = _grid(nk=8)
+    Rlay, _ = abi.layer_densities(d.nk)
+    inp = R.inputs(d, M, GV)
+    for name in ("eos", "body", "tidal", "rlay"):
+        P, eos, ps, ray, _ = R.switch_case(name, form=abi.WRIGHT)
+        one, _ = R.run(d, M, GV, P, inp, eos=eos, Rlay=Rlay, give_ps=ps, give_ray=ray)
+        for layout, pe in CUT_TILES:
+            dt, Mt = H.benchmark_small(nk=8, layout=layout, pe=pe)[1:]
+            tile, _ = R.run(dt, Mt, GV, P, R.inputs(dt, Mt, GV), eos=eos, Rlay=Rlay, give_ps=ps, give_ray=ray)
+            for n in one:
+                slt, slg = cut(None, d, dt, n[-1])
+                _bits(tile[n][..., slt[0], slt[1]], one[n][..., slg[0], slg[1]], f"tile {layout} {pe} {name}:{n}")
+            if layout == (2, 2):      # the corner that points to the middle of the basin is open water
+                ci, cj = (dt.ni if pe[0] == 0 else -1), (dt.nj if pe[1] == 0 else -1)
+                assert Mt[G["mask2dT"]][dt.joff + cj, dt.ioff + ci] > 0

@@ -1,23 +1,27 @@
 """mom6x_set_viscous_BBL on the device (mom6_amd/csrc/set_visc.hip) against the restatement tests/setvisc_ref.py, bit for bit:
 every switch set and EOS form on coasts, narrowed faces and vanished bottom layers; the faces it must leave alone; the headline
-grid's quarter turn, unit scaling and bounds; and a 2 x 1 tile cut of the same problem."""
+grid's quarter turn, unit scaling and bounds; and 2 x 1 and 2 x 2 tile cuts of the same problem."""
 import numpy as np
 import pytest
 
 from mom6_amd import abi
 from tests import helpers as H
 from tests import setvisc_ref as R
+from tests.test_thickness_diffuse_cpu import CUT_TILES, cut
 
 pytestmark = pytest.mark.gpu
 G = abi.G
 FORMS = (abi.LINEAR, abi.WRIGHT, abi.WRIGHT_FULL, abi.WRIGHT_REDUCED, abi.UNESCO, abi.ROQUET_RHO, abi.JACKETT06, abi.ROQUET_SPV)
 
 
-def _device(d, M, GV, P, inp, eos=None, Rlay=None, give_ps=False, give_ray=False, fill=np.nan):
-    """One mom6x_set_viscous_BBL call on inputs that live on the host; outputs start as `fill`."""
+def _device(d, M, GV, P, inp, eos=None, Rlay=None, give_ps=False, give_ray=False, fill=np.nan, dy=None):
+    """One mom6x_set_viscous_BBL call on inputs that live on the host; outputs start as `fill`.  In a context of its own, or in
+    the caller's `dy`, which is then left open."""
     import torch
     from mom6_amd.dycore import Dycore
-    dy = Dycore(d, M, GV)
+    own = dy is None
+    if own:
+        dy = Dycore(d, M, GV)
     try:
         if Rlay is not None:
             dy.PressureForce_init(abi.pgf_params_default(GV.Rho0), Rlay, np.full(d.nk, GV.g_Earth))
@@ -32,7 +36,8 @@ def _device(d, M, GV, P, inp, eos=None, Rlay=None, give_ps=False, give_ray=False
         dy.sync()
         return {n: a.cpu().numpy() for n, a in out.items()}
     finally:
-        dy.close()
+        if own:
+            dy.close()
 
 
 def _bits(a, b, name):
@@ -133,8 +138,9 @@ def test_off_and_refused_settings():
 
 
 def test_tile_cut_2x1():
-    """Each tile of a 2 x 1 layout, called on its cut of the inputs (halos included), gives its part of the one-tile result,
-    the west and south edge faces (I = isc-1, J = jsc-1) included."""
+    """Each tile of a 2 x 1 and of a 2 x 2 layout, called on its cut of the inputs (halos included), gives its part of the one-tile
+    result, the west and south edge faces (I = isc-1, J = jsc-1) included.  The 2 x 2 cut is the one with open water in a halo
+    corner next to a coast: v(i+1, J-1) of a u face, u(I-1, j+1) of a v face."""
     GV = abi.vgrid_default()
     d, M = H.benchmark_small(nk=8)[1:]
     inp = R.inputs(d, M, GV)
@@ -142,20 +148,16 @@ def test_tile_cut_2x1():
         P, eos, ps, ray, _ = R.switch_case(name, form=abi.WRIGHT)
         Rlay, _ = abi.layer_densities(d.nk)
         one = _device(d, M, GV, P, inp, eos=eos, Rlay=Rlay, give_ps=ps, give_ray=ray)
-        for px in (0, 1):
-            gg, dt, Mt = H.benchmark_small(nk=8, layout=(2, 1), pe=(px, 0))
+        for layout, pe in CUT_TILES:
+            gg, dt, Mt = H.benchmark_small(nk=8, layout=layout, pe=pe)
             it = R.inputs(dt, Mt, GV)
-            i0 = dt.i_glob0
             for s in "uv":
-                slt = H.interior(dt, s)
-                slg = (slt[0], slice(slt[1].start + i0 - dt.ioff + d.ioff, slt[1].stop + i0 - dt.ioff + d.ioff))
+                slt, slg = cut(None, d, dt, s)
                 _bits(it["u" if s == "u" else "v"][:, slt[0], slt[1]], inp[s][:, slg[0], slg[1]], f"input {s}")
             tile = _device(dt, Mt, GV, P, it, eos=eos, Rlay=Rlay, give_ps=ps, give_ray=ray)
             for n in one:
-                s = n[-1]
-                slt = H.interior(dt, s)
-                slg = (slt[0], slice(slt[1].start + i0 - dt.ioff + d.ioff, slt[1].stop + i0 - dt.ioff + d.ioff))
-                _bits(tile[n][..., slt[0], slt[1]], one[n][..., slg[0], slg[1]], f"tile {px} {name}:{n}")
+                slt, slg = cut(None, d, dt, n[-1])
+                _bits(tile[n][..., slt[0], slt[1]], one[n][..., slg[0], slg[1]], f"tile {layout} {pe} {name}:{n}")
 
 
 # -- the headline grid, device only ----------------------------------------------------------------------------------------------

@@ -225,11 +225,16 @@ def test_unit_scaling_by_2_to_the_11(name, dims, orc):
 
 
 def cut(one, d, dt_, s):
-    """The part of a one-tile array that a tile's points of stagger `s` cover, and the tile's own slices."""
+    """The part of a one-tile array that a tile's points of stagger `s` cover (a cut in x, in y or in both), and the tile's own
+    slices."""
     slt = H.interior(dt_, s)
-    i0 = dt_.i_glob0
-    slg = (slt[0], slice(slt[1].start + i0 - dt_.ioff + d.ioff, slt[1].stop + i0 - dt_.ioff + d.ioff))
+    i0, j0 = dt_.i_glob0 - dt_.ioff + d.ioff, dt_.j_glob0 - dt_.joff + d.joff
+    slg = (slice(slt[0].start + j0, slt[0].stop + j0), slice(slt[1].start + i0, slt[1].stop + i0))
     return slt, slg
+
+
+# both tiles of the 2 x 1 layout and the four of the 2 x 2 one: the only cut with open water in a halo corner next to a coast
+CUT_TILES = [((2, 1), (0, 0)), ((2, 1), (1, 0)), ((2, 2), (0, 0)), ((2, 2), (1, 0)), ((2, 2), (0, 1)), ((2, 2), (1, 1))]
 
 
 @pytest.mark.parametrize("name", ["eos", "noeos", "gm"])
@@ -237,13 +242,13 @@ def test_tile_cut_2x1(name, orc):
     GV = abi.vgrid_default()
     d, M = H.benchmark_small(nk=8)[1:]
     _, one, _, _ = _case_run(d, M, GV, name, orc=orc)
-    for px in (0, 1):
-        dt_, Mt = H.benchmark_small(nk=8, layout=(2, 1), pe=(px, 0))[1:]
+    for layout, pe in CUT_TILES:
+        dt_, Mt = H.benchmark_small(nk=8, layout=layout, pe=pe)[1:]
         _, tile, _, _ = _case_run(dt_, Mt, GV, name, orc=orc)
         for n in one:
             s = {"h": "h", "uhtr": "u", "vhtr": "v", "uhGM": "u", "vhGM": "v"}[n]
             slt, slg = cut(one, d, dt_, s)
-            _bits(tile[n][:, slt[0], slt[1]], one[n][:, slg[0], slg[1]], f"tile {px} {name}:{n}")
+            _bits(tile[n][:, slt[0], slt[1]], one[n][:, slg[0], slg[1]], f"tile {layout} {pe} {name}:{n}")
 
 
 REQUIRED = ("bottom_zero_pos", "bottom_zero_neg", "bottom_scale_pos", "bottom_scale_neg", "mag_grad2_zero", "rsum_clip_lo",

@@ -1,6 +1,6 @@
 """mom6x_thickness_diffuse on the device (mom6_amd/csrc/thickness_diffuse.hip) against the restatement tests/thickdiff_ref.py,
 bit for bit: every switch set and EOS form on coasts, narrowed faces and vanished layers, whole arrays included; layer counts
-around the edges of the column pass; 360 x 180 x 75; refused settings; a 2 x 1 tile cut; the headline grid's quarter turn, unit
+around the edges of the column pass; 360 x 180 x 75; refused settings; 2 x 1 and 2 x 2 tile cuts; the headline grid's quarter turn, unit
 scaling and bounds; and four coupled dynamics steps with tracer advection in the order of step_MOM."""
 import numpy as np
 import pytest
@@ -8,7 +8,7 @@ import pytest
 from mom6_amd import abi
 from tests import helpers as H
 from tests import thickdiff_ref as R
-from tests.test_thickness_diffuse_cpu import GRIDS, REQUIRED, cut, scaled
+from tests.test_thickness_diffuse_cpu import CUT_TILES, GRIDS, REQUIRED, cut, scaled
 
 pytestmark = pytest.mark.gpu
 G = abi.G
@@ -16,11 +16,14 @@ FORMS = (abi.LINEAR, abi.WRIGHT, abi.WRIGHT_FULL, abi.WRIGHT_REDUCED, abi.UNESCO
 CASES = [(n, None) for n in R.CASES if n != "eos"] + [("eos", f) for f in FORMS]
 
 
-def _device(d, M, GV, P, inp, dt, eos=None, give_ps=False, stored=False, give_gm=False, fill=np.nan):
-    """One mom6x_thickness_diffuse call on inputs that live on the host; uhGM, vhGM start as `fill`."""
+def _device(d, M, GV, P, inp, dt, eos=None, give_ps=False, stored=False, give_gm=False, fill=np.nan, dy=None):
+    """One mom6x_thickness_diffuse call on inputs that live on the host; uhGM, vhGM start as `fill`.  In a context of its own, or
+    in the caller's `dy`, which is then left open."""
     import torch
     from mom6_amd.dycore import Dycore
-    dy = Dycore(d, M, GV)
+    own = dy is None
+    if own:
+        dy = Dycore(d, M, GV)
     try:
         t = {n: dy.to_dev(a) for n, a in inp.items()}
         dy.thickness_diffuse_init(P, eos, t["khth2d"] if P.read_khth else None)
@@ -32,7 +35,8 @@ def _device(d, M, GV, P, inp, dt, eos=None, give_ps=False, stored=False, give_gm
         out = dict(h=t["h"], uhtr=t["uhtr"], vhtr=t["vhtr"], **gm)
         return {n: a.cpu().numpy() for n, a in out.items()}
     finally:
-        dy.close()
+        if own:
+            dy.close()
 
 
 def _bits(a, b, name):
@@ -152,19 +156,19 @@ def test_off_and_refused_settings():
 
 @pytest.mark.parametrize("name", ["eos", "noeos", "gm", "khth2d"])
 def test_tile_cut_2x1(name, orc):
-    """Each tile of a 2 x 1 layout, called on its cut of the inputs (halos included), gives its part of the one-tile result, the
-    west and south edge faces (I = isc-1, J = jsc-1) included."""
+    """Each tile of a 2 x 1 and of a 2 x 2 layout, called on its cut of the inputs (halos included), gives its part of the one-tile
+    result, the west and south edge faces (I = isc-1, J = jsc-1) included."""
     GV = abi.vgrid_default()
     d, M = H.benchmark_small(nk=8)[1:]
     P, eos, ps, stored, gm, dt, opts = R.case(name, form=abi.WRIGHT)
     one = _device(d, M, GV, P, R.inputs(d, M, GV, **opts), dt, eos=eos, give_ps=ps, stored=stored, give_gm=gm)
-    for px in (0, 1):
-        dt_, Mt = H.benchmark_small(nk=8, layout=(2, 1), pe=(px, 0))[1:]
+    for layout, pe in CUT_TILES:
+        dt_, Mt = H.benchmark_small(nk=8, layout=layout, pe=pe)[1:]
         tile = _device(dt_, Mt, GV, P, R.inputs(dt_, Mt, GV, **opts), dt, eos=eos, give_ps=ps, stored=stored, give_gm=gm)
         for n in one:
             s = {"h": "h", "uhtr": "u", "vhtr": "v", "uhGM": "u", "vhGM": "v"}[n]
             slt, slg = cut(one, d, dt_, s)
-            _bits(tile[n][:, slt[0], slt[1]], one[n][:, slg[0], slg[1]], f"tile {px} {name}:{n}")
+            _bits(tile[n][:, slt[0], slt[1]], one[n][:, slg[0], slg[1]], f"tile {layout} {pe} {name}:{n}")
 
 
 # -- the headline grid, device only ----------------------------------------------------------------------------------------------

@@ -239,13 +239,16 @@ def cut2(d, dt_, s):
     return slt, slg
 
 
-TILES = [((2, 1), (0, 0)), ((2, 1), (1, 0)), ((1, 2), (0, 0)), ((1, 2), (0, 1))]
+# (2, 2): the only cut with open water in a halo corner next to a coast (the four-face averages read those corners)
+TILES = [((2, 1), (0, 0)), ((2, 1), (1, 0)), ((1, 2), (0, 0)), ((1, 2), (0, 1)),
+         ((2, 2), (0, 0)), ((2, 2), (1, 0)), ((2, 2), (0, 1)), ((2, 2), (1, 1))]
 
 
 @pytest.mark.parametrize("name", ["eady_diag", "visbeck_diag", "just_e"])
 def test_tile_cuts(name, orc):
-    """Each tile of a 2 x 1 and of a 1 x 2 layout, on its cut of the inputs (halos two wide and more), gives its own faces of the
-    one-tile result.  The y cut puts open water on a tile's rows jsc-1 and jec+1 (the grids have a rim of land there)."""
+    """Each tile of a 2 x 1, of a 1 x 2 and of a 2 x 2 layout, on its cut of the inputs (halos two wide and more), gives its own
+    faces of the one-tile result.  The y cut puts open water on a tile's rows jsc-1 and jec+1 (the grids have a rim of land
+    there), the 2 x 2 cut also in the halo corner that points to the middle of the basin."""
     GV = abi.vgrid_default()
     d, M = H.benchmark_small(nk=8)[1:]
     _, _, one, _ = _case_run(d, M, GV, name, orc=orc)

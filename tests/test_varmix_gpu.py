@@ -1,7 +1,7 @@
 """mom6x_calc_slope_functions on the device (mom6_amd/csrc/lateral_mixing_coeffs.hip) against the restatement tests/varmix_ref.py,
 bit for bit and on whole arrays (every output starts as NaN, so the points the reference leaves alone are checked too): every case
 of the list and EOS form on coasts, narrowed faces and vanished layers; layer counts around the edges of the column pass; L2u, L2v
-of the init call; refused settings and error paths; 2 x 1 and 1 x 2 tile cuts; and the chain into mom6x_thickness_diffuse and
+of the init call; refused settings and error paths; 2 x 1, 1 x 2 and 2 x 2 tile cuts; and the chain into mom6x_thickness_diffuse and
 mom6x_tracer_hordiff with device pointers handed on."""
 import functools
 
@@ -18,12 +18,14 @@ pytestmark = pytest.mark.gpu
 G = abi.G
 
 
-def _device(d, M, GV, P, inp, dt, eos=None, give_ps=False, give_diag=False, fill=np.nan):
+def _device(d, M, GV, P, inp, dt, eos=None, give_ps=False, give_diag=False, fill=np.nan, dy=None):
     """One mom6x_varmix_init and one mom6x_calc_slope_functions call on inputs that live on the host; every output starts as
-    `fill`."""
+    `fill`.  In a context of its own, or in the caller's `dy`, which is then left open."""
     import torch
     from mom6_amd.dycore import Dycore
-    dy = Dycore(d, M, GV)
+    own = dy is None
+    if own:
+        dy = Dycore(d, M, GV)
     try:
         t = {n: dy.to_dev(a) for n, a in inp.items()}
         out = {n: dy.to_dev(a) for n, a in R.outputs(d, P, give_diag, fill).items()}
@@ -36,7 +38,8 @@ def _device(d, M, GV, P, inp, dt, eos=None, give_ps=False, give_diag=False, fill
             _bits(t[n].cpu().numpy(), inp[n], n + " is only read")
         return {n: a.cpu().numpy() for n, a in out.items()}
     finally:
-        dy.close()
+        if own:
+            dy.close()
 
 
 @functools.lru_cache(maxsize=None)
@@ -192,10 +195,11 @@ def test_off_and_refused_settings():
 @pytest.mark.parametrize("layout,pe", TILES)
 @pytest.mark.parametrize("name", ["eady_diag", "visbeck_diag", "just_e"])
 def test_tile_cuts(name, layout, pe):
-    """Each tile of a 2 x 1 and of a 1 x 2 layout, called on its cut of the inputs with the halos of h, T, S filled (two points are
-    read): whole arrays bit for bit against the restatement on the same tile -- the y cut puts open water on the rows jsc-1 and
-    jec+1, the x cut on the columns isc-1 and iec+1, which on the closed grids are land -- and its own faces, the west and south
-    edge faces (I = isc-1, J = jsc-1) included, equal to the one-tile result of the device."""
+    """Each tile of a 2 x 1, of a 1 x 2 and of a 2 x 2 layout, called on its cut of the inputs with the halos of h, T, S filled (two
+    points are read): whole arrays bit for bit against the restatement on the same tile -- the y cut puts open water on the rows
+    jsc-1 and jec+1, the x cut on the columns isc-1 and iec+1, the 2 x 2 cut on both and on the halo corner between them, which on
+    the closed grids are land -- and its own faces, the west and south edge faces (I = isc-1, J = jsc-1) included, equal to the
+    one-tile result of the device."""
     from oracle import orc
     orc.build()
     GV = abi.vgrid_default()
