@@ -34,7 +34,7 @@ module mom6x_c_api
   public :: mom6x_initialize_dyn_split_RK2, mom6x_dyn_split_RK2_new_run, mom6x_dyn_split_RK2_restart_fills, mom6x_rk2_field, mom6x_rk2_set_CAu_pred_stored
   public :: mom6x_step_dyn_split_RK2, mom6x_comm_unique_id, mom6x_comm_init, mom6x_pass_fields
   public :: mom6x_transport, mom6x_comm_set_transport
-  public :: mom6x_abi_version, mom6x_device_count, MOM6X_ABI_BUILT_FOR, mom6x_barotropic_field, mom6x_lane_launch_shape
+  public :: mom6x_abi_version, mom6x_device_count, MOM6X_ABI_BUILT_FOR, mom6x_barotropic_field, mom6x_lane_launch_shape, mom6x_tile_steps
   public :: MOM6X_RK2_HAVE_ETA, MOM6X_RK2_HAVE_DIFFU, MOM6X_RK2_HAVE_U2, MOM6X_RK2_HAVE_CAU, MOM6X_RK2_HAVE_UH, MOM6X_RK2_HAVE_H2
   public :: mom6x_tracer_advect_init, mom6x_advect_tracer, mom6x_triDiagTS, mom6x_triDiagTS_Eulerian
   public :: mom6x_tracer_vertdiff, mom6x_tracer_vertdiff_Eulerian, mom6x_diabatic_is_trivial
@@ -239,6 +239,12 @@ module mom6x_c_api
     integer(c_int) function mom6x_lane_launch_shape(bx, by, i_first) bind(C, name="mom6x_lane_launch_shape")
       import :: c_int
       integer(c_int), intent(out) :: bx, by, i_first
+    end function
+    !> the steps along i and j of the tiled kernels: which = 0 CorAdCalc, 1 horizontal_viscosity, 2 advect_tracer (x tile, y segment)
+    integer(c_int) function mom6x_tile_steps(which, sx, sy) bind(C, name="mom6x_tile_steps")
+      import :: c_int
+      integer(c_int), value :: which
+      integer(c_int), intent(out) :: sx, sy
     end function
     !> ubtav (0), vbtav (1), ... of barotropic_CS: the arrays register_barotropic_restarts (MOM_barotropic.F90:6253) registers
     type(c_ptr) function mom6x_barotropic_field(ctx, which) bind(C, name="mom6x_barotropic_field")

@@ -349,6 +349,10 @@ int  mom6x_abi_version(void);
 /* The work-group (lanes along i, rows) of the kernels that give each cell or face of a plane a lane, and the i of their first lane
  * (a cache line before the first own point).  For tests that place a grid's edges where a launch extent rounds up to another block. */
 int  mom6x_lane_launch_shape(int *bx, int *by, int *i_first);
+/* The points along i and j by which the tiles of a tiled kernel advance: which = 0 CorAdCalc (k_corad_lds, k_corad_fused: the tile
+ * minus its frame), 1 horizontal_viscosity (k_hv_fused), 2 advect_tracer (the cells of a tile of the x passes, the rows of a segment
+ * of the y passes).  For tests that place a grid's edges on a whole number of tiles and one point more. */
+int  mom6x_tile_steps(int which, int *sx, int *sy);
 /* hipGetDeviceCount: lets a host with one process per GPU pick its device as (local rank) mod (count).  < 0 on error. */
 int  mom6x_device_count(void);
 /* sizeof() of the public structs (0 dims, 1 vgrid, 2 continuity_params, 3 BT_cont, 4 barotropic_params,

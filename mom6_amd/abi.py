@@ -607,3 +607,16 @@ def lane_launch_shape(lib=None):
     bx, by, i0 = C.c_int(0), C.c_int(0), C.c_int(0)
     check(lib, lib.mom6x_lane_launch_shape(C.byref(bx), C.byref(by), C.byref(i0)))
     return bx.value, by.value, i0.value
+
+
+TILE_CORAD, TILE_HOR_VISC, TILE_TRACER_ADVECT = 0, 1, 2
+
+
+def tile_steps(which, lib=None):
+    """(points along i, points along j) by which the tiles of CorAdCalc's (TILE_CORAD) and horizontal_viscosity's (TILE_HOR_VISC)
+    fused kernels advance, or the cells of an x tile and the rows of a y segment of advect_tracer (TILE_TRACER_ADVECT):
+    mom6x_tile_steps.  Needs the library, not a GPU."""
+    lib = lib or load_library()
+    sx, sy = C.c_int(0), C.c_int(0)
+    check(lib, lib.mom6x_tile_steps(int(which), C.byref(sx), C.byref(sy)))
+    return sx.value, sy.value

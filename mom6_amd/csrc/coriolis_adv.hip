@@ -607,6 +607,9 @@ k_corad_lds(Dm d, const double *__restrict__ G, const double *__restrict__ u, co
 
 }  // namespace
 
+// the points by which the tiles of k_corad_lds / k_corad_fused advance (mom6x_tile_steps, ctx.hip)
+void corad_tile_steps(int *sx, int *sy) { *sx = CF_X - 2; *sy = CF_Y - 2; }
+
 // ---------------------------------------------------------------------------------------------
 extern "C" int mom6x_CoriolisAdv_init(mom6x_ctx *c, const mom6x_coriolis_params *p) {
   REQUIRE(c && p, MOM6X_EINVAL, "mom6x_CoriolisAdv_init: null argument");

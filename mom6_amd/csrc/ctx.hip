@@ -118,6 +118,20 @@ extern "C" int mom6x_lane_launch_shape(int *bx, int *by, int *i_first) {
   return MOM6X_OK;
 }
 
+// the steps of the tiled kernels of the dynamics, for tests that place a grid's edges on a whole number of tiles and one point more:
+// which = 0 CorAdCalc (k_corad_lds, k_corad_fused), 1 horizontal_viscosity (k_hv_fused), 2 advect_tracer (cells of an x tile, rows
+// of a y segment)
+extern "C" int mom6x_tile_steps(int which, int *sx, int *sy) {
+  REQUIRE(which >= 0 && which <= 2, MOM6X_EINVAL, "mom6x_tile_steps: which must be 0 (CorAdCalc), 1 (hor_visc) or 2 (tracer advection)");
+  int x = 0, y = 0;
+  if (which == 0) corad_tile_steps(&x, &y);
+  else if (which == 1) hor_visc_tile_steps(&x, &y);
+  else tracer_advect_tile_steps(&x, &y);
+  if (sx) *sx = x;
+  if (sy) *sy = y;
+  return MOM6X_OK;
+}
+
 extern "C" int mom6x_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) { mom6x_set_error("mom6x_device_count: hipGetDeviceCount failed"); return -1; }

@@ -947,6 +947,8 @@ k_hv_fused(Dm d, const double *__restrict__ G, const double *__restrict__ P, mom
 }  // namespace
 
 void hor_visc_free(mom6x_ctx *c) { (void)hipFree(c->hv_planes); c->hv_planes = nullptr; }
+// the points by which the tiles of k_hv_fused advance (mom6x_tile_steps, ctx.hip)
+void hor_visc_tile_steps(int *sx, int *sy) { *sx = HV_TX - 2 * HT_H; *sy = HV_TY - 2 * HT_H; }
 
 extern "C" int mom6x_hor_visc_init(mom6x_ctx *c, const mom6x_hor_visc_params *p) {
   REQUIRE(c && p, MOM6X_EINVAL, "mom6x_hor_visc_init: null argument");

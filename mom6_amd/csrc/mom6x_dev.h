@@ -171,6 +171,10 @@ int ctx_scratch(mom6x_ctx *c, int slot, int nlev, double **out);
 int work_fill_byte();   // 0, or 0xFF with MOM6X_POISON_WORK=1 (ctx.hip): the initial contents of work arrays   // ctx.hip
 void hor_visc_free(mom6x_ctx *c);                                  // hor_visc.hip
 void diag_sums_free(mom6x_ctx *c);                                 // diag_sums.hip
+// what mom6x_tile_steps (ctx.hip) reports, each defined next to the constants of its kernels
+void corad_tile_steps(int *sx, int *sy);                           // coriolis_adv.hip: CF_X - 2, CF_Y - 2
+void hor_visc_tile_steps(int *sx, int *sy);                        // hor_visc.hip: HV_TX - 2 * HT_H, HV_TY - 2 * HT_H
+void tracer_advect_tile_steps(int *sx, int *sy);                   // tracer_advect.hip: TX, SEGY
 int CorAdCalc_bc(mom6x_ctx *c, const double *u, const double *v, const double *h, const double *uh, const double *vh, double *CAu,
                  double *CAv, const double *PFu, const double *PFv, const double *diffu, const double *diffv, double *u_bc,
                  double *v_bc, double *uhtr, double *vhtr, double dt_tr);   // coriolis_adv.hip

@@ -658,6 +658,9 @@ k_ta_y_tile(Dm d, const double *__restrict__ G, double *__restrict__ vhr, double
 
 }  // namespace
 
+// the cells of a tile of the x passes and the rows of a segment of the y passes (mom6x_tile_steps, ctx.hip)
+void tracer_advect_tile_steps(int *sx, int *sy) { *sx = TX; *sy = SEGY; }
+
 void ta_state_free(mom6x_ctx *c) {
   TAState *s = (TAState *)c->ta;
   if (!s) return;

@@ -139,6 +139,16 @@ def assert_bitwise(a, b, name, sl=None, signed_zero_ok=None):
                              f"at {idx}: {a[idx]!r} vs {b[idx]!r}; n_diff={np.count_nonzero(ne)}")
 
 
+def assert_untouched_beyond(a, cover, name):
+    """An output that started as NaN: every word outside the slices `cover` (the points a kernel's launch reaches) is still NaN."""
+    out = np.ones(a.shape, dtype=bool)
+    out[(Ellipsis,) + tuple(cover)] = False
+    hit = out & ~np.isnan(a)
+    if hit.any():
+        idx = np.unravel_index(np.argmax(hit), hit.shape)
+        raise AssertionError(f"{name}: {np.count_nonzero(hit)} words beyond the launch's range were written (first at {idx}: {a[idx]!r})")
+
+
 def assert_close(a, b, name, rtol, sl=None):
     a = np.asarray(a); b = np.asarray(b)
     if sl is not None:
@@ -188,6 +198,16 @@ def roughen(h, seed=17):
     rng = np.random.default_rng(seed)
     f = rng.choice([1.0, 1.0, 1.0, 0.5, 0.2, 0.05, 1e-2, 1e-3, 1e-6, 2.0, 5.0], size=h.shape)
     return np.ascontiguousarray(h * f)
+
+
+def uneven_cell_areas(d, M, seed=43):
+    """A copy of the metrics with cell areas G%areaT (and G%IareaT) that differ from cell to cell by up to 20 %: on the Cartesian
+    grids every cell has the same area, and a kernel that fetched the area of a wrong neighbour would get the right number."""
+    from mom6_amd import abi, synth
+    M2 = np.array(M, copy=True)
+    M2[abi.G["areaT"]] = M[abi.G["areaT"]] * (1.0 + 0.2 * synth.smooth_field(d, seed, ox=0.5, oy=0.5))
+    M2[abi.G["IareaT"]] = np.where(M[abi.G["mask2dT"]] > 0, 1.0 / M2[abi.G["areaT"]], M[abi.G["IareaT"]])
+    return M2
 
 
 def narrowed_faces(d, M):

@@ -25,25 +25,31 @@ def visc_coefs(d, M, seed=3):
     return [np.ascontiguousarray(x) for x in (a_u, a_v, h_u, h_v, Ray, Ray.copy())]
 
 
+# the option sets of test_CorAdCalc (tests/test_dyn_edges_gpu.py runs them on the torus as well)
+CORAD_MODS = [dict(), dict(KE_Scheme=abi.KE_GUDONOV), dict(KE_Scheme=abi.KE_SIMPLE_GUDONOV, no_slip=1),   # (k_corad_lds)
+              dict(bound_Coriolis=1), dict(Coriolis_Scheme=abi.ARAKAWA_HSU90, KE_Scheme=abi.KE_GUDONOV),
+              dict(Coriolis_Scheme=abi.SADOURNY75_ENSTRO, KE_Scheme=abi.KE_SIMPLE_GUDONOV, no_slip=1, bound_Coriolis=1),
+              dict(Coriolis_En_Dis=1), dict(Coriolis_En_Dis=1, bound_Coriolis=1, KE_Scheme=abi.KE_GUDONOV),
+              dict(Coriolis_En_Dis=1, Coriolis_Scheme=abi.ARAKAWA_HSU90),
+              dict(Coriolis_Scheme=abi.ARAKAWA_LAMB81),
+              dict(Coriolis_Scheme=abi.ARAKAWA_LAMB81, bound_Coriolis=1, KE_Scheme=abi.KE_SIMPLE_GUDONOV, no_slip=1),
+              dict(Coriolis_Scheme=abi.AL_BLEND, rough=1),
+              dict(Coriolis_Scheme=abi.AL_BLEND, F_eff_max_blend=3.0, wt_lin_blend=0.5, bound_Coriolis=1, rough=1),
+              dict(Coriolis_Scheme=abi.AL_BLEND, F_eff_max_blend=2.0, wt_lin_blend=0.0),
+              dict(Coriolis_Scheme=abi.ROBUST_ENSTRO, rough=1),
+              dict(Coriolis_Scheme=abi.ROBUST_ENSTRO, PV_Adv_Scheme=abi.PV_ADV_UPWIND1, bound_Coriolis=1,
+                   Coriolis_En_Dis=1, rough=1)]
+
+
 @pytest.mark.parametrize("cfg", ["double_gyre", "channel", "benchmark_small"])
-@pytest.mark.parametrize("mods", [dict(), dict(KE_Scheme=abi.KE_GUDONOV), dict(KE_Scheme=abi.KE_SIMPLE_GUDONOV, no_slip=1),   # (k_corad_lds)
-                                  dict(bound_Coriolis=1), dict(Coriolis_Scheme=abi.ARAKAWA_HSU90, KE_Scheme=abi.KE_GUDONOV),
-                                  dict(Coriolis_Scheme=abi.SADOURNY75_ENSTRO, KE_Scheme=abi.KE_SIMPLE_GUDONOV, no_slip=1, bound_Coriolis=1),
-                                  dict(Coriolis_En_Dis=1), dict(Coriolis_En_Dis=1, bound_Coriolis=1, KE_Scheme=abi.KE_GUDONOV),
-                                  dict(Coriolis_En_Dis=1, Coriolis_Scheme=abi.ARAKAWA_HSU90),
-                                  dict(Coriolis_Scheme=abi.ARAKAWA_LAMB81),
-                                  dict(Coriolis_Scheme=abi.ARAKAWA_LAMB81, bound_Coriolis=1, KE_Scheme=abi.KE_SIMPLE_GUDONOV, no_slip=1),
-                                  dict(Coriolis_Scheme=abi.AL_BLEND, rough=1),
-                                  dict(Coriolis_Scheme=abi.AL_BLEND, F_eff_max_blend=3.0, wt_lin_blend=0.5, bound_Coriolis=1, rough=1),
-                                  dict(Coriolis_Scheme=abi.AL_BLEND, F_eff_max_blend=2.0, wt_lin_blend=0.0),
-                                  dict(Coriolis_Scheme=abi.ROBUST_ENSTRO, rough=1),
-                                  dict(Coriolis_Scheme=abi.ROBUST_ENSTRO, PV_Adv_Scheme=abi.PV_ADV_UPWIND1, bound_Coriolis=1,
-                                       Coriolis_En_Dis=1, rough=1)],
-                         ids=lambda m: "-".join(f"{k}={v}" for k, v in m.items()) or "default")
+@pytest.mark.parametrize("mods", CORAD_MODS, ids=lambda m: "-".join(f"{k}={v}" for k, v in m.items()) or "default")
 def test_CorAdCalc(orc, cfg, mods):
-    import torch
-    from mom6_amd.dycore import Dycore
-    gg, d, M = getattr(H, cfg)()
+    CorAdCalc_case(orc, getattr(H, cfg)(), mods)
+
+
+def CorAdCalc_inputs(orc, cfg, mods):
+    """The seeded inputs of a CorAdCalc case on any grid and the oracle's CAu, CAv: (GV, CS, (u, v, h, uh, vh), CAu, CAv)."""
+    gg, d, M = cfg
     GV = abi.vgrid_default()
     CS = abi.coriolis_params_default()
     mods = dict(mods); rough = mods.pop("rough", 0)
@@ -66,17 +72,36 @@ def test_CorAdCalc(orc, cfg, mods):
     uh = np.ascontiguousarray(uh); vh = np.ascontiguousarray(vh)
     CAu = np.zeros_like(h); CAv = np.zeros_like(h)
     orc.CorAdCalc(d, M, GV, CS, u, v, h, uh, vh, CAu, CAv)
+    return GV, CS, (u, v, h, uh, vh), CAu, CAv
+
+
+def CorAdCalc_case(orc, cfg, mods, cover=None):
+    """The body of test_CorAdCalc on any grid; returns the launches (mom6x_prof_report) of the call.  With `cover` (numpy slices)
+    the device's CAu and CAv start as NaN, the comparison makes no allowance for the sign of a zero, and every word outside
+    `cover` must still be NaN afterwards."""
+    import torch
+    from mom6_amd.dycore import Dycore, prof_enable, prof_report
+    gg, d, M = cfg
+    GV, CS, inp, CAu, CAv = CorAdCalc_inputs(orc, cfg, mods)
     dyc = Dycore(d, M, GV)
     dyc.CoriolisAdv_init(CS)
     gu, gv = dyc.zeros3(), dyc.zeros3()
-    T = [dyc.to_dev(x) for x in (u, v, h, uh, vh)]
+    if cover is not None:
+        gu.fill_(float("nan")); gv.fill_(float("nan"))
+    T = [dyc.to_dev(x) for x in inp]
     torch.cuda.synchronize()
+    prof_enable(dyc, True)
     dyc.CorAdCalc(*T, gu, gv)
     dyc.sync()
-    H.assert_bitwise(gu.cpu().numpy(), CAu, "CAu", H.interior(d, "u"))
-    H.assert_bitwise(gv.cpu().numpy(), CAv, "CAv", H.interior(d, "v"))
+    rep = prof_report(dyc); prof_enable(dyc, False)
+    zero_ok = None if cover is None else False
+    H.assert_bitwise(gu.cpu().numpy(), CAu, "CAu", H.interior(d, "u"), signed_zero_ok=zero_ok)
+    H.assert_bitwise(gv.cpu().numpy(), CAv, "CAv", H.interior(d, "v"), signed_zero_ok=zero_ok)
     assert np.abs(CAu).max() > 0
+    if cover is not None:
+        H.assert_untouched_beyond(gu.cpu().numpy(), cover, "CAu"); H.assert_untouched_beyond(gv.cpu().numpy(), cover, "CAv")
     dyc.close()
+    return rep
 
 
 def test_CorAdCalc_other_kernels_are_bit_identical_too():
@@ -97,9 +122,16 @@ def test_CorAdCalc_other_kernels_are_bit_identical_too():
 @pytest.mark.parametrize("cfg", ["double_gyre", "channel", "benchmark_small"])
 @pytest.mark.parametrize("bug", [1, 0])
 def test_PressureForce(orc, cfg, bug):
+    PressureForce_case(orc, getattr(H, cfg)(), bug)
+
+
+def PressureForce_case(orc, cfg, bug, cover=None):
+    """The body of test_PressureForce (the layered path) on any grid.  With `cover` (numpy slices) the device's outputs start as
+    NaN, the comparison makes no allowance for the sign of a zero, and every word outside `cover` must still be NaN afterwards."""
     import torch
     from mom6_amd.dycore import Dycore
-    gg, d, M = getattr(H, cfg)()
+    gg, d, M = cfg
+    zero_ok = None if cover is None else False
     GV = abi.vgrid_default()
     CS = abi.pgf_params_default(GV.Rho0)
     CS.rho_ref_bug = bug
@@ -112,16 +144,22 @@ def test_PressureForce(orc, cfg, bug):
     dyc = Dycore(d, M, GV)
     dyc.PressureForce_init(CS, Rlay, gp)
     g = dict(PFu=dyc.zeros3(), PFv=dyc.zeros3(), pbce=dyc.zeros3(), eta=dyc.zeros2())
+    if cover is not None:
+        for a in g.values():
+            a.fill_(float("nan"))
     hd = dyc.to_dev(h)
     torch.cuda.synchronize()
     dyc.PressureForce(hd, g["PFu"], g["PFv"], g["pbce"], g["eta"])
     dyc.sync()
-    H.assert_bitwise(g["PFu"].cpu().numpy(), o["PFu"], "PFu", H.interior(d, "u"))
-    H.assert_bitwise(g["PFv"].cpu().numpy(), o["PFv"], "PFv", H.interior(d, "v"))
+    H.assert_bitwise(g["PFu"].cpu().numpy(), o["PFu"], "PFu", H.interior(d, "u"), signed_zero_ok=zero_ok)
+    H.assert_bitwise(g["PFv"].cpu().numpy(), o["PFv"], "PFv", H.interior(d, "v"), signed_zero_ok=zero_ok)
     sl = d.sl(-1, d.ni, -1, d.nj)
-    H.assert_bitwise(g["pbce"].cpu().numpy(), o["pbce"], "pbce", sl)
-    H.assert_bitwise(g["eta"].cpu().numpy(), o["eta"], "eta", sl)
+    H.assert_bitwise(g["pbce"].cpu().numpy(), o["pbce"], "pbce", sl, signed_zero_ok=zero_ok)
+    H.assert_bitwise(g["eta"].cpu().numpy(), o["eta"], "eta", sl, signed_zero_ok=zero_ok)
     assert np.abs(o["PFu"]).max() > 0
+    if cover is not None:
+        for n in g:
+            H.assert_untouched_beyond(g[n].cpu().numpy(), cover, n)
     dyc.close()
 
 
@@ -141,10 +179,13 @@ def test_PressureForce(orc, cfg, bug):
 def test_PressureForce_with_equation_of_state(orc, cfg, form, mods):
     """The use_EOS branch (int_density_dz -> analytic linear / Wright integrals, or with Recon_Scheme = 1 the PLM edge values
     and the generic 5-point quadratures; Set_pbce_Bouss with T and S)."""
-    import torch
-    from mom6_amd.dycore import Dycore
+    PressureForce_eos_case(orc, getattr(H, cfg)(), form, mods)
+
+
+def PressureForce_eos_inputs(orc, cfg, form, mods):
+    """The seeded inputs of a use_EOS PressureForce case on any grid: (GV, CS, eos, Rlay, gp, h, T, S)."""
     from tests import cases
-    gg, d, M = getattr(H, cfg)()
+    gg, d, M = cfg
     GV = abi.vgrid_default()
     CS = abi.pgf_params_default(GV.Rho0)
     eos = abi.eos_params_default(getattr(abi, form))
@@ -156,6 +197,18 @@ def test_PressureForce_with_equation_of_state(orc, cfg, form, mods):
     Rlay, gp = abi.layer_densities(d.nk, GV.Rho0, GV.g_Earth)
     h, _, _ = synth.make_state(d, M, thin_frac=0.05)
     T, S = cases.thermo_state(d, M)
+    return GV, CS, eos, Rlay, gp, h, T, S
+
+
+def PressureForce_eos_case(orc, cfg, form, mods, cover=None):
+    """The body of test_PressureForce_with_equation_of_state on any grid.  With `cover` (numpy slices) the device's outputs start
+    as NaN, the comparison makes no allowance for the sign of a zero, and every word outside `cover` must still be NaN after the
+    use_EOS call."""
+    import torch
+    from mom6_amd.dycore import Dycore
+    gg, d, M = cfg
+    GV, CS, eos, Rlay, gp, h, T, S = PressureForce_eos_inputs(orc, cfg, form, mods)
+    zero_ok = None if cover is None else False
     o = dict(PFu=np.zeros_like(h), PFv=np.zeros_like(h), pbce=np.zeros_like(h), eta=np.zeros(d.shape2()))
     if eos.form in (abi.UNESCO, abi.ROQUET_RHO, abi.JACKETT06, abi.ROQUET_SPV) and not (eos.Recon_Scheme or eos.EOS_quadrature):   # MOM_EOS.F90:1495
         dyc = Dycore(d, M, GV)
@@ -177,16 +230,22 @@ def test_PressureForce_with_equation_of_state(orc, cfg, form, mods):
     Td, Sd = dyc.to_dev(T), dyc.to_dev(S)
     dyc.PressureForce_set_tv(Td, Sd, eos)
     g = dict(PFu=dyc.zeros3(), PFv=dyc.zeros3(), pbce=dyc.zeros3(), eta=dyc.zeros2())
+    if cover is not None:
+        for a in g.values():
+            a.fill_(float("nan"))
     hd = dyc.to_dev(h)
     torch.cuda.synchronize()
     dyc.PressureForce(hd, g["PFu"], g["PFv"], g["pbce"], g["eta"])
     dyc.sync()
-    H.assert_bitwise(g["PFu"].cpu().numpy(), o["PFu"], "PFu", H.interior(d, "u"))
-    H.assert_bitwise(g["PFv"].cpu().numpy(), o["PFv"], "PFv", H.interior(d, "v"))
+    H.assert_bitwise(g["PFu"].cpu().numpy(), o["PFu"], "PFu", H.interior(d, "u"), signed_zero_ok=zero_ok)
+    H.assert_bitwise(g["PFv"].cpu().numpy(), o["PFv"], "PFv", H.interior(d, "v"), signed_zero_ok=zero_ok)
     sl = d.sl(-1, d.ni, -1, d.nj)
-    H.assert_bitwise(g["pbce"].cpu().numpy(), o["pbce"], "pbce", sl)
-    H.assert_bitwise(g["eta"].cpu().numpy(), o["eta"], "eta", sl)
+    H.assert_bitwise(g["pbce"].cpu().numpy(), o["pbce"], "pbce", sl, signed_zero_ok=zero_ok)
+    H.assert_bitwise(g["eta"].cpu().numpy(), o["eta"], "eta", sl, signed_zero_ok=zero_ok)
     assert np.abs(o["PFu"]).max() > 0 and np.isfinite(o["PFu"]).all()
+    if cover is not None:
+        for n in g:
+            H.assert_untouched_beyond(g[n].cpu().numpy(), cover, n)
     if eos.Recon_Scheme == 1:   # ALE_PLM_edge_values itself (public in MOM_ALE), through its own entry point
         Qt_o, Qb_o = np.zeros_like(h), np.zeros_like(h)
         orc.ALE_PLM_edge_values(d, GV, h, T, eos.boundary_extrap, Qt_o, Qb_o)

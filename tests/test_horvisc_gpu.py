@@ -55,21 +55,30 @@ def test_horizontal_viscosity(orc, cfg, flags):
     horizontal_viscosity_case(orc, (gg, d, M), flags)
 
 
-def horizontal_viscosity_case(orc, cfg, flags):
-    """The body of test_horizontal_viscosity on any grid; returns the launches (mom6x_prof_report) of the call."""
-    import torch
-    from mom6_amd.dycore import Dycore, prof_enable, prof_report
+def horizontal_viscosity_inputs(orc, cfg, flags):
+    """The seeded inputs of a case on any grid and the oracle's diffu, diffv: (GV, P, (u, v, h), diffu, diffv)."""
     gg, d, M = cfg
     GV = abi.vgrid_default()
     P = hv_params(FLAGS[flags])
     h, u, v = synth.make_state(d, M, thin_frac=0.15)
-    planes = orc.hor_visc_init(d, M, P)
     o_du, o_dv = np.zeros_like(u), np.zeros_like(v)
-    orc.horizontal_viscosity(d, M, GV, P, planes, u, v, h, o_du, o_dv)
+    orc.horizontal_viscosity(d, M, GV, P, orc.hor_visc_init(d, M, P), u, v, h, o_du, o_dv)
+    return GV, P, (u, v, h), o_du, o_dv
+
+
+def horizontal_viscosity_case(orc, cfg, flags, cover=None):
+    """The body of test_horizontal_viscosity on any grid; returns the launches (mom6x_prof_report) of the call.  With `cover`
+    (numpy slices) the device's diffu and diffv start as NaN and every word outside `cover` must still be NaN afterwards."""
+    import torch
+    from mom6_amd.dycore import Dycore, prof_enable, prof_report
+    gg, d, M = cfg
+    GV, P, (u, v, h), o_du, o_dv = horizontal_viscosity_inputs(orc, cfg, flags)
     dyc = Dycore(d, M, GV)
     dyc.hor_visc_init(P)
     ud, vd, hd = dyc.to_dev(u), dyc.to_dev(v), dyc.to_dev(h)
     du, dv = torch.zeros_like(ud), torch.zeros_like(vd)
+    if cover is not None:
+        du.fill_(float("nan")); dv.fill_(float("nan"))
     torch.cuda.synchronize()
     prof_enable(dyc, True)
     dyc.horizontal_viscosity(ud, vd, hd, du, dv)
@@ -78,6 +87,8 @@ def horizontal_viscosity_case(orc, cfg, flags):
     H.assert_bitwise(du.cpu().numpy(), o_du, "diffu", H.interior(d, "u"), signed_zero_ok=False)
     H.assert_bitwise(dv.cpu().numpy(), o_dv, "diffv", H.interior(d, "v"), signed_zero_ok=False)
     assert np.isfinite(o_du).all() and np.abs(o_du).max() > 0 and np.abs(o_dv).max() > 0
+    if cover is not None:
+        H.assert_untouched_beyond(du.cpu().numpy(), cover, "diffu"); H.assert_untouched_beyond(dv.cpu().numpy(), cover, "diffv")
     if "leith" in flags:   # the Leith terms are felt: the same call without them gives another answer
         P0 = hv_params({k: v for k, v in FLAGS[flags].items() if "Leith" not in k and "leith" not in k.lower()})
         r_du, r_dv = np.zeros_like(u), np.zeros_like(v)

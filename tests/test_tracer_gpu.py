@@ -31,12 +31,14 @@ def transports(orc, d, M, GV, dt, scale, post=1.0):
     return hn, np.ascontiguousarray(uh * dt * post), np.ascontiguousarray(vh * dt * post)
 
 
+# (schemes of the tracers: 0 PLM, 1 PPM:H3, 2 PPM; first direction; factor on the accumulated transports)
+ADVECT_CASES = [([0, 0], 0, 1.0), ([1, 1, 2], 0, 60.0), ([2, 0, 1], 1, 60.0), ([1], 1, 1.0), ([0], 0, 60.0),
+                ([0, 1, 2, 2, 1], 0, 60.0)]      # five tracers: the 8-tracer instantiations
+
+
 @pytest.mark.parametrize("cfg", ["double_gyre", "channel", "benchmark_small", "wide", "ragged", "narrow"])
-@pytest.mark.parametrize("schemes,first,post", [([0, 0], 0, 1.0), ([1, 1, 2], 0, 60.0), ([2, 0, 1], 1, 60.0), ([1], 1, 1.0), ([0], 0, 60.0),
-                                                ([0, 1, 2, 2, 1], 0, 60.0)])      # five tracers: the 8-tracer instantiations
+@pytest.mark.parametrize("schemes,first,post", ADVECT_CASES)
 def test_advect_tracer(orc, cfg, schemes, first, post):
-    import torch
-    from mom6_amd.dycore import Dycore
     # "wide": 600 x 300 cells, i.e. three 255-cell tiles along i and three 128-row segments along j on the tiled path, whose
     # boundaries the limiter and the 5-point stencils reach across; re-entrant in x
     if cfg == "wide":
@@ -45,11 +47,27 @@ def test_advect_tracer(orc, cfg, schemes, first, post):
         gg, d, M = H.double_gyre(nk=3, ni=17, nj=9) if cfg == "ragged" else H.double_gyre(nk=2, ni=9, nj=33)
     else:
         gg, d, M = getattr(H, cfg)()
+    advect_tracer_case(orc, (gg, d, M), schemes, first, post, limited=cfg not in ("ragged", "narrow"))
+
+
+def advect_tracer_inputs(orc, cfg, schemes, post):
+    """The seeded inputs of an advect_tracer case on any grid: (GV, dt_dyn, dt, h_end, uhtr, vhtr, tracers)."""
+    gg, d, M = cfg
     GV = abi.vgrid_default()
     dt_dyn, dt = 900.0, 3600.0
     h_end, uhtr, vhtr = transports(orc, d, M, GV, dt, scale=3.0, post=post)
     trs = [np.ascontiguousarray(10.0 + 5.0 * synth.smooth_field(d, 70 + m, nk=d.nk, ox=0.5, oy=0.5) * M[G["mask2dT"]][None])
            for m in range(len(schemes))]
+    return GV, dt_dyn, dt, h_end, uhtr, vhtr, trs
+
+
+def advect_tracer_case(orc, cfg, schemes, first, post, limited=True):
+    """The body of test_advect_tracer on any grid; `limited`: with post > 1 the limiter must have asked for more passes than the
+    halo cycle alone needs.  Returns the launches (mom6x_prof_report) of the call."""
+    import torch
+    from mom6_amd.dycore import Dycore, prof_enable, prof_report
+    gg, d, M = cfg
+    GV, dt_dyn, dt, h_end, uhtr, vhtr, trs = advect_tracer_inputs(orc, cfg, schemes, post)
     tro = [t.copy() for t in trs]
     uhr_o = np.zeros_like(h_end); vhr_o = np.zeros_like(h_end)
     it_o = orc.advect_tracer(d, M, GV, first, dt_dyn, 0, h_end, uhtr, vhtr, dt, tro, schemes, uhr_out=uhr_o, vhr_out=vhr_o)
@@ -59,10 +77,12 @@ def test_advect_tracer(orc, cfg, schemes, first, post):
     uhr_g, vhr_g = dyc.zeros3(), dyc.zeros3()
     hd, ud, vd = dyc.to_dev(h_end), dyc.to_dev(uhtr), dyc.to_dev(vhtr)
     torch.cuda.synchronize()
+    prof_enable(dyc, True)
     it_g = dyc.advect_tracer(hd, ud, vd, dt, trg, schemes, uhr_out=uhr_g, vhr_out=vhr_g)
     dyc.sync()
+    rep = prof_report(dyc); prof_enable(dyc, False)
     assert it_g == it_o, (it_g, it_o)
-    if post > 1.0 and cfg not in ("ragged", "narrow"):
+    if post > 1.0 and limited:
         assert it_o >= 3, it_o      # the limiter was active: more passes than the halo cycle alone needs
     sl = H.interior(d, "h")
     for m in range(len(schemes)):
@@ -71,6 +91,7 @@ def test_advect_tracer(orc, cfg, schemes, first, post):
     H.assert_bitwise(uhr_g.cpu().numpy(), uhr_o, "uhr", H.interior(d, "u"))
     H.assert_bitwise(vhr_g.cpu().numpy(), vhr_o, "vhr", H.interior(d, "v"))
     dyc.close()
+    return rep
 
 
 @pytest.mark.parametrize("cfg", ["double_gyre", "benchmark_small", "benchmark_75"])
