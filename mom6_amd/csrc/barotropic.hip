@@ -23,7 +23,6 @@
 #include <cmath>
 #include "mom6x_dev.h"
 
-void halo_wrap(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n);  // halo.hip
 
 enum BTW {   // 2-D work planes
   W_q = 0, W_DCor_u, W_DCor_v, W_gtot_E, W_gtot_W, W_gtot_N, W_gtot_S, W_eta, W_eta_PF,
@@ -52,13 +51,13 @@ struct BTState {
   // device; the first offender's eta, bathyT, i, j next to them
   unsigned long long *warn;
   double *warn_info;
-  // btstep_layer_accel deferred to the consumer (LayerAccelSrc, mom6x_dev.h)
-  bool la_defer, la_pending;
+  // btstep_layer_accel deferred to the consumer (LayerAccelSrc, mom6x_dev.h): the result of the last btstep waits in the work block
+  bool la_pending;
   const double *la_pbce;
   double la_underflow;
   // btcalc deferred to btstep's column pass (inside the RK2 step): frhatu / frhatv = hf * (mask / sum(hf)) are formed there from
   // the face thicknesses and never written; fr_pending: frhatu / frhatv are NOT current, fr_hu / fr_hv are their source
-  bool fr_defer, fr_pending;
+  bool fr_pending;
   const double *fr_hu, *fr_hv;
 };
 
@@ -927,15 +926,6 @@ k_layer_accel(Dm d, const double *__restrict__ G, const double *__restrict__ wor
 
 }  // namespace
 
-void bt_defer_layer_accel(mom6x_ctx *c, bool on) { if (c->bts) c->bts->la_defer = on; }
-
-// btcalc inside the RK2 step: with `on`, mom6x_btcalc(h_u, h_v) only notes its operands; btstep's column pass forms the
-// thickness fractions from them (k_bt_col<., true>), and whoever else wants frhatu / frhatv (set_dtbt, mom6x_barotropic_field)
-// gets them through bt_frhat_materialize.  MOM6X_BTCALC=eager: btcalc always writes them.
-void bt_defer_btcalc(mom6x_ctx *c, bool on) {
-  static const bool eager = [] { const char *e = getenv("MOM6X_BTCALC"); return e && !strcmp(e, "eager"); }();
-  if (c->bts) c->bts->fr_defer = on && !eager;
-}
 // btcalc :4360 with h_u, h_v given (BT_THICK_SCHEME = FROM_BT_CONT): the column in registers up to COLS_NK_BOUND layers
 static void btcalc_from_faces(mom6x_ctx *c, const double *h_u, const double *h_v) {
   const Dm d = c->d;
@@ -1080,6 +1070,12 @@ extern "C" int mom6x_btcalc_strict(mom6x_ctx *c, const double *h, const double *
   return mom6x_btcalc(c, h, h_u, h_v);
 }
 extern "C" int mom6x_btcalc(mom6x_ctx *c, const double *h, const double *h_u, const double *h_v) {
+  return btcalc_deferrable(c, h, h_u, h_v, false);
+}
+// btcalc inside the RK2 step: with `defer`, btcalc(h_u, h_v) only notes its operands; btstep's column pass forms the
+// thickness fractions from them (k_bt_col<., true>), and whoever else wants frhatu / frhatv (set_dtbt, mom6x_barotropic_field)
+// gets them through bt_frhat_materialize.
+int btcalc_deferrable(mom6x_ctx *c, const double *h, const double *h_u, const double *h_v, bool defer) {
   REQUIRE(c && c->bt_init, MOM6X_EINVAL, "btcalc: Module MOM_barotropic must be initialized before it is used.");
   REQUIRE((h_u != nullptr) == (h_v != nullptr), MOM6X_EINVAL, "btcalc: Inconsistent settings of optional arguments");
   REQUIRE(h_u || h, MOM6X_EINVAL, "btcalc: h is required when h_u/h_v are absent");
@@ -1087,7 +1083,7 @@ extern "C" int mom6x_btcalc(mom6x_ctx *c, const double *h, const double *h_u, co
   const Dm d = c->d;
   const dim3 b = blk2();
   c->bts->fr_pending = false;
-  if (h_u && c->bts->fr_defer) { c->bts->fr_pending = true; c->bts->fr_hu = h_u; c->bts->fr_hv = h_v; return MOM6X_OK; }
+  if (h_u && defer) { c->bts->fr_pending = true; c->bts->fr_hu = h_u; c->bts->fr_hv = h_v; return MOM6X_OK; }
   if (h_u) {
     btcalc_from_faces(c, h_u, h_v);
     HIPCHK(hipGetLastError());
@@ -1176,6 +1172,17 @@ extern "C" int mom6x_btstep(mom6x_ctx *c, const double *U_in, const double *V_in
                             const mom6x_BT_cont *BT_cont, const double *taux_bot, const double *tauy_bot,
                             const double *uh0, const double *vh0, const double *u_uh0, const double *v_vh0,
                             double *etaav) {
+  return btstep_deferrable(c, U_in, V_in, eta_in, dt, bc_accel_u, bc_accel_v, taux, tauy, pbce, eta_PF_in, U_Cor, V_Cor, accel_layer_u,
+                           accel_layer_v, eta_out, uhbtav, vhbtav, visc_rem_u, visc_rem_v, BT_cont, taux_bot, tauy_bot, uh0, vh0, u_uh0,
+                           v_vh0, etaav, false);
+}
+
+int btstep_deferrable(mom6x_ctx *c, const double *U_in, const double *V_in, const double *eta_in, double dt, const double *bc_accel_u,
+                      const double *bc_accel_v, const double *taux, const double *tauy, const double *pbce, const double *eta_PF_in,
+                      const double *U_Cor, const double *V_Cor, double *accel_layer_u, double *accel_layer_v, double *eta_out,
+                      double *uhbtav, double *vhbtav, const double *visc_rem_u, const double *visc_rem_v, const mom6x_BT_cont *BT_cont,
+                      const double *taux_bot, const double *tauy_bot, const double *uh0, const double *vh0, const double *u_uh0,
+                      const double *v_vh0, double *etaav, bool defer_layer_accel) {
   REQUIRE(c && c->bt_init, MOM6X_EINVAL, "btstep: Module MOM_barotropic must be initialized before it is used.");
   // BT_cont == NULL: USE_BT_CONT_TYPE = False (k_face_areas_as_fits); BOUND_BT_CORRECTION then bounds eta_cor by eta_cor_bound
   // (:6164-6173, :1582-1585), as it does behind a BT_cont_type with BT_CONT_CORR_BOUNDS = False
@@ -1229,7 +1236,7 @@ extern "C" int mom6x_btstep(mom6x_ctx *c, const double *U_in, const double *V_in
   Av.ubt_Cor = work + W_vbt_Cor * slab; Av.gtot_m = work + W_gtot_N * slab; Av.gtot_p = work + W_gtot_S * slab;
   Av.uh0sum = work + W_vh0sum * slab; Av.ubt0 = work + W_vbt0 * slab; Av.ubt = work + W_vbt * slab;
   Av.BT_force = work + W_BT_force_v * slab; Av.bt_rem = work + W_bt_rem_v * slab;
-  if (s->fr_pending) {   // btcalc's thickness fractions formed in the column pass (bt_defer_btcalc)
+  if (s->fr_pending) {   // btcalc's thickness fractions formed in the column pass (btcalc_deferrable)
     Au.hf = s->fr_hu; Av.hf = s->fr_hv; Au.h_neglect = Av.h_neglect = c->GV.H_subroundoff;
     KLAUNCH(c, "k_bt_col<0>", (k_bt_col<0, true>), grid3(nxa(d.ni + 1, -1), d.nj, 1, b), b, d, c->G, Au);
     KLAUNCH(c, "k_bt_col<1>", (k_bt_col<1, true>), grid3(d.ni, d.nj + 1, 1, b), b, d, c->G, Av);
@@ -1425,7 +1432,7 @@ extern "C" int mom6x_btstep(mom6x_ctx *c, const double *U_in, const double *V_in
   // btstep_layer_accel :3432-3504.  Inside the RK2 step the consumer of accel_layer_u / _v (the velocity estimate vertvisc_coef
   // forms) evaluates it from pbce and the 2-D results left in the work block: 3 words per cell-layer less, twice per step.
   s->la_pending = false;
-  if (s->la_defer) { s->la_pending = true; s->la_pbce = pbce; s->la_underflow = P.vel_underflow * Idt; }
+  if (defer_layer_accel) { s->la_pending = true; s->la_pbce = pbce; s->la_underflow = P.vel_underflow * Idt; }
   else
     KLAUNCH(c, "k_layer_accel", k_layer_accel, grid3(nxa(d.ni + 1, -1), d.nj + 1, nchunks(d.nk), b), b, d, c->G, work, pbce, accel_layer_u,
                        accel_layer_v, P.vel_underflow * Idt);

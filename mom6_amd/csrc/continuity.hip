@@ -362,7 +362,7 @@ template <int DIR>
 int run_direction(mom6x_ctx *c, const double *u, const double *h_src, double *h, double *uh, double dt,
                   int ish, int ieh, int jsh, int jeh, const double *uhbt, const double *visc_rem,
                   double *u_cor, const mom6x_BT_cont *BT, double *du_cor, const double *hin_conv,
-                  double h_min_conv, bool first_pass) {
+                  double h_min_conv, bool first_pass, const ContFold &fold) {
   const Dm d = c->d;
   const mom6x_continuity_params &P = c->cont;
   const dim3 blk(64, 4, 1);
@@ -443,14 +443,14 @@ int run_direction(mom6x_ctx *c, const double *u, const double *h_src, double *h,
                          P.marginal_faces, visc_rem, A.a0, A.a1, A.b0, A.b1, P.vol_CFL);
     }
   }
-  if (first_pass || !c->cont_h_unused)   // (the second direction's new thicknesses are the routine's result -- unless nobody wants it)
+  if (first_pass || !fold.h_unused)   // (the second direction's new thicknesses are the routine's result -- unless nobody wants it)
   {
-    // the time average of the thicknesses the RK2 step wants next to this convergence (c->cont_av_*; 0: none)
+    // the time average of the thicknesses the RK2 step wants next to this convergence (ContFold; 0: none)
     int av_mode = 0;
-    if (c->cont_av_kind == 1 && !first_pass) av_mode = 1;
-    if (c->cont_av_kind == 2) av_mode = first_pass ? 2 : 3;
+    if (fold.av_kind == 1 && !first_pass) av_mode = 1;
+    if (fold.av_kind == 2) av_mode = first_pass ? 2 : 3;
     KLAUNCH(c, "k_convergence<DIR>", k_convergence<DIR>, grid3(nxa(ieh - ish + 1, ish), jeh - jsh + 1, nchunks(d.nk), blk), blk, d, c->G,
-                       h, uh, dt, hin_conv, h_min_conv, ish, ieh, jsh, jeh, c->flag, c->cont_av, c->cont_av_src, av_mode);
+                       h, uh, dt, hin_conv, h_min_conv, ish, ieh, jsh, jeh, c->flag, fold.av, fold.av_src, av_mode);
   }
   HIPCHK(hipGetLastError());
   return MOM6X_OK;
@@ -495,6 +495,13 @@ extern "C" int mom6x_continuity_PPM(mom6x_ctx *c, const double *u, const double 
                                     const double *vhbt, const double *visc_rem_u, const double *visc_rem_v,
                                     double *u_cor, double *v_cor, const mom6x_BT_cont *BT, double *du_cor,
                                     double *dv_cor) {
+  return continuity_PPM_fold(c, u, v, hin, h, uh, vh, dt, uhbt, vhbt, visc_rem_u, visc_rem_v, u_cor, v_cor, BT, du_cor, dv_cor,
+                             ContFold{ 0, nullptr, nullptr, false });
+}
+
+int continuity_PPM_fold(mom6x_ctx *c, const double *u, const double *v, const double *hin, double *h, double *uh, double *vh, double dt,
+                        const double *uhbt, const double *vhbt, const double *visc_rem_u, const double *visc_rem_v, double *u_cor,
+                        double *v_cor, const mom6x_BT_cont *BT, double *du_cor, double *dv_cor, const ContFold &fold) {
   REQUIRE(c && c->cont_init, MOM6X_EINVAL,
           "MOM_continuity_PPM: Module must be initialized before it is used.");
   REQUIRE(u && v && hin && h && uh && vh, MOM6X_EINVAL, "continuity_PPM: null mandatory array");
@@ -512,14 +519,14 @@ extern "C" int mom6x_continuity_PPM(mom6x_ctx *c, const double *u, const double 
   int rc;
   if (x_first) {
     rc = run_direction<0>(c, u, hin, h, uh, dt, is, ie, js - stencil, je + stencil, uhbt, visc_rem_u, u_cor, BT,
-                          du_cor, hin, 0.0, true);
+                          du_cor, hin, 0.0, true, fold);
     if (rc) return rc;
-    rc = run_direction<1>(c, v, h, h, vh, dt, is, ie, js, je, vhbt, visc_rem_v, v_cor, BT, dv_cor, h, h_min, false);
+    rc = run_direction<1>(c, v, h, h, vh, dt, is, ie, js, je, vhbt, visc_rem_v, v_cor, BT, dv_cor, h, h_min, false, fold);
   } else {
     rc = run_direction<1>(c, v, hin, h, vh, dt, is - stencil, ie + stencil, js, je, vhbt, visc_rem_v, v_cor, BT,
-                          dv_cor, hin, 0.0, true);
+                          dv_cor, hin, 0.0, true, fold);
     if (rc) return rc;
-    rc = run_direction<0>(c, u, h, h, uh, dt, is, ie, js, je, uhbt, visc_rem_u, u_cor, BT, du_cor, h, h_min, false);
+    rc = run_direction<0>(c, u, h, h, uh, dt, is, ie, js, je, uhbt, visc_rem_u, u_cor, BT, du_cor, h, h_min, false, fold);
   }
   return rc;
 }

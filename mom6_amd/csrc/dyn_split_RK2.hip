@@ -10,8 +10,6 @@
 #include <cstring>
 #include "mom6x_dev.h"
 
-void halo_wrap(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n);
-
 struct RK2State {
   mom6x_rk2_params P;
   // MOM_dyn_split_RK2_CS arrays (RK2.F90:85-273)
@@ -131,16 +129,6 @@ __global__ void k_eta(Dm d, const double *__restrict__ G, double *eta, const dou
   eta[x] = e;
 }
 
-int pass3(mom6x_ctx *c, std::initializer_list<double *> f, std::initializer_list<int> stg, int nk) {
-  double *ff[16]; int ss[16], nn[16]; int n = 0;
-  auto s = stg.begin();
-  for (double *p : f) { ff[n] = p; ss[n] = *s++; nn[n] = nk; n++; }
-  c->pass_w = c->dyn_pass_width;
-  halo_wrap(c, ff, ss, nn, n);
-  c->pass_w = 0;
-  return MOM6X_OK;
-}
-
 // The widths the reference gives its group passes (create_group_pass(..., halo=), RK2.F90:476-495): cont = continuity_stencil
 // (continuity_PPM.F90:2757: 3, SIMPLE_2ND 2, UPWIND_1ST 1), vel = max(2, hor_visc_vel_stencil) (hor_visc.F90:3305: 3 with a Leith
 // viscosity).  The device sent NIHALO = 4 rows of everything through round 3; MOM6X_PASS_WIDTHS=full still does.
@@ -152,45 +140,28 @@ PassWidths pass_widths(const mom6x_ctx *c) {
   const int vel = (c->hv_init && (c->hv.Leith_Kh || c->hv.Leith_Ah)) ? 3 : 2;
   return PassWidths{ cont, vel };
 }
-void set_widths(mom6x_ctx *c, std::initializer_list<int> w) {
-  c->pass_wf_n = 0;
-  for (int x : w) { if (c->pass_wf_n < 16) c->pass_wf[c->pass_wf_n++] = x; }
-}
 
-// start_group_pass of 3-D fields on the halo stream (G%nonblocking_updates); halo_complete() is its complete_group_pass
-int start3(mom6x_ctx *c, std::initializer_list<double *> f, std::initializer_list<int> stg, int nk, std::initializer_list<int> widths = {}) {
-  double *ff[16]; int ss[16], nn[16]; int n = 0;
-  auto s = stg.begin();
-  for (double *p : f) { ff[n] = p; ss[n] = *s++; nn[n] = nk; n++; }
-  c->pass_w = c->dyn_pass_width;
-  set_widths(c, widths);
-  halo_start(c, ff, ss, nn, n);
-  c->pass_w = 0; c->pass_wf_n = 0;
-  return MOM6X_OK;
+// The step's group passes, all at the base width mom6x_set_dyn_pass_width gave (NIHALO rows of the 3-D fields in a context widened
+// for BTHALO).  Fields with different numbers of levels in one list: consecutive do_group_pass calls of the reference that no
+// computation separates are sent as ONE packed message per neighbour.
+struct PassList {
+  double *f[16]; int stg[16], nk[16]; int n = 0;
+  PassList(std::initializer_list<double *> fl, std::initializer_list<int> sl, std::initializer_list<int> kl) {
+    auto s = sl.begin(); auto q = kl.begin();
+    for (double *p : fl) { f[n] = p; stg[n] = *s++; nk[n] = (kl.size() == 1) ? *kl.begin() : *q++; n++; }
+  }
+};
+// do_group_pass of 3-D fields
+void pass(mom6x_ctx *c, std::initializer_list<double *> f, std::initializer_list<int> stg, int nk) {
+  const PassList L(f, stg, { nk });
+  halo_wrap(c, L.f, L.stg, L.nk, L.n, PassWidth{ c->dyn_pass_width, nullptr, 0 });
 }
-
-int startn(mom6x_ctx *c, std::initializer_list<double *> f, std::initializer_list<int> stg, std::initializer_list<int> nks,
-           std::initializer_list<int> widths = {}) {
-  double *ff[16]; int ss[16], nn[16]; int n = 0;
-  auto s = stg.begin(); auto q = nks.begin();
-  for (double *p : f) { ff[n] = p; ss[n] = *s++; nn[n] = *q++; n++; }
-  c->pass_w = c->dyn_pass_width;   // (mom6x_set_dyn_pass_width: NIHALO rows of the 3-D fields in a context widened for BTHALO)
-  set_widths(c, widths);
-  halo_start(c, ff, ss, nn, n);
-  c->pass_w = 0; c->pass_wf_n = 0;
-  return MOM6X_OK;
-}
-
-// One group pass of fields with different numbers of levels: consecutive do_group_pass calls of the reference
-// that no computation separates are sent as ONE packed message per neighbour.
-int passn(mom6x_ctx *c, std::initializer_list<double *> f, std::initializer_list<int> stg, std::initializer_list<int> nks) {
-  double *ff[16]; int ss[16], nn[16]; int n = 0;
-  auto s = stg.begin(); auto q = nks.begin();
-  for (double *p : f) { ff[n] = p; ss[n] = *s++; nn[n] = *q++; n++; }
-  c->pass_w = c->dyn_pass_width;
-  halo_wrap(c, ff, ss, nn, n);
-  c->pass_w = 0;
-  return MOM6X_OK;
+// start_group_pass on the halo stream (G%nonblocking_updates) with the fields' own widths; halo_complete() is its complete_group_pass.
+// nks: the fields' numbers of levels, or one number for all of them
+void start(mom6x_ctx *c, std::initializer_list<double *> f, std::initializer_list<int> stg, std::initializer_list<int> nks,
+           std::initializer_list<int> widths) {
+  const PassList L(f, stg, nks);
+  halo_start(c, L.f, L.stg, L.nk, L.n, PassWidth{ c->dyn_pass_width, widths.begin(), (int)widths.size() });
 }
 
 }  // namespace
@@ -267,9 +238,9 @@ extern "C" int mom6x_remap_dyn_split_RK2_aux_vars(mom6x_ctx *c, const mom6x_rema
   if (!s->P.remap_aux) return MOM6X_OK;
   if (s->P.store_CAu) {
     CHK(mom6x_ALE_remap_velocities(c, p, h_old_u, h_old_v, h_new_u, h_new_v, s->u_av, s->v_av));
-    CHK(pass3(c, {s->u_av, s->v_av}, {1, 2}, c->d.nk));
+    pass(c, {s->u_av, s->v_av}, {1, 2}, c->d.nk);
     CHK(mom6x_ALE_remap_velocities(c, p, h_old_u, h_old_v, h_new_u, h_new_v, s->CAu_pred, s->CAv_pred));
-    CHK(pass3(c, {s->CAu_pred, s->CAv_pred}, {1, 2}, c->d.nk));
+    pass(c, {s->CAu_pred, s->CAv_pred}, {1, 2}, c->d.nk);
   }
   CHK(mom6x_ALE_remap_velocities(c, p, h_old_u, h_old_v, h_new_u, h_new_v, s->diffu, s->diffv));
   REQUIRE(!c->halo_error, MOM6X_EHIP, mom6x_last_error());
@@ -298,22 +269,22 @@ extern "C" int mom6x_dyn_split_RK2_restart_fills(mom6x_ctx *c, const double *u, 
     s->CAu_pred_stored = true;
   } else {
     if ((have & MOM6X_RK2_HAVE_UH) && (have & MOM6X_RK2_HAVE_H2)) {   // :1621-1628: an older file's uh, vh, h2
-      pass3(c, { s->h_av }, { 0 }, d.nk);
+      pass(c, { s->h_av }, { 0 }, d.nk);
     } else {
       // h_tmp = h ; continuity(u_av, v_av, h, h_tmp, uh, vh, dt) ; h_av = 0.5*(h + h_tmp)  :1629-1636
       double *h_tmp = s->hp;
       HIPCHK(hipMemcpyAsync(h_tmp, h, n3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
       CHK(mom6x_continuity_PPM(c, s->u_av, s->v_av, h, h_tmp, uh, vh, dt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                nullptr, nullptr, nullptr));
-      pass3(c, { h_tmp }, { 0 }, d.nk);
+      pass(c, { h_tmp }, { 0 }, d.nk);
       KLAUNCH(c, "k_h_av", k_h_av, gridk(nxa(d.ni + 2 * d.halo, -d.halo), d.nj + 2 * d.halo, d.nk, b), b, d, s->h_av, h, (const double *)h_tmp, 0, 0.0, d.halo, 0);
     }
-    pass3(c, { s->u_av, s->v_av, uh, vh }, { 1, 2, 1, 2 }, d.nk);
+    pass(c, { s->u_av, s->v_av, uh, vh }, { 1, 2, 1, 2 }, d.nk);
     CHK(mom6x_CorAdCalc(c, s->u_av, s->v_av, s->h_av, uh, vh, s->CAu_pred, s->CAv_pred));
     s->CAu_pred_stored = true;
   }
   // :1670-1679 (pass_av_h_uvh): the auxiliary velocities and the stored accelerations with their halos
-  if (have & (MOM6X_RK2_HAVE_U2 | MOM6X_RK2_HAVE_CAU)) pass3(c, { s->u_av, s->v_av, s->CAu_pred, s->CAv_pred }, { 1, 2, 1, 2 }, d.nk);
+  if (have & (MOM6X_RK2_HAVE_U2 | MOM6X_RK2_HAVE_CAU)) pass(c, { s->u_av, s->v_av, s->CAu_pred, s->CAv_pred }, { 1, 2, 1, 2 }, d.nk);
   HIPCHK(hipGetLastError());
   REQUIRE(!c->halo_error, MOM6X_EHIP, mom6x_last_error());
   return MOM6X_OK;
@@ -333,10 +304,6 @@ extern "C" int mom6x_step_dyn_split_RK2(mom6x_ctx *c, double *u_inst, double *v_
   REQUIRE(c->a_u, MOM6X_EINVAL, "step_MOM_dyn_split_RK2: vertical viscosity coefficients have not been set");
   HIPCHK(hipSetDevice(c->device));
   RK2State *s = c->rk2;
-  // On EVERY way out of the step (a failed callee returns early) the deferrals it switches on for its own btstep / btcalc calls
-  // are switched off again: a btstep called from outside the step writes its accel_layer arrays (the pending result of the
-  // step's last btstep stays), and a btcalc called from outside writes frhatu / frhatv.
-  struct DeferGuard { mom6x_ctx *c; ~DeferGuard() { bt_defer_layer_accel(c, false); bt_defer_btcalc(c, false); } } defer_guard{c};
   const mom6x_rk2_params &R = s->P;
   const Dm d = c->d;
   const dim3 b = blk2();
@@ -377,16 +344,10 @@ extern "C" int mom6x_step_dyn_split_RK2(mom6x_ctx *c, double *u_inst, double *v_
   const bool fold_bc = s->CAu_pred_stored && !host_coef;
   // (and the column sum of h that bt_mass_source :629 is about to form from the same array: one pass over h less)
   static const bool ms_own = [] { const char *e = getenv("MOM6X_BT_MASS_SOURCE"); return e && !strcmp(e, "own"); }();
-  c->pgf_fold = BcFold{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ms_own ? nullptr : s->eta_h };
-  if (fold_bc) c->pgf_fold = BcFold{ s->CAu_pred, s->CAv_pred, s->diffu, s->diffv, u_bc, v_bc, ms_own ? nullptr : s->eta_h };
+  BcFold fold = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ms_own ? nullptr : s->eta_h };
+  if (fold_bc) fold = BcFold{ s->CAu_pred, s->CAv_pred, s->diffu, s->diffv, u_bc, v_bc, ms_own ? nullptr : s->eta_h };
   bool have_eta_h = false;
-  {
-    const int rc_pf = mom6x_PressureForce(c, h, s->PFu, s->PFv, s->pbce, s->eta_PF);
-    c->pgf_fold = BcFold{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    have_eta_h = c->pgf_eta_h_written;
-    c->pgf_eta_h_written = false;
-    if (rc_pf) return rc_pf;
-  }
+  CHK(PressureForce_bc(c, h, s->PFu, s->PFv, s->pbce, s->eta_PF, fold, &have_eta_h));
   if (!s->CAu_pred_stored) CHK(mom6x_CorAdCalc(c, u_av, v_av, h_av, uh, vh, s->CAu_pred, s->CAv_pred));   // :552-557
   if (!fold_bc)
     KLAUNCH(c, "k_bc_accel", k_bc_accel, gridk(nxa(d.ni + 1, -1), d.nj + 1, nk, b), b, d, c->G, s->CAu_pred, s->CAv_pred, s->PFu, s->PFv,
@@ -400,35 +361,29 @@ extern "C" int mom6x_step_dyn_split_RK2(mom6x_ctx *c, double *u_inst, double *v_
   }
   // pass_eta :549/:617 + pass_visc_rem :618/:641 as ONE group started here; bt_mass_source (own cells only) and the own rows of
   // the continuity call below run while it travels; continuity completes it before it touches a halo row
-  startn(c, { eta, s->visc_rem_u, s->visc_rem_v }, { 0, 1, 2 }, { 1, nk, nk }, { 0, PW.cont, PW.cont });   // :484-486
+  start(c, { eta, s->visc_rem_u, s->visc_rem_v }, { 0, 1, 2 }, { 1, nk, nk }, { 0, PW.cont, PW.cont });   // :484-486
 
-  if (!BTp) { bt_defer_btcalc(c, false); CHK(mom6x_btcalc_strict(c, h, nullptr, nullptr)); }   // :627-628 (BT_THICK_SCHEME = HYBRID, HARMONIC or ARITHMETIC)
+  if (!BTp) CHK(mom6x_btcalc_strict(c, h, nullptr, nullptr));   // :627-628 (BT_THICK_SCHEME = HYBRID, HARMONIC or ARITHMETIC)
   if (have_eta_h) CHK(bt_mass_source_from(c, s->eta_h, eta, 1));        // :629, with the sum k_pgf_main left
   else CHK(mom6x_bt_mass_source(c, h, eta, 1));
   // continuity(u, v, h, hp, uh_in, vh_in, dt, visc_rem_u, visc_rem_v, BT_cont)  :646
   // (hp of this call is never read: :781 overwrites it -- the last convergence is skipped; uh_in, vh_in and BT_cont are the results)
-  c->cont_h_unused = true;
-  {
-    const int rc_c = mom6x_continuity_PPM(c, u_inst, v_inst, h, hp, s->uh_in, s->vh_in, dt, nullptr, nullptr, s->visc_rem_u, s->visc_rem_v,
-                                          nullptr, nullptr, BTp, nullptr, nullptr);
-    c->cont_h_unused = false;
-    if (rc_c) return rc_c;
-  }
+  CHK(continuity_PPM_fold(c, u_inst, v_inst, h, hp, s->uh_in, s->vh_in, dt, nullptr, nullptr, s->visc_rem_u, s->visc_rem_v, nullptr, nullptr,
+                          BTp, nullptr, nullptr, ContFold{ 0, nullptr, nullptr, true }));
   halo_complete(c);
-  if (BTp) {
-    bt_defer_btcalc(c, true);          // (the step's own btstep follows: its column pass forms the thickness fractions)
-    CHK(mom6x_btcalc(c, h, s->BT.h_u, s->BT.h_v));                      // :649-652
-  }
+  // (the step's own btstep follows each of its btcalc calls: its column pass forms the thickness fractions.  MOM6X_BTCALC=eager:
+  //  btcalc writes them)
+  static const bool defer_fr = [] { const char *e = getenv("MOM6X_BTCALC"); return !(e && !strcmp(e, "eager")); }();
+  if (BTp) CHK(btcalc_deferrable(c, h, s->BT.h_u, s->BT.h_v, defer_fr));   // :649-652
   if (calc_dtbt) CHK(set_dtbt_eta(c, s->pbce, BTp ? nullptr : eta));    // :659-668 (eta matters with NONLINEAR_BT_CONTINUITY only)
   // predictor btstep :673-676.  accel_layer_u / _v are only read by the velocity estimates below: with the device's own
   // vertvisc_coef they are evaluated there (LayerAccelSrc) and never written; mom6x_rk2_field materialises them on request.
   const bool defer_la = dev_coef && !host_coef;
-  bt_defer_layer_accel(c, defer_la);
   s->accel_bt_deferred = defer_la;
   LayerAccelSrc LAu, LAv;
-  CHK(mom6x_btstep(c, u_inst, v_inst, eta, dt, u_bc, v_bc, taux, tauy, s->pbce, s->eta_PF, u_av, v_av, s->u_accel_bt,
-                   s->v_accel_bt, s->eta_pred, s->uhbt, s->vhbt, s->visc_rem_u, s->visc_rem_v, BTp, taux_bot, tauy_bot,
-                   s->uh_in, s->vh_in, u_inst, v_inst, nullptr));
+  CHK(btstep_deferrable(c, u_inst, v_inst, eta, dt, u_bc, v_bc, taux, tauy, s->pbce, s->eta_PF, u_av, v_av, s->u_accel_bt,
+                        s->v_accel_bt, s->eta_pred, s->uhbt, s->vhbt, s->visc_rem_u, s->visc_rem_v, BTp, taux_bot, tauy_bot,
+                        s->uh_in, s->vh_in, u_inst, v_inst, nullptr, defer_la));
 
   const double dt_pred = dt * R.be;                                     // :679
   if (!host_coef) {   // (with the callback, it needs up/vp before the solve: no fusion)
@@ -452,22 +407,17 @@ extern "C" int mom6x_step_dyn_split_RK2(mom6x_ctx *c, double *u_inst, double *v_
       CHK(mom6x_vertvisc_remnant(c, s->visc_rem_u, s->visc_rem_v, dt));                            // :763-767
     }
   }
-  start3(c, { s->visc_rem_u, s->visc_rem_v, up, vp }, { 1, 2, 1, 2 }, nk, { PW.cont, PW.cont, PW.cont, PW.cont });   // pass_visc_rem :769 + pass_uvp :761/:773 (halo = max(1, cont_stencil) :485-487): completed inside continuity
+  start(c, { s->visc_rem_u, s->visc_rem_v, up, vp }, { 1, 2, 1, 2 }, { nk }, { PW.cont, PW.cont, PW.cont, PW.cont });   // pass_visc_rem :769 + pass_uvp :761/:773 (halo = max(1, cont_stencil) :485-487): completed inside continuity
 
   // uh = u_av * h ; hp = h + dt * div . uh  :779-781
   // (h_av = 0.5 * (h + hp) of :808-810 on the tile's own cells is written by the call's last convergence kernel, which has
   //  hp in a register and reads nothing twice)
-  c->cont_av_kind = 1; c->cont_av = h_av; c->cont_av_src = h;
-  {
-    const int rc_c = mom6x_continuity_PPM(c, up, vp, h, hp, uh, vh, dt, s->uhbt, s->vhbt, s->visc_rem_u, s->visc_rem_v, u_av, v_av, BTp,
-                                          nullptr, nullptr);
-    c->cont_av_kind = 0;
-    if (rc_c) return rc_c;
-  }
+  CHK(continuity_PPM_fold(c, up, vp, h, hp, uh, vh, dt, s->uhbt, s->vhbt, s->visc_rem_u, s->visc_rem_v, u_av, v_av, BTp, nullptr, nullptr,
+                          ContFold{ 1, h_av, h, false }));
   halo_complete(c);
   // hp (pass_hp_uv :785), the averaged velocities and the transports (pass_av_uvh :804 ... :865) travel on the halo stream
   // while the barotropic mass source is formed; the frame of h_av follows the completion
-  start3(c, { hp, u_av, v_av, uh, vh }, { 0, 1, 2, 1, 2 }, nk, { PW.vel ? 2 : 0, PW.vel, PW.vel, PW.vel, PW.vel });   // :488-490
+  start(c, { hp, u_av, v_av, uh, vh }, { 0, 1, 2, 1, 2 }, { nk }, { PW.vel ? 2 : 0, PW.vel, PW.vel, PW.vel, PW.vel });   // :488-490
 
   // ---- corrector
   CHK(mom6x_bt_mass_source(c, hp, s->eta_pred, 0));                     // :820
@@ -477,10 +427,7 @@ extern "C" int mom6x_step_dyn_split_RK2(mom6x_ctx *c, double *u_inst, double *v_
     KLAUNCH(c, "k_h_av", k_h_av, gridk(nxa(d.ni + 2, -1), d.nj + 2, nk, b), b, d, hp, (const double *)h, (const double *)nullptr, 3, R.begw, 1, 0);
     CHK(mom6x_PressureForce(c, hp, s->PFu, s->PFv, s->pbce, s->eta_PF));
   }
-  if (BTp) {
-    bt_defer_btcalc(c, true);
-    CHK(mom6x_btcalc(c, h, s->BT.h_u, s->BT.h_v));                      // :864-867
-  }
+  if (BTp) CHK(btcalc_deferrable(c, h, s->BT.h_u, s->BT.h_v, defer_fr));   // :864-867
   if (hooks && hooks->horizontal_viscosity) {                           // :884-888
     HIPCHK(hipStreamSynchronize(c->stream));
     int rc = hooks->horizontal_viscosity(hooks->user, u_av, v_av, h_av, uh, vh, s->diffu, s->diffv);
@@ -491,9 +438,9 @@ extern "C" int mom6x_step_dyn_split_RK2(mom6x_ctx *c, double *u_inst, double *v_
   // :893 + :900-907: u_bc_accel = (CAu + PFu) + diffu is formed by the kernel that makes CAu
   CHK(CorAdCalc_bc(c, u_av, v_av, h_av, uh, vh, s->CAu, s->CAv, s->PFu, s->PFv, s->diffu, s->diffv, u_bc, v_bc, nullptr, nullptr, 0.0));
   // corrector btstep :939-942
-  CHK(mom6x_btstep(c, u_inst, v_inst, eta, dt, u_bc, v_bc, taux, tauy, s->pbce, s->eta_PF, u_av, v_av, s->u_accel_bt,
-                   s->v_accel_bt, s->eta_pred, s->uhbt, s->vhbt, s->visc_rem_u, s->visc_rem_v, BTp, taux_bot, tauy_bot, uh, vh,
-                   u_av, v_av, eta_av));
+  CHK(btstep_deferrable(c, u_inst, v_inst, eta, dt, u_bc, v_bc, taux, tauy, s->pbce, s->eta_PF, u_av, v_av, s->u_accel_bt,
+                        s->v_accel_bt, s->eta_pred, s->uhbt, s->vhbt, s->visc_rem_u, s->visc_rem_v, BTp, taux_bot, tauy_bot, uh, vh,
+                        u_av, v_av, eta_av, defer_la));
   KLAUNCH(c, "k_eta", k_eta, grid3(d.ni, d.nj, 1, b), b, d, c->G, eta, (const double *)s->eta_pred, (const double *)nullptr, 0.0);   // :946
   // u = mask*(u + dt*(u_bc_accel + u_accel_bt))  :957-966
   if (!host_coef) {   // :957-966 + :1002-1003 + :1013 + :1022, in place
@@ -512,17 +459,12 @@ extern "C" int mom6x_step_dyn_split_RK2(mom6x_ctx *c, double *u_inst, double *v_
   // the frame of halo cells is copied here and averaged after the group pass has brought the new thicknesses
   KLAUNCH(c, "k_h_av", k_h_av, gridk(nxa(d.ni + 4, -2), d.nj + 4, nk, b), b, d, h_av, (const double *)h, (const double *)nullptr, 1, 0.0, 2, 2);
   const int w_uv = PW.cont ? std::max(2, PW.cont) : 0;   // pass_uv, pass_h: halo = max(2, cont_stencil) :492-493
-  start3(c, { s->visc_rem_u, s->visc_rem_v, u_inst, v_inst }, { 1, 2, 1, 2 }, nk, { PW.cont, PW.cont, w_uv, w_uv });   // pass_visc_rem :1030 + pass_uv :1019/:1034: completed inside continuity
+  start(c, { s->visc_rem_u, s->visc_rem_v, u_inst, v_inst }, { 1, 2, 1, 2 }, { nk }, { PW.cont, PW.cont, w_uv, w_uv });   // pass_visc_rem :1030 + pass_uv :1019/:1034: completed inside continuity
   // uh = u_av * h ; h = h + dt * div . uh  :1041-1043
-  c->cont_av_kind = 2; c->cont_av = h_av; c->cont_av_src = nullptr;
-  {
-    const int rc_c = mom6x_continuity_PPM(c, u_inst, v_inst, h, h, uh, vh, dt, s->uhbt, s->vhbt, s->visc_rem_u, s->visc_rem_v, u_av, v_av,
-                                          nullptr, nullptr, nullptr);
-    c->cont_av_kind = 0;
-    if (rc_c) return rc_c;
-  }
+  CHK(continuity_PPM_fold(c, u_inst, v_inst, h, h, uh, vh, dt, s->uhbt, s->vhbt, s->visc_rem_u, s->visc_rem_v, u_av, v_av, nullptr, nullptr,
+                          nullptr, ContFold{ 2, h_av, nullptr, false }));
   halo_complete(c);
-  start3(c, { h, u_av, v_av, uh, vh }, { 0, 1, 2, 1, 2 }, nk, { w_uv, PW.vel, PW.vel, PW.vel, PW.vel });   // pass_h :1045 + start_group_pass(CS%pass_av_uvh) :1054 (:493-495)
+  start(c, { h, u_av, v_av, uh, vh }, { 0, 1, 2, 1, 2 }, { nk }, { w_uv, PW.vel, PW.vel, PW.vel, PW.vel });   // pass_h :1045 + start_group_pass(CS%pass_av_uvh) :1054 (:493-495)
   halo_complete(c);                                                     // :1072
   KLAUNCH(c, "k_h_av", k_h_av, gridk(nxa(d.ni + 4, -2), d.nj + 4, nk, b), b, d, h_av, (const double *)h, (const double *)nullptr, 2, 0.0, 2, 2);
   // :1072-1079 uhtr += uh*dt: the ring of halo faces here, the box of own faces inside the kernel below, which reads uh, vh anyway

@@ -451,24 +451,28 @@ static int exchange(mom6x_ctx *c, Comm *m, const WrapArgs &A, hipStream_t st, bo
   return MOM6X_OK;
 }
 
-void halo_complete(mom6x_ctx *c);
+// The kernel argument of one pass: fields base .. base + n - 1 of the caller's lists at the widths pw asks for (PassWidth, mom6x_dev.h)
+static WrapArgs wrap_args(const mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int base, int n,
+                          const PassWidth &pw) {
+  WrapArgs A;
+  A.n = n; A.rx = c->dims.reentrant_x;
+  A.w = (pw.w > 0 && pw.w < c->dims.halo) ? pw.w : c->dims.halo; A.w2 = c->dims.halo;
+  for (int q = 0; q < n; q++) {
+    A.f[q] = fields[base + q]; A.stg[q] = staggers[base + q]; A.nk[q] = nks[base + q];
+    A.wf[q] = (base + q < pw.nwf && pw.wf[base + q] > 0 && pw.wf[base + q] < A.w) ? pw.wf[base + q] : 0;
+  }
+  return A;
+}
 
-void halo_wrap(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n) {
+void halo_wrap(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n, PassWidth pw) {
   const Dm d = c->d;
   Comm *m = (Comm *)c->comm;
   if (c->pass_pending) halo_complete(c);   // the message buffers are shared: one group pass at a time
   if (!m && !c->dims.reentrant_x && !c->dims.reentrant_y) return;
   for (int base = 0; base < n; base += MAXF) {
-    WrapArgs A;
-    A.n = (n - base < MAXF) ? (n - base) : MAXF;
-    A.rx = c->dims.reentrant_x;
-    A.w = (c->pass_w > 0 && c->pass_w < d.halo) ? c->pass_w : d.halo; A.w2 = d.halo;
+    const WrapArgs A = wrap_args(c, fields, staggers, nks, base, (n - base < MAXF) ? (n - base) : MAXF, pw);
     int nkmax = 1;
-    for (int q = 0; q < A.n; q++) {
-      A.f[q] = fields[base + q]; A.stg[q] = staggers[base + q]; A.nk[q] = nks[base + q];
-      A.wf[q] = (base + q < c->pass_wf_n && c->pass_wf[base + q] > 0 && c->pass_wf[base + q] < A.w) ? c->pass_wf[base + q] : 0;
-      if (A.nk[q] > nkmax) nkmax = A.nk[q];
-    }
+    for (int q = 0; q < A.n; q++) { if (A.nk[q] > nkmax) nkmax = A.nk[q]; }
     if (m) {
       if (exchange(c, m, A, c->stream) != MOM6X_OK) c->halo_error = true;
       continue;
@@ -497,21 +501,15 @@ void halo_wrap(mom6x_ctx *c, double *const *fields, const int *staggers, const i
 // the context's SECOND stream -- pack, RCCL send/recv, unpack -- while the compute stream goes on with kernels that neither
 // write the passing fields nor read their halos; halo_complete makes the compute stream wait for it.  At most one pass is
 // in flight (a blocking pass completes it first).  Without a communicator (one tile) the pass is done at once.
-void halo_start(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n) {
+void halo_start(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n, PassWidth pw) {
   Comm *m = (Comm *)c->comm;
-  if (!m || !m->comm || n > MAXF) { halo_wrap(c, fields, staggers, nks, n); return; }
+  if (!m || !m->comm || n > MAXF) { halo_wrap(c, fields, staggers, nks, n, pw); return; }
   if (c->pass_pending) halo_complete(c);
   if (!c->ev_ready) {
     if (hipEventCreateWithFlags(&c->ev_ready, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming) != hipSuccess) { c->halo_error = true; return; }
   }
-  WrapArgs A;
-  A.n = n; A.rx = c->dims.reentrant_x;
-  A.w = (c->pass_w > 0 && c->pass_w < c->dims.halo) ? c->pass_w : c->dims.halo; A.w2 = c->dims.halo;
-  for (int q = 0; q < n; q++) {
-    A.f[q] = fields[q]; A.stg[q] = staggers[q]; A.nk[q] = nks[q];
-    A.wf[q] = (q < c->pass_wf_n && c->pass_wf[q] > 0 && c->pass_wf[q] < A.w) ? c->pass_wf[q] : 0;
-  }
+  const WrapArgs A = wrap_args(c, fields, staggers, nks, 0, n, pw);
   // the second stream starts when the compute stream has produced the fields ...
   if (hipEventRecord(c->ev_ready, c->stream) != hipSuccess || hipStreamWaitEvent(c->halo_stream, c->ev_ready, 0) != hipSuccess ||
       exchange(c, m, A, c->halo_stream) != MOM6X_OK || hipEventRecord(c->ev_done, c->halo_stream) != hipSuccess) {
@@ -523,21 +521,15 @@ void halo_start(mom6x_ctx *c, double *const *fields, const int *staggers, const 
 // The same for a pass whose SEND regions the compute stream is about to rewrite (the barotropic sub-cycle: the kernels that run while
 // the messages travel update eta in place next to the tile's edge): the pack runs on the compute stream, in order with them; messages
 // and unpack on the second stream.  false: no communicator that can overlap (the pass has been made, blocking).
-bool halo_start_packed(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n) {
+bool halo_start_packed(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n, PassWidth pw) {
   Comm *m = (Comm *)c->comm;
-  if (!m || !m->comm || n > MAXF) { halo_wrap(c, fields, staggers, nks, n); return false; }
+  if (!m || !m->comm || n > MAXF) { halo_wrap(c, fields, staggers, nks, n, pw); return false; }
   if (c->pass_pending) halo_complete(c);
   if (!c->ev_ready) {
     if (hipEventCreateWithFlags(&c->ev_ready, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming) != hipSuccess) { c->halo_error = true; return false; }
   }
-  WrapArgs A;
-  A.n = n; A.rx = c->dims.reentrant_x;
-  A.w = (c->pass_w > 0 && c->pass_w < c->dims.halo) ? c->pass_w : c->dims.halo; A.w2 = c->dims.halo;
-  for (int q = 0; q < n; q++) {
-    A.f[q] = fields[q]; A.stg[q] = staggers[q]; A.nk[q] = nks[q];
-    A.wf[q] = (q < c->pass_wf_n && c->pass_wf[q] > 0 && c->pass_wf[q] < A.w) ? c->pass_wf[q] : 0;
-  }
+  const WrapArgs A = wrap_args(c, fields, staggers, nks, 0, n, pw);
   if (exchange(c, m, A, c->halo_stream, true) != MOM6X_OK || hipEventRecord(c->ev_done, c->halo_stream) != hipSuccess) {
     c->halo_error = true;
     return false;

@@ -64,7 +64,7 @@ struct BTState;   // barotropic.hip
 struct RK2State;  // dyn_split_RK2.hip
 
 // u_bc_accel = (CAu + PFu) + diffu of the RK2 predictor (RK2.F90:565-572) formed by the pressure-force kernel that has just made
-// PFu (all null: PressureForce on its own)
+// PFu (all null: PressureForce on its own); the RK2 step hands it to PressureForce_bc
 struct BcFold { const double *CAu, *CAv, *diffu, *diffv; double *u_bc, *v_bc; double *eta_h; };   // eta_h: bt_mass_source's column sum (h summed top-down, less the depth), a by-product
 struct mom6x_ctx {
   mom6x_dims dims;
@@ -111,22 +111,12 @@ struct mom6x_ctx {
   bool bt_overlap;          // btstep's own group pass of eta, ubt, vbt overlapped with the own-points half of the next sub-step (mom6x_comm_overlap_btstep)
   bool halo_error;          // set by a failed halo exchange inside a stream-ordered sequence
   hipEvent_t ev_ready, ev_done; bool pass_pending;   // halo.hip: the group pass in flight on the halo stream (start_/complete_group_pass)
-  // the RK2 step's h_av formed by the convergence kernels of a continuity call (continuity.hip k_convergence): kind 1: h_av =
-  // 0.5 * (hin + h) (RK2.F90:808-810); 2: h_av = 0.5 * (h_old + h_new) of an in-place call (:1025-1027 + :1064-1066); 0: off
-  int cont_av_kind; double *cont_av; const double *cont_av_src;
-  // halo width of the NEXT pass (0: the context's); dyn_pass_width: what the RK2 step sets for its own group passes -- a context
-  // whose halo was widened for the barotropic solver (BTHALO) still sends NIHALO rows of the 3-D fields (mom6x_set_dyn_pass_width)
-  int pass_w = 0, dyn_pass_width = 0;
-  // ... and, field by field, the widths create_group_pass(..., halo=) gave the fields of the NEXT pass (pass_wf_n of them; 0 entries
-  // and fields beyond pass_wf_n: pass_w); the RK2 step sends the reference's own 2-3 rows instead of NIHALO = 4 (RK2.F90:484-495)
-  int pass_wf[16] = {0}, pass_wf_n = 0;
+  // the base width of the RK2 step's own group passes (0: the context's halo) -- a context whose halo was widened for the
+  // barotropic solver (BTHALO) still sends NIHALO rows of the 3-D fields (mom6x_set_dyn_pass_width)
+  int dyn_pass_width = 0;
   long long n_exchanges = 0, n_exchange_bytes = 0;
-  BcFold pgf_fold = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-  bool pgf_eta_h_written = false;                                     // the last PressureForce call filled pgf_fold.eta_h   // set by the RK2 step around its PressureForce call
   bool cont_stats_on;               // the statistics-collecting (slower) variant of the mass-flux kernel is in use
   unsigned long long *cont_stats;   // device: Newton statistics of the wave-owned mass-flux kernel (mom6x_continuity_stats), or null
-  bool cont_h_unused;       // the caller of continuity_PPM does not look at the new thicknesses (RK2.F90:646: hp is overwritten at :781
-                            // before anybody reads it): the convergence of the second direction is not computed
   // set_visc.hip: set_visc_CS of set_viscous_BBL, tv%eqn_of_state when use_BBL_EOS, CS%tideamp (caller-owned device array)
   mom6x_set_visc_params sv; bool sv_init = false; bool sv_use_eos = false; mom6x_eos_params sv_eos; const double *sv_tideamp = nullptr;
   // thickness_diffuse.hip: thickness_diffuse_CS, tv%eqn_of_state, CS%khth2d (caller-owned device array) and the work arrays of
@@ -142,9 +132,14 @@ void tracer_hor_diff_free(mom6x_ctx *c);                              // tracer_
 void varmix_free(mom6x_ctx *c);                                       // lateral_mixing_coeffs.hip
 void mixedlayer_restrat_free(mom6x_ctx *c);                           // mixed_layer_restrat.hip
 void comm_free(mom6x_ctx *c);                                         // halo.hip
-void halo_start(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n);   // start_group_pass
+// The widths of one group pass (create_group_pass(..., halo=)).  w: rows / columns of halo filled for its 3-D fields (0: the context's
+// halo); wf[0 .. nwf - 1]: the widths of single 3-D fields (0 entries and fields beyond nwf: w).  The default is what every pass but the
+// RK2 step's own asks for; the step sends the reference's own 2-3 rows instead of NIHALO = 4 (RK2.F90:484-495).
+struct PassWidth { int w = 0; const int *wf = nullptr; int nwf = 0; };
+void halo_wrap(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n, PassWidth pw = {});    // do_group_pass
+void halo_start(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n, PassWidth pw = {});   // start_group_pass
 void halo_complete(mom6x_ctx *c);                                     // complete_group_pass
-bool halo_start_packed(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n);   // ... packed on the compute stream
+bool halo_start_packed(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n, PassWidth pw = {});   // ... packed on the compute stream
 bool halo_can_overlap(const mom6x_ctx *c);
 int comm_allreduce_scalar(mom6x_ctx *c, double *value, int op);       // halo.hip: 0 min, 1 max, 2 sum
 
@@ -189,11 +184,31 @@ struct LayerAccelSrc {
   const double *a2d;       // u_accel_bt | v_accel_bt (2-D)
   double underflow;        // accel_underflow = vel_underflow / dt
 };
+// pressure_force.hip, for the RK2 step: PressureForce whose kernel also forms what `fold` names.  *eta_h_written: fold.eta_h has been
+// filled (the layered path only; with an equation of state nothing of the fold is formed)
+int PressureForce_bc(mom6x_ctx *c, const double *h, double *PFu, double *PFv, double *pbce, double *eta, const BcFold &fold,
+                     bool *eta_h_written);
+// continuity.hip, for the RK2 step: continuity_PPM with the step's extras.  av_kind: the time average of the thicknesses that the
+// convergence kernels write to `av` on the tile's own cells -- 1: av = 0.5 * (av_src + h) (RK2.F90:808-810); 2: av = 0.5 * (h_old +
+// h_new) of an in-place call (:1025-1027 + :1064-1066); 0: none.  h_unused: the caller does not look at the new thicknesses
+// (:646: hp is overwritten at :781 before anybody reads it), the convergence of the second direction is not computed.
+struct ContFold { int av_kind; double *av; const double *av_src; bool h_unused; };
+int continuity_PPM_fold(mom6x_ctx *c, const double *u, const double *v, const double *hin, double *h, double *uh, double *vh, double dt,
+                        const double *uhbt, const double *vhbt, const double *visc_rem_u, const double *visc_rem_v, double *u_cor,
+                        double *v_cor, const mom6x_BT_cont *BT, double *du_cor, double *dv_cor, const ContFold &fold);
 int bt_mass_source_from(mom6x_ctx *c, const double *eta_h, const double *eta, int set_cor);   // bt_mass_source with the column sum given
 int set_dtbt_eta(mom6x_ctx *c, const double *pbce, const double *eta);      // barotropic.hip: set_dtbt(pbce, eta=eta) RK2.F90:667
-void bt_defer_btcalc(mom6x_ctx *c, bool on);                            // barotropic.hip: btcalc's fractions formed by btstep's column pass while on
+// barotropic.hip, for the RK2 step.  btcalc with h_u, h_v and `defer`: only the operands are noted, the next btstep's column pass
+// forms the thickness fractions from them.  btstep with `defer_layer_accel`: k_layer_accel is skipped and accel_layer_u / _v are
+// not written; the result stays pending in the work block (bt_layer_accel_src / _materialize).  The public entries pass false.
+int btcalc_deferrable(mom6x_ctx *c, const double *h, const double *h_u, const double *h_v, bool defer);
+int btstep_deferrable(mom6x_ctx *c, const double *U_in, const double *V_in, const double *eta_in, double dt, const double *bc_accel_u,
+                      const double *bc_accel_v, const double *taux, const double *tauy, const double *pbce, const double *eta_PF_in,
+                      const double *U_Cor, const double *V_Cor, double *accel_layer_u, double *accel_layer_v, double *eta_out,
+                      double *uhbtav, double *vhbtav, const double *visc_rem_u, const double *visc_rem_v, const mom6x_BT_cont *BT_cont,
+                      const double *taux_bot, const double *tauy_bot, const double *uh0, const double *vh0, const double *u_uh0,
+                      const double *v_vh0, double *etaav, bool defer_layer_accel);
 int bt_frhat_materialize(mom6x_ctx *c);                                 // writes frhatu / frhatv if a deferred btcalc is pending
-void bt_defer_layer_accel(mom6x_ctx *c, bool on);                       // barotropic.hip: btstep skips k_layer_accel while on
 bool bt_layer_accel_src(mom6x_ctx *c, LayerAccelSrc *u, LayerAccelSrc *v);   // false if no deferred result is pending
 int bt_layer_accel_materialize(mom6x_ctx *c, double *accel_layer_u, double *accel_layer_v);
 // vert_friction.hip, for the RK2 step.  Which kernels serve a call (one per direction with the column on chip, vertvisc_coef + the

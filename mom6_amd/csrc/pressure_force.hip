@@ -564,10 +564,16 @@ extern "C" int mom6x_PressureForce_init(mom6x_ctx *c, const mom6x_pgf_params *p,
 }
 
 extern "C" int mom6x_PressureForce(mom6x_ctx *c, const double *h, double *PFu, double *PFv, double *pbce, double *eta) {
+  bool eta_h_written;
+  return PressureForce_bc(c, h, PFu, PFv, pbce, eta, BcFold{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr }, &eta_h_written);
+}
+
+int PressureForce_bc(mom6x_ctx *c, const double *h, double *PFu, double *PFv, double *pbce, double *eta, const BcFold &fold,
+                     bool *eta_h_written) {
+  *eta_h_written = false;
   REQUIRE(c && c->pgf_init, MOM6X_EINVAL, "MOM_PressureForce_FV_Bouss: Module must be initialized before it is used.");
   REQUIRE(h && PFu && PFv, MOM6X_EINVAL, "PressureForce: null array");
   HIPCHK(hipSetDevice(c->device));
-  c->pgf_eta_h_written = false;
   const Dm d = c->d;
   double *e;
   int rc;
@@ -602,7 +608,7 @@ extern "C" int mom6x_PressureForce(mom6x_ctx *c, const double *h, double *PFu, d
     }
 #define PGF_EOS(F, P, NAME) KLAUNCH(c, NAME, (k_pgf_main_eos<F, P>), g, b, d, c->G, h, e, c->tv_T, c->tv_S, Tt, Tb, St, Sb, E, PFu, PFv,   \
                                     pbce, eta, GV.g_Earth, GV.H_to_Z, GV.Z_to_H, c->pgf.rho_ref, GxRho_ref, c->pgf.Z_ref, GV.Rho0, \
-                                    rho0_alt, GV.H_subroundoff, GV.dZ_subroundoff, c->pgf_fold)
+                                    rho0_alt, GV.H_subroundoff, GV.dZ_subroundoff, fold)
 #define PGF_FORM(F, N) do { if (mode == 1) PGF_EOS(F, 1, "k_pgf_main_plm<" N ">"); else if (mode == 2) PGF_EOS(F, 2, "k_pgf_main_ppm<" N ">"); \
                             else if (mode == 3) PGF_EOS(F, 3, "k_pgf_main_pcm<" N ">"); else PGF_EOS(F, 0, "k_pgf_main_eos<" N ">"); } while (0)
     if (E.form == MOM6X_EOS_UNESCO) {   // quadratures only
@@ -632,8 +638,8 @@ extern "C" int mom6x_PressureForce(mom6x_ctx *c, const double *h, double *PFu, d
   }
   KLAUNCH(c, "k_pgf_main", k_pgf_main, grid3(nxa(d.ni + 2, -1), d.nj + 2, 1, b), b, d, c->G, h, e, c->Rlay, c->g_prime, PFu, PFv,
           pbce, eta, GV.g_Earth, GV.H_to_Z, GV.Z_to_H, c->pgf.rho_ref, GxRho_ref, c->pgf.Z_ref, 1.0 / GV.Rho0,
-          GV.H_subroundoff, GV.dZ_subroundoff, c->pgf_fold);
-  c->pgf_eta_h_written = (c->pgf_fold.eta_h != nullptr);
+          GV.H_subroundoff, GV.dZ_subroundoff, fold);
+  *eta_h_written = (fold.eta_h != nullptr);
   HIPCHK(hipGetLastError());
   return MOM6X_OK;
 }

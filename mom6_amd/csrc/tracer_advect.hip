@@ -15,7 +15,6 @@
 #include <vector>
 #include "mom6x_dev.h"
 
-void halo_wrap(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n);
 int comm_allreduce_int_sum(mom6x_ctx *c, int *dev, int n);   // halo.hip
 
 #define MAXTR 8

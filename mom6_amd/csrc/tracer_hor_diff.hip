@@ -18,8 +18,6 @@
 #include <cmath>
 #include <cfloat>
 
-void halo_wrap(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n);   // halo.hip
-
 constexpr int HD_TX = 240;     // columns of a work-group's tile (15 x 128 B: tiles start on cache lines); threads HD_TX and HD_TX + 1
                                // fetch the column west and east of the tile
 constexpr int HD_TY = 64;      // rows of a work-group's segment
@@ -358,7 +356,6 @@ extern "C" int mom6x_tracer_hordiff(mom6x_ctx *c, const double *h, double dt, do
     }
     const dim3 g(s->ntx, s->nseg, d.nk);
     for (int itt = 0; itt < num_itts; itt++) {
-      c->pass_w = 0; c->pass_wf_n = 0;
       halo_wrap(c, L.t, stg, nks, L.n);                                        // do_group_pass(CS%pass_t) :545
       KLAUNCH(c, "k_thd_save_x", k_thd_save_x, dim3((d.nj + 255) / 256, s->ntx + 1, d.nk), dim3(256), d, L, s->save_x, s->ntx);
       KLAUNCH(c, "k_thd_save_y", k_thd_save_y, dim3((d.ni + 255) / 256, s->nseg + 1, d.nk), dim3(256), d, L, s->save_y, s->nseg);
