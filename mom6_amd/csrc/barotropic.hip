@@ -43,7 +43,8 @@ enum BTW {   // 2-D work planes
 enum BTC { B_FA_EE = 0, B_FA_E0, B_FA_W0, B_FA_WW, B_uBT_WW, B_uBT_EE, B_crvW, B_crvE, B_uh_WW, B_uh_EE };
 
 struct BTState {
-  // persistent barotropic_CS members
+  mom6x_barotropic_params P;   // barotropic_CS parameters (P.dtbt: CS%dtbt, set by set_dtbt and mom6x_barotropic_dtbt)
+  // persistent barotropic_CS members (device arrays, owned)
   double *frhatu, *frhatv, *IDatu, *IDatv, *ubtav, *vbtav, *eta_cor, *q_D, *D_u_Cor, *D_v_Cor;
   double *work;   // W_COUNT planes
   int nstep_last;
@@ -981,6 +982,8 @@ int bt_layer_accel_materialize(mom6x_ctx *c, double *accel_layer_u, double *acce
   return MOM6X_OK;
 }
 
+bool barotropic_ready(const mom6x_ctx *c) { return c->bts != nullptr; }
+
 void bt_state_free(mom6x_ctx *c) {
   if (!c->bts) return;
   BTState *s = c->bts;
@@ -1004,6 +1007,20 @@ extern "C" int mom6x_btstep_warnings(mom6x_ctx *c, int reset, long long *count, 
   return MOM6X_OK;
 }
 
+// the arrays of a fresh (zeroed) state
+static int bt_state_alloc(mom6x_ctx *c, BTState *s) {
+  const Dm d = c->d;
+  const size_t n2 = (size_t)d.slab, n3 = n2 * d.nk;
+  double **p3[] = { &s->frhatu, &s->frhatv };
+  for (double **q : p3) { HIPCHK(hipMalloc(q, n3 * sizeof(double))); HIPCHK(hipMemsetAsync(*q, 0, n3 * sizeof(double), c->stream)); }
+  double **p2[] = { &s->IDatu, &s->IDatv, &s->ubtav, &s->vbtav, &s->eta_cor, &s->q_D, &s->D_u_Cor, &s->D_v_Cor };
+  for (double **q : p2) { HIPCHK(hipMalloc(q, n2 * sizeof(double))); HIPCHK(hipMemsetAsync(*q, 0, n2 * sizeof(double), c->stream)); }
+  HIPCHK(hipMalloc(&s->work, (size_t)W_COUNT * n2 * sizeof(double)));
+  HIPCHK(hipMalloc(&s->warn, 2 * sizeof(unsigned long long))); HIPCHK(hipMemsetAsync(s->warn, 0, 2 * sizeof(unsigned long long), c->stream));
+  HIPCHK(hipMalloc(&s->warn_info, 4 * sizeof(double))); HIPCHK(hipMemsetAsync(s->warn_info, 0, 4 * sizeof(double), c->stream));
+  return MOM6X_OK;
+}
+
 extern "C" int mom6x_barotropic_init(mom6x_ctx *c, const mom6x_barotropic_params *p) {
   REQUIRE(c && p, MOM6X_EINVAL, "mom6x_barotropic_init: null argument");
   REQUIRE(p->bt_thick_scheme >= MOM6X_BT_THICK_FROM_BT_CONT && p->bt_thick_scheme <= MOM6X_BT_THICK_ARITHMETIC, MOM6X_EINVAL,
@@ -1013,22 +1030,13 @@ extern "C" int mom6x_barotropic_init(mom6x_ctx *c, const mom6x_barotropic_params
           "barotropic_init: BTHALO exceeds the halo of the tile context; create the context with halo = max(NIHALO, BTHALO)");
   REQUIRE(p->min_stencil >= 0 && p->min_stencil <= c->dims.halo, MOM6X_EINVAL, "barotropic_init: bad BT_WIDE_HALO_MIN_STENCIL");
   HIPCHK(hipSetDevice(c->device));
-  c->bt = *p;
   const Dm d = c->d;
-  if (!c->bts) {
-    BTState *s = new BTState();
-    memset(s, 0, sizeof(*s));
-    const size_t n2 = (size_t)d.slab, n3 = n2 * d.nk;
-    double **p3[] = { &s->frhatu, &s->frhatv };
-    for (double **q : p3) { HIPCHK(hipMalloc(q, n3 * sizeof(double))); HIPCHK(hipMemsetAsync(*q, 0, n3 * sizeof(double), c->stream)); }
-    double **p2[] = { &s->IDatu, &s->IDatv, &s->ubtav, &s->vbtav, &s->eta_cor, &s->q_D, &s->D_u_Cor, &s->D_v_Cor };
-    for (double **q : p2) { HIPCHK(hipMalloc(q, n2 * sizeof(double))); HIPCHK(hipMemsetAsync(*q, 0, n2 * sizeof(double), c->stream)); }
-    HIPCHK(hipMalloc(&s->work, (size_t)W_COUNT * n2 * sizeof(double)));
-    HIPCHK(hipMalloc(&s->warn, 2 * sizeof(unsigned long long))); HIPCHK(hipMemsetAsync(s->warn, 0, 2 * sizeof(unsigned long long), c->stream));
-    HIPCHK(hipMalloc(&s->warn_info, 4 * sizeof(double))); HIPCHK(hipMemsetAsync(s->warn_info, 0, 4 * sizeof(double), c->stream));
-    c->bts = s;
+  if (!c->bts) {   // (a second init keeps the state: the restart fields are not zeroed again)
+    c->bts = new BTState();
+    if (const int rc = bt_state_alloc(c, c->bts)) { bt_state_free(c); return rc; }   // (no state without its arrays)
   }
   BTState *s = c->bts;
+  s->P = *p;
   s->nstep_last = 0;
   const dim3 b = blk2();
   KLAUNCH(c, "k_bt_init_static", k_bt_init_static, grid3(d.ni + 1, d.nj + 1, 1, b), b, d, c->G, c->GV.Z_to_H, p->Z_ref,
@@ -1037,7 +1045,6 @@ extern "C" int mom6x_barotropic_init(mom6x_ctx *c, const mom6x_barotropic_params
   const int stg[] = { 3, 1, 2 }, nks[] = { 1, 1, 1 };
   halo_wrap(c, f, stg, nks, 3);
   HIPCHK(hipGetLastError());
-  c->bt_init = true;
   return MOM6X_OK;
 }
 
@@ -1056,16 +1063,16 @@ extern "C" double *mom6x_barotropic_field(mom6x_ctx *c, int which) {
 // CS%dtbt, the scalar restart variable "DTBT" (register_barotropic_restarts :6290): read it for save_restart, set it
 // after restore_state (barotropic_init :5962-5970 keeps a restart's positive DTBT instead of its own estimate).
 extern "C" int mom6x_barotropic_dtbt(mom6x_ctx *c, double *get, const double *set) {
-  REQUIRE(c && c->bt_init, MOM6X_EINVAL, "mom6x_barotropic_dtbt: Module MOM_barotropic must be initialized before it is used.");
-  if (set) { REQUIRE(*set > 0.0, MOM6X_EINVAL, "mom6x_barotropic_dtbt: DTBT must be positive"); c->bt.dtbt = *set; }
-  if (get) *get = c->bt.dtbt;
+  REQUIRE(c && c->bts, MOM6X_EINVAL, "mom6x_barotropic_dtbt: Module MOM_barotropic must be initialized before it is used.");
+  if (set) { REQUIRE(*set > 0.0, MOM6X_EINVAL, "mom6x_barotropic_dtbt: DTBT must be positive"); c->bts->P.dtbt = *set; }
+  if (get) *get = c->bts->P.dtbt;
   return MOM6X_OK;
 }
 
 // btcalc without may_use_default (the calls of step_MOM_dyn_split_RK2 :628, :650, :868): :4426-4429
 extern "C" int mom6x_btcalc_strict(mom6x_ctx *c, const double *h, const double *h_u, const double *h_v) {
-  REQUIRE(c && c->bt_init, MOM6X_EINVAL, "btcalc: Module MOM_barotropic must be initialized before it is used.");
-  REQUIRE((h_u && h_v) || c->bt.bt_thick_scheme != MOM6X_BT_THICK_FROM_BT_CONT, MOM6X_EINVAL,
+  REQUIRE(c && c->bts, MOM6X_EINVAL, "btcalc: Module MOM_barotropic must be initialized before it is used.");
+  REQUIRE((h_u && h_v) || c->bts->P.bt_thick_scheme != MOM6X_BT_THICK_FROM_BT_CONT, MOM6X_EINVAL,
           "btcalc: Inconsistent settings of optional arguments and hvel_scheme.");
   return mom6x_btcalc(c, h, h_u, h_v);
 }
@@ -1076,7 +1083,7 @@ extern "C" int mom6x_btcalc(mom6x_ctx *c, const double *h, const double *h_u, co
 // thickness fractions from them (k_bt_col<., true>), and whoever else wants frhatu / frhatv (set_dtbt, mom6x_barotropic_field)
 // gets them through bt_frhat_materialize.
 int btcalc_deferrable(mom6x_ctx *c, const double *h, const double *h_u, const double *h_v, bool defer) {
-  REQUIRE(c && c->bt_init, MOM6X_EINVAL, "btcalc: Module MOM_barotropic must be initialized before it is used.");
+  REQUIRE(c && c->bts, MOM6X_EINVAL, "btcalc: Module MOM_barotropic must be initialized before it is used.");
   REQUIRE((h_u != nullptr) == (h_v != nullptr), MOM6X_EINVAL, "btcalc: Inconsistent settings of optional arguments");
   REQUIRE(h_u || h, MOM6X_EINVAL, "btcalc: h is required when h_u/h_v are absent");
   HIPCHK(hipSetDevice(c->device));
@@ -1089,7 +1096,7 @@ int btcalc_deferrable(mom6x_ctx *c, const double *h, const double *h_u, const do
     HIPCHK(hipGetLastError());
     return MOM6X_OK;
   }
-  const int scheme = (c->bt.bt_thick_scheme == MOM6X_BT_THICK_FROM_BT_CONT) ? MOM6X_BT_THICK_HYBRID : c->bt.bt_thick_scheme;   // (use_default :4421-4424)
+  const int scheme = (c->bts->P.bt_thick_scheme == MOM6X_BT_THICK_FROM_BT_CONT) ? MOM6X_BT_THICK_HYBRID : c->bts->P.bt_thick_scheme;   // (use_default :4421-4424)
   KLAUNCH(c, "k_btcalc<0>", k_btcalc<0>, grid3(nxa(d.ni + 1, -1), d.nj, 1, b), b, d, c->G, h, h_u, c->bts->frhatu,
                      c->GV.H_subroundoff, c->GV.Z_to_H, scheme);
   KLAUNCH(c, "k_btcalc<1>", k_btcalc<1>, grid3(d.ni, d.nj + 1, 1, b), b, d, c->G, h, h_v, c->bts->frhatv,
@@ -1099,7 +1106,7 @@ int btcalc_deferrable(mom6x_ctx *c, const double *h, const double *h_u, const do
 }
 
 extern "C" int mom6x_bt_mass_source(mom6x_ctx *c, const double *h, const double *eta, int set_cor) {
-  REQUIRE(c && c->bt_init, MOM6X_EINVAL, "bt_mass_source: Module MOM_barotropic must be initialized before it is used.");
+  REQUIRE(c && c->bts, MOM6X_EINVAL, "bt_mass_source: Module MOM_barotropic must be initialized before it is used.");
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
   const dim3 b = blk2();
@@ -1110,7 +1117,7 @@ extern "C" int mom6x_bt_mass_source(mom6x_ctx *c, const double *h, const double 
 }
 
 int bt_mass_source_from(mom6x_ctx *c, const double *eta_h, const double *eta, int set_cor) {
-  REQUIRE(c && c->bt_init, MOM6X_EINVAL, "bt_mass_source: Module MOM_barotropic must be initialized before it is used.");
+  REQUIRE(c && c->bts, MOM6X_EINVAL, "bt_mass_source: Module MOM_barotropic must be initialized before it is used.");
   const Dm d = c->d;
   const dim3 b = blk2();
   KLAUNCH(c, "k_bt_mass_source_from", k_bt_mass_source_from, grid3(d.ni, d.nj, 1, b), b, d, eta_h, eta, c->bts->eta_cor, set_cor);
@@ -1127,7 +1134,7 @@ extern "C" int mom6x_set_dtbt(mom6x_ctx *c, const double *pbce, double gtot_est,
 // find_face_areas(add_max=add_SSH) :5208-5219 otherwise -- the harmonic-mean form of :5221-5236 is never reached from set_dtbt.
 extern "C" int mom6x_set_dtbt_pbce_eta(mom6x_ctx *c, const double *pbce, const double *eta, double SSH_add, double *dtbt_out) {
   REQUIRE(pbce, MOM6X_EINVAL, "set_dtbt: Either pbce or gtot_est must be present.");
-  const bool nonlin = c && c->bt_init && c->bt.nonlinear_continuity && eta;
+  const bool nonlin = c && c->bts && c->bts->P.nonlinear_continuity && eta;
   return set_dtbt_impl(c, pbce, 0.0, nonlin ? 0 : 1, nonlin ? 0.0 : SSH_add, dtbt_out, nonlin ? eta : nullptr);
 }
 // ... as called from step_MOM_dyn_split_RK2 :667 behind a BT_cont_type (eta has no part)
@@ -1136,7 +1143,7 @@ extern "C" int mom6x_set_dtbt_pbce(mom6x_ctx *c, const double *pbce, double *dtb
 }
 int set_dtbt_eta(mom6x_ctx *c, const double *pbce, const double *eta) { return mom6x_set_dtbt_pbce_eta(c, pbce, eta, 0.0, nullptr); }
 static int set_dtbt_impl(mom6x_ctx *c, const double *pbce, double gtot_est, int add_max, double SSH_add, double *dtbt_out, const double *eta) {
-  REQUIRE(c && c->bt_init, MOM6X_EINVAL, "set_dtbt: Module MOM_barotropic must be initialized before it is used.");
+  REQUIRE(c && c->bts, MOM6X_EINVAL, "set_dtbt: Module MOM_barotropic must be initialized before it is used.");
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
   const dim3 b = blk2();
@@ -1145,7 +1152,7 @@ static int set_dtbt_impl(mom6x_ctx *c, const double *pbce, double gtot_est, int 
   double *tmp = s->work + (size_t)W_eta_pred * d.slab;   // scratch plane
   HIPCHK(hipMemsetAsync(tmp, 0, sizeof(double) * d.slab, c->stream));
   KLAUNCH(c, "k_set_dtbt", k_set_dtbt, grid3(d.ni, d.nj, 1, b), b, d, c->G, pbce, s->frhatu, s->frhatv, gtot_est,
-                     c->GV.Z_to_H, c->bt.Z_ref + SSH_add, add_max, c->bt.bebt, c->bt.BT_Coriolis_scale * c->bt.BT_Coriolis_scale, tmp, eta);
+                     c->GV.Z_to_H, c->bts->P.Z_ref + SSH_add, add_max, c->bts->P.bebt, c->bts->P.BT_Coriolis_scale * c->bts->P.BT_Coriolis_scale, tmp, eta);
   HIPCHK(hipGetLastError());
   // min over the tile in the reference's (j outer, i inner) order is order-independent for min():
   std::vector<double> host((size_t)d.slab);
@@ -1156,11 +1163,11 @@ static int set_dtbt_impl(mom6x_ctx *c, const double *pbce, double gtot_est, int 
     const double I2 = host[(size_t)(i + d.ioff) + (size_t)(j + d.joff) * d.pitch];
     if (I2 * min_max_dt2 > 1.0) min_max_dt2 = 1.0 / I2;
   }
-  const double dgeo_de = 1.0 + fmax(0.0, c->bt.G_extra);
+  const double dgeo_de = 1.0 + fmax(0.0, c->bts->P.G_extra);
   double dtbt_max = sqrt(min_max_dt2 / dgeo_de);
   { int rc_ = comm_allreduce_scalar(c, &dtbt_max, 0); if (rc_) return rc_; }   // min_across_PEs(dtbt_max) :3622
-  c->bt.dtbt = c->bt.dtbt_fraction * dtbt_max;
-  if (dtbt_out) *dtbt_out = c->bt.dtbt;
+  c->bts->P.dtbt = c->bts->P.dtbt_fraction * dtbt_max;
+  if (dtbt_out) *dtbt_out = c->bts->P.dtbt;
   return MOM6X_OK;
 }
 
@@ -1183,7 +1190,7 @@ int btstep_deferrable(mom6x_ctx *c, const double *U_in, const double *V_in, cons
                       double *uhbtav, double *vhbtav, const double *visc_rem_u, const double *visc_rem_v, const mom6x_BT_cont *BT_cont,
                       const double *taux_bot, const double *tauy_bot, const double *uh0, const double *vh0, const double *u_uh0,
                       const double *v_vh0, double *etaav, bool defer_layer_accel) {
-  REQUIRE(c && c->bt_init, MOM6X_EINVAL, "btstep: Module MOM_barotropic must be initialized before it is used.");
+  REQUIRE(c && c->bts, MOM6X_EINVAL, "btstep: Module MOM_barotropic must be initialized before it is used.");
   // BT_cont == NULL: USE_BT_CONT_TYPE = False (k_face_areas_as_fits); BOUND_BT_CORRECTION then bounds eta_cor by eta_cor_bound
   // (:6164-6173, :1582-1585), as it does behind a BT_cont_type with BT_CONT_CORR_BOUNDS = False
   REQUIRE(U_in && V_in && eta_in && bc_accel_u && bc_accel_v && taux && tauy && pbce && eta_PF_in && U_Cor && V_Cor &&
@@ -1195,7 +1202,7 @@ int btstep_deferrable(mom6x_ctx *c, const double *U_in, const double *V_in, cons
   REQUIRE((taux_bot != nullptr) == (tauy_bot != nullptr), MOM6X_EINVAL, "btstep: taux_bot and tauy_bot come together");
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
-  const mom6x_barotropic_params &P = c->bt;
+  const mom6x_barotropic_params &P = c->bts->P;
   BTState *s = c->bts;
   double *work = s->work;
   const size_t slab = (size_t)d.slab;

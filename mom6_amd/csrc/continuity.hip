@@ -364,7 +364,8 @@ int run_direction(mom6x_ctx *c, const double *u, const double *h_src, double *h,
                   double *u_cor, const mom6x_BT_cont *BT, double *du_cor, const double *hin_conv,
                   double h_min_conv, bool first_pass, const ContFold &fold) {
   const Dm d = c->d;
-  const mom6x_continuity_params &P = c->cont;
+  const mom6x_continuity_params &P = c->cont->P;
+  double *const hL = c->cont->hL, *const hR = c->cont->hR;
   const dim3 blk(64, 4, 1);
   // edge thicknesses: one cell beyond the LB bounds in the sweep direction
   int ei0 = ish, ei1 = ieh, ej0 = jsh, ej1 = jeh;
@@ -378,10 +379,10 @@ int run_direction(mom6x_ctx *c, const double *u, const double *h_src, double *h,
   const bool lds = !special && (wave || use_lds_path(d.nk));
   if (!lds)
     KLAUNCH(c, "k_edge<DIR>", k_edge<DIR>, grid3(ei1 - ei0 + 1, ej1 - ej0 + 1, d.nk, blk), blk, d, c->G, h_src,
-                       c->hL, c->hR, 2.0 * c->GV.Angstrom_H, scheme, P.monotonic, ei0, ei1, ej0, ej1);
+                       hL, hR, 2.0 * c->GV.Angstrom_H, scheme, P.monotonic, ei0, ei1, ej0, ej1);
   FluxArgs A;
   memset(&A, 0, sizeof(A));
-  A.u = u; A.h_in = h_src; A.hL = c->hL; A.hR = c->hR; A.uh = uh; A.uhbt = uhbt; A.visc_rem = visc_rem;
+  A.u = u; A.h_in = h_src; A.hL = hL; A.hR = hR; A.uh = uh; A.uhbt = uhbt; A.visc_rem = visc_rem;
   A.u_cor = u_cor; A.du_cor = du_cor; A.set_BT_cont = (BT != nullptr);
   if (BT) {
     if (DIR == 0) { A.FA_m0 = BT->FA_u_W0; A.FA_mm = BT->FA_u_WW; A.uBT_mm = BT->uBT_WW;
@@ -439,7 +440,7 @@ int run_direction(mom6x_ctx *c, const double *u, const double *h_src, double *h,
     KLAUNCH(c, "k_mass_flux<DIR>", k_mass_flux<DIR>, grid3(A.a1 - A.a0 + 1, A.b1 - A.b0 + 1, 1, blk), blk, d, c->G, A);
     if (BT_h) {
       KLAUNCH(c, "k_flux_thickness<DIR>", k_flux_thickness<DIR>, grid3(A.a1 - A.a0 + 1, A.b1 - A.b0 + 1, d.nk, blk), blk,
-                         d, c->G, (u_cor ? (const double *)u_cor : u), h_src, c->hL, c->hR, BT_h, dt,
+                         d, c->G, (u_cor ? (const double *)u_cor : u), h_src, hL, hR, BT_h, dt,
                          P.marginal_faces, visc_rem, A.a0, A.a1, A.b0, A.b1, P.vol_CFL);
     }
   }
@@ -458,15 +459,42 @@ int run_direction(mom6x_ctx *c, const double *u, const double *h_src, double *h,
 
 }  // namespace
 
+// created by whichever of mom6x_continuity_init and mom6x_continuity_stats a host calls first
+static ContState *cont_state(mom6x_ctx *c) {
+  if (!c->cont) c->cont = new ContState();
+  return c->cont;
+}
+
 extern "C" int mom6x_continuity_init(mom6x_ctx *c, const mom6x_continuity_params *p) {
   REQUIRE(c && p, MOM6X_EINVAL, "mom6x_continuity_init: null argument");
   REQUIRE(p->sum_order == MOM6X_SUM_REFERENCE || p->sum_order == MOM6X_SUM_TREE16 || p->sum_order == MOM6X_SUM_TREE16_FMA, MOM6X_EINVAL,
           "continuity_PPM: sum_order must be MOM6X_SUM_REFERENCE (0), MOM6X_SUM_TREE16 (1) or MOM6X_SUM_TREE16_FMA (2)");
   REQUIRE(p->sum_order == MOM6X_SUM_REFERENCE || mass_flux_wave_usable(c->d.nk), MOM6X_EUNSUPPORTED,
           "continuity_PPM: sum_order = MOM6X_SUM_TREE16(_FMA) carries at most 128 layers; use MOM6X_SUM_REFERENCE");
-  c->cont = *p;
-  c->cont_init = true;
+  HIPCHK(hipSetDevice(c->device));
+  ContState *S = cont_state(c);
+  const size_t n3 = (size_t)c->dims.slab * c->dims.nk * sizeof(double);
+  if (!S->hL) { HIPCHK(hipMalloc(&S->hL, n3)); HIPCHK(hipMemset(S->hL, work_fill_byte(), n3)); }
+  if (!S->hR) { HIPCHK(hipMalloc(&S->hR, n3)); HIPCHK(hipMemset(S->hR, work_fill_byte(), n3)); }
+  S->P = *p;
+  S->init = true;
   return MOM6X_OK;
+}
+
+void continuity_free(mom6x_ctx *c) {
+  ContState *S = c->cont;
+  if (!S) return;
+  (void)hipFree(S->hL); (void)hipFree(S->hR); (void)hipFree(S->retry); (void)hipFree(S->stats);
+  delete S;
+  c->cont = nullptr;
+}
+
+bool continuity_ready(const mom6x_ctx *c) { return c->cont && c->cont->init; }
+
+// continuity_stencil (MOM_continuity_PPM.F90): the halo width that continuity_PPM reads
+int continuity_stencil(const mom6x_ctx *c) {
+  const mom6x_continuity_params &P = c->cont->P;
+  return P.upwind_1st ? 1 : (P.simple_2nd ? 2 : 3);
 }
 
 // Newton statistics of the mass-flux kernel (sum_order TREE16 only): out[0] = flux re-evaluations (whole column sweeps, counted
@@ -477,16 +505,17 @@ extern "C" int mom6x_continuity_init(mom6x_ctx *c, const mom6x_continuity_params
 extern "C" int mom6x_continuity_stats(mom6x_ctx *c, int mode, unsigned long long *out3) {
   REQUIRE(c, MOM6X_EINVAL, "mom6x_continuity_stats: null context");
   const int reset = (mode == 1);
-  if (mode == 1) c->cont_stats_on = true;
-  if (mode == 0) c->cont_stats_on = false;
+  ContState *S = cont_state(c);
+  if (mode == 1) S->stats_on = true;
+  if (mode == 0) S->stats_on = false;
   HIPCHK(hipSetDevice(c->device));
-  if (!c->cont_stats) {
-    HIPCHK(hipMalloc(&c->cont_stats, 4 * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(c->cont_stats, 0, 4 * sizeof(unsigned long long), c->stream));
+  if (!S->stats) {
+    HIPCHK(hipMalloc(&S->stats, 4 * sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(S->stats, 0, 4 * sizeof(unsigned long long), c->stream));
   }
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (out3) HIPCHK(hipMemcpy(out3, c->cont_stats, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  if (reset) HIPCHK(hipMemsetAsync(c->cont_stats, 0, 4 * sizeof(unsigned long long), c->stream));
+  if (out3) HIPCHK(hipMemcpy(out3, S->stats, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (reset) HIPCHK(hipMemsetAsync(S->stats, 0, 4 * sizeof(unsigned long long), c->stream));
   return MOM6X_OK;
 }
 
@@ -502,7 +531,7 @@ extern "C" int mom6x_continuity_PPM(mom6x_ctx *c, const double *u, const double 
 int continuity_PPM_fold(mom6x_ctx *c, const double *u, const double *v, const double *hin, double *h, double *uh, double *vh, double dt,
                         const double *uhbt, const double *vhbt, const double *visc_rem_u, const double *visc_rem_v, double *u_cor,
                         double *v_cor, const mom6x_BT_cont *BT, double *du_cor, double *dv_cor, const ContFold &fold) {
-  REQUIRE(c && c->cont_init, MOM6X_EINVAL,
+  REQUIRE(c && continuity_ready(c), MOM6X_EINVAL,
           "MOM_continuity_PPM: Module must be initialized before it is used.");
   REQUIRE(u && v && hin && h && uh && vh, MOM6X_EINVAL, "continuity_PPM: null mandatory array");
   REQUIRE((visc_rem_u != nullptr) == (visc_rem_v != nullptr), MOM6X_EINVAL,
@@ -510,9 +539,8 @@ int continuity_PPM_fold(mom6x_ctx *c, const double *u, const double *v, const do
           "in call to continuity_PPM.");
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
-  const mom6x_continuity_params &P = c->cont;
   const double h_min = c->GV.Angstrom_H;
-  int stencil = 3; if (P.simple_2nd) stencil = 2; if (P.upwind_1st) stencil = 1;
+  const int stencil = continuity_stencil(c);
   REQUIRE(d.halo >= stencil, MOM6X_EINVAL, "continuity_PPM: halo smaller than the continuity stencil");
   const bool x_first = ((c->first_direction % 2) == 0);
   const int is = 0, ie = d.ni - 1, js = 0, je = d.nj - 1;

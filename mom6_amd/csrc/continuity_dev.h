@@ -2,6 +2,15 @@
 #pragma once
 #include "mom6x_dev.h"
 
+// The continuity module's state (continuity.hip creates and frees it; continuity_lds.hip and continuity_wave.hip use their parts).
+struct ContState {
+  mom6x_continuity_params P; bool init;   // continuity_PPM_CS (init: mom6x_continuity_init has run; mom6x_continuity_stats may come first)
+  double *hL, *hR;                        // edge values of the PPM reconstruction for one direction at a time (work arrays, nk levels)
+  int *retry; size_t retry_cap;           // continuity_lds.hip: tiles whose Newton solve needs the exact CFL limits
+  bool stats_on;                          // the statistics-collecting (slower) variant of the mass-flux kernel is in use
+  unsigned long long *stats;              // Newton statistics of the wave-owned mass-flux kernel (mom6x_continuity_stats), or null
+};
+
 struct DirMetrics {
   const double *Lface, *IdT, *dT, *dC, *maskC, *IareaT, *mask2dT, *areaT;
   int vol_CFL;   // CONT_PPM_VOLUME_BASED_CFL (the thread-per-column kernels of continuity.hip only)

@@ -728,14 +728,15 @@ int launch(mom6x_ctx *c, const FluxArgs &A, const LdsArgs &E0, size_t lds_bytes)
   E.retry = nullptr;
   if (two_pass) {
     const size_t ntile = (size_t)grid.x;
-    if (c->retry_cap < ntile) {
+    ContState *S = c->cont;
+    if (S->retry_cap < ntile) {
       HIPCHK(hipStreamSynchronize(c->stream));
-      (void)hipFree(c->retry);
-      HIPCHK(hipMalloc(&c->retry, ntile * sizeof(int)));
-      c->retry_cap = ntile;
+      (void)hipFree(S->retry); S->retry = nullptr; S->retry_cap = 0;
+      HIPCHK(hipMalloc(&S->retry, ntile * sizeof(int)));
+      S->retry_cap = ntile;
     }
-    HIPCHK(hipMemsetAsync(c->retry, 0, ntile * sizeof(int), c->stream));
-    E.retry = c->retry;
+    HIPCHK(hipMemsetAsync(S->retry, 0, ntile * sizeof(int), c->stream));
+    E.retry = S->retry;
   }
   auto k_lazy = k_mass_flux_lds<DIR, KL, MAXL, true>;
   auto k_exact = k_mass_flux_lds<DIR, KL, MAXL, false>;

@@ -978,8 +978,8 @@ int launch(mom6x_ctx *c, const FluxArgs &A, const LdsArgs &E0) {
   E.retry = nullptr; E.force_walk = 0;
   // The Newton statistics are a separate instantiation: the counters cost the 253-register kernel its last free registers
   // (139 spills), so they are only compiled into the variant that runs while mom6x_continuity_stats is switched on.
-  const bool stats = (c->cont_stats != nullptr) && c->cont_stats_on;
-  E.stats = stats ? c->cont_stats : nullptr;
+  const bool stats = (c->cont->stats != nullptr) && c->cont->stats_on;
+  E.stats = stats ? c->cont->stats : nullptr;
   // store_pairs writes 16 bytes at (array + row + k slab 8 + (i0 + ioff) 8), i0 + ioff a multiple of 4: aligned when the slab is even
   // and the arrays start on 16 bytes (the context's own arrays do; an array a host hands in need not)
   E.no_pairs = ((d_slab_of(c) & 1) || (((uintptr_t)A.uh | (uintptr_t)A.u_cor | (uintptr_t)E.h_face) & 15)) ? 1 : 0;

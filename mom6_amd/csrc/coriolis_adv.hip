@@ -611,6 +611,8 @@ k_corad_lds(Dm d, const double *__restrict__ G, const double *__restrict__ u, co
 void corad_tile_steps(int *sx, int *sy) { *sx = CF_X - 2; *sy = CF_Y - 2; }
 
 // ---------------------------------------------------------------------------------------------
+struct CorState { mom6x_coriolis_params P; };   // CoriolisAdv_CS, with the overrides of CoriolisAdv_init applied
+
 extern "C" int mom6x_CoriolisAdv_init(mom6x_ctx *c, const mom6x_coriolis_params *p) {
   REQUIRE(c && p, MOM6X_EINVAL, "mom6x_CoriolisAdv_init: null argument");
   REQUIRE(p->Coriolis_Scheme >= MOM6X_SADOURNY75_ENERGY && p->Coriolis_Scheme <= MOM6X_AL_BLEND, MOM6X_EINVAL,
@@ -618,13 +620,17 @@ extern "C" int mom6x_CoriolisAdv_init(mom6x_ctx *c, const mom6x_coriolis_params 
   REQUIRE(p->KE_Scheme >= MOM6X_KE_ARAKAWA && p->KE_Scheme <= MOM6X_KE_GUDONOV, MOM6X_EINVAL, "CoriolisAdv: bad KE_SCHEME");
   REQUIRE(p->PV_Adv_Scheme == 0 || p->PV_Adv_Scheme == MOM6X_PV_ADV_CENTERED || p->PV_Adv_Scheme == MOM6X_PV_ADV_UPWIND1, MOM6X_EINVAL,
           "CoriolisAdv_init: PV_ADV_SCHEME is invalid");
-  c->cor = *p;
-  if (c->cor.Coriolis_Scheme == MOM6X_ROBUST_ENSTRO) { c->cor.Coriolis_En_Dis = 0; c->cor.bound_Coriolis = 0; }   // :1118, :1158
+  if (!c->cor) c->cor = new CorState();
+  mom6x_coriolis_params &P = c->cor->P;
+  P = *p;
+  if (P.Coriolis_Scheme == MOM6X_ROBUST_ENSTRO) { P.Coriolis_En_Dis = 0; P.bound_Coriolis = 0; }   // :1118, :1158
   // CoriolisAdv_init :1158: with CORIOLIS_EN_DIS and SADOURNY75_ENERGY the bound is always effectively off
-  if (c->cor.Coriolis_En_Dis && c->cor.Coriolis_Scheme == MOM6X_SADOURNY75_ENERGY) c->cor.bound_Coriolis = 0;
-  c->cor_init = true;
+  if (P.Coriolis_En_Dis && P.Coriolis_Scheme == MOM6X_SADOURNY75_ENERGY) P.bound_Coriolis = 0;
   return MOM6X_OK;
 }
+
+void CoriolisAdv_free(mom6x_ctx *c) { delete c->cor; c->cor = nullptr; }
+bool CoriolisAdv_ready(const mom6x_ctx *c) { return c->cor != nullptr; }
 
 extern "C" int mom6x_CorAdCalc(mom6x_ctx *c, const double *u, const double *v, const double *h, const double *uh,
                                const double *vh, double *CAu, double *CAv) {
@@ -635,28 +641,29 @@ extern "C" int mom6x_CorAdCalc(mom6x_ctx *c, const double *u, const double *v, c
 int CorAdCalc_bc(mom6x_ctx *c, const double *u, const double *v, const double *h, const double *uh, const double *vh, double *CAu,
                  double *CAv, const double *PFu, const double *PFv, const double *diffu, const double *diffv, double *u_bc,
                  double *v_bc, double *uhtr, double *vhtr, double dt_tr) {
-  REQUIRE(c && c->cor_init, MOM6X_EINVAL, "MOM_CoriolisAdv: Module must be initialized before it is used.");
+  REQUIRE(c && c->cor, MOM6X_EINVAL, "MOM_CoriolisAdv: Module must be initialized before it is used.");
   REQUIRE(u && v && h && uh && vh && CAu && CAv, MOM6X_EINVAL, "CorAdCalc: null array");
   REQUIRE(c->dims.halo >= 3, MOM6X_EINVAL, "CorAdCalc: halo >= 3 required");
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
+  const mom6x_coriolis_params &P = c->cor->P;
   double *q, *KE, *absv = nullptr;
   int rc;
   if ((rc = ctx_scratch(c, SCR_q, d.nk, &q))) return rc;
   if ((rc = ctx_scratch(c, SCR_KE, d.nk, &KE))) return rc;
-  const int scheme = c->cor.Coriolis_Scheme;
+  const int scheme = P.Coriolis_Scheme;
   // the schemes of the default k_corad_fused; ROBUST_ENSTRO, ARAKAWA_LAMB81 and ARAKAWA_LAMB_BLEND take the two-kernel form
   const bool fusable = (scheme == MOM6X_SADOURNY75_ENERGY || scheme == MOM6X_SADOURNY75_ENSTRO || scheme == MOM6X_ARAKAWA_HSU90);
-  if ((c->cor.bound_Coriolis || scheme == MOM6X_ROBUST_ENSTRO) && (rc = ctx_scratch(c, SCR_absv, d.nk, &absv))) return rc;
+  if ((P.bound_Coriolis || scheme == MOM6X_ROBUST_ENSTRO) && (rc = ctx_scratch(c, SCR_absv, d.nk, &absv))) return rc;
   double *Ihq = nullptr;
   if (scheme == MOM6X_AL_BLEND && (rc = ctx_scratch(c, SCR_t0, d.nk, &Ihq))) return rc;
   CoradAcc X0 = {};
-  X0.Fe_m2 = c->cor.F_eff_max_blend - 2.0;                                            // :544-548
-  X0.wt_lin = c->cor.wt_lin_blend < 1e-16 ? 1e-16 : (c->cor.wt_lin_blend > 1.0 ? 1.0 : c->cor.wt_lin_blend);   // :1139
+  X0.Fe_m2 = P.F_eff_max_blend - 2.0;                                            // :544-548
+  X0.wt_lin = P.wt_lin_blend < 1e-16 ? 1e-16 : (P.wt_lin_blend > 1.0 ? 1.0 : P.wt_lin_blend);   // :1139
   X0.rat_lin = 1.5 * X0.Fe_m2 / (X0.wt_lin > 1.0e-16 ? X0.wt_lin : 1.0e-16);
-  if (c->cor.F_eff_max_blend <= 2.0) { X0.Fe_m2 = -1.; X0.rat_lin = -1.0; }
+  if (P.F_eff_max_blend <= 2.0) { X0.Fe_m2 = -1.; X0.rat_lin = -1.0; }
   X0.eps_vel = 1.0e-10 * 1.0; X0.h_tiny = c->GV.Angstrom_H;                              // :242-243
-  X0.pv_upwind = (c->cor.PV_Adv_Scheme == MOM6X_PV_ADV_UPWIND1);
+  X0.pv_upwind = (P.PV_Adv_Scheme == MOM6X_PV_ADV_UPWIND1);
   const dim3 b = blk2();
   const double vol_neglect = c->GV.H_subroundoff * ((1e-4 * 1.0) * (1e-4 * 1.0));
   // (A barrier-free form -- every thread evaluating q at its own vertex and the one to the south, the western one by a lane
@@ -669,21 +676,21 @@ int CorAdCalc_bc(mom6x_ctx *c, const double *u, const double *v, const double *h
     constexpr int xcd_order = 1;   // (the launch-order walk of the tiles lost in round 4 and is gone: profiles/README.md)
     const dim3 gt((unsigned)(((gx * gy * gz + 7) / 8) * 8), 1, 1);
     // the default configuration has its own kernel (inputs, q and KE through LDS); every other one the generic k_corad_fused
-    const bool lean = (scheme == MOM6X_SADOURNY75_ENERGY) && !c->cor.bound_Coriolis && !c->cor.Coriolis_En_Dis;
+    const bool lean = (scheme == MOM6X_SADOURNY75_ENERGY) && !P.bound_Coriolis && !P.Coriolis_En_Dis;
     if (lean)
       KLAUNCH(c, "k_corad_lds", k_corad_lds, gt, bt, d, c->G, u, v, uh, vh, CAu, CAv, h, PFu, PFv, diffu, diffv, u_bc, v_bc, uhtr, vhtr, dt_tr,
-              c->cor.no_slip, c->cor.KE_Scheme, vol_neglect, kc, gx, gy, gz, xcd_order);
+              P.no_slip, P.KE_Scheme, vol_neglect, kc, gx, gy, gz, xcd_order);
     else
-      KLAUNCH(c, "k_corad_fused", k_corad_fused<false>, gt, bt, d, c->G, u, v, uh, vh, CAu, CAv, c->cor.Coriolis_Scheme, c->cor.bound_Coriolis, h,
-              c->cor.Coriolis_En_Dis, PFu, PFv, diffu, diffv, u_bc, v_bc, uhtr, vhtr, dt_tr, c->cor.no_slip, c->cor.KE_Scheme, vol_neglect, kc, gx, gy, gz,
+      KLAUNCH(c, "k_corad_fused", k_corad_fused<false>, gt, bt, d, c->G, u, v, uh, vh, CAu, CAv, P.Coriolis_Scheme, P.bound_Coriolis, h,
+              P.Coriolis_En_Dis, PFu, PFv, diffu, diffv, u_bc, v_bc, uhtr, vhtr, dt_tr, P.no_slip, P.KE_Scheme, vol_neglect, kc, gx, gy, gz,
               xcd_order);
     HIPCHK(hipGetLastError());
     return MOM6X_OK;
   }
   KLAUNCH(c, "k_corad_q", k_corad_q, gridk(nxa(d.ni + 3, -2), d.nj + 3, d.nk, b), b, d, c->G, u, v, h, q, absv, KE,
-          c->cor.no_slip, c->cor.KE_Scheme, vol_neglect, Ihq);
+          P.no_slip, P.KE_Scheme, vol_neglect, Ihq);
   KLAUNCH(c, "k_corad_acc", k_corad_acc, gridk(nxa(d.ni + 1, -1), d.nj + 1, d.nk, b), b, d, c->G, u, v, uh, vh, q, absv, KE,
-          CAu, CAv, c->cor.Coriolis_Scheme, c->cor.bound_Coriolis, h, c->cor.Coriolis_En_Dis, PFu, PFv, diffu, diffv, u_bc, v_bc,
+          CAu, CAv, P.Coriolis_Scheme, P.bound_Coriolis, h, P.Coriolis_En_Dis, PFu, PFv, diffu, diffv, u_bc, v_bc,
           uhtr, vhtr, dt_tr, (const double *)Ihq, X0);
   HIPCHK(hipGetLastError());
   return MOM6X_OK;

@@ -68,6 +68,15 @@ static void prof_collect(mom6x_ctx *c) {
   p->recs.clear();
 }
 
+static void prof_free(mom6x_ctx *c) {
+  Prof *p = c->prof;
+  if (!p) return;
+  for (auto &r : p->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+  for (hipEvent_t e : p->pool) (void)hipEventDestroy(e);
+  delete p;
+  c->prof = nullptr;
+}
+
 extern "C" int mom6x_prof_enable(mom6x_ctx *c, int on) {
   REQUIRE(c, MOM6X_EINVAL, "mom6x_prof_enable: null ctx");
   HIPCHK(hipSetDevice(c->device));
@@ -181,9 +190,17 @@ extern "C" int mom6x_dims_init(mom6x_dims *d, int ni, int nj, int nk, int halo) 
   return MOM6X_OK;
 }
 
-void bt_state_free(mom6x_ctx *ctx);   // barotropic.hip
-void rk2_state_free(mom6x_ctx *ctx);  // dyn_split_RK2.hip
-void ta_state_free(mom6x_ctx *ctx);   // tracer_advect.hip
+// the streams and arrays of a context whose members are otherwise set (on failure mom6x_ctx_create destroys what there is)
+static int ctx_alloc(mom6x_ctx *c, const double *metrics_host) {
+  HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&c->halo_stream, hipStreamNonBlocking));
+  const size_t nG = (size_t)MOM6X_G_COUNT * c->dims.slab;
+  HIPCHK(hipMalloc(&c->G, nG * sizeof(double)));
+  HIPCHK(hipMemcpy(c->G, metrics_host, nG * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc(&c->flag, sizeof(int)));
+  HIPCHK(hipMemset(c->flag, 0, sizeof(int)));
+  return MOM6X_OK;
+}
 
 extern "C" int mom6x_ctx_create(mom6x_ctx **out, const mom6x_dims *dims, int device,
                                 const double *metrics_host, const mom6x_vgrid *GV,
@@ -200,30 +217,14 @@ extern "C" int mom6x_ctx_create(mom6x_ctx **out, const mom6x_dims *dims, int dev
   REQUIRE(ndev > 0 && device >= 0 && device < ndev, MOM6X_EHIP,
           "mom6x_ctx_create: no such HIP device (the product path has no CPU fallback)");
   HIPCHK(hipSetDevice(device));
-  mom6x_ctx *c = new mom6x_ctx();
+  mom6x_ctx *c = new mom6x_ctx();   // (all members zero: no stream, no array, no module state)
   c->dims = *dims;
   c->d = make_dm(*dims);
   c->device = device;
   c->GV = *GV;
   c->first_direction = first_direction;
-  c->cont_init = false; c->bt_init = false;
-  c->prof_on = false; c->prof = nullptr; c->comm = nullptr; c->halo_error = false; c->ta = nullptr;
-  c->cor_init = false; c->pgf_init = false; c->Rlay = c->g_prime = nullptr;
-  c->a_u = c->a_v = c->h_u = c->h_v = c->Ray_u = c->Ray_v = nullptr;
-  for (int m = 0; m < MOM6X_NSCR; m++) { c->scr[m] = nullptr; c->scr_nlev[m] = 0; }
-  c->hL = c->hR = nullptr; c->bts = nullptr; c->rk2 = nullptr; c->flag = nullptr; c->G = nullptr;
-  HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIPCHK(hipStreamCreateWithFlags(&c->halo_stream, hipStreamNonBlocking));
-  size_t nG = (size_t)MOM6X_G_COUNT * dims->slab;
-  HIPCHK(hipMalloc(&c->G, nG * sizeof(double)));
-  HIPCHK(hipMemcpy(c->G, metrics_host, nG * sizeof(double), hipMemcpyHostToDevice));
-  size_t n3 = (size_t)dims->slab * dims->nk;
-  HIPCHK(hipMalloc(&c->hL, n3 * sizeof(double)));
-  HIPCHK(hipMalloc(&c->hR, n3 * sizeof(double)));
-  HIPCHK(hipMemset(c->hL, work_fill_byte(), n3 * sizeof(double)));
-  HIPCHK(hipMemset(c->hR, work_fill_byte(), n3 * sizeof(double)));
-  HIPCHK(hipMalloc(&c->flag, sizeof(int)));
-  HIPCHK(hipMemset(c->flag, 0, sizeof(int)));
+  const int rc = ctx_alloc(c, metrics_host);
+  if (rc) { (void)mom6x_ctx_destroy(c); return rc; }
   *out = c;
   return MOM6X_OK;
 }
@@ -231,25 +232,30 @@ extern "C" int mom6x_ctx_create(mom6x_ctx **out, const mom6x_dims *dims, int dev
 extern "C" int mom6x_ctx_destroy(mom6x_ctx *c) {
   if (!c) return MOM6X_OK;
   (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipStreamSynchronize(c->halo_stream);
-  bt_state_free(c);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->halo_stream) (void)hipStreamSynchronize(c->halo_stream);
+  bt_state_free(c);    // (before the step's: with no barotropic state left, a deferred btcalc is dropped, not completed)
   rk2_state_free(c);
-  comm_free(c);
-  ta_state_free(c);
-  for (int m = 0; m < MOM6X_NSCR; m++) (void)hipFree(c->scr[m]);
-  (void)hipFree(c->Rlay); (void)hipFree(c->g_prime); (void)hipFree(c->retry); (void)hipFree(c->cont_stats);
+  continuity_free(c);
+  CoriolisAdv_free(c);
+  PressureForce_free(c);
+  vertvisc_free(c);
   hor_visc_free(c);
+  ALE_free(c);
+  ta_state_free(c);
   diag_sums_free(c);
+  set_visc_free(c);
   thickness_diffuse_free(c);
   tracer_hor_diff_free(c);
   varmix_free(c);
   mixedlayer_restrat_free(c);
-  (void)hipFree(c->regrid_res); (void)hipFree(c->regrid_vec); (void)hipFree(c->remap_src); (void)hipFree(c->remap_hvel);
-  (void)hipFree(c->vv_a_u); (void)hipFree(c->vv_a_v); (void)hipFree(c->vv_h_u); (void)hipFree(c->vv_h_v);
-  (void)hipFree(c->G); (void)hipFree(c->hL); (void)hipFree(c->hR); (void)hipFree(c->flag);
+  comm_free(c);
+  for (int m = 0; m < MOM6X_NSCR; m++) (void)hipFree(c->scr[m]);
+  (void)hipFree(c->G); (void)hipFree(c->flag);
   if (c->ev_ready) { (void)hipEventDestroy(c->ev_ready); (void)hipEventDestroy(c->ev_done); }
-  (void)hipStreamDestroy(c->stream); (void)hipStreamDestroy(c->halo_stream);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
+  if (c->halo_stream) (void)hipStreamDestroy(c->halo_stream);
+  prof_free(c);
   delete c;
   return MOM6X_OK;
 }

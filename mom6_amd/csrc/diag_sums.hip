@@ -12,6 +12,24 @@
 #include <vector>
 #include "mom6x_dev.h"
 
+// The reductions' integer accumulators and the members of Sum_output_CS the sums of write_energy read.  Whichever comes first, a
+// checksum or mom6x_sum_output_init, creates the state
+struct DiagState {
+  long long *red; size_t red_cap;           // integer accumulators of the reproducing sums / checksums (grown on demand), owned
+  bool init;                                // mom6x_sum_output_init has run: what follows is set
+  mom6x_sum_output_params p;
+  int listsize;                             // Depth_List: 1-based arrays of listsize entries
+  std::vector<double> depth, area, vol_below;
+  std::vector<int> lH;                      // CS%lH: where each interface's volume was found last time
+  std::vector<double> g_prime;
+  double *g_prime_dev, *z0_dev;             // GV%g_prime(1:nk), Z_0APE(1:nk+1), owned
+  long long *cfl_dev;                       // the two CFL maxima as bit patterns (non-negative doubles order like integers), owned
+};
+static DiagState *diag_state(mom6x_ctx *c) {
+  if (!c->diag) c->diag = new DiagState();
+  return c->diag;
+}
+
 namespace {
 
 constexpr int NI_EFP = 6;
@@ -197,13 +215,14 @@ static int reduce_src(mom6x_ctx *c, const Src &src, const char *kname, int nk, i
   REQUIRE(is >= -D.halo - 1 && ie < D.ni + D.halo && js >= -D.halo - 1 && je < D.nj + D.halo && is <= ie + 1 && js <= je + 1,
           MOM6X_EINVAL, "reduce: the index range leaves the data domain");
   const size_t nwords = (size_t)nk * (A_NSUM + 1 + 4);
-  if (c->red_cap < nwords) {
-    if (c->red) HIPCHK(hipFree(c->red));
-    c->red = nullptr; c->red_cap = 0;
-    HIPCHK(hipMalloc(&c->red, nwords * sizeof(long long)));
-    c->red_cap = nwords;
+  DiagState *S = diag_state(c);
+  if (S->red_cap < nwords) {
+    if (S->red) HIPCHK(hipFree(S->red));
+    S->red = nullptr; S->red_cap = 0;
+    HIPCHK(hipMalloc(&S->red, nwords * sizeof(long long)));
+    S->red_cap = nwords;
   }
-  AccPtr A; A.sum = c->red; A.mn = A.sum + (size_t)nk * A_NSUM; A.mx = A.mn + nk;
+  AccPtr A; A.sum = S->red; A.mn = A.sum + (size_t)nk * A_NSUM; A.mx = A.mn + nk;
   KLAUNCH(c, "k_red_init", k_red_init, dim3((nk + 63) / 64), dim3(64), A, nk);
   const int nx = ie - is + 1, ny = je - js + 1;
   if (nx > 0 && ny > 0)
@@ -216,7 +235,7 @@ static int reduce_src(mom6x_ctx *c, const Src &src, const char *kname, int nk, i
   }
   H.sum.resize((size_t)nk * A_NSUM); H.mn.resize(nk); H.mx.resize((size_t)nk * 4);
   std::vector<long long> buf(nwords);
-  HIPCHK(hipMemcpyAsync(buf.data(), c->red, nwords * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(buf.data(), S->red, nwords * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   memcpy(H.sum.data(), buf.data(), H.sum.size() * 8);
   memcpy(H.mn.data(), buf.data() + H.sum.size(), H.mn.size() * 8);
@@ -425,16 +444,6 @@ extern "C" int mom6x_field_chksum(mom6x_ctx *c, const double *array, int nk, int
 // ---- write_energy (MOM_sum_output.F90:321) ---------------------------------------------------------------------------
 namespace {
 
-struct DiagState {                          // the members of Sum_output_CS the sums of write_energy read
-  mom6x_sum_output_params p;
-  int listsize;                             // Depth_List: 1-based arrays of listsize entries
-  std::vector<double> depth, area, vol_below;
-  std::vector<int> lH;                      // CS%lH: where each interface's volume was found last time
-  std::vector<double> g_prime;
-  double *g_prime_dev, *z0_dev;             // GV%g_prime(1:nk), Z_0APE(1:nk+1)
-  long long *cfl_dev;                       // the two CFL maxima as bit patterns (non-negative doubles order like integers)
-};
-
 // PE_pt of the Boussinesq branch :623-634: one thread per column, from the bottom up; plane nk+1 is zero
 __global__ void __launch_bounds__(256)
 k_pe_pt(Dm d, const double *__restrict__ G, const double *__restrict__ h, const double *__restrict__ Z_0APE,
@@ -519,12 +528,6 @@ k_max_cfl(Dm d, const double *__restrict__ G, const double *__restrict__ u, cons
   }
 }
 
-void diag_state_free(DiagState *s) {
-  if (!s) return;
-  (void)hipFree(s->g_prime_dev); (void)hipFree(s->z0_dev); (void)hipFree(s->cfl_dev);
-  delete s;
-}
-
 }  // namespace
 
 int comm_allreduce_f64(mom6x_ctx *c, double *dev, size_t n, int op);             // halo.hip
@@ -581,16 +584,23 @@ static void create_depth_list(DiagState *S, const std::vector<double> &Dlist, co
   S->depth[listsize] = S->depth[listsize - 1];
 }
 
+// back to the state before mom6x_sum_output_init
+static void sum_output_end(DiagState *S) {
+  (void)hipFree(S->g_prime_dev); (void)hipFree(S->z0_dev); (void)hipFree(S->cfl_dev);
+  S->g_prime_dev = S->z0_dev = nullptr; S->cfl_dev = nullptr;
+  S->listsize = 0; S->depth.clear(); S->area.clear(); S->vol_below.clear();
+  S->init = false;
+}
+
 // MOM_sum_output_init :147 (the members the sums need) + depth_list_setup :1161 (the list is created, not read)
 extern "C" int mom6x_sum_output_init(mom6x_ctx *c, const mom6x_sum_output_params *p, const double *g_prime) {
   REQUIRE(c && p && g_prime, MOM6X_EINVAL, "mom6x_sum_output_init: null argument");
   REQUIRE(c->GV.Boussinesq == 1, MOM6X_EUNSUPPORTED, "write_energy: only the Boussinesq branches are on the device path");
   const mom6x_dims &D = c->dims;
   const int nk = D.nk;
-  diag_state_free((DiagState *)c->diag); c->diag = nullptr;
-  DiagState *S = new DiagState();
-  S->p = *p; S->g_prime_dev = S->z0_dev = nullptr; S->cfl_dev = nullptr; S->listsize = 0;
-  c->diag = S;
+  DiagState *S = diag_state(c);
+  sum_output_end(S);   // (a second init starts over; the accumulators stay)
+  S->p = *p;
   S->g_prime.assign(g_prime, g_prime + nk);
   HIPCHK(hipMalloc(&S->g_prime_dev, sizeof(double) * nk));
   HIPCHK(hipMalloc(&S->z0_dev, sizeof(double) * (nk + 1)));
@@ -626,12 +636,13 @@ extern "C" int mom6x_sum_output_init(mom6x_ctx *c, const mom6x_sum_output_params
     create_depth_list(S, Dv, Av, mls);
   }
   S->lH.assign(nk, S->listsize - 1);                                             // :1194-1196
+  S->init = true;
   return MOM6X_OK;
 }
 
 extern "C" int mom6x_depth_list(const mom6x_ctx *c, int *listsize, double *depth, double *area, double *vol_below) {
-  REQUIRE(c && c->diag && listsize, MOM6X_EINVAL, "mom6x_depth_list: mom6x_sum_output_init has not been called");
-  const DiagState *S = (const DiagState *)c->diag;
+  REQUIRE(c && c->diag && c->diag->init && listsize, MOM6X_EINVAL, "mom6x_depth_list: mom6x_sum_output_init has not been called");
+  const DiagState *S = c->diag;
   *listsize = S->listsize;
   for (int n = 0; n < S->listsize; n++) {
     if (depth) depth[n] = S->depth[n + 1];
@@ -645,8 +656,8 @@ extern "C" int mom6x_depth_list(const mom6x_ctx *c, int *listsize, double *depth
 extern "C" int mom6x_write_energy(mom6x_ctx *c, const double *u, const double *v, const double *h, const double *T, const double *S_,
                                   mom6x_energy_sums *out, double *mass_lay, double *KE, double *PE, double *Z_0APE) {
   REQUIRE(c && u && v && h && out && mass_lay && KE && PE && Z_0APE, MOM6X_EINVAL, "mom6x_write_energy: null argument");
-  REQUIRE(c->diag, MOM6X_EINVAL, "write_energy: Module must be initialized before it is used.");
-  DiagState *S = (DiagState *)c->diag;
+  REQUIRE(c->diag && c->diag->init, MOM6X_EINVAL, "write_energy: Module must be initialized before it is used.");
+  DiagState *S = c->diag;
   REQUIRE(!S->p.use_temperature || (T && S_), MOM6X_EINVAL, "write_energy: ENABLE_THERMODYNAMICS needs tv%T and tv%S");
   const mom6x_dims &D = c->dims;
   const Dm d = c->d;
@@ -714,7 +725,9 @@ extern "C" int mom6x_write_energy(mom6x_ctx *c, const double *u, const double *v
 }
 
 void diag_sums_free(mom6x_ctx *c) {
-  if (c->red) (void)hipFree(c->red);
-  c->red = nullptr; c->red_cap = 0;
-  diag_state_free((DiagState *)c->diag); c->diag = nullptr;
+  DiagState *S = c->diag;
+  if (!S) return;
+  (void)hipFree(S->red); (void)hipFree(S->g_prime_dev); (void)hipFree(S->z0_dev); (void)hipFree(S->cfl_dev);
+  delete S;
+  c->diag = nullptr;
 }

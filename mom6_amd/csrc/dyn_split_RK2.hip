@@ -136,9 +136,7 @@ struct PassWidths { int cont, vel; };
 PassWidths pass_widths(const mom6x_ctx *c) {
   static const bool full = [] { const char *e = getenv("MOM6X_PASS_WIDTHS"); return e && !strcmp(e, "full"); }();
   if (full) return PassWidths{ 0, 0 };
-  const int cont = c->cont.upwind_1st ? 1 : (c->cont.simple_2nd ? 2 : 3);
-  const int vel = (c->hv_init && (c->hv.Leith_Kh || c->hv.Leith_Ah)) ? 3 : 2;
-  return PassWidths{ cont, vel };
+  return PassWidths{ continuity_stencil(c), hor_visc_vel_stencil(c) };
 }
 
 // The step's group passes, all at the base width mom6x_set_dyn_pass_width gave (NIHALO rows of the 3-D fields in a context widened
@@ -180,18 +178,8 @@ void rk2_state_free(mom6x_ctx *c) {
   c->rk2 = nullptr;
 }
 
-extern "C" int mom6x_initialize_dyn_split_RK2(mom6x_ctx *c, const mom6x_rk2_params *p) {
-  REQUIRE(c && p, MOM6X_EINVAL, "mom6x_initialize_dyn_split_RK2: null argument");
-  REQUIRE(c->cont_init && c->bt_init && c->cor_init && c->pgf_init, MOM6X_EINVAL,
-          "initialize_dyn_split_RK2: continuity, barotropic, CoriolisAdv and PressureForce must be initialised first");
-  REQUIRE(!p->remap_aux || p->store_CAu, MOM6X_EINVAL, "REMAP_AUXILIARY_VARS requires that STORE_CORIOLIS_ACCEL = True.");   // :1474
-  REQUIRE(p->BT_use_layer_fluxes && p->store_CAu, MOM6X_EUNSUPPORTED,
-          "dyn_split_RK2: only BT_USE_LAYER_FLUXES=True and STORE_CORIOLIS_ACCEL=True are supported");
-  HIPCHK(hipSetDevice(c->device));
-  if (c->rk2) rk2_state_free(c);
-  RK2State *s = new RK2State();
-  memset(s, 0, sizeof(*s));
-  s->P = *p;
+// the arrays of a fresh (zeroed) state
+static int rk2_state_alloc(mom6x_ctx *c, RK2State *s) {
   const size_t n2 = (size_t)c->dims.slab, n3 = n2 * c->dims.nk;
   double **p3[] = { &s->CAu, &s->CAv, &s->CAu_pred, &s->CAv_pred, &s->PFu, &s->PFv, &s->diffu, &s->diffv, &s->visc_rem_u,
                     &s->visc_rem_v, &s->u_accel_bt, &s->v_accel_bt, &s->u_av, &s->v_av, &s->h_av, &s->pbce, &s->up, &s->vp,
@@ -201,8 +189,21 @@ extern "C" int mom6x_initialize_dyn_split_RK2(mom6x_ctx *c, const mom6x_rk2_para
                     &s->BT.FA_u_E0, &s->BT.FA_u_W0, &s->BT.FA_u_WW, &s->BT.uBT_WW, &s->BT.uBT_EE, &s->BT.FA_v_NN, &s->BT.FA_v_N0,
                     &s->BT.FA_v_S0, &s->BT.FA_v_SS, &s->BT.vBT_SS, &s->BT.vBT_NN };
   for (double **q : p2) { HIPCHK(hipMalloc(q, n2 * sizeof(double))); HIPCHK(hipMemsetAsync(*q, 0, n2 * sizeof(double), c->stream)); }
-  s->CAu_pred_stored = false;
-  c->rk2 = s;
+  return MOM6X_OK;
+}
+
+extern "C" int mom6x_initialize_dyn_split_RK2(mom6x_ctx *c, const mom6x_rk2_params *p) {
+  REQUIRE(c && p, MOM6X_EINVAL, "mom6x_initialize_dyn_split_RK2: null argument");
+  REQUIRE(continuity_ready(c) && barotropic_ready(c) && CoriolisAdv_ready(c) && PressureForce_ready(c), MOM6X_EINVAL,
+          "initialize_dyn_split_RK2: continuity, barotropic, CoriolisAdv and PressureForce must be initialised first");
+  REQUIRE(!p->remap_aux || p->store_CAu, MOM6X_EINVAL, "REMAP_AUXILIARY_VARS requires that STORE_CORIOLIS_ACCEL = True.");   // :1474
+  REQUIRE(p->BT_use_layer_fluxes && p->store_CAu, MOM6X_EUNSUPPORTED,
+          "dyn_split_RK2: only BT_USE_LAYER_FLUXES=True and STORE_CORIOLIS_ACCEL=True are supported");
+  HIPCHK(hipSetDevice(c->device));
+  rk2_state_free(c);
+  c->rk2 = new RK2State();
+  c->rk2->P = *p;
+  if (const int rc = rk2_state_alloc(c, c->rk2)) { rk2_state_free(c); return rc; }   // (no state without its arrays)
   return MOM6X_OK;
 }
 
@@ -260,7 +261,7 @@ extern "C" int mom6x_dyn_split_RK2_restart_fills(mom6x_ctx *c, const double *u, 
   const dim3 b = blk2();
   if (!(have & MOM6X_RK2_HAVE_ETA))     // :1578-1590
     KLAUNCH(c, "k_eta", k_eta, grid3(d.ni, d.nj, 1, b), b, d, c->G, s->eta, (const double *)nullptr, h, c->GV.Z_to_H);
-  if (!(have & MOM6X_RK2_HAVE_DIFFU) && c->hv_init) CHK(mom6x_horizontal_viscosity(c, u, v, h, s->diffu, s->diffv));   // :1599-1606
+  if (!(have & MOM6X_RK2_HAVE_DIFFU) && hor_visc_ready(c)) CHK(mom6x_horizontal_viscosity(c, u, v, h, s->diffu, s->diffv));   // :1599-1606
   if (!(have & MOM6X_RK2_HAVE_U2)) {    // :1608-1614
     HIPCHK(hipMemcpyAsync(s->u_av, u, n3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(s->v_av, v, n3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -301,7 +302,7 @@ extern "C" int mom6x_step_dyn_split_RK2(mom6x_ctx *c, double *u_inst, double *v_
   REQUIRE(c && c->rk2, MOM6X_EINVAL, "step_MOM_dyn_split_RK2: initialize_dyn_split_RK2 must be called first");
   REQUIRE(u_inst && v_inst && h && uh && vh && uhtr && vhtr && eta_av && taux && tauy, MOM6X_EINVAL,
           "step_MOM_dyn_split_RK2: null mandatory array");
-  REQUIRE(c->a_u, MOM6X_EINVAL, "step_MOM_dyn_split_RK2: vertical viscosity coefficients have not been set");
+  REQUIRE(vertvisc_has_coef(c), MOM6X_EINVAL, "step_MOM_dyn_split_RK2: vertical viscosity coefficients have not been set");
   HIPCHK(hipSetDevice(c->device));
   RK2State *s = c->rk2;
   const mom6x_rk2_params &R = s->P;
@@ -318,8 +319,7 @@ extern "C" int mom6x_step_dyn_split_RK2(mom6x_ctx *c, double *u_inst, double *v_
   const double *tauy_bot = R.split_bottom_stress ? s->tauy_bot : nullptr;
   // vertvisc_coef at the three places of the step: the host callback if one is given, else the device routine if
   // vertvisc_init was called, else nothing (the coefficient arrays handed to mom6x_vertvisc_set_coef stay as they are)
-  if (c->ds_Hmix > 0.0) c->ds_h = h;   // vertvisc(up, vp, h, ...) :754 and vertvisc(u, v, h, ...) :1013 both carry the step's h
-  const bool dev_coef = c->vv_init && !(hooks && hooks->vertvisc_coef);
+  const bool dev_coef = vertvisc_ready(c) && !(hooks && hooks->vertvisc_coef);
   auto coef_hook = [&](int stage, const double *uu, const double *vv, double dtt) -> int {
     if (hooks && hooks->vertvisc_coef) {
       HIPCHK(hipStreamSynchronize(c->stream));
@@ -401,9 +401,10 @@ extern "C" int mom6x_step_dyn_split_RK2(mom6x_ctx *c, double *u_inst, double *v_
     CHK(coef_hook(1, up, vp, dt_pred));                                   // :737-738
     if (R.visc_rem_dt_bug) {   // :754 + :763-767 share dt: one sweep
       CHK(vertvisc_fused(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, up, vp, taux, tauy, dt_pred, s->taux_bot,
-                         s->tauy_bot, s->visc_rem_u, s->visc_rem_v));
+                         s->tauy_bot, s->visc_rem_u, s->visc_rem_v, h));
     } else {
-      CHK(mom6x_vertvisc(c, up, vp, taux, tauy, dt_pred, s->taux_bot, s->tauy_bot));               // :754
+      CHK(vertvisc_fused(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, up, vp, taux, tauy, dt_pred, s->taux_bot,
+                         s->tauy_bot, nullptr, nullptr, h));                                       // :754 vertvisc(up, vp, h, ...)
       CHK(mom6x_vertvisc_remnant(c, s->visc_rem_u, s->visc_rem_v, dt));                            // :763-767
     }
   }
@@ -432,7 +433,7 @@ extern "C" int mom6x_step_dyn_split_RK2(mom6x_ctx *c, double *u_inst, double *v_
     HIPCHK(hipStreamSynchronize(c->stream));
     int rc = hooks->horizontal_viscosity(hooks->user, u_av, v_av, h_av, uh, vh, s->diffu, s->diffv);
     REQUIRE(rc == 0, MOM6X_EINVAL, "step_MOM_dyn_split_RK2: horizontal_viscosity callback failed");
-  } else if (c->hv_init) {
+  } else if (hor_visc_ready(c)) {
     CHK(mom6x_horizontal_viscosity(c, u_av, v_av, h_av, s->diffu, s->diffv));
   }
   // :893 + :900-907: u_bc_accel = (CAu + PFu) + diffu is formed by the kernel that makes CAu
@@ -452,7 +453,7 @@ extern "C" int mom6x_step_dyn_split_RK2(mom6x_ctx *c, double *u_inst, double *v_
             (const double *)v_inst, u_bc, v_bc, s->u_accel_bt, s->v_accel_bt, u_inst, v_inst, dt);
     CHK(coef_hook(2, u_inst, v_inst, dt));                                // :1002-1003
     CHK(vertvisc_fused(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, u_inst, v_inst, taux, tauy, dt, s->taux_bot,
-                       s->tauy_bot, s->visc_rem_u, s->visc_rem_v));       // :1013 + :1022
+                       s->tauy_bot, s->visc_rem_u, s->visc_rem_v, h));    // :1013 + :1022
   }
   // h_av = h :1025-1027 and h_av = 0.5 * (h_av + h) :1064-1066: on the tile's own cells both ride on the convergence kernels of
   // the in-place continuity call between them (the first keeps the old thickness it is about to overwrite, the second averages);

@@ -299,7 +299,7 @@ extern "C" int mom6x_comm_unique_id(char *id128) {
 }
 
 void comm_free(mom6x_ctx *c) {
-  Comm *m = (Comm *)c->comm;
+  Comm *m = c->comm;
   if (!m) return;
   for (int d = 0; d < 8; d++) { (void)hipFree(m->sbuf[d]); (void)hipFree(m->rbuf[d]); }
   (void)hipFree(m->red);
@@ -342,11 +342,11 @@ extern "C" int mom6x_comm_init(mom6x_ctx *c, int npx, int npy, int px, int py, c
   return MOM6X_OK;
 }
 
-extern "C" int mom6x_comm_rank(const mom6x_ctx *c) { return (c && c->comm) ? ((Comm *)c->comm)->rank : 0; }
+extern "C" int mom6x_comm_rank(const mom6x_ctx *c) { return (c && c->comm) ? c->comm->rank : 0; }
 
 // min_across_PEs / max_across_PEs / sum_across_PEs of one scalar (MOM_coms.F90): op 0 min, 1 max, 2 sum.
 int comm_allreduce_scalar(mom6x_ctx *c, double *value, int op) {
-  Comm *m = (Comm *)c->comm;
+  Comm *m = c->comm;
   if (!m || !m->comm || m->nranks == 1) return MOM6X_OK;
   NcclApi *api = m->api;
   HIPCHK(hipMemcpyAsync(m->red, value, sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -360,7 +360,7 @@ int comm_allreduce_scalar(mom6x_ctx *c, double *value, int op) {
 // sum_across_PEs / min_across_PEs / max_across_PEs of 64-bit integers, in place on the device and in stream order
 // (diag_sums.hip: the limbs of the reproducing sums, bit counts, order keys): op 0 min, 1 max, 2 sum.
 int comm_allreduce_i64(mom6x_ctx *c, long long *dev, size_t n, int op) {
-  Comm *m = (Comm *)c->comm;
+  Comm *m = c->comm;
   if (!m || !m->comm || m->nranks == 1 || n == 0) return MOM6X_OK;
   NcclApi *api = m->api;
   const ncclRedOp_t rop = (op == 0) ? ncclMin : ((op == 1) ? ncclMax : ncclSum);
@@ -368,14 +368,14 @@ int comm_allreduce_i64(mom6x_ctx *c, long long *dev, size_t n, int op) {
   return MOM6X_OK;
 }
 int comm_allreduce_f64(mom6x_ctx *c, double *dev, size_t n, int op) {
-  Comm *m = (Comm *)c->comm;
+  Comm *m = c->comm;
   if (!m || !m->comm || m->nranks == 1 || n == 0) return MOM6X_OK;
   NcclApi *api = m->api;
   const ncclRedOp_t rop = (op == 0) ? ncclMin : ((op == 1) ? ncclMax : ncclSum);
   NCCLCHK(api->AllReduce(dev, dev, n, ncclDouble, rop, m->comm, c->stream));
   return MOM6X_OK;
 }
-int comm_nranks(const mom6x_ctx *c) { const Comm *m = (const Comm *)c->comm; return (m && m->comm) ? m->nranks : 1; }
+int comm_nranks(const mom6x_ctx *c) { const Comm *m = c->comm; return (m && m->comm) ? m->nranks : 1; }
 
 // pack_first: the pack kernel runs on the COMPUTE stream, ahead of whatever the caller launches next there, and the rest (messages,
 // unpack) on `st` once it is done -- for a pass whose send regions the overlapped kernels are about to rewrite (halo_start_packed)
@@ -466,7 +466,7 @@ static WrapArgs wrap_args(const mom6x_ctx *c, double *const *fields, const int *
 
 void halo_wrap(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n, PassWidth pw) {
   const Dm d = c->d;
-  Comm *m = (Comm *)c->comm;
+  Comm *m = c->comm;
   if (c->pass_pending) halo_complete(c);   // the message buffers are shared: one group pass at a time
   if (!m && !c->dims.reentrant_x && !c->dims.reentrant_y) return;
   for (int base = 0; base < n; base += MAXF) {
@@ -502,7 +502,7 @@ void halo_wrap(mom6x_ctx *c, double *const *fields, const int *staggers, const i
 // write the passing fields nor read their halos; halo_complete makes the compute stream wait for it.  At most one pass is
 // in flight (a blocking pass completes it first).  Without a communicator (one tile) the pass is done at once.
 void halo_start(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n, PassWidth pw) {
-  Comm *m = (Comm *)c->comm;
+  Comm *m = c->comm;
   if (!m || !m->comm || n > MAXF) { halo_wrap(c, fields, staggers, nks, n, pw); return; }
   if (c->pass_pending) halo_complete(c);
   if (!c->ev_ready) {
@@ -522,7 +522,7 @@ void halo_start(mom6x_ctx *c, double *const *fields, const int *staggers, const 
 // the messages travel update eta in place next to the tile's edge): the pack runs on the compute stream, in order with them; messages
 // and unpack on the second stream.  false: no communicator that can overlap (the pass has been made, blocking).
 bool halo_start_packed(mom6x_ctx *c, double *const *fields, const int *staggers, const int *nks, int n, PassWidth pw) {
-  Comm *m = (Comm *)c->comm;
+  Comm *m = c->comm;
   if (!m || !m->comm || n > MAXF) { halo_wrap(c, fields, staggers, nks, n, pw); return false; }
   if (c->pass_pending) halo_complete(c);
   if (!c->ev_ready) {
@@ -537,7 +537,7 @@ bool halo_start_packed(mom6x_ctx *c, double *const *fields, const int *staggers,
   c->pass_pending = true;
   return true;
 }
-bool halo_can_overlap(const mom6x_ctx *c) { const Comm *m = (const Comm *)c->comm; return m && m->comm; }
+bool halo_can_overlap(const mom6x_ctx *c) { const Comm *m = c->comm; return m && m->comm; }
 // ... and the compute stream waits here for the halos
 void halo_complete(mom6x_ctx *c) {
   if (!c->pass_pending) return;
@@ -569,7 +569,7 @@ extern "C" int mom6x_pass_fields(mom6x_ctx *c, double *const *fields, const int 
 
 // sum_across_PEs of an int array that lives on the device (MOM_coms.F90; advect_tracer :331), in place.
 int comm_allreduce_int_sum(mom6x_ctx *c, int *dev, int n) {
-  Comm *m = (Comm *)c->comm;
+  Comm *m = c->comm;
   if (!m || !m->comm || m->nranks == 1) return MOM6X_OK;
   NcclApi *api = m->api;
   NCCLCHK(api->AllReduce(dev, dev, (size_t)n, ncclInt, ncclSum, m->comm, c->stream));

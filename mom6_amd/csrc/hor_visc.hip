@@ -944,7 +944,17 @@ k_hv_fused(Dm d, const double *__restrict__ G, const double *__restrict__ P, mom
 
 }  // namespace
 
-void hor_visc_free(mom6x_ctx *c) { (void)hipFree(c->hv_planes); c->hv_planes = nullptr; }
+// hor_visc_CS: the parameters as hor_visc_init leaves them and its 2-D coefficient planes [HV_COUNT][slab], owned
+struct HvState { mom6x_hor_visc_params P; double *planes; };
+void hor_visc_free(mom6x_ctx *c) {
+  if (!c->hv) return;
+  (void)hipFree(c->hv->planes);
+  delete c->hv;
+  c->hv = nullptr;
+}
+bool hor_visc_ready(const mom6x_ctx *c) { return c->hv != nullptr; }
+// hor_visc_vel_stencil (MOM_hor_visc.F90): the halo width of the velocities that horizontal_viscosity reads
+int hor_visc_vel_stencil(const mom6x_ctx *c) { return (c->hv && (c->hv->P.Leith_Kh || c->hv->P.Leith_Ah)) ? 3 : 2; }
 // the points by which the tiles of k_hv_fused advance (mom6x_tile_steps, ctx.hip)
 void hor_visc_tile_steps(int *sx, int *sy) { *sx = HV_TX - 2 * HT_H; *sy = HV_TY - 2 * HT_H; }
 
@@ -961,34 +971,35 @@ extern "C" int mom6x_hor_visc_init(mom6x_ctx *c, const mom6x_hor_visc_params *p)
           "ERROR: NOSLIP and BIHARMONIC cannot be defined at the same time in MOM.");
   REQUIRE(c->dims.halo >= 3, MOM6X_EINVAL, "hor_visc_init: halo >= 3 required");
   HIPCHK(hipSetDevice(c->device));
-  c->hv = cs;
   const Dm d = c->d;
   const size_t bytes = (size_t)HV_COUNT * d.slab * sizeof(double);
-  if (!c->hv_planes) HIPCHK(hipMalloc(&c->hv_planes, bytes));
-  HIPCHK(hipMemsetAsync(c->hv_planes, 0, bytes, c->stream));
+  double *planes = c->hv ? c->hv->planes : nullptr;   // (a second init keeps the planes)
+  if (!planes) HIPCHK(hipMalloc(&planes, bytes));
+  if (!c->hv) c->hv = new HvState();
+  c->hv->P = cs; c->hv->planes = planes;
+  HIPCHK(hipMemsetAsync(planes, 0, bytes, c->stream));
   if (cs.Laplacian || cs.biharmonic) {
     const dim3 b = blk2();
     const dim3 g = grid3(d.ni + 2 * d.halo, d.nj + 2 * d.halo, 1, b);
-    KLAUNCH(c, "k_hv_init1", k_hv_init1, g, b, d, c->G, cs, c->hv_planes);
-    KLAUNCH(c, "k_hv_init2", k_hv_init2, g, b, d, c->G, cs, c->hv_planes);
-    KLAUNCH(c, "k_hv_init3", k_hv_init3, g, b, d, c->G, cs, c->hv_planes);
+    KLAUNCH(c, "k_hv_init1", k_hv_init1, g, b, d, c->G, cs, planes);
+    KLAUNCH(c, "k_hv_init2", k_hv_init2, g, b, d, c->G, cs, planes);
+    KLAUNCH(c, "k_hv_init3", k_hv_init3, g, b, d, c->G, cs, planes);
     if ((cs.Leith_Kh || cs.Leith_Ah) && cs.use_beta_in_Leith) {   // G%dF_dx, G%dF_dy (+ their pass_vector)
-      KLAUNCH(c, "k_hv_grad_Coriolis", k_hv_grad_Coriolis, grid3(d.ni, d.nj, 1, b), b, d, c->G, c->hv_planes);
-      double *f[] = { c->hv_planes + (size_t)HV_dF_dx * d.slab, c->hv_planes + (size_t)HV_dF_dy * d.slab };
+      KLAUNCH(c, "k_hv_grad_Coriolis", k_hv_grad_Coriolis, grid3(d.ni, d.nj, 1, b), b, d, c->G, planes);
+      double *f[] = { planes + (size_t)HV_dF_dx * d.slab, planes + (size_t)HV_dF_dy * d.slab };
       const int stg[] = { 0, 0 }, nks[] = { 1, 1 };
       halo_wrap(c, f, stg, nks, 2);
     }
     HIPCHK(hipGetLastError());
   }
-  c->hv_init = true;
   return MOM6X_OK;
 }
 
 extern "C" int mom6x_horizontal_viscosity(mom6x_ctx *c, const double *u, const double *v, const double *h, double *diffu,
                                           double *diffv) {
-  REQUIRE(c && c->hv_init, MOM6X_EINVAL, "MOM_hor_visc: Module must be initialized before it is used.");
+  REQUIRE(c && c->hv, MOM6X_EINVAL, "MOM_hor_visc: Module must be initialized before it is used.");
   REQUIRE(u && v && h && diffu && diffv, MOM6X_EINVAL, "horizontal_viscosity: null array");
-  const mom6x_hor_visc_params &CS = c->hv;
+  const mom6x_hor_visc_params &CS = c->hv->P;
   if (!(CS.Laplacian || CS.biharmonic)) return MOM6X_OK;
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
@@ -999,7 +1010,7 @@ extern "C" int mom6x_horizontal_viscosity(mom6x_ctx *c, const double *u, const d
       (rc = ctx_scratch(c, SCR_q, d.nk, &str_xx)) || (rc = ctx_scratch(c, SCR_KE, d.nk, &str_xy)))
     return rc;
   const dim3 b = blk2();
-  const double *P = c->hv_planes;
+  const double *P = c->hv->planes;
   // Default: the four stages in one LDS-tiled kernel (k_hv_fused: 3 reads + 2 writes per cell-layer instead of 20);
   // MOM6X_HORVISC=legacy: the four kernels.  Measured round 3 at 1440 x 1080 x 75 (bench switches): 4.75 ms on 32 x 16 tiles
   // against 6.0 ms for the four kernels.  The first version was SLOWER (7.5 ms; 6.8 on 64 x 16 tiles) and was shelved as

@@ -20,6 +20,15 @@
 #include "eos_dev.h"
 #include "isopycnal_slopes_dev.h"
 
+// VarMix_CS and the work arrays of mom6x_varmix_init
+struct VmState {
+  mom6x_varmix_params p;
+  bool use_eos;
+  mom6x_eos_params eos;
+  double *Rlay, *g_prime;   // device copies (nk): one allocation, Rlay owns it
+  double *work;             // [e (nk+1) | pres, T_f, S_f, c1 (nk each, with an EOS) | N2_u, N2_v (nk+1 each, Visbeck) | SN raw u, v (2 planes, Eady)]
+};
+
 namespace {
 
 struct VmK {
@@ -29,14 +38,6 @@ struct VmK {
   int crop, Ktop, use_dztot;
 };
 struct VmDiag { double *N2[2], *dz[2], *dzSN[2]; };
-
-struct VmState {
-  mom6x_varmix_params p;
-  bool use_eos;
-  mom6x_eos_params eos;
-  double *Rlay, *g_prime;   // device copies (nk)
-  double *work;             // [e (nk+1) | pres, T_f, S_f, c1 (nk each, with an EOS) | N2_u, N2_v (nk+1 each, Visbeck) | SN raw u, v (2 planes, Eady)]
-};
 
 // find_eta(halo_size=2) :91-97, pres (MOM_isopycnal_slopes.F90:231-247) and vert_fill_TS(halo+1) on cells isc-2..iec+2,
 // jsc-2..jec+2.  e[K], pres[K]: at the interface ABOVE layer K (e has nk+1 planes).  Lanes start at i = -IAL.
@@ -294,12 +295,36 @@ k_vm_L2(Dm d, const double *__restrict__ G, double L2, int by_area, int nrows, d
 }  // namespace
 
 void varmix_free(mom6x_ctx *c) {
-  VmState *s = (VmState *)c->vm;
+  VmState *s = c->vm;
   if (!s) return;
   (void)hipFree(s->work);
   (void)hipFree(s->Rlay);
   delete s;
   c->vm = nullptr;
+}
+
+// the device copies and work arrays of a state whose parameters are set
+static int varmix_alloc(mom6x_ctx *c, VmState *s, const double *Rlay, const double *g_prime) {
+  const mom6x_varmix_params *p = &s->p;
+  const Dm d = c->d;
+  const bool slopes = p->calculate_Eady_growth_rate && p->use_stored_slopes;
+  if (p->calculate_Eady_growth_rate) {
+    const size_t nk = (size_t)d.nk;
+    HIPCHK(hipMalloc(&s->Rlay, 2 * nk * sizeof(double)));
+    s->g_prime = s->Rlay + nk;
+    HIPCHK(hipMemsetAsync(s->Rlay, 0, 2 * nk * sizeof(double), c->stream));
+    if (Rlay) HIPCHK(hipMemcpyAsync(s->Rlay, Rlay, nk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (g_prime) HIPCHK(hipMemcpyAsync(s->g_prime, g_prime, nk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    size_t planes = nk + 1;
+    if (slopes && s->use_eos) planes += 4 * nk;
+    if (slopes && !p->use_simpler_Eady_growth_rate) planes += 2 * (nk + 1);
+    if (p->use_simpler_Eady_growth_rate) planes += 2;
+    const size_t n = planes * d.slab * sizeof(double);
+    HIPCHK(hipMalloc(&s->work, n));
+    HIPCHK(hipMemsetAsync(s->work, work_fill_byte(), n, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the host arrays may go once the call returns)
+  }
+  return MOM6X_OK;
 }
 
 extern "C" int mom6x_varmix_init(mom6x_ctx *c, const mom6x_varmix_params *p, const mom6x_eos_params *eos, const double *Rlay,
@@ -323,25 +348,9 @@ extern "C" int mom6x_varmix_init(mom6x_ctx *c, const mom6x_varmix_params *p, con
   s->p = *p;
   s->use_eos = eos != nullptr;
   if (eos) s->eos = *eos;
-  s->Rlay = s->g_prime = s->work = nullptr;
   c->vm = s;
   const Dm d = c->d;
-  if (p->calculate_Eady_growth_rate) {
-    const size_t nk = (size_t)d.nk;
-    HIPCHK(hipMalloc(&s->Rlay, 2 * nk * sizeof(double)));
-    s->g_prime = s->Rlay + nk;
-    HIPCHK(hipMemsetAsync(s->Rlay, 0, 2 * nk * sizeof(double), c->stream));
-    if (Rlay) HIPCHK(hipMemcpyAsync(s->Rlay, Rlay, nk * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (g_prime) HIPCHK(hipMemcpyAsync(s->g_prime, g_prime, nk * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    size_t planes = nk + 1;
-    if (slopes && eos) planes += 4 * nk;
-    if (slopes && !p->use_simpler_Eady_growth_rate) planes += 2 * (nk + 1);
-    if (p->use_simpler_Eady_growth_rate) planes += 2;
-    const size_t n = planes * d.slab * sizeof(double);
-    HIPCHK(hipMalloc(&s->work, n));
-    HIPCHK(hipMemsetAsync(s->work, work_fill_byte(), n, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));   // (the host arrays may go once the call returns)
-  }
+  if (const int rc = varmix_alloc(c, s, Rlay, g_prime)) { varmix_free(c); return rc; }   // (no state without its arrays)
   if (L2u || L2v) {
     const int nrows = d.slab / d.pitch;
     double L2;
@@ -360,7 +369,7 @@ extern "C" int mom6x_calc_slope_functions(mom6x_ctx *c, const double *h, const d
                                           double *S2_v) {
   REQUIRE(c && c->vm, MOM6X_EINVAL,
           "MOM_lateral_mixing_coeffs.F90, calc_slope_functions: Module must be initialized before it is used.");
-  const VmState *s = (const VmState *)c->vm;
+  const VmState *s = c->vm;
   const mom6x_varmix_params &P = s->p;
   if (!P.calculate_Eady_growth_rate) return MOM6X_OK;   // :708
   REQUIRE(h, MOM6X_EINVAL, "calc_slope_functions: null array");

@@ -18,6 +18,13 @@
 #include "mom6x_dev.h"
 #include "eos_dev.h"
 
+// mixedlayer_restrat_CS, tv%eqn_of_state and the work array of mom6x_mixedlayer_restrat_init
+struct MleState {
+  mom6x_mixedlayer_restrat_params p;
+  mom6x_eos_params eos;
+  double *work;   // [htot_fast | htot_slow | Rml_av_fast | Rml_av_slow (2-D) | uhml | vhml (nk each)]
+};
+
 namespace {
 
 struct MleK {
@@ -27,12 +34,6 @@ struct MleK {
   int detect, filt1, filt2, res_upscale;
 };
 struct MleDiag { double *ts[2], *Dml[2]; };
-
-struct MleState {
-  mom6x_mixedlayer_restrat_params p;
-  mom6x_eos_params eos;
-  double *work;   // [htot_fast | htot_slow | Rml_av_fast | Rml_av_slow (2-D) | uhml | vhml (nk each)]
-};
 
 // mu(sigma, dh) :717-751.  below: sigma is at or under the base of the extended mixed layer in a way that holds for every smaller
 // sigma as well (2*sigma+1 <= -1 and the un-clamped xp >= 1; both are monotone in sigma in floating point): mu is +0 there.
@@ -280,7 +281,7 @@ k_mle_mu(const double *__restrict__ sigma, const double *__restrict__ dh, double
 }  // namespace
 
 void mixedlayer_restrat_free(mom6x_ctx *c) {
-  MleState *s = (MleState *)c->mle;
+  MleState *s = c->mle;
   if (!s) return;
   (void)hipFree(s->work);
   delete s;
@@ -302,13 +303,14 @@ extern "C" int mom6x_mixedlayer_restrat_init(mom6x_ctx *c, const mom6x_mixedlaye
   REQUIRE(c->d.halo >= 1, MOM6X_EINVAL, "mixedlayer_restrat_init: mixedlayer_restrat needs a halo of one");
   HIPCHK(hipSetDevice(c->device));
   mixedlayer_restrat_free(c);
+  const size_t n = (4 + 2 * (size_t)c->d.nk) * c->d.slab * sizeof(double);
+  double *work = nullptr;
+  HIPCHK(hipMalloc(&work, n));
   MleState *s = new MleState();
   s->p = *p;
   s->eos = *eos;
-  s->work = nullptr;
+  s->work = work;
   c->mle = s;
-  const size_t n = (4 + 2 * (size_t)c->d.nk) * c->d.slab * sizeof(double);
-  HIPCHK(hipMalloc(&s->work, n));
   HIPCHK(hipMemsetAsync(s->work, work_fill_byte(), n, c->stream));
   return MOM6X_OK;
 }
@@ -319,7 +321,7 @@ extern "C" int mom6x_mixedlayer_restrat(mom6x_ctx *c, double *h, double *uhtr, d
                                         double *vhml, double *utimescale, double *vtimescale, double *uDml, double *vDml,
                                         double *MLD_fast_out, double *MLD_slow_out, double *Rml_av_fast_out) {
   REQUIRE(c && c->mle, MOM6X_EINVAL, "mixedlayer_restrat: Module must be initialized before it is used.");
-  const MleState *s = (const MleState *)c->mle;
+  const MleState *s = c->mle;
   const mom6x_mixedlayer_restrat_params &P = s->p;
   REQUIRE(h && uhtr && vhtr && T && S && ustar, MOM6X_EINVAL, "mixedlayer_restrat: null array (h, uhtr, vhtr, tv%T, tv%S, forces%ustar)");
   REQUIRE(dt > 0., MOM6X_EINVAL, "mixedlayer_restrat: dt must be positive");

@@ -60,13 +60,18 @@ void mom6x_set_error(const char *fmt, ...);
 // The context (opaque to C callers).
 #define MOM6X_NSCR 12
 enum Scr { SCR_q = 0, SCR_KE, SCR_absv, SCR_e, SCR_c1, SCR_t0, SCR_t1, SCR_t2, SCR_t3 };
-struct BTState;   // barotropic.hip
-struct RK2State;  // dyn_split_RK2.hip
+// One state struct per module, defined in the module's own file (ContState: continuity_dev.h, the module has three files).  It holds
+// the module's parameter copy, its caller-owned pointers, the device arrays it allocates and an `init` flag where a setter may come
+// before the init call.  The context only owns them: a typed pointer each, null until the module is first touched.
+struct ContState; struct BTState; struct CorState; struct PgfState; struct VvState; struct HvState; struct RK2State; struct AleState;
+struct TAState; struct DiagState; struct SvState; struct TdState; struct ThdState; struct VmState; struct MleState;
+struct Comm;   // halo.hip: tile layout + RCCL communicator (null: single tile, wrap only)
 
 // u_bc_accel = (CAu + PFu) + diffu of the RK2 predictor (RK2.F90:565-572) formed by the pressure-force kernel that has just made
 // PFu (all null: PressureForce on its own); the RK2 step hands it to PressureForce_bc
 struct BcFold { const double *CAu, *CAv, *diffu, *diffv; double *u_bc, *v_bc; double *eta_h; };   // eta_h: bt_mass_source's column sum (h summed top-down, less the depth), a by-product
 struct mom6x_ctx {
+  // what every module shares
   mom6x_dims dims;
   Dm d;
   int device;
@@ -75,63 +80,31 @@ struct mom6x_ctx {
   double *G;                // device metric block [MOM6X_G_COUNT][slab]
   mom6x_vgrid GV;
   int first_direction;
-  mom6x_continuity_params cont; bool cont_init;
-  mom6x_barotropic_params bt; bool bt_init;
-  // continuity scratch: edge values of the PPM reconstruction for one direction at a time
-  double *hL, *hR;
-  int *retry; size_t retry_cap;   // continuity_lds.hip: tiles whose Newton solve needs the exact CFL limits
-  BTState *bts;
-  RK2State *rk2;
   int *flag;                // device-side error flag (NaN / negative thickness)
-  // MOM_CoriolisAdv / MOM_PressureForce / MOM_vert_friction
-  mom6x_coriolis_params cor; bool cor_init;
-  mom6x_pgf_params pgf; bool pgf_init;
-  double *Rlay, *g_prime;   // device copies of GV%Rlay, GV%g_prime (nk)
-  const double *tv_T, *tv_S; mom6x_eos_params eos;   // tv%T, tv%S, tv%eqn_of_state (null: layered PressureForce path)
-  const double *a_u, *a_v, *h_u, *h_v, *Ray_u, *Ray_v;   // vertvisc coefficients (host-owned device arrays, or vv_* below)
-  // vertvisc_init / vertvisc_coef on the device: parameters, vertvisc_type inputs, CS%a_u.. owned by the context
-  mom6x_vertvisc_params vv; bool vv_init;
-  const double *Kv_bbl_u, *Kv_bbl_v, *bbl_thick_u, *bbl_thick_v, *Kv_shear;
-  double *vv_a_u, *vv_a_v, *vv_h_u, *vv_h_v;
-  // hor_visc.hip: hor_visc_CS parameters and the 2-D coefficient planes of hor_visc_init
-  mom6x_hor_visc_params hv; bool hv_init; double *hv_planes;
-  double ds_Hmix; const double *ds_h;   // DIRECT_STRESS: HMIX_STRESS (0 = off) and vertvisc's h argument
-  double *regrid_res;       // remap.hip: coordinateResolution of the z* coordinate (nk)
-  double *remap_hvel;       // remap.hip: h_u, h_v of both grids for mom6x_ALE_remap_velocities_from_h outside OM4's switch set (allocated on first use)
-  double *remap_src;        // remap.hip: the un-remapped velocity of ALE_remap_velocities' KE-conserving correction (allocated on first use)
-  double *regrid_vec;       // remap.hip: the host vectors of the density coordinates (resolution | targets | max depths | max thicknesses)
   // lazily allocated 3-D scratch arrays (slot -> nlev levels)
   double *scr[MOM6X_NSCR]; int scr_nlev[MOM6X_NSCR];
   bool prof_on;
   struct Prof *prof;
-  void *ta;                 // tracer_advect.hip: tracer-advection state (TAState)
-  long long *red; size_t red_cap;   // diag_sums.hip: integer accumulators of the reproducing sums / checksums
-  void *diag;               // diag_sums.hip: Sum_output_CS state (depth list, lH) of write_energy
-  void *comm;               // halo.hip: tile layout + RCCL communicator (null: single tile, wrap only)
+  // halo.hip: the bookkeeping of the group passes
   bool bt_overlap;          // btstep's own group pass of eta, ubt, vbt overlapped with the own-points half of the next sub-step (mom6x_comm_overlap_btstep)
   bool halo_error;          // set by a failed halo exchange inside a stream-ordered sequence
-  hipEvent_t ev_ready, ev_done; bool pass_pending;   // halo.hip: the group pass in flight on the halo stream (start_/complete_group_pass)
+  hipEvent_t ev_ready, ev_done; bool pass_pending;   // the group pass in flight on the halo stream (start_/complete_group_pass)
   // the base width of the RK2 step's own group passes (0: the context's halo) -- a context whose halo was widened for the
   // barotropic solver (BTHALO) still sends NIHALO rows of the 3-D fields (mom6x_set_dyn_pass_width)
-  int dyn_pass_width = 0;
-  long long n_exchanges = 0, n_exchange_bytes = 0;
-  bool cont_stats_on;               // the statistics-collecting (slower) variant of the mass-flux kernel is in use
-  unsigned long long *cont_stats;   // device: Newton statistics of the wave-owned mass-flux kernel (mom6x_continuity_stats), or null
-  // set_visc.hip: set_visc_CS of set_viscous_BBL, tv%eqn_of_state when use_BBL_EOS, CS%tideamp (caller-owned device array)
-  mom6x_set_visc_params sv; bool sv_init = false; bool sv_use_eos = false; mom6x_eos_params sv_eos; const double *sv_tideamp = nullptr;
-  // thickness_diffuse.hip: thickness_diffuse_CS, tv%eqn_of_state, CS%khth2d (caller-owned device array) and the work arrays of
-  // mom6x_thickness_diffuse_init: td_work = [uhD | vhD | h_avail_rsum] and, with an EOS, [h_frac | pres | T_f | S_f], nk levels each
-  mom6x_thickness_diffuse_params td; bool td_init = false; bool td_use_eos = false; mom6x_eos_params td_eos;
-  const double *td_khth2d = nullptr; double *td_work = nullptr;
-  void *thd = nullptr;      // tracer_hor_diff.hip: tracer_hor_diff_CS and the work arrays of mom6x_tracer_hor_diff_init (ThdState)
-  void *vm = nullptr;       // lateral_mixing_coeffs.hip: VarMix_CS and the work arrays of mom6x_varmix_init (VmState)
-  void *mle = nullptr;      // mixed_layer_restrat.hip: mixedlayer_restrat_CS and the work arrays of mom6x_mixedlayer_restrat_init (MleState)
+  int dyn_pass_width;
+  long long n_exchanges, n_exchange_bytes;
+  // the modules' states
+  ContState *cont; BTState *bts; CorState *cor; PgfState *pgf; VvState *vv; HvState *hv; RK2State *rk2; AleState *ale;
+  TAState *ta; DiagState *diag; SvState *sv; TdState *td; ThdState *thd; VmState *vm; MleState *mle; Comm *comm;
 };
-void thickness_diffuse_free(mom6x_ctx *c);                            // thickness_diffuse.hip
-void tracer_hor_diff_free(mom6x_ctx *c);                              // tracer_hor_diff.hip
-void varmix_free(mom6x_ctx *c);                                       // lateral_mixing_coeffs.hip
-void mixedlayer_restrat_free(mom6x_ctx *c);                           // mixed_layer_restrat.hip
-void comm_free(mom6x_ctx *c);                                         // halo.hip
+// Each frees every device pointer its struct owns, deletes the struct and nulls the context's pointer (a null pointer: nothing to
+// do).  mom6x_ctx_destroy calls them all; apart from them it frees only what mom6x_ctx_create allocated.
+void continuity_free(mom6x_ctx *c);  void bt_state_free(mom6x_ctx *c);          void CoriolisAdv_free(mom6x_ctx *c);
+void PressureForce_free(mom6x_ctx *c);  void vertvisc_free(mom6x_ctx *c);       void hor_visc_free(mom6x_ctx *c);
+void rk2_state_free(mom6x_ctx *c);   void ALE_free(mom6x_ctx *c);               void ta_state_free(mom6x_ctx *c);
+void diag_sums_free(mom6x_ctx *c);   void set_visc_free(mom6x_ctx *c);          void thickness_diffuse_free(mom6x_ctx *c);
+void tracer_hor_diff_free(mom6x_ctx *c);  void varmix_free(mom6x_ctx *c);       void mixedlayer_restrat_free(mom6x_ctx *c);
+void comm_free(mom6x_ctx *c);
 // The widths of one group pass (create_group_pass(..., halo=)).  w: rows / columns of halo filled for its 3-D fields (0: the context's
 // halo); wf[0 .. nwf - 1]: the widths of single 3-D fields (0 entries and fields beyond nwf: w).  The default is what every pass but the
 // RK2 step's own asks for; the step sends the reference's own 2-3 rows instead of NIHALO = 4 (RK2.F90:484-495).
@@ -164,12 +137,18 @@ void prof_end(mom6x_ctx *c);
 
 int ctx_scratch(mom6x_ctx *c, int slot, int nlev, double **out);
 int work_fill_byte();   // 0, or 0xFF with MOM6X_POISON_WORK=1 (ctx.hip): the initial contents of work arrays   // ctx.hip
-void hor_visc_free(mom6x_ctx *c);                                  // hor_visc.hip
-void diag_sums_free(mom6x_ctx *c);                                 // diag_sums.hip
 // what mom6x_tile_steps (ctx.hip) reports, each defined next to the constants of its kernels
 void corad_tile_steps(int *sx, int *sy);                           // coriolis_adv.hip: CF_X - 2, CF_Y - 2
 void hor_visc_tile_steps(int *sx, int *sy);                        // hor_visc.hip: HV_TX - 2 * HT_H, HV_TY - 2 * HT_H
 void tracer_advect_tile_steps(int *sx, int *sy);                   // tracer_advect.hip: TX, SEGY
+// What one module asks of another (each lives in the file that owns the state).  xxx_ready: the module's init call has run
+bool continuity_ready(const mom6x_ctx *c);  bool barotropic_ready(const mom6x_ctx *c);  bool CoriolisAdv_ready(const mom6x_ctx *c);
+bool PressureForce_ready(const mom6x_ctx *c);  bool hor_visc_ready(const mom6x_ctx *c);
+bool vertvisc_ready(const mom6x_ctx *c);                           // vert_friction.hip: vertvisc_coef is on the device (mom6x_vertvisc_init)
+bool vertvisc_has_coef(const mom6x_ctx *c);                        // vert_friction.hip: there are coefficients to solve with (vertvisc_init or _set_coef)
+int continuity_stencil(const mom6x_ctx *c);                        // continuity.hip: 3, SIMPLE_2ND 2, UPWIND_1ST 1 (needs continuity_ready)
+int hor_visc_vel_stencil(const mom6x_ctx *c);                      // hor_visc.hip: 3 with a Leith viscosity, else 2
+const double *PressureForce_Rlay(const mom6x_ctx *c);              // pressure_force.hip: the device copy of GV%Rlay (nk), or null before its init
 int CorAdCalc_bc(mom6x_ctx *c, const double *u, const double *v, const double *h, const double *uh, const double *vh, double *CAu,
                  double *CAv, const double *PFu, const double *PFv, const double *diffu, const double *diffv, double *u_bc,
                  double *v_bc, double *uhtr, double *vhtr, double dt_tr);   // coriolis_adv.hip
@@ -223,10 +202,11 @@ int vertvisc_stage_solve(mom6x_ctx *c, const double *u_in, const double *v_in, c
                          const double *h, double *u, double *v, const double *taux, const double *tauy, double *taux_bot, double *tauy_bot,
                          double *vr_u, double *vr_v, bool keep_coef);
 // [u = mask*(u_in + dtx*(u_bc + u_abt));] vertvisc(u, v, dt); [vertvisc_remnant(vr_u, vr_v, dt)] in one sweep, with the coefficients
-// the context holds (the step's host-callback arms, which call back between the pieces)
+// the context holds (the step's host-callback arms, which call back between the pieces).  h: vertvisc's thickness argument, read
+// under DIRECT_STRESS only (null: the array mom6x_vertvisc_set_direct_stress was given -- the public vertvisc)
 int vertvisc_fused(mom6x_ctx *c, const double *u_in, const double *v_in, const double *u_bc, const double *v_bc,
                    const double *u_abt, const double *v_abt, double dtx, double *u, double *v, const double *taux,
-                   const double *tauy, double dt, double *taux_bot, double *tauy_bot, double *vr_u, double *vr_v);
+                   const double *tauy, double dt, double *taux_bot, double *tauy_bot, double *vr_u, double *vr_v, const double *h);
 
 // k-chunking for "column-walk" kernels: a thread keeps its 2-D coefficients in registers and walks
 // KCHUNK consecutive layers, so the 2-D metric planes are read nk/KCHUNK times instead of nk times.

@@ -534,9 +534,30 @@ k_pgf_main_eos(Dm d, const double *__restrict__ G, const double *__restrict__ h,
 }
 }  // namespace
 
+// PressureForce_FV_CS and what tv hands it.  mom6x_PressureForce_set_tv may come before mom6x_PressureForce_init: whichever is first
+// creates the state
+struct PgfState {
+  mom6x_pgf_params P; bool init;
+  double *Rlay, *g_prime;                             // device copies of GV%Rlay, GV%g_prime (nk), owned
+  const double *tv_T, *tv_S; mom6x_eos_params eos;    // tv%T, tv%S (caller-owned), tv%eqn_of_state (tv_T null: the layered path)
+};
+static PgfState *pgf_state(mom6x_ctx *c) {
+  if (!c->pgf) c->pgf = new PgfState();
+  return c->pgf;
+}
+void PressureForce_free(mom6x_ctx *c) {
+  PgfState *S = c->pgf;
+  if (!S) return;
+  (void)hipFree(S->Rlay); (void)hipFree(S->g_prime);
+  delete S;
+  c->pgf = nullptr;
+}
+bool PressureForce_ready(const mom6x_ctx *c) { return c->pgf && c->pgf->init; }
+const double *PressureForce_Rlay(const mom6x_ctx *c) { return c->pgf ? c->pgf->Rlay : nullptr; }
+
 extern "C" int mom6x_PressureForce_set_tv(mom6x_ctx *c, const double *T, const double *S, const mom6x_eos_params *eos) {
   REQUIRE(c, MOM6X_EINVAL, "mom6x_PressureForce_set_tv: null ctx");
-  if (!T) { c->tv_T = nullptr; c->tv_S = nullptr; return MOM6X_OK; }
+  if (!T) { if (c->pgf) c->pgf->tv_T = c->pgf->tv_S = nullptr; return MOM6X_OK; }
   REQUIRE(S && eos, MOM6X_EINVAL, "mom6x_PressureForce_set_tv: tv%T without tv%S or tv%eqn_of_state");
   REQUIRE(eos->form >= MOM6X_EOS_LINEAR && eos->form <= MOM6X_EOS_ROQUET_SPV, MOM6X_EUNSUPPORTED,
           "PressureForce: EQN_OF_STATE must be LINEAR, WRIGHT, WRIGHT_FULL, WRIGHT_REDUCED, UNESCO, ROQUET_RHO (NEMO), JACKETT_06 or ROQUET_SPV");
@@ -547,19 +568,22 @@ extern "C" int mom6x_PressureForce_set_tv(mom6x_ctx *c, const double *T, const d
           "PressureForce_FV_init: PRESSURE_RECONSTRUCTION_SCHEME must be 1 (PLM) or 2 (PPM), or 0 without RECONSTRUCT_FOR_PRESSURE");
   REQUIRE(eos->Recon_Scheme != 2 || c->dims.nk >= 4, MOM6X_EUNSUPPORTED,
           "PressureForce_FV: PRESSURE_RECONSTRUCTION_SCHEME = 2 (edge_values_implicit_h4) needs NK >= 4");
-  c->tv_T = T; c->tv_S = S; c->eos = *eos;
+  PgfState *S_ = pgf_state(c);
+  S_->tv_T = T; S_->tv_S = S; S_->eos = *eos;
   return MOM6X_OK;
 }
 
 extern "C" int mom6x_PressureForce_init(mom6x_ctx *c, const mom6x_pgf_params *p, const double *Rlay, const double *g_prime) {
   REQUIRE(c && p && Rlay && g_prime, MOM6X_EINVAL, "mom6x_PressureForce_init: null argument");
   HIPCHK(hipSetDevice(c->device));
-  c->pgf = *p;
+  PgfState *S = pgf_state(c);
+  S->P = *p;
   const size_t n = (size_t)c->dims.nk * sizeof(double);
-  if (!c->Rlay) { HIPCHK(hipMalloc(&c->Rlay, n)); HIPCHK(hipMalloc(&c->g_prime, n)); }
-  HIPCHK(hipMemcpy(c->Rlay, Rlay, n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(c->g_prime, g_prime, n, hipMemcpyHostToDevice));
-  c->pgf_init = true;
+  if (!S->Rlay) HIPCHK(hipMalloc(&S->Rlay, n));
+  if (!S->g_prime) HIPCHK(hipMalloc(&S->g_prime, n));
+  HIPCHK(hipMemcpy(S->Rlay, Rlay, n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(S->g_prime, g_prime, n, hipMemcpyHostToDevice));
+  S->init = true;
   return MOM6X_OK;
 }
 
@@ -571,43 +595,46 @@ extern "C" int mom6x_PressureForce(mom6x_ctx *c, const double *h, double *PFu, d
 int PressureForce_bc(mom6x_ctx *c, const double *h, double *PFu, double *PFv, double *pbce, double *eta, const BcFold &fold,
                      bool *eta_h_written) {
   *eta_h_written = false;
-  REQUIRE(c && c->pgf_init, MOM6X_EINVAL, "MOM_PressureForce_FV_Bouss: Module must be initialized before it is used.");
+  REQUIRE(c && PressureForce_ready(c), MOM6X_EINVAL, "MOM_PressureForce_FV_Bouss: Module must be initialized before it is used.");
   REQUIRE(h && PFu && PFv, MOM6X_EINVAL, "PressureForce: null array");
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
+  const PgfState &S = *c->pgf;
+  const mom6x_pgf_params &pgf = S.P;
+  const mom6x_eos_params &eos = S.eos;
   double *e;
   int rc;
   if ((rc = ctx_scratch(c, SCR_e, d.nk + 1, &e))) return rc;
   const dim3 b = blk2();
   const mom6x_vgrid &GV = c->GV;
   const double GxRho0 = GV.g_Earth * GV.Rho0;
-  const double GxRho_ref = c->pgf.rho_ref_bug ? GxRho0 : GV.g_Earth * c->pgf.rho_ref;
+  const double GxRho_ref = pgf.rho_ref_bug ? GxRho0 : GV.g_Earth * pgf.rho_ref;
   KLAUNCH(c, "k_pgf_e", k_pgf_e, grid3(nxa(d.ni + 2, -1), d.nj + 2, 1, b), b, d, c->G, h, e, GV.H_to_Z);
-  if (c->tv_T) {   // use_EOS = associated(tv%eqn_of_state) :1125
+  if (S.tv_T) {   // use_EOS = associated(tv%eqn_of_state) :1125
     EosDev E;
-    E.form = c->eos.form; E.Rho_T0_S0 = c->eos.Rho_T0_S0; E.dRho_dT = c->eos.dRho_dT; E.dRho_dS = c->eos.dRho_dS;
-    E.dRho_dp = c->eos.dRho_dp; E.do_mw = c->eos.MassWghtInterp & 1; E.top_mw = (c->eos.MassWghtInterp >> 1) & 1;
-    E.ssh_z0 = c->eos.use_SSH_in_Z0p;
-    E.van_only = c->eos.MassWghtInterpVanOnly; E.dz_nv = GV.H_to_Z * c->eos.h_nonvanished;   // dz_nonvanished :1128
-    const double rho0_alt = c->pgf.rho_ref_bug ? c->pgf.rho_ref : GV.Rho0;   // rho0_int_density = rho0_set_pbce
+    E.form = eos.form; E.Rho_T0_S0 = eos.Rho_T0_S0; E.dRho_dT = eos.dRho_dT; E.dRho_dS = eos.dRho_dS;
+    E.dRho_dp = eos.dRho_dp; E.do_mw = eos.MassWghtInterp & 1; E.top_mw = (eos.MassWghtInterp >> 1) & 1;
+    E.ssh_z0 = eos.use_SSH_in_Z0p;
+    E.van_only = eos.MassWghtInterpVanOnly; E.dz_nv = GV.H_to_Z * eos.h_nonvanished;   // dz_nonvanished :1128
+    const double rho0_alt = pgf.rho_ref_bug ? pgf.rho_ref : GV.Rho0;   // rho0_int_density = rho0_set_pbce
     const dim3 g = grid3(nxa(d.ni + 2, -1), d.nj + 2, 1, b);
     // 0: analytic_int_density_dz; 1: TS_PLM_edge_values + int_density_dz_generic_plm; 2: TS_PPM_edge_values + ..._generic_ppm;
     // 3: EOS_QUADRATURE without a reconstruction: int_density_dz_generic_pcm (int_density_dz, MOM_density_integrals.F90:95-99)
-    const int mode = c->eos.Recon_Scheme ? c->eos.Recon_Scheme : (c->eos.EOS_quadrature ? 3 : 0);
+    const int mode = eos.Recon_Scheme ? eos.Recon_Scheme : (eos.EOS_quadrature ? 3 : 0);
     double *Tt = nullptr, *Tb = nullptr, *St = nullptr, *Sb = nullptr;
     if (mode == 1 || mode == 2) {   // TS_PLM_edge_values (MOM_ALE.F90:1495) | TS_PPM_edge_values (:1581): S first, then T
       if ((rc = ctx_scratch(c, SCR_t0, d.nk, &Tt)) || (rc = ctx_scratch(c, SCR_t1, d.nk, &Tb)) ||
           (rc = ctx_scratch(c, SCR_t2, d.nk, &St)) || (rc = ctx_scratch(c, SCR_t3, d.nk, &Sb))) return rc;
       if (mode == 1) {
-        if ((rc = mom6x_ALE_PLM_edge_values(c, h, c->tv_S, c->eos.boundary_extrap, St, Sb))) return rc;
-        if ((rc = mom6x_ALE_PLM_edge_values(c, h, c->tv_T, c->eos.boundary_extrap, Tt, Tb))) return rc;
+        if ((rc = mom6x_ALE_PLM_edge_values(c, h, S.tv_S, eos.boundary_extrap, St, Sb))) return rc;
+        if ((rc = mom6x_ALE_PLM_edge_values(c, h, S.tv_T, eos.boundary_extrap, Tt, Tb))) return rc;
       } else {
-        if ((rc = mom6x_ALE_PPM_edge_values(c, h, c->tv_S, c->eos.boundary_extrap, St, Sb))) return rc;
-        if ((rc = mom6x_ALE_PPM_edge_values(c, h, c->tv_T, c->eos.boundary_extrap, Tt, Tb))) return rc;
+        if ((rc = mom6x_ALE_PPM_edge_values(c, h, S.tv_S, eos.boundary_extrap, St, Sb))) return rc;
+        if ((rc = mom6x_ALE_PPM_edge_values(c, h, S.tv_T, eos.boundary_extrap, Tt, Tb))) return rc;
       }
     }
-#define PGF_EOS(F, P, NAME) KLAUNCH(c, NAME, (k_pgf_main_eos<F, P>), g, b, d, c->G, h, e, c->tv_T, c->tv_S, Tt, Tb, St, Sb, E, PFu, PFv,   \
-                                    pbce, eta, GV.g_Earth, GV.H_to_Z, GV.Z_to_H, c->pgf.rho_ref, GxRho_ref, c->pgf.Z_ref, GV.Rho0, \
+#define PGF_EOS(F, P, NAME) KLAUNCH(c, NAME, (k_pgf_main_eos<F, P>), g, b, d, c->G, h, e, S.tv_T, S.tv_S, Tt, Tb, St, Sb, E, PFu, PFv,   \
+                                    pbce, eta, GV.g_Earth, GV.H_to_Z, GV.Z_to_H, pgf.rho_ref, GxRho_ref, pgf.Z_ref, GV.Rho0, \
                                     rho0_alt, GV.H_subroundoff, GV.dZ_subroundoff, fold)
 #define PGF_FORM(F, N) do { if (mode == 1) PGF_EOS(F, 1, "k_pgf_main_plm<" N ">"); else if (mode == 2) PGF_EOS(F, 2, "k_pgf_main_ppm<" N ">"); \
                             else if (mode == 3) PGF_EOS(F, 3, "k_pgf_main_pcm<" N ">"); else PGF_EOS(F, 0, "k_pgf_main_eos<" N ">"); } while (0)
@@ -636,8 +663,8 @@ int PressureForce_bc(mom6x_ctx *c, const double *h, double *PFu, double *PFv, do
     HIPCHK(hipGetLastError());
     return MOM6X_OK;
   }
-  KLAUNCH(c, "k_pgf_main", k_pgf_main, grid3(nxa(d.ni + 2, -1), d.nj + 2, 1, b), b, d, c->G, h, e, c->Rlay, c->g_prime, PFu, PFv,
-          pbce, eta, GV.g_Earth, GV.H_to_Z, GV.Z_to_H, c->pgf.rho_ref, GxRho_ref, c->pgf.Z_ref, 1.0 / GV.Rho0,
+  KLAUNCH(c, "k_pgf_main", k_pgf_main, grid3(nxa(d.ni + 2, -1), d.nj + 2, 1, b), b, d, c->G, h, e, S.Rlay, S.g_prime, PFu, PFv,
+          pbce, eta, GV.g_Earth, GV.H_to_Z, GV.Z_to_H, pgf.rho_ref, GxRho_ref, pgf.Z_ref, 1.0 / GV.Rho0,
           GV.H_subroundoff, GV.dZ_subroundoff, fold);
   *eta_h_written = (fold.eta_h != nullptr);
   HIPCHK(hipGetLastError());

@@ -1700,6 +1700,25 @@ k_remap_conserve_ke(Dm d, const double *__restrict__ G, int mask_plane, int i0, 
   for (int k = 0; k < nz; k++) { const size_t c = x + (size_t)k * slab; u_tgt[c] = u_bt + rescale_coef * (u_tgt[c] - u_bt); }
 }
 
+// The arrays the ALE entry points allocate on first use (they have no initialisation of their own) and keep until the context goes
+struct AleState {
+  double *regrid_res;   // coordinateResolution of the z* coordinate (nk)
+  double *regrid_vec;   // the host vectors of the density coordinates (resolution | targets | max depths | max thicknesses)
+  double *remap_src;    // the un-remapped velocity of ALE_remap_velocities' KE-conserving correction
+  double *remap_hvel;   // h_u, h_v of both grids for mom6x_ALE_remap_velocities_from_h outside OM4's switch set
+};
+static AleState *ale_state(mom6x_ctx *c) {
+  if (!c->ale) c->ale = new AleState();
+  return c->ale;
+}
+void ALE_free(mom6x_ctx *c) {
+  AleState *S = c->ale;
+  if (!S) return;
+  (void)hipFree(S->regrid_res); (void)hipFree(S->regrid_vec); (void)hipFree(S->remap_src); (void)hipFree(S->remap_hvel);
+  delete S;
+  c->ale = nullptr;
+}
+
 static int remap_velocities(mom6x_ctx *c, const mom6x_remapping_params *p, const double *h_old_u, const double *h_old_v,
                             const double *h_new_u, const double *h_new_v, double *u, double *v, bool conserve_ke) {
   REQUIRE(c && p && h_old_u && h_old_v && h_new_u && h_new_v && u && v, MOM6X_EINVAL, "ALE_remap_velocities: null argument");
@@ -1711,20 +1730,21 @@ static int remap_velocities(mom6x_ctx *c, const mom6x_remapping_params *p, const
   // ORDER: the reference masks the near-bottom velocities (mask_near_bottom_vel, BBL_h_vel_mask / h_vel_mask; MOM_ALE.F90:1194-1200)
   // AFTER the correction.  The device carries neither mask (both default to 0: nothing is masked); whoever adds them must apply them
   // after k_remap_conserve_ke, not inside remap_field.
-  if (conserve_ke && !c->remap_src) HIPCHK(hipMalloc(&c->remap_src, n3 * sizeof(double)));
+  AleState *A = ale_state(c);
+  if (conserve_ke && !A->remap_src) HIPCHK(hipMalloc(&A->remap_src, n3 * sizeof(double)));
   const dim3 b(64, 4, 1);
-  if (conserve_ke) HIPCHK(hipMemcpyAsync(c->remap_src, u, n3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  if (conserve_ke) HIPCHK(hipMemcpyAsync(A->remap_src, u, n3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   int rc = remap_field(c, p, MOM6X_G_mask2dCu, -1, d.ni - 1, 0, d.nj - 1, h_old_u, h_new_u, u);
   if (rc) return rc;
   if (conserve_ke)
     KLAUNCH(c, "k_remap_conserve_ke", k_remap_conserve_ke, grid3(d.ni + 1, d.nj, 1, b), b, d, c->G, (int)MOM6X_G_mask2dCu, -1, d.ni - 1, 0, d.nj - 1,
-            h_old_u, h_new_u, (const double *)c->remap_src, u, c->GV.H_subroundoff);
-  if (conserve_ke) HIPCHK(hipMemcpyAsync(c->remap_src, v, n3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            h_old_u, h_new_u, (const double *)A->remap_src, u, c->GV.H_subroundoff);
+  if (conserve_ke) HIPCHK(hipMemcpyAsync(A->remap_src, v, n3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   rc = remap_field(c, p, MOM6X_G_mask2dCv, 0, d.ni - 1, -1, d.nj - 1, h_old_v, h_new_v, v);
   if (rc) return rc;
   if (conserve_ke)
     KLAUNCH(c, "k_remap_conserve_ke", k_remap_conserve_ke, grid3(d.ni, d.nj + 1, 1, b), b, d, c->G, (int)MOM6X_G_mask2dCv, 0, d.ni - 1, -1, d.nj - 1,
-            h_old_v, h_new_v, (const double *)c->remap_src, v, c->GV.H_subroundoff);
+            h_old_v, h_new_v, (const double *)A->remap_src, v, c->GV.H_subroundoff);
   HIPCHK(hipGetLastError());
   return MOM6X_OK;
 }
@@ -1748,8 +1768,9 @@ extern "C" int mom6x_ALE_remap_velocities_from_h(mom6x_ctx *c, const mom6x_remap
     return remap_fields(c, p, MOM6X_G_mask2dCv, 0, d.ni - 1, -1, d.nj - 1, h_old, h_new, &v, 1, d.pitch);
   }
   const size_t n3 = (size_t)d.slab * d.nk;
-  if (!c->remap_hvel) { HIPCHK(hipMalloc(&c->remap_hvel, 4 * n3 * sizeof(double))); HIPCHK(hipMemsetAsync(c->remap_hvel, 0, 4 * n3 * sizeof(double), c->stream)); }
-  double *hu0 = c->remap_hvel, *hv0 = hu0 + n3, *hu1 = hv0 + n3, *hv1 = hu1 + n3;
+  AleState *A = ale_state(c);
+  if (!A->remap_hvel) { HIPCHK(hipMalloc(&A->remap_hvel, 4 * n3 * sizeof(double))); HIPCHK(hipMemsetAsync(A->remap_hvel, 0, 4 * n3 * sizeof(double), c->stream)); }
+  double *hu0 = A->remap_hvel, *hv0 = hu0 + n3, *hu1 = hv0 + n3, *hv1 = hu1 + n3;
   int rc = mom6x_ALE_remap_set_h_vel(c, h_old, hu0, hv0);
   if (rc) return rc;
   if ((rc = mom6x_ALE_remap_set_h_vel(c, h_new, hu1, hv1))) return rc;
@@ -1769,8 +1790,9 @@ extern "C" int mom6x_ALE_regrid_zstar(mom6x_ctx *c, const mom6x_regrid_zstar_par
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
   REQUIRE(d.halo >= 1, MOM6X_EINVAL, "ALE_regrid: one halo point needed");
-  if (!c->regrid_res) HIPCHK(hipMalloc(&c->regrid_res, (size_t)d.nk * sizeof(double)));
-  HIPCHK(hipMemcpyAsync(c->regrid_res, coordinateResolution, (size_t)d.nk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  AleState *S = ale_state(c);
+  if (!S->regrid_res) HIPCHK(hipMalloc(&S->regrid_res, (size_t)d.nk * sizeof(double)));
+  HIPCHK(hipMemcpyAsync(S->regrid_res, coordinateResolution, (size_t)d.nk * sizeof(double), hipMemcpyHostToDevice, c->stream));
   double *zOld;
   int rc = ctx_scratch(c, SCR_e, d.nk + 1, &zOld);
   if (rc) return rc;
@@ -1778,12 +1800,12 @@ extern "C" int mom6x_ALE_regrid_zstar(mom6x_ctx *c, const mom6x_regrid_zstar_par
   if (d.nk <= COLS_NK_BOUND) {   // the layer counts the on-chip column kernel is built for
     // (the profile label carries the template argument, so that a test can see which instantiation ran)
 #define RZC(NKT) KLAUNCH_LDS(c, "k_regrid_zstar_cols<" #NKT ">", (k_regrid_zstar_cols<NKT>), dim3((unsigned)((nxa(d.ni + 2, -1) + 63) / 64), (unsigned)(d.nj + 2), 1), dim3(64, 1, 1), \
-                (size_t)(NK_OF(NKT) + 1) * 64 * sizeof(double), d, c->G, *p, c->GV.Z_to_H, (const double *)c->regrid_res, h, h_new, dzRegrid, c->flag)
+                (size_t)(NK_OF(NKT) + 1) * 64 * sizeof(double), d, c->G, *p, c->GV.Z_to_H, (const double *)S->regrid_res, h, h_new, dzRegrid, c->flag)
     COLS_NK_DISPATCH(d.nk, RZC);
 #undef RZC
   } else
   KLAUNCH(c, "k_regrid_zstar", k_regrid_zstar, grid3(nxa(d.ni + 2, -1), d.nj + 2, 1, b), b, d, c->G, *p, c->GV.Z_to_H,
-          (const double *)c->regrid_res, h, h_new, dzRegrid, zOld, c->flag);
+          (const double *)S->regrid_res, h, h_new, dzRegrid, zOld, c->flag);
   int flag = 0;
   HIPCHK(hipMemcpyAsync(&flag, c->flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1810,13 +1832,14 @@ static int regrid_density(mom6x_ctx *c, bool hycom, const mom6x_regrid_rho_param
   REQUIRE(d.nk >= 2, MOM6X_EINVAL, "ALE_regrid: a density coordinate needs at least two layers");
   // host vectors -> one device buffer: res (nk) | target (nk+1) | max depths (nk+1) | max thickness (nk)
   const size_t nk = (size_t)d.nk, nv = 4 * nk + 2;
-  if (!c->regrid_vec) HIPCHK(hipMalloc(&c->regrid_vec, nv * sizeof(double)));
+  AleState *R = ale_state(c);
+  if (!R->regrid_vec) HIPCHK(hipMalloc(&R->regrid_vec, nv * sizeof(double)));
   std::vector<double> hv(nv, 0.0);
   if (coordinateResolution) for (size_t k = 0; k < nk; k++) hv[k] = coordinateResolution[k];
   for (size_t k = 0; k <= nk; k++) hv[nk + k] = target_density[k];
   if (max_interface_depths) for (size_t k = 0; k <= nk; k++) hv[2 * nk + 1 + k] = max_interface_depths[k];
   if (max_layer_thickness) for (size_t k = 0; k < nk; k++) hv[3 * nk + 2 + k] = max_layer_thickness[k];
-  HIPCHK(hipMemcpyAsync(c->regrid_vec, hv.data(), nv * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(R->regrid_vec, hv.data(), nv * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));   // (hv leaves scope)
   DensArgs A;
   A.CS = *p;
@@ -1831,7 +1854,7 @@ static int regrid_density(mom6x_ctx *c, bool hycom, const mom6x_regrid_rho_param
     return rc;
   const dim3 b(64, 4, 1);
   const dim3 g = grid3(nxa(d.ni + 2, -1), d.nj + 2, 1, b);
-  const double *res = c->regrid_vec, *tgt = res + nk, *mid = tgt + nk + 1, *mlt = mid + nk + 1;
+  const double *res = R->regrid_vec, *tgt = res + nk, *mid = tgt + nk + 1, *mlt = mid + nk + 1;
   if (hycom) KLAUNCH(c, "k_regrid_density<hycom1>", k_regrid_density<true>, g, b, d, c->G, A, res, tgt, mid, mlt, h, T, S, h_new, dzRegrid, W, c->flag);
   else KLAUNCH(c, "k_regrid_density<rho>", k_regrid_density<false>, g, b, d, c->G, A, res, tgt, mid, mlt, h, T, S, h_new, dzRegrid, W, c->flag);
   int flag = 0;

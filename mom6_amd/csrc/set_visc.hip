@@ -238,6 +238,10 @@ k_set_viscous_BBL(Dm d, const double *__restrict__ G, SvK K, const double *__res
 
 }  // namespace
 
+// set_visc_CS of set_viscous_BBL, tv%eqn_of_state when use_BBL_EOS, CS%tideamp (caller-owned device array); owns no device memory
+struct SvState { mom6x_set_visc_params P; bool use_eos; mom6x_eos_params eos; const double *tideamp; };
+void set_visc_free(mom6x_ctx *c) { delete c->sv; c->sv = nullptr; }
+
 extern "C" int mom6x_set_visc_init(mom6x_ctx *c, const mom6x_set_visc_params *p, const mom6x_eos_params *eos, const double *tideamp) {
   REQUIRE(c && p, MOM6X_EINVAL, "mom6x_set_visc_init: null argument");
   REQUIRE(!p->channel_drag, MOM6X_EINVAL, "set_visc_init: CHANNEL_DRAG (find_L_open_*) is not on the device");
@@ -247,26 +251,29 @@ extern "C" int mom6x_set_visc_init(mom6x_ctx *c, const mom6x_set_visc_params *p,
   REQUIRE(!p->SpV_avg && c->GV.Boussinesq, MOM6X_EINVAL, "set_visc_init: the non-Boussinesq tv%SpV_avg forms are not on the device");
   REQUIRE(!(p->bottomdraglaw && p->BBL_use_tidal_bg) || tideamp, MOM6X_EINVAL, "set_visc_init: BBL_USE_TIDAL_BG needs CS%tideamp");
   REQUIRE(!eos || eos_form_known(eos), MOM6X_EINVAL, "set_visc_init: unknown EQN_OF_STATE form");
-  c->sv = *p;
-  c->sv_use_eos = eos && p->BBL_use_EOS;   // use_BBL_EOS (:340)
-  if (eos) c->sv_eos = *eos;
-  c->sv_tideamp = tideamp;
-  c->sv_init = true;
+  if (!c->sv) c->sv = new SvState();
+  SvState *s = c->sv;
+  s->P = *p;
+  s->use_eos = eos && p->BBL_use_EOS;   // use_BBL_EOS (:340)
+  if (eos) s->eos = *eos;
+  s->tideamp = tideamp;
   return MOM6X_OK;
 }
 
 extern "C" int mom6x_set_viscous_BBL(mom6x_ctx *c, const double *u, const double *v, const double *h, const double *T, const double *S,
                                      const double *p_surf, double *Kv_bbl_u, double *Kv_bbl_v, double *bbl_thick_u, double *bbl_thick_v,
                                      double *Ray_u, double *Ray_v) {
-  REQUIRE(c && c->sv_init, MOM6X_EINVAL, "MOM_set_viscosity(BBL): Module must be initialized before it is used.");
-  const mom6x_set_visc_params &P = c->sv;
+  REQUIRE(c && c->sv, MOM6X_EINVAL, "MOM_set_viscosity(BBL): Module must be initialized before it is used.");
+  const SvState *s = c->sv;
+  const mom6x_set_visc_params &P = s->P;
+  const double *Rlay = PressureForce_Rlay(c);   // the device copy of GV%Rlay
   if (!P.bottomdraglaw) return MOM6X_OK;   // :323
   REQUIRE(u && v && h && bbl_thick_u && bbl_thick_v, MOM6X_EINVAL, "set_viscous_BBL: null array");
   REQUIRE((Kv_bbl_u != nullptr) == (Kv_bbl_v != nullptr), MOM6X_EINVAL, "set_viscous_BBL: Kv_bbl_u and Kv_bbl_v come together");
   REQUIRE((Ray_u != nullptr) == (Ray_v != nullptr), MOM6X_EINVAL, "set_viscous_BBL: Ray_u and Ray_v come together");
   REQUIRE(!P.body_force_drag || Ray_u, MOM6X_EINVAL, "set_viscous_BBL: DRAG_AS_BODY_FORCE needs visc%Ray_u/v");
-  REQUIRE(!c->sv_use_eos || (T && S), MOM6X_EINVAL, "set_viscous_BBL: BBL_USE_EOS needs tv%T and tv%S");
-  REQUIRE(c->sv_use_eos || c->Rlay, MOM6X_EINVAL, "set_viscous_BBL: without BBL_USE_EOS the walk needs GV%Rlay (mom6x_PressureForce_init)");
+  REQUIRE(!s->use_eos || (T && S), MOM6X_EINVAL, "set_viscous_BBL: BBL_USE_EOS needs tv%T and tv%S");
+  REQUIRE(s->use_eos || Rlay, MOM6X_EINVAL, "set_viscous_BBL: without BBL_USE_EOS the walk needs GV%Rlay (mom6x_PressureForce_init)");
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
   const mom6x_vgrid &GV = c->GV;
@@ -281,7 +288,7 @@ extern "C" int mom6x_set_viscous_BBL(mom6x_ctx *c, const double *u, const double
   K.Rho0x400_G = 400.0 * (GV.H_to_RZ / ((P.L_to_Z * P.L_to_Z) * GV.g_Earth));
   K.HRg = GV.H_to_RZ * GV.g_Earth;
   K.H_to_Z = GV.H_to_Z; K.h_neglect = GV.H_subroundoff; K.dz_neglect = GV.dZ_subroundoff; K.Angstrom_H = GV.Angstrom_H;
-  K.dRho_dT = c->sv_eos.dRho_dT; K.dRho_dS = c->sv_eos.dRho_dS;
+  K.dRho_dT = s->eos.dRho_dT; K.dRho_dS = s->eos.dRho_dS;
   K.linear_drag = P.linear_drag; K.tidal_bg = P.BBL_use_tidal_bg; K.body_force = P.body_force_drag;
   K.correct_bounds = P.correct_BBL_bounds; K.RiNo_mix = P.RiNo_mix;
   if (Ray_u) {   // :442-443
@@ -290,10 +297,10 @@ extern "C" int mom6x_set_viscous_BBL(mom6x_ctx *c, const double *u, const double
   }
   const dim3 b = blk2(), g = grid3(d.ni + IAL, d.nj + 1, 2, b);
 #define SVB(F)                                                                                                              \
-  KLAUNCH(c, "k_set_viscous_BBL<" #F ">", k_set_viscous_BBL<F>, g, b, d, c->G, K, u, v, h, T, S, p_surf, c->sv_tideamp,      \
-          c->Rlay, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Ray_u, Ray_v)
-  if (!c->sv_use_eos) SVB(0);
-  else EOS_FORM_DISPATCH(c->sv_eos.form, SVB);
+  KLAUNCH(c, "k_set_viscous_BBL<" #F ">", k_set_viscous_BBL<F>, g, b, d, c->G, K, u, v, h, T, S, p_surf, s->tideamp,      \
+          Rlay, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Ray_u, Ray_v)
+  if (!s->use_eos) SVB(0);
+  else EOS_FORM_DISPATCH(s->eos.form, SVB);
 #undef SVB
   HIPCHK(hipGetLastError());
   return MOM6X_OK;

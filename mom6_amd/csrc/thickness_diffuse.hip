@@ -171,9 +171,19 @@ k_td_update(Dm d, const double *__restrict__ G, double dt, double Angstrom_H, do
 
 }  // namespace
 
+// thickness_diffuse_CS, tv%eqn_of_state, CS%khth2d and the work arrays of mom6x_thickness_diffuse_init
+struct TdState {
+  mom6x_thickness_diffuse_params P;
+  bool use_eos; mom6x_eos_params eos;
+  const double *khth2d;   // caller-owned device array (READ_KHTH)
+  double *work;           // [uhD | vhD | h_avail_rsum] and, with an EOS, [h_frac | pres | T_f | S_f], nk levels each; null: nothing to diffuse
+};
+
 void thickness_diffuse_free(mom6x_ctx *c) {
-  (void)hipFree(c->td_work);
-  c->td_work = nullptr;
+  if (!c->td) return;
+  (void)hipFree(c->td->work);
+  delete c->td;
+  c->td = nullptr;
 }
 
 extern "C" int mom6x_thickness_diffuse_init(mom6x_ctx *c, const mom6x_thickness_diffuse_params *p, const mom6x_eos_params *eos,
@@ -201,32 +211,34 @@ extern "C" int mom6x_thickness_diffuse_init(mom6x_ctx *c, const mom6x_thickness_
   REQUIRE(!eos || eos_form_known(eos), MOM6X_EINVAL, "thickness_diffuse_init: unknown EQN_OF_STATE form");
   REQUIRE(!eos || c->d.nk >= 2, MOM6X_EINVAL, "thickness_diffuse_init: vert_fill_TS needs two layers");
   HIPCHK(hipSetDevice(c->device));
-  c->td = *p;
-  c->td_use_eos = eos != nullptr;
-  if (eos) c->td_eos = *eos;
-  c->td_khth2d = khth2d;
-  c->td_init = false;
   thickness_diffuse_free(c);
-  if (p->thickness_diffuse && (p->Khth > 0.0 || p->read_khth)) {
-    const size_t n = (size_t)(eos ? 7 : 3) * c->d.nk * c->d.slab * sizeof(double);
-    HIPCHK(hipMalloc(&c->td_work, n));
-    HIPCHK(hipMemsetAsync(c->td_work, work_fill_byte(), n, c->stream));
-  }
-  c->td_init = true;
+  double *work = nullptr;
+  const size_t n = (size_t)(eos ? 7 : 3) * c->d.nk * c->d.slab * sizeof(double);
+  const bool active = p->thickness_diffuse && (p->Khth > 0.0 || p->read_khth);
+  if (active) HIPCHK(hipMalloc(&work, n));
+  TdState *s = new TdState();
+  s->P = *p;
+  s->use_eos = eos != nullptr;
+  if (eos) s->eos = *eos;
+  s->khth2d = khth2d;
+  s->work = work;
+  c->td = s;
+  if (active) HIPCHK(hipMemsetAsync(work, work_fill_byte(), n, c->stream));
   return MOM6X_OK;
 }
 
 extern "C" int mom6x_thickness_diffuse(mom6x_ctx *c, double *h, double *uhtr, double *vhtr, const double *T, const double *S,
                                        const double *p_surf, const double *slope_x, const double *slope_y, double dt,
                                        double *uhGM, double *vhGM) {
-  REQUIRE(c && c->td_init, MOM6X_EINVAL, "MOM_thickness_diffuse: Module must be initialized before it is used.");
-  const mom6x_thickness_diffuse_params &P = c->td;
+  REQUIRE(c && c->td, MOM6X_EINVAL, "MOM_thickness_diffuse: Module must be initialized before it is used.");
+  const TdState *s = c->td;
+  const mom6x_thickness_diffuse_params &P = s->P;
   if (!P.thickness_diffuse || !(P.Khth > 0.0 || P.read_khth)) return MOM6X_OK;   // :195-197
   REQUIRE(h && uhtr && vhtr, MOM6X_EINVAL, "thickness_diffuse: null array");
   REQUIRE(dt > 0.0, MOM6X_EINVAL, "thickness_diffuse: dt must be positive");
   REQUIRE((slope_x != nullptr) == (slope_y != nullptr), MOM6X_EINVAL, "thickness_diffuse: slope_x and slope_y come together");
   REQUIRE((uhGM != nullptr) == (vhGM != nullptr), MOM6X_EINVAL, "thickness_diffuse: uhGM and vhGM come together");
-  const bool use_eos = c->td_use_eos, stored = slope_x != nullptr;
+  const bool use_eos = s->use_eos, stored = slope_x != nullptr;
   REQUIRE(!use_eos || stored || (T && S), MOM6X_EINVAL, "thickness_diffuse: an equation of state needs tv%T and tv%S");
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
@@ -243,9 +255,9 @@ extern "C" int mom6x_thickness_diffuse(mom6x_ctx *c, double *h, double *uhtr, do
   K.qCFL = 0.25 * P.max_Khth_CFL;                              // :226
   K.kap_dt_x2 = (2.0 * (P.kappa_smooth * dt)) * P.Z_to_H_fill;  // MOM_isopycnal_slopes.F90:655
   K.h0 = 1.0e-16 * sqrt(0.5 * K.kap_dt_x2);                    // :658
-  K.dRho_dT = c->td_eos.dRho_dT; K.dRho_dS = c->td_eos.dRho_dS;
+  K.dRho_dT = s->eos.dRho_dT; K.dRho_dS = s->eos.dRho_dS;
   const size_t n3 = (size_t)d.nk * d.slab;
-  double *W = c->td_work;
+  double *W = s->work;
   double *uD = uhGM ? uhGM : W, *vD = vhGM ? vhGM : W + n3, *rsum = W + 2 * n3;
   double *hfrac = use_eos ? W + 3 * n3 : nullptr;
   const bool derivs = use_eos && !stored;                      // calc_derivatives :924-925
@@ -258,7 +270,7 @@ extern "C" int mom6x_thickness_diffuse(mom6x_ctx *c, double *h, double *uhtr, do
   const double *Tr = fill ? Tf : T, *Sr = fill ? Sf : S;
   const dim3 g = grid3(d.ni + IAL, d.nj + 1, 2, b);
 #define TDF(F, M)                                                                                                            \
-  KLAUNCH(c, "k_td_faces<" #F "," #M ">", (k_td_faces<F, M>), g, b, d, c->G, K, h, uhtr, vhtr, c->td_khth2d, slope_x, slope_y, \
+  KLAUNCH(c, "k_td_faces<" #F "," #M ">", (k_td_faces<F, M>), g, b, d, c->G, K, h, uhtr, vhtr, s->khth2d, slope_x, slope_y, \
           rsum, hfrac, pres, Tr, Sr, uD, vD)
   if (!use_eos) {
     if (stored) TDF(0, 3); else TDF(0, 0);
@@ -266,7 +278,7 @@ extern "C" int mom6x_thickness_diffuse(mom6x_ctx *c, double *h, double *uhtr, do
     TDF(0, 2);
   } else {
 #define TDF_1(F) TDF(F, 1)
-    EOS_FORM_DISPATCH(c->td_eos.form, TDF_1);
+    EOS_FORM_DISPATCH(s->eos.form, TDF_1);
 #undef TDF_1
   }
 #undef TDF

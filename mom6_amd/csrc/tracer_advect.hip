@@ -661,7 +661,7 @@ k_ta_y_tile(Dm d, const double *__restrict__ G, double *__restrict__ vhr, double
 void tracer_advect_tile_steps(int *sx, int *sy) { *sx = TX; *sy = SEGY; }
 
 void ta_state_free(mom6x_ctx *c) {
-  TAState *s = (TAState *)c->ta;
+  TAState *s = c->ta;
   if (!s) return;
   (void)hipFree(s->hprev); (void)hipFree(s->uhr); (void)hipFree(s->vhr); (void)hipFree(s->uhh);
   for (int m = 0; m < MAXTR; m++) (void)hipFree(s->flux[m]);
@@ -671,24 +671,28 @@ void ta_state_free(mom6x_ctx *c) {
   c->ta = nullptr;
 }
 
+// the arrays of a fresh (zeroed) state
+static int ta_state_alloc(mom6x_ctx *c, TAState *s) {
+  const size_t n3 = (size_t)c->dims.slab * c->dims.nk;
+  const size_t nf = (size_t)(c->dims.nj + 2 * c->dims.halo + 1) * c->dims.nk;
+  double **p3[] = { &s->hprev, &s->uhr, &s->vhr };   // (uhh and the flux arrays belong to the legacy path: allocated on its first use)
+  for (double **q : p3) { HIPCHK(hipMalloc(q, n3 * sizeof(double))); HIPCHK(hipMemsetAsync(*q, work_fill_byte(), n3 * sizeof(double), c->stream)); }
+  int **pf[] = { &s->dmu, &s->dmv, &s->limu, &s->limv };
+  for (int **q : pf) { HIPCHK(hipMalloc(q, nf * sizeof(int))); HIPCHK(hipMemsetAsync(*q, 0, nf * sizeof(int), c->stream)); }
+  HIPCHK(hipMalloc(&s->dmk, c->dims.nk * sizeof(int)));
+  return MOM6X_OK;
+}
+
 // tracer_advect_init :1155 (DT, TRACER_ADVECTION_SCHEME, USE_HUYNH_STENCIL_BUG)
 extern "C" int mom6x_tracer_advect_init(mom6x_ctx *c, double dt_dyn, int default_scheme, int useHuynhStencilBug) {
   REQUIRE(c && dt_dyn > 0.0, MOM6X_EINVAL, "mom6x_tracer_advect_init: bad arguments");
   REQUIRE(default_scheme >= 0 && default_scheme <= 2, MOM6X_EINVAL, "tracer_advect_init: unknown TRACER_ADVECTION_SCHEME");
   HIPCHK(hipSetDevice(c->device));
   if (!c->ta) {
-    TAState *s = new TAState();
-    memset(s, 0, sizeof(*s));
-    const size_t n3 = (size_t)c->dims.slab * c->dims.nk;
-    const size_t nf = (size_t)(c->dims.nj + 2 * c->dims.halo + 1) * c->dims.nk;
-    double **p3[] = { &s->hprev, &s->uhr, &s->vhr };   // (uhh and the flux arrays belong to the legacy path: allocated on its first use)
-    for (double **q : p3) { HIPCHK(hipMalloc(q, n3 * sizeof(double))); HIPCHK(hipMemsetAsync(*q, work_fill_byte(), n3 * sizeof(double), c->stream)); }
-    int **pf[] = { &s->dmu, &s->dmv, &s->limu, &s->limv };
-    for (int **q : pf) { HIPCHK(hipMalloc(q, nf * sizeof(int))); HIPCHK(hipMemsetAsync(*q, 0, nf * sizeof(int), c->stream)); }
-    HIPCHK(hipMalloc(&s->dmk, c->dims.nk * sizeof(int)));
-    c->ta = s;
+    c->ta = new TAState();
+    if (const int rc = ta_state_alloc(c, c->ta)) { ta_state_free(c); return rc; }   // (no state without its arrays)
   }
-  TAState *s = (TAState *)c->ta;
+  TAState *s = c->ta;
   s->dt_dyn = dt_dyn; s->default_scheme = default_scheme; s->useHuynhStencilBug = useHuynhStencilBug;
   return MOM6X_OK;
 }
@@ -717,7 +721,7 @@ extern "C" int mom6x_advect_tracer(mom6x_ctx *c, const double *h_end, const doub
     // tracer gets the bits it would get in one pass (and the groups' leftover transports are identical).
     // The stencil (:118-127) is the registry's, not a group's: a PLM-only group next to a PPM one must walk the same work ranges, halo
     // cadence and iteration count as the single pass would (every group then does, and the iteration count is the same for all).
-    TAState *s0 = (TAState *)c->ta;
+    TAState *s0 = c->ta;
     const int st_all = advect_stencil(schemes, ntr, s0->default_scheme, s0->useHuynhStencilBug);
     int rc = MOM6X_OK, it_max = 0;
     for (int m0 = 0; m0 < ntr && rc == MOM6X_OK; m0 += MAXTR) {
@@ -734,7 +738,7 @@ extern "C" int mom6x_advect_tracer(mom6x_ctx *c, const double *h_end, const doub
     return rc;
   }
   HIPCHK(hipSetDevice(c->device));
-  TAState *s = (TAState *)c->ta;
+  TAState *s = c->ta;
   const Dm d = c->d;
   const int is = 0, ie = d.ni - 1, js = 0, je = d.nj - 1, nz = d.nk, w = d.halo;
   const size_t n3 = (size_t)d.slab * nz;

@@ -238,7 +238,7 @@ struct ThdState {
 };
 
 void tracer_hor_diff_free(mom6x_ctx *c) {
-  ThdState *s = (ThdState *)c->thd;
+  ThdState *s = c->thd;
   if (!s) return;
   (void)hipFree(s->planes); (void)hipFree(s->max_bits); (void)hipFree(s->save_x); (void)hipFree(s->save_y);
   delete s;
@@ -250,6 +250,23 @@ extern "C" int mom6x_tracer_hordiff_tile(int *tx, int *ty, int *max_tracers) {
   if (tx) *tx = HD_TX;
   if (ty) *ty = HD_TY;
   if (max_tracers) *max_tracers = HD_MAXT;
+  return MOM6X_OK;
+}
+
+// the work arrays of a state whose parameters are set
+static int tracer_hor_diff_alloc(mom6x_ctx *c, ThdState *s) {
+  const Dm d = c->d;
+  s->ntx = (d.ni + HD_TX - 1) / HD_TX; s->nseg = (d.nj + HD_TY - 1) / HD_TY;
+  const size_t n2 = 3 * (size_t)d.slab * sizeof(double);
+  const size_t nx = (size_t)d.nk * HD_MAXT * (s->ntx + 1) * 2 * d.nj * sizeof(double);
+  const size_t ny = (size_t)d.nk * (s->nseg + 1) * HD_MAXT * 2 * d.ni * sizeof(double);
+  HIPCHK(hipMalloc(&s->planes, n2));
+  HIPCHK(hipMalloc(&s->max_bits, sizeof(unsigned long long)));
+  HIPCHK(hipMalloc(&s->save_x, nx));
+  HIPCHK(hipMalloc(&s->save_y, ny));
+  HIPCHK(hipMemsetAsync(s->planes, work_fill_byte(), n2, c->stream));
+  HIPCHK(hipMemsetAsync(s->save_x, work_fill_byte(), nx, c->stream));
+  HIPCHK(hipMemsetAsync(s->save_y, work_fill_byte(), ny, c->stream));
   return MOM6X_OK;
 }
 
@@ -266,18 +283,7 @@ extern "C" int mom6x_tracer_hor_diff_init(mom6x_ctx *c, const mom6x_tracer_hor_d
   ThdState *s = new ThdState;
   c->thd = s;
   s->P = *p;
-  const Dm d = c->d;
-  s->ntx = (d.ni + HD_TX - 1) / HD_TX; s->nseg = (d.nj + HD_TY - 1) / HD_TY;
-  const size_t n2 = 3 * (size_t)d.slab * sizeof(double);
-  const size_t nx = (size_t)d.nk * HD_MAXT * (s->ntx + 1) * 2 * d.nj * sizeof(double);
-  const size_t ny = (size_t)d.nk * (s->nseg + 1) * HD_MAXT * 2 * d.ni * sizeof(double);
-  HIPCHK(hipMalloc(&s->planes, n2));
-  HIPCHK(hipMalloc(&s->max_bits, sizeof(unsigned long long)));
-  HIPCHK(hipMalloc(&s->save_x, nx));
-  HIPCHK(hipMalloc(&s->save_y, ny));
-  HIPCHK(hipMemsetAsync(s->planes, work_fill_byte(), n2, c->stream));
-  HIPCHK(hipMemsetAsync(s->save_x, work_fill_byte(), nx, c->stream));
-  HIPCHK(hipMemsetAsync(s->save_y, work_fill_byte(), ny, c->stream));
+  if (const int rc = tracer_hor_diff_alloc(c, s)) { tracer_hor_diff_free(c); return rc; }   // (no state without its arrays)
   return MOM6X_OK;
 }
 
@@ -286,7 +292,7 @@ extern "C" int mom6x_tracer_hordiff(mom6x_ctx *c, const double *h, double dt, do
                                     const double *Res_fn_h, const double *Rd_dx_h, const double *MEKE_Kh, double *const *df_x,
                                     double *const *df_y, double *khdt_x_out, double *khdt_y_out, double *cfl_out, int *num_itts_out) {
   REQUIRE(c && c->thd, MOM6X_EINVAL, "MOM_tracer_hor_diff: tracer_hor_diff_init must be called before tracer_hordiff.");
-  ThdState *s = (ThdState *)c->thd;
+  ThdState *s = c->thd;
   const mom6x_tracer_hor_diff_params &P = s->P;
   REQUIRE(ntr >= 0, MOM6X_EINVAL, "tracer_hordiff: negative tracer count");
   if (num_itts_out) *num_itts_out = 0;

@@ -7,6 +7,29 @@
 // form used by the reference), lane index = i (coalesced).
 #include "mom6x_dev.h"
 
+// vertvisc_CS and what visc hands it.  The setters (mom6x_vertvisc_set_visc, _set_coef, _set_direct_stress) may come before
+// mom6x_vertvisc_init: whichever is first creates the state
+struct VvState {
+  mom6x_vertvisc_params P; bool init;                      // init: mom6x_vertvisc_init has run (vertvisc_coef is on the device)
+  const double *a_u, *a_v, *h_u, *h_v, *Ray_u, *Ray_v;     // the coefficients in use: own_* below, or a host's (mom6x_vertvisc_set_coef)
+  const double *Kv_bbl_u, *Kv_bbl_v, *bbl_thick_u, *bbl_thick_v, *Kv_shear;   // vertvisc_type inputs (caller-owned)
+  double *own_a_u, *own_a_v, *own_h_u, *own_h_v;           // CS%a_u .. CS%h_v of mom6x_vertvisc_init, owned
+  double ds_Hmix; const double *ds_h;                      // DIRECT_STRESS: HMIX_STRESS (0 = off) and the thicknesses of the public vertvisc
+};
+static VvState *vv_state(mom6x_ctx *c) {
+  if (!c->vv) c->vv = new VvState();
+  return c->vv;
+}
+void vertvisc_free(mom6x_ctx *c) {
+  VvState *S = c->vv;
+  if (!S) return;
+  (void)hipFree(S->own_a_u); (void)hipFree(S->own_a_v); (void)hipFree(S->own_h_u); (void)hipFree(S->own_h_v);
+  delete S;
+  c->vv = nullptr;
+}
+bool vertvisc_ready(const mom6x_ctx *c) { return c->vv && c->vv->init; }
+bool vertvisc_has_coef(const mom6x_ctx *c) { return c->vv && c->vv->a_u; }
+
 namespace {
 
 // DIRECT_STRESS (:707-720 / :958-971): the wind stress as a body force over the topmost HMIX_STRESS instead of a stress
@@ -24,8 +47,11 @@ struct DSWalk {
     return uk;
   }
 };
-static DirectStress direct_stress_of(const mom6x_ctx *c) {
-  DirectStress S; S.Hmix = c->ds_Hmix; S.I_Hmix = (c->ds_Hmix > 0.0) ? 1.0 / c->ds_Hmix : 0.0; S.h_neglect = c->GV.H_subroundoff; S.h = c->ds_h;
+// h: vertvisc's thickness argument (the RK2 step's), or null: what mom6x_vertvisc_set_direct_stress stored (the public vertvisc)
+static DirectStress direct_stress_of(const mom6x_ctx *c, const double *h) {
+  const double Hmix = c->vv->ds_Hmix;
+  DirectStress S; S.Hmix = Hmix; S.I_Hmix = (Hmix > 0.0) ? 1.0 / Hmix : 0.0; S.h_neglect = c->GV.H_subroundoff;
+  S.h = (Hmix > 0.0) ? (h ? h : c->vv->ds_h) : nullptr;
   return S;
 }
 
@@ -334,10 +360,10 @@ static bool vertvisc_cols_usable(int nk, const double *Ray, const DirectStress &
 template <int DIR, bool UPD, bool REM>
 static void launch_vertvisc_fused(mom6x_ctx *c, const double *u_in, const double *u_bc, const double *u_abt, double dtx, double *u,
                                   double *vr, const double *a, const double *h, const double *Ray, const double *tau, double *c1,
-                                  double dt, double *tau_bot) {
+                                  double dt, double *tau_bot, const double *h_ds) {
   const Dm d = c->d;
   const double dt_Rho0 = dt / c->GV.H_to_RZ, HR = c->GV.H_to_RZ;
-  const DirectStress S = direct_stress_of(c);
+  const DirectStress S = direct_stress_of(c, h_ds);
   if (vertvisc_cols_usable(d.nk, Ray, S)) {
     const dim3 bc(64, 1, 1);
     const dim3 gc((unsigned)(((DIR ? d.ni : nxa(d.ni + 1, -1)) + 63) / 64), (unsigned)(DIR ? d.nj + 1 : d.nj), 1);
@@ -359,24 +385,26 @@ static void launch_vertvisc_fused(mom6x_ctx *c, const double *u_in, const double
 template <bool UPD, bool REM>
 static int vertvisc_fused_as(mom6x_ctx *c, const double *u_in, const double *v_in, const double *u_bc, const double *v_bc,
                              const double *u_abt, const double *v_abt, double dtx, double *u, double *v, const double *taux,
-                             const double *tauy, double dt, double *taux_bot, double *tauy_bot, double *vr_u, double *vr_v) {
-  REQUIRE(c && c->a_u, MOM6X_EINVAL, "MOM_vert_friction(visc): Module must be initialized before it is used.");
+                             const double *tauy, double dt, double *taux_bot, double *tauy_bot, double *vr_u, double *vr_v,
+                             const double *h) {
+  REQUIRE(c && vertvisc_has_coef(c), MOM6X_EINVAL, "MOM_vert_friction(visc): Module must be initialized before it is used.");
   HIPCHK(hipSetDevice(c->device));
+  const VvState &S = *c->vv;
   double *c1;
   int rc;
   if ((rc = ctx_scratch(c, SCR_c1, c->d.nk, &c1))) return rc;
-  launch_vertvisc_fused<0, UPD, REM>(c, UPD ? u_in : u, u_bc, u_abt, dtx, u, vr_u, c->a_u, c->h_u, c->Ray_u, taux, c1, dt, taux_bot);
-  launch_vertvisc_fused<1, UPD, REM>(c, UPD ? v_in : v, v_bc, v_abt, dtx, v, vr_v, c->a_v, c->h_v, c->Ray_v, tauy, c1, dt, tauy_bot);
+  launch_vertvisc_fused<0, UPD, REM>(c, UPD ? u_in : u, u_bc, u_abt, dtx, u, vr_u, S.a_u, S.h_u, S.Ray_u, taux, c1, dt, taux_bot, h);
+  launch_vertvisc_fused<1, UPD, REM>(c, UPD ? v_in : v, v_bc, v_abt, dtx, v, vr_v, S.a_v, S.h_v, S.Ray_v, tauy, c1, dt, tauy_bot, h);
   HIPCHK(hipGetLastError());
   return MOM6X_OK;
 }
 int vertvisc_fused(mom6x_ctx *c, const double *u_in, const double *v_in, const double *u_bc, const double *v_bc,
                    const double *u_abt, const double *v_abt, double dtx, double *u, double *v, const double *taux,
-                   const double *tauy, double dt, double *taux_bot, double *tauy_bot, double *vr_u, double *vr_v) {
+                   const double *tauy, double dt, double *taux_bot, double *tauy_bot, double *vr_u, double *vr_v, const double *h) {
   const bool upd = (u_bc != nullptr), rem = (vr_u != nullptr);
   auto *f = upd ? (rem ? vertvisc_fused_as<true, true> : vertvisc_fused_as<true, false>)
                 : (rem ? vertvisc_fused_as<false, true> : vertvisc_fused_as<false, false>);
-  return f(c, u_in, v_in, u_bc, v_bc, u_abt, v_abt, dtx, u, v, taux, tauy, dt, taux_bot, tauy_bot, vr_u, vr_v);
+  return f(c, u_in, v_in, u_bc, v_bc, u_abt, v_abt, dtx, u, v, taux, tauy, dt, taux_bot, tauy_bot, vr_u, vr_v, h);
 }
 
 // One layer of the bottom-up walk of vertvisc_coef :1357 + find_coupling_coef :2314 (see k_vertvisc_coef): the thickness at the velocity
@@ -779,16 +807,17 @@ k_vertvisc_coef_cols(Dm d, const double *__restrict__ G, mom6x_vertvisc_params C
 extern "C" int mom6x_vertvisc_init(mom6x_ctx *c, const mom6x_vertvisc_params *p) {
   REQUIRE(c && p, MOM6X_EINVAL, "mom6x_vertvisc_init: null argument");
   HIPCHK(hipSetDevice(c->device));
-  c->vv = *p;
+  VvState *S = vv_state(c);
+  S->P = *p;
   const size_t n3 = (size_t)c->dims.slab * c->dims.nk, n3i = (size_t)c->dims.slab * (c->dims.nk + 1);
-  if (!c->vv_a_u) {
-    HIPCHK(hipMalloc(&c->vv_a_u, n3i * sizeof(double))); HIPCHK(hipMalloc(&c->vv_a_v, n3i * sizeof(double)));
-    HIPCHK(hipMalloc(&c->vv_h_u, n3 * sizeof(double))); HIPCHK(hipMalloc(&c->vv_h_v, n3 * sizeof(double)));
-  }
-  HIPCHK(hipMemsetAsync(c->vv_a_u, 0, n3i * sizeof(double), c->stream)); HIPCHK(hipMemsetAsync(c->vv_a_v, 0, n3i * sizeof(double), c->stream));
-  HIPCHK(hipMemsetAsync(c->vv_h_u, 0, n3 * sizeof(double), c->stream)); HIPCHK(hipMemsetAsync(c->vv_h_v, 0, n3 * sizeof(double), c->stream));
-  c->a_u = c->vv_a_u; c->a_v = c->vv_a_v; c->h_u = c->vv_h_u; c->h_v = c->vv_h_v;
-  c->vv_init = true;
+  if (!S->own_a_u) HIPCHK(hipMalloc(&S->own_a_u, n3i * sizeof(double)));
+  if (!S->own_a_v) HIPCHK(hipMalloc(&S->own_a_v, n3i * sizeof(double)));
+  if (!S->own_h_u) HIPCHK(hipMalloc(&S->own_h_u, n3 * sizeof(double)));
+  if (!S->own_h_v) HIPCHK(hipMalloc(&S->own_h_v, n3 * sizeof(double)));
+  HIPCHK(hipMemsetAsync(S->own_a_u, 0, n3i * sizeof(double), c->stream)); HIPCHK(hipMemsetAsync(S->own_a_v, 0, n3i * sizeof(double), c->stream));
+  HIPCHK(hipMemsetAsync(S->own_h_u, 0, n3 * sizeof(double), c->stream)); HIPCHK(hipMemsetAsync(S->own_h_v, 0, n3 * sizeof(double), c->stream));
+  S->a_u = S->own_a_u; S->a_v = S->own_a_v; S->h_u = S->own_h_u; S->h_v = S->own_h_v;
+  S->init = true;
   return MOM6X_OK;
 }
 
@@ -796,14 +825,15 @@ extern "C" int mom6x_vertvisc_set_visc(mom6x_ctx *c, const double *Kv_bbl_u, con
                                        const double *bbl_thick_v, const double *Kv_shear, const double *Ray_u, const double *Ray_v) {
   REQUIRE(c, MOM6X_EINVAL, "mom6x_vertvisc_set_visc: null ctx");
   REQUIRE((Ray_u != nullptr) == (Ray_v != nullptr), MOM6X_EINVAL, "mom6x_vertvisc_set_visc: Ray_u and Ray_v come together");
-  c->Kv_bbl_u = Kv_bbl_u; c->Kv_bbl_v = Kv_bbl_v; c->bbl_thick_u = bbl_thick_u; c->bbl_thick_v = bbl_thick_v;
-  c->Kv_shear = Kv_shear; c->Ray_u = Ray_u; c->Ray_v = Ray_v;
+  VvState *S = vv_state(c);
+  S->Kv_bbl_u = Kv_bbl_u; S->Kv_bbl_v = Kv_bbl_v; S->bbl_thick_u = bbl_thick_u; S->bbl_thick_v = bbl_thick_v;
+  S->Kv_shear = Kv_shear; S->Ray_u = Ray_u; S->Ray_v = Ray_v;
   return MOM6X_OK;
 }
 
 extern "C" double *mom6x_vertvisc_field(mom6x_ctx *c, int which) {
-  if (!c || !c->vv_init) return nullptr;
-  double *t[] = { c->vv_a_u, c->vv_a_v, c->vv_h_u, c->vv_h_v };
+  if (!c || !vertvisc_ready(c)) return nullptr;
+  double *t[] = { c->vv->own_a_u, c->vv->own_a_v, c->vv->own_h_u, c->vv->own_h_v };
   return (which >= 0 && which < 4) ? t[which] : nullptr;
 }
 
@@ -813,22 +843,23 @@ extern "C" double *mom6x_vertvisc_field(mom6x_ctx *c, int which) {
 static int vertvisc_coef_launch(mom6x_ctx *c, int mode, const double *u, const double *v, const double *u_bc, const double *v_bc,
                                 const double *u_abt, const double *v_abt, const LayerAccelSrc &LAu, const LayerAccelSrc &LAv, double dtx,
                                 const double *h, double dt, double *u_out, double *v_out) {
-  REQUIRE(c && c->vv_init, MOM6X_EINVAL, "MOM_vert_friction(coef): Module must be initialized before it is used.");
+  REQUIRE(c && vertvisc_ready(c), MOM6X_EINVAL, "MOM_vert_friction(coef): Module must be initialized before it is used.");
   REQUIRE(u && v && h, MOM6X_EINVAL, "vertvisc_coef: null array");
-  REQUIRE(!c->vv.bottomdraglaw || (c->Kv_bbl_u && c->Kv_bbl_v && c->bbl_thick_u && c->bbl_thick_v), MOM6X_EINVAL,
+  const VvState &S = *c->vv;
+  REQUIRE(!S.P.bottomdraglaw || (S.Kv_bbl_u && S.Kv_bbl_v && S.bbl_thick_u && S.bbl_thick_v), MOM6X_EINVAL,
           "vertvisc_coef: BOTTOMDRAGLAW needs visc%Kv_bbl_u/v and visc%bbl_thick_u/v (mom6x_vertvisc_set_visc)");
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
   const dim3 b = blk2();
   const mom6x_vgrid &GV = c->GV;
   const double a_cpl_max = 1.0e37 * GV.Z_to_H;
-  const double I_amax = (c->vv.answer_date < 20190101) ? (1.0e-10 * GV.H_to_Z) * dt : 0.0;
+  const double I_amax = (S.P.answer_date < 20190101) ? (1.0e-10 * GV.H_to_Z) * dt : 0.0;
   const dim3 gu = grid3(nxa(d.ni + 1, -1), d.nj, 1, b), gv = grid3(d.ni, d.nj + 1, 1, b);
 #define VVC(M)                                                                                                                  \
-  KLAUNCH(c, "k_vertvisc_coef<0>", (k_vertvisc_coef<0, M>), gu, b, d, c->G, c->vv, u, u_out, u_bc, u_abt, dtx, h, c->Kv_bbl_u, c->bbl_thick_u, \
-          c->Kv_shear, c->vv_a_u, c->vv_h_u, GV.H_to_Z, GV.H_subroundoff, GV.dZ_subroundoff, a_cpl_max, I_amax, LAu);           \
-  KLAUNCH(c, "k_vertvisc_coef<1>", (k_vertvisc_coef<1, M>), gv, b, d, c->G, c->vv, v, v_out, v_bc, v_abt, dtx, h, c->Kv_bbl_v, c->bbl_thick_v, \
-          c->Kv_shear, c->vv_a_v, c->vv_h_v, GV.H_to_Z, GV.H_subroundoff, GV.dZ_subroundoff, a_cpl_max, I_amax, LAv)
+  KLAUNCH(c, "k_vertvisc_coef<0>", (k_vertvisc_coef<0, M>), gu, b, d, c->G, S.P, u, u_out, u_bc, u_abt, dtx, h, S.Kv_bbl_u, S.bbl_thick_u, \
+          S.Kv_shear, S.own_a_u, S.own_h_u, GV.H_to_Z, GV.H_subroundoff, GV.dZ_subroundoff, a_cpl_max, I_amax, LAu);           \
+  KLAUNCH(c, "k_vertvisc_coef<1>", (k_vertvisc_coef<1, M>), gv, b, d, c->G, S.P, v, v_out, v_bc, v_abt, dtx, h, S.Kv_bbl_v, S.bbl_thick_v, \
+          S.Kv_shear, S.own_a_v, S.own_h_v, GV.H_to_Z, GV.H_subroundoff, GV.dZ_subroundoff, a_cpl_max, I_amax, LAv)
   if (mode == 0) { VVC(0); } else if (mode == 1) { VVC(1); } else if (mode == 2) { VVC(2); } else { VVC(3); }
 #undef VVC
   HIPCHK(hipGetLastError());
@@ -838,9 +869,11 @@ static int vertvisc_coef_launch(mom6x_ctx *c, int mode, const double *u, const d
 // vertvisc_coef + the solve of the RK2 step as one kernel per direction (k_vertvisc_coef_cols) where it exists: up to COLS_NK_BOUND
 // layers, no Rayleigh drag, no direct stress, no KV_ML_INVZ2.  MOM6X_VERTVISC=walk|pair: the two kernels.
 static bool vertvisc_coef_solve_usable(mom6x_ctx *c) {
-  return vertvisc_form() == VV_DEFAULT && c->vv_init && c->d.nk <= COLS_NK_BOUND && !c->Ray_u && !(direct_stress_of(c).Hmix > 0.0) && !(c->vv.Kvml_invZ2 > 0.0) &&
-         c->a_u == c->vv_a_u && c->a_v == c->vv_a_v && c->h_u == c->vv_h_u && c->h_v == c->vv_h_v &&   // (the solve reads what vertvisc_coef writes)
-         (!c->vv.bottomdraglaw || (c->Kv_bbl_u && c->Kv_bbl_v && c->bbl_thick_u && c->bbl_thick_v));
+  if (!vertvisc_ready(c)) return false;
+  const VvState &S = *c->vv;
+  return vertvisc_form() == VV_DEFAULT && c->d.nk <= COLS_NK_BOUND && !S.Ray_u && !(S.ds_Hmix > 0.0) && !(S.P.Kvml_invZ2 > 0.0) &&
+         S.a_u == S.own_a_u && S.a_v == S.own_a_v && S.h_u == S.own_h_u && S.h_v == S.own_h_v &&   // (the solve reads what vertvisc_coef writes)
+         (!S.P.bottomdraglaw || (S.Kv_bbl_u && S.Kv_bbl_v && S.bbl_thick_u && S.bbl_thick_v));
 }
 static int vertvisc_coef_cols_launch(mom6x_ctx *c, int mode, const double *u_in, const double *v_in, const double *u_bc, const double *v_bc,
                                      const LayerAccelSrc &LAu, const LayerAccelSrc &LAv, double dtx, const double *h, double dt_coef,
@@ -848,20 +881,21 @@ static int vertvisc_coef_cols_launch(mom6x_ctx *c, int mode, const double *u_in,
                                      double *vr_u, double *vr_v, bool keep_coef) {
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
+  const VvState &S = *c->vv;
   const mom6x_vgrid &GV = c->GV;
   const double a_cpl_max = 1.0e37 * GV.Z_to_H;
-  const double I_amax = (c->vv.answer_date < 20190101) ? (1.0e-10 * GV.H_to_Z) * dt_coef : 0.0;
+  const double I_amax = (S.P.answer_date < 20190101) ? (1.0e-10 * GV.H_to_Z) * dt_coef : 0.0;
   const double dt_Rho0 = dt / GV.H_to_RZ, HR = GV.H_to_RZ;
   const dim3 bc(64, 1, 1);
   const dim3 gu((unsigned)((nxa(d.ni + 1, -1) + 63) / 64), (unsigned)d.nj, 1), gv((unsigned)((d.ni + 63) / 64), (unsigned)(d.nj + 1), 1);
   const bool rem = (vr_u != nullptr);
 #define VCS(DIR, M, R, WC, NKT, g, uin, ubc, LA, uo, vro, tau, taub, Kb, bt, ao, ho)                                                  \
   KLAUNCH_LDS(c, DIR ? "k_vertvisc_coef_cols<1>" : "k_vertvisc_coef_cols<0>", (k_vertvisc_coef_cols<DIR, M, R, WC, NKT>), g, bc,       \
-              (size_t)NK_OF(NKT) * 64 * sizeof(double), d, c->G, c->vv, uin, ubc,                                                       \
-              dtx, h, Kb, bt, c->Kv_shear, ao, ho, GV.H_to_Z, GV.H_subroundoff, GV.dZ_subroundoff, a_cpl_max, I_amax, LA, uo, vro, tau, dt, dt_Rho0, HR, taub)
+              (size_t)NK_OF(NKT) * 64 * sizeof(double), d, c->G, S.P, uin, ubc,                                                       \
+              dtx, h, Kb, bt, S.Kv_shear, ao, ho, GV.H_to_Z, GV.H_subroundoff, GV.dZ_subroundoff, a_cpl_max, I_amax, LA, uo, vro, tau, dt, dt_Rho0, HR, taub)
 #define VCS2(M, R, WC, NKT) do { \
-    VCS(0, M, R, WC, NKT, gu, u_in, u_bc, LAu, u, vr_u, taux, taux_bot, c->Kv_bbl_u, c->bbl_thick_u, c->vv_a_u, c->vv_h_u); \
-    VCS(1, M, R, WC, NKT, gv, v_in, v_bc, LAv, v, vr_v, tauy, tauy_bot, c->Kv_bbl_v, c->bbl_thick_v, c->vv_a_v, c->vv_h_v); } while (0)
+    VCS(0, M, R, WC, NKT, gu, u_in, u_bc, LAu, u, vr_u, taux, taux_bot, S.Kv_bbl_u, S.bbl_thick_u, S.own_a_u, S.own_h_u); \
+    VCS(1, M, R, WC, NKT, gv, v_in, v_bc, LAv, v, vr_v, tauy, tauy_bot, S.Kv_bbl_v, S.bbl_thick_v, S.own_a_v, S.own_h_v); } while (0)
 #define VCS_ALL(NKT) do {                                                                                                               \
     if (mode == 1) VCS2(1, true, false, NKT);   /* (nobody sees the coefficients of :602-609: :737 replaces them) */                    \
     else if (rem && keep_coef) VCS2(3, true, true, NKT);                                                                                \
@@ -889,7 +923,7 @@ int vertvisc_stage_remnant(mom6x_ctx *c, const double *u, const double *v, const
     return vertvisc_coef_cols_launch(c, 1, u, v, u_bc, v_bc, none, none, dt, h, dt, nullptr, nullptr, nullptr, nullptr, dt, nullptr, nullptr,
                                      vr_u, vr_v, false);
   }
-  if (c->vv_init && (rc = vertvisc_coef_launch(c, 1, u, v, u_bc, v_bc, nullptr, nullptr, none, none, dt, h, dt, nullptr, nullptr))) return rc;
+  if (vertvisc_ready(c) && (rc = vertvisc_coef_launch(c, 1, u, v, u_bc, v_bc, nullptr, nullptr, none, none, dt, h, dt, nullptr, nullptr))) return rc;
   return mom6x_vertvisc_remnant(c, vr_u, vr_v, dt);
 }
 
@@ -906,9 +940,9 @@ int vertvisc_stage_solve(mom6x_ctx *c, const double *u_in, const double *v_in, c
   REQUIRE((LAu != nullptr) == (LAv != nullptr) && (LAu || (u_abt && v_abt)), MOM6X_EINVAL,
           "vertvisc_stage_solve: the barotropic accelerations come as two arrays or as two LayerAccelSrc");
   REQUIRE((vr_u != nullptr) == (vr_v != nullptr), MOM6X_EINVAL, "vertvisc_stage_solve: visc_rem_u and visc_rem_v come together");
-  if (!c->vv_init) {
+  if (!vertvisc_ready(c)) {
     REQUIRE(u_abt && v_abt, MOM6X_EINVAL, "vertvisc_stage_solve: without device coefficients the accelerations come as arrays");
-    return vertvisc_fused(c, u_in, v_in, u_bc, v_bc, u_abt, v_abt, dt, u, v, taux, tauy, dt, taux_bot, tauy_bot, vr_u, vr_v);
+    return vertvisc_fused(c, u_in, v_in, u_bc, v_bc, u_abt, v_abt, dt, u, v, taux, tauy, dt, taux_bot, tauy_bot, vr_u, vr_v, h);
   }
   if (LAu && vertvisc_coef_solve_usable(c))
     return vertvisc_coef_cols_launch(c, 3, u_in, v_in, u_bc, v_bc, *LAu, *LAv, dt, h, dt, u, v, taux, tauy, dt, taux_bot, tauy_bot, vr_u, vr_v,
@@ -917,7 +951,7 @@ int vertvisc_stage_solve(mom6x_ctx *c, const double *u_in, const double *v_in, c
   const LayerAccelSrc none = {};
   if ((rc = vertvisc_coef_launch(c, LAu ? 3 : 2, u_in, v_in, u_bc, v_bc, LAu ? nullptr : u_abt, LAu ? nullptr : v_abt, LAu ? *LAu : none,
                                  LAu ? *LAv : none, dt, h, dt, u, v))) return rc;
-  return vertvisc_fused(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, u, v, taux, tauy, dt, taux_bot, tauy_bot, vr_u, vr_v);
+  return vertvisc_fused(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, u, v, taux, tauy, dt, taux_bot, tauy_bot, vr_u, vr_v, h);
 }
 
 extern "C" int mom6x_vertvisc_coef(mom6x_ctx *c, const double *u, const double *v, const double *h, double dt) {
@@ -929,39 +963,43 @@ extern "C" int mom6x_vertvisc_set_coef(mom6x_ctx *c, const double *a_u, const do
                                        const double *h_v, const double *Ray_u, const double *Ray_v) {
   REQUIRE(c && a_u && a_v && h_u && h_v, MOM6X_EINVAL, "mom6x_vertvisc_set_coef: null mandatory array");
   REQUIRE((Ray_u != nullptr) == (Ray_v != nullptr), MOM6X_EINVAL, "mom6x_vertvisc_set_coef: Ray_u and Ray_v come together");
-  c->a_u = a_u; c->a_v = a_v; c->h_u = h_u; c->h_v = h_v; c->Ray_u = Ray_u; c->Ray_v = Ray_v;
+  VvState *S = vv_state(c);
+  S->a_u = a_u; S->a_v = a_v; S->h_u = h_u; S->h_v = h_v; S->Ray_u = Ray_u; S->Ray_v = Ray_v;
   return MOM6X_OK;
 }
 
 extern "C" int mom6x_vertvisc(mom6x_ctx *c, double *u, double *v, const double *taux, const double *tauy, double dt,
                               double *taux_bot, double *tauy_bot) {
-  REQUIRE(c && c->a_u, MOM6X_EINVAL, "MOM_vert_friction(visc): Module must be initialized before it is used.");
+  REQUIRE(c && vertvisc_has_coef(c), MOM6X_EINVAL, "MOM_vert_friction(visc): Module must be initialized before it is used.");
   REQUIRE(u && v && taux && tauy, MOM6X_EINVAL, "vertvisc: null array");
-  return vertvisc_fused(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, u, v, taux, tauy, dt, taux_bot, tauy_bot, nullptr, nullptr);
+  return vertvisc_fused(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, u, v, taux, tauy, dt, taux_bot, tauy_bot, nullptr, nullptr,
+                        nullptr);
 }
 
 extern "C" int mom6x_vertvisc_set_direct_stress(mom6x_ctx *c, double Hmix_stress, const double *h) {
   REQUIRE(c, MOM6X_EINVAL, "vertvisc_set_direct_stress: null context");
   REQUIRE(!(Hmix_stress > 0.0) || h, MOM6X_EINVAL, "vertvisc: DIRECT_STRESS needs the layer thicknesses");
-  c->ds_Hmix = (Hmix_stress > 0.0) ? Hmix_stress : 0.0;
-  c->ds_h = (Hmix_stress > 0.0) ? h : nullptr;
+  VvState *S = vv_state(c);
+  S->ds_Hmix = (Hmix_stress > 0.0) ? Hmix_stress : 0.0;
+  S->ds_h = (Hmix_stress > 0.0) ? h : nullptr;
   return MOM6X_OK;
 }
 
 extern "C" int mom6x_vertvisc_remnant(mom6x_ctx *c, double *visc_rem_u, double *visc_rem_v, double dt) {
-  REQUIRE(c && c->a_u, MOM6X_EINVAL, "MOM_vert_friction(remant): Module must be initialized before it is used.");
+  REQUIRE(c && vertvisc_has_coef(c), MOM6X_EINVAL, "MOM_vert_friction(remant): Module must be initialized before it is used.");
   REQUIRE(visc_rem_u && visc_rem_v, MOM6X_EINVAL, "vertvisc_remnant: null array");
   HIPCHK(hipSetDevice(c->device));
   const Dm d = c->d;
+  const VvState &S = *c->vv;
   double *c1;
   int rc;
-  if (vertvisc_cols_usable(d.nk, c->Ray_u, DirectStress{}) && !c->Ray_v) {
+  if (vertvisc_cols_usable(d.nk, S.Ray_u, DirectStress{}) && !S.Ray_v) {
     const dim3 bc(64, 1, 1);
 #define VRC(NKT) do {                                                                                                                   \
     KLAUNCH(c, "k_vertvisc_remnant_cols<0>", (k_vertvisc_remnant_cols<0, NKT>), dim3((unsigned)((nxa(d.ni + 1, -1) + 63) / 64), (unsigned)d.nj, 1), bc, \
-            d, c->G, visc_rem_u, c->a_u, c->h_u, dt);                                                                                    \
+            d, c->G, visc_rem_u, S.a_u, S.h_u, dt);                                                                                    \
     KLAUNCH(c, "k_vertvisc_remnant_cols<1>", (k_vertvisc_remnant_cols<1, NKT>), dim3((unsigned)((d.ni + 63) / 64), (unsigned)(d.nj + 1), 1), bc, \
-            d, c->G, visc_rem_v, c->a_v, c->h_v, dt); } while (0)
+            d, c->G, visc_rem_v, S.a_v, S.h_v, dt); } while (0)
     COLS_NK_DISPATCH(d.nk, VRC);
 #undef VRC
     HIPCHK(hipGetLastError());
@@ -969,10 +1007,10 @@ extern "C" int mom6x_vertvisc_remnant(mom6x_ctx *c, double *visc_rem_u, double *
   }
   if ((rc = ctx_scratch(c, SCR_c1, d.nk, &c1))) return rc;
   const dim3 b = blk2();
-  KLAUNCH(c, "k_vertvisc_remnant<0>", k_vertvisc_remnant<0>, grid3(nxa(d.ni + 1, -1), d.nj, 1, b), b, d, c->G, visc_rem_u, c->a_u, c->h_u,
-          c->Ray_u, c1, dt);
-  KLAUNCH(c, "k_vertvisc_remnant<1>", k_vertvisc_remnant<1>, grid3(d.ni, d.nj + 1, 1, b), b, d, c->G, visc_rem_v, c->a_v, c->h_v,
-          c->Ray_v, c1, dt);
+  KLAUNCH(c, "k_vertvisc_remnant<0>", k_vertvisc_remnant<0>, grid3(nxa(d.ni + 1, -1), d.nj, 1, b), b, d, c->G, visc_rem_u, S.a_u, S.h_u,
+          S.Ray_u, c1, dt);
+  KLAUNCH(c, "k_vertvisc_remnant<1>", k_vertvisc_remnant<1>, grid3(d.ni, d.nj + 1, 1, b), b, d, c->G, visc_rem_v, S.a_v, S.h_v,
+          S.Ray_v, c1, dt);
   HIPCHK(hipGetLastError());
   return MOM6X_OK;
 }
