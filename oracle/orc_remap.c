@@ -716,7 +716,7 @@ int orc_ALE_regrid_zstar(const mom6x_dims *d, const double *G, const mom6x_vgrid
   double *dz = (double *)calloc((size_t)(2 * (nz + 3)), sizeof(double)), *hc = dz + nz + 3;
   int rc = MOM6X_OK;
   for (size_t n = 0; n < slab * (size_t)(nz + 1); n++) dzRegrid[n] = 0.0;            /* ALE_regrid :539 */
-  for (int j = -1; j <= d->nj; j++) for (int i = -1; i <= d->ni; i++) {
+  for (int j = -1; j <= d->nj && !rc; j++) for (int i = -1; i <= d->ni; i++) {       /* (a FATAL stops at its column) */
     const size_t x = IX2(d, i, j);
     if (mT[x] == 0.) {                                                                /* :1300-1303, :1030-1033 */
       for (int k = 0; k < nz; k++) h_new[x + k * slab] = h[x + k * slab];

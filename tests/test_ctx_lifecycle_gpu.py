@@ -27,11 +27,17 @@ def _bits(a, b, name):
 
 
 def _nan3(dyc, nk=None):
-    return dyc.zeros3(nk).fill_(float("nan"))
+    # (the fill on the context's stream, like the zeros before it: on torch's own stream nothing orders the two, and the first
+    # work of a fresh context's stream can start late enough for its zeros to land on top of the NaNs)
+    import torch
+    with torch.cuda.stream(dyc.torch_stream()):
+        return dyc.zeros3(nk).fill_(float("nan"))
 
 
 def _nan2(dyc):
-    return dyc.zeros2().fill_(float("nan"))
+    import torch
+    with torch.cuda.stream(dyc.torch_stream()):
+        return dyc.zeros2().fill_(float("nan"))
 
 
 # ---- 1. use before init

@@ -301,6 +301,45 @@ def regrid_zstar_remap_case(orc, cfg, mods):
     return rep
 
 
+@pytest.mark.parametrize("nk", [4, 80])
+def test_ALE_regrid_refuses_an_impossible_grid_and_recovers(orc, nk):
+    """adjust_interface_motion's FATAL ("implied h<0 is larger than roundoff", MOM_regridding.F90:1826) on the device: a wet column
+    with a layer of minus half its total thickness makes ALE_regrid raise, from the on-chip kernel k_regrid_zstar_cols<-52> (nk = 4) and
+    from the walking k_regrid_zstar (nk = 80).  The oracle refuses the same input.  The error leaves nothing behind: the next call on
+    the same context, with the thicknesses as they were, gives the oracle's grid bit for bit (the device flag was cleared)."""
+    import torch
+    from mom6_amd.dycore import Dycore, prof_enable, prof_report
+    gg, d, M = H.double_gyre(nk=nk)
+    GV = abi.vgrid_default()
+    h, u, v = synth.make_state(d, M, thin_frac=0.2)
+    depth = float(M[G["bathyT"]].max())
+    cr = np.linspace(1.0, 6.0, d.nk); cr *= depth / cr.sum()
+    RP = abi.regrid_zstar_params_default(old_grid_weight=0.5, depth_of_time_filter_shallow=0.0, depth_of_time_filter_deep=0.0)
+    j, i = d.joff + d.nj // 2, d.ioff + d.ni // 2
+    assert M[G["mask2dT"]][j, i] > 0
+    h_bad = h.copy(); h_bad[1, j, i] = -0.5 * h[:, j, i].sum()
+    hn_o = np.zeros_like(h); dz_o = np.zeros((d.nk + 1,) + d.shape2())
+    with pytest.raises(RuntimeError):
+        orc.ALE_regrid_zstar(d, M, GV, RP, cr, h_bad, hn_o, dz_o)
+    orc.ALE_regrid_zstar(d, M, GV, RP, cr, h, hn_o, dz_o)
+
+    dyc = Dycore(d, M, GV)
+    hn_g = torch.zeros_like(dyc.to_dev(h)); dz_g = torch.zeros((d.nk + 1,) + d.shape2(), dtype=torch.float64, device=dyc.device)
+    prof_enable(dyc, True)
+    with pytest.raises(RuntimeError, match="implied h<0 is larger than roundoff"):
+        dyc.ALE_regrid_zstar(RP, cr, dyc.to_dev(h_bad), hn_g, dz_g)
+    ran = {k: n for k, (n, _) in prof_report(dyc).items() if k.startswith("k_regrid_zstar")}
+    assert ran == {"k_regrid_zstar_cols<-52>" if nk == 4 else "k_regrid_zstar": 1}, ran
+    prof_enable(dyc, False)
+    dyc.ALE_regrid_zstar(RP, cr, dyc.to_dev(h), hn_g, dz_g)
+    dyc.sync()
+    sl1 = H.interior(d, "h", 1)
+    H.assert_bitwise(hn_g.cpu().numpy(), hn_o, "h_new", sl1, signed_zero_ok=False)
+    H.assert_bitwise(dz_g.cpu().numpy(), dz_o, "dzRegrid", sl1, signed_zero_ok=False)
+    assert np.abs(dz_o).max() > 1.0
+    dyc.close()
+
+
 @pytest.mark.parametrize("cfg", ["island_basin", "benchmark_small"])
 @pytest.mark.parametrize("which", ["rho", "hycom1"])
 @pytest.mark.parametrize("mods", [dict(), dict(interp_scheme=abi.INTERP_PLM, boundary_extrapolation=1),
