@@ -359,7 +359,7 @@ int  mom6x_device_count(void);
  * 5 coriolis_params, 6 pgf_params, 7 rk2_params, 8 rk2_hooks, 9 eos_params, 10 vertvisc_params, 11 hor_visc_params,
  * 12 remapping_params, 13 regrid_zstar_params, 14 chksum_result, 15 sum_output_params, 16 energy_sums, 17 regrid_rho_params,
  * 18 set_visc_params, 19 thickness_diffuse_params, 20 tracer_hor_diff_params, 21 varmix_params,
- * 22 mixedlayer_restrat_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
+ * 22 mixedlayer_restrat_params, 23 MEKE_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
 int  mom6x_struct_size(int which);
 
 /* Create a context for one tile on HIP device `device`.  `metrics_host` is a
@@ -909,6 +909,120 @@ int mom6x_mixedlayer_restrat(mom6x_ctx *ctx, double *h, double *uhtr, double *vh
                              double *Rml_av_fast_out);
 /* A test hook: the device's mu(sigma, dh) (:717) at n values; sigma, dh and out are DEVICE arrays of n.                          */
 int mom6x_mixedlayer_restrat_mu(mom6x_ctx *ctx, const double *sigma, const double *dh, double *out, int n);
+
+/* ------------------------------------------------------------------------- */
+/* MOM_MEKE: step_forward_MEKE (mesoscale eddy kinetic energy, EKE_SOURCE = prog) */
+/* MEKE_CS (src/parameterizations/lateral/MOM_MEKE.F90:54-168; MEKE_init :1329-1750): the members that the EKE_SOURCE = prog arm of
+ * step_forward_MEKE (:174-982), MEKE_equilibrium (:987), MEKE_equilibrium_restoring (:1148), MEKE_lengthScales (:1183) and
+ * MEKE_lengthScales_0d (:1258) read on a Boussinesq grid with G%Z_ref = 0.  GV%H_to_RZ, GV%RZ_to_H, GV%Z_to_H and GV%H_subroundoff
+ * are the context's (mom6x_vgrid).  Logicals are ints.  The members marked "must be 0" are refused with MOM6X_EUNSUPPORTED.     */
+typedef struct mom6x_MEKE_params {
+  double MEKE_damping;          /* MEKE_DAMPING (0, :1400) [T-1]: the depth-independent dissipation rate (:542)                    */
+  double MEKE_Cd_scale;         /* MEKE_CD_SCALE (0, :1403): gamma_b of :1283                                                      */
+  double MEKE_Cb;               /* MEKE_CB (25, :1408): > 0 brings the **0.8 of :1284                                              */
+  double MEKE_min_gamma;        /* MEKE_MIN_GAMMA2 (1e-4, :1412)                                                                   */
+  double MEKE_Ct;               /* MEKE_CT (50, :1415): > 0 brings the **0.25 of :1289                                             */
+  double MEKE_GMcoeff;          /* MEKE_GMCOEFF (-1, :1419): scales MEKE%GM_src (:486-503); < 0: MEKE_src_GM is not registered     */
+  int    MEKE_GEOMETRIC;        /* MEKE_GEOMETRIC (F, :1424): MEKE%Kh is not written (:883)                                        */
+  double MEKE_GEOMETRIC_alpha;  /* MEKE_GEOMETRIC_ALPHA (0.05, :1427): the two equilibrium formulas :1037, :1174                   */
+  int    MEKE_equilibrium_alt;  /* MEKE_EQUILIBRIUM_ALT (F, :1430): the closed form :1037 instead of the root find                 */
+  int    MEKE_equilibrium_restoring; /* MEKE_EQUILIBRIUM_RESTORING (F, :1433): the nudging of :505-511                            */
+  double MEKE_restoring_rate;   /* 1 / MEKE_RESTORING_TIMESCALE (1e6 s, :1437-1440) [T-1]                                          */
+  double MEKE_FrCoeff;          /* MEKE_FRCOEFF (-1, :1443): > 0 reads MEKE%mom_src (:444)                                         */
+  double MEKE_bhFrCoeff;        /* MEKE_BHFRCOEFF (-1, :1447): scales MEKE%mom_src_bh (:451-461)                                   */
+  double MEKE_GMECoeff;         /* MEKE_GMECOEFF (-1, :1451): scales MEKE%GME_snk (:479-484)                                       */
+  double MEKE_BGsrc;            /* MEKE_BGSRC (0, :1455) [L2 T-3]                                                                  */
+  double MEKE_Kh;               /* MEKE_KH (-1, :1458) [L2 T-1]; >= 0: Laplacian diffusion and the Strang split                    */
+  double MEKE_K4;               /* MEKE_K4 (-1, :1462) [L4 T-1]; >= 0: biharmonic diffusion (needs a halo of two)                  */
+  double MEKE_dtScale;          /* MEKE_DTSCALE (1, :1466)                                                                         */
+  int    MEKE_positive;         /* MEKE_POSITIVE (F, :1469): MEKE = MAX(0, MEKE) at :870                                           */
+  double MEKE_KhCoeff;          /* MEKE_KHCOEFF (1, :1480): > 0 writes MEKE%Kh (:882)                                              */
+  double MEKE_Uscale;           /* MEKE_USCALE (0, :1487) [L T-1]                                                                  */
+  int    GM_src_alt;            /* MEKE_GM_SRC_ALT (F, :1490): the GM source over the total depth (:487-492)                       */
+  double MEKE_min_depth_tot;    /* MEKE_MIN_DEPTH_TOT (1 m, :1493) [H]                                                             */
+  int    visc_drag;             /* MEKE_VISC_DRAG (T, :1497): drag_rate_visc from visc%Kv_bbl_u/v, visc%bbl_thick_u/v (:330-351)    */
+  double KhMEKE_Fac;            /* MEKE_KHMEKE_FAC (0, :1504): MEKE%Kh in the diffusivity of MEKE itself (:687-689)                */
+  int    use_old_lscale;        /* MEKE_OLD_LSCALE (F, :1507)                                                                      */
+  int    use_min_lscale;        /* MEKE_MIN_LSCALE (F, :1511)                                                                      */
+  double lscale_maxval;         /* MEKE_LSCALE_MAX_VAL (1e7 m, :1515) [L]                                                          */
+  int    Rd_as_max_scale;       /* MEKE_RD_MAX_SCALE (F, :1520)                                                                    */
+  double viscosity_coeff_Ku;    /* MEKE_VISCOSITY_COEFF_KU (0, :1524): /= 0 writes MEKE%Ku (:910)                                  */
+  double viscosity_coeff_Au;    /* MEKE_VISCOSITY_COEFF_AU (0, :1530): /= 0 writes MEKE%Au (:916)                                  */
+  double Lfixed;                /* MEKE_FIXED_MIXING_LENGTH (0, :1536) [L]                                                         */
+  int    fixed_total_depth;     /* MEKE_FIXED_TOTAL_DEPTH (T, :1540): depth_tot from G%bathyT (:371-376) instead of the mass       */
+  double aDeform;               /* MEKE_ALPHA_DEFORM (0, :1550)                                                                    */
+  double aRhines;               /* MEKE_ALPHA_RHINES (0, :1554)                                                                    */
+  double aEady;                 /* MEKE_ALPHA_EADY (0, :1558)                                                                      */
+  double aFrict;                /* MEKE_ALPHA_FRICT (0, :1562)                                                                     */
+  double aGrid;                 /* MEKE_ALPHA_GRID (0, :1566)                                                                      */
+  double MEKE_advection_factor; /* MEKE_ADVECTION_FACTOR (0, :1580): > 0 reads hu, hv                                              */
+  int    MEKE_advection_bug;    /* MEKE_ADVECTION_BUG (F, :1585): the transports of layer nz only (:317-326)                       */
+  double MEKE_topographic_beta; /* MEKE_TOPOGRAPHIC_BETA (0, :1589)                                                                */
+  double cdrag;                 /* MEKE_CDRAG (CDRAG = 0.003) times US%L_to_m*GV%m_to_H, as :1602-1604 leave it [H L-1]             */
+  double T_to_s;                /* US%T_to_s (1): the floors of :1299, :1301                                                       */
+  double L_to_m;                /* US%L_to_m (1): the floor of :1299                                                               */
+  double m_s_to_L_T;            /* US%m_s_to_L_T (1): the bracket and the tolerance of MEKE_equilibrium (:1027, :1065, :1094)      */
+  int    cold_start;            /* MEKE_COLD_START (F, :1570): CS%initialize is false from the start (:1721)                       */
+  int    eke_source_file;       /* EKE_SOURCE = file (:1385-1396): must be 0                                                       */
+  int    eke_source_dbclient;   /* EKE_SOURCE = dbclient (ML_MEKE_init): must be 0                                                 */
+  int    use_Kh_diff;           /* USE_KH_IN_MEKE, MEKE%Kh_diff allocated (:690, :707, :1734): must be 0                           */
+  int    non_Boussinesq;        /* not GV%Boussinesq (:377-381, MEKE_TOTAL_DEPTH_RHO): must be 0                                   */
+  int    open_bcs;              /* open boundaries (G%OBCmaskCu/v differ from mask2dCu/v, :620, :630): must be 0                   */
+  int    debug;                 /* DEBUG (F, :1614): the checksums of :272-287, :397-406, :513, :851: must be 0                    */
+} mom6x_MEKE_params;
+/* MEKE_init :1329 for the members above: checks them, keeps them, sets CS%kh_flux_enabled (:1617-1619) and CS%initialize =
+ * .not. cold_start (:1720-1721: a new run), and allocates every work plane the step needs.  dF_dx, dF_dy: G%dF_dx, G%dF_dy, HOST
+ * planes at h points in the tile layout, copied; read at i = isc..iec, j = jsc..jec; required unless use_old_lscale.  The context
+ * needs a halo of two with MEKE_K4 >= 0 and of one otherwise.  Left to the host: the checks of LAPLACIAN / BIHARMONIC against the
+ * two viscosity coefficients (:1608-1612), MEKE%Le = sqrt(areaT) of a new run (:1724-1729) and the two group passes of
+ * :1735, :1742-1744 (mom6x_pass_fields).                                                                                          */
+int mom6x_MEKE_init(mom6x_ctx *ctx, const mom6x_MEKE_params *p, const double *dF_dx, const double *dF_dy);
+/* The restart arm of :1720: initialized != 0 says that MEKE%MEKE came from a restart file, CS%initialize is cleared and the next
+ * step does not call MEKE_equilibrium; the host then owes the halo update of :1735.  initialized = 0 sets it again (unless
+ * cold_start).                                                                                                                   */
+int mom6x_MEKE_set_initialized(mom6x_ctx *ctx, int initialized);
+/* step_forward_MEKE(MEKE, h, SN_u, SN_v, visc, dt, G, GV, US, CS, hu, hv, ...) :174 on the context's stream, without a host
+ * synchronisation or an allocation; the reference's group passes (:611 with kh_flux_enabled or MEKE_K4 >= 0, :878 always, :925 of
+ * whichever of Kh, Ku, Au, Le are given) run inside through the context's halo layer.  All arrays are DEVICE arrays.
+ * MEKE, Kh, Ku, Au, Le: MEKE%MEKE, MEKE%Kh, MEKE%Ku, MEKE%Au, MEKE%Le, the caller's resident planes (the restart fields MEKE,
+ * MEKE_Kh, MEKE_Ku, MEKE_Au, MEKE_Le), updated in place; the last four are nullable, NULL meaning "not allocated"
+ * (MEKE_alloc_register_restart :2074-2113).  GM_src, mom_src, mom_src_bh, GME_snk: MEKE%GM_src ..., nullable with the same
+ * meaning.  Rd_dx_h: MEKE%Rd_dx_h, NULL stands for the zeros of :2088.  Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v: the members
+ * of visc; with visc_drag off or any of them NULL drag_rate_visc is 0 (:330, :352).  hu, hv: the accumulated mass fluxes (uhtr,
+ * vhtr), read with MEKE_advection_factor > 0 only.  MOM6X_EINVAL, naming the plane, when a coefficient asks for an absent one
+ * (mom_src with MEKE_FrCoeff > 0 or with MEKE_src_mom_lp wanted; Kh with MEKE_KhCoeff > 0 unless MEKE_GEOMETRIC; Ku, Au with their
+ * coefficients; hu, hv): the reference would fault there.
+ * Read: h at i = isc-1..iec+1, j = jsc-1..jec+1 (ONE valid halo point), all layers in the order k = 1..nz; hu at I = isc-1..iec,
+ * j = jsc..jec, hv at i = isc..iec, J = jsc-1..jec; SN_u, Kv_bbl_u, bbl_thick_u and SN_v, Kv_bbl_v, bbl_thick_v on the same
+ * faces; the four sources, Rd_dx_h and MEKE on the computational domain; Kh on isc-1..iec+1 x jsc-1..jec+1 when given and
+ * kh_flux_enabled (its halo is the previous call's).
+ * Written: MEKE on the computational domain and then its whole halo by the passes (with MEKE_K4 >= 0 two halo points are read
+ * after the first pass); Kh (unless MEKE_GEOMETRIC or MEKE_KhCoeff <= 0), Ku, Au (with their coefficients) and Le (always, :411) on
+ * the computational domain and then their halos by the pass of :925.  Every other point keeps its value.
+ * The remaining arguments are nullable diagnostics, written on the computational domain (Kh_u at I = isc-1..iec, j = jsc..jec,
+ * Kh_v at i = isc..iec, J = jsc-1..jec) as the reference posts them; a given plane plays the role of id_* > 0, so the `damping`
+ * factors of :556-606 and :792-848 are applied exactly when src_GM, src_mom_lp, src_mom_bh or src_btm_drag (first stage) or any of
+ * those, src_adv or src_mom_K4 (second stage) is given.  As in the reference, decay is written only inside those two blocks.  A
+ * plane whose diagnostic the reference does not register is left alone: src_mom_K4 with MEKE_K4 < 0 (:1653), src_GM with
+ * MEKE_GMcoeff < 0, src_mom_lp with MEKE_FrCoeff < 0, src_mom_bh with MEKE_bhFrCoeff < 0, Kh_u, Kh_v without kh_flux_enabled; so are
+ * LRhines and LEady with use_old_lscale, where MEKE_lengthScales_0d does not set them.  Ue, Ub, Ut: :933-949; gamma_b, gamma_t:
+ * the square roots of :969-979.
+ * MEKE_equilibrium runs on the first call while CS%initialize is set; its two `stop`s (:1095, :1133) raise the context's numeric
+ * flag (bit 64; MOM6X_ENUMERIC at the next mom6x_ctx_sync, whose message names MEKE_equilibrium) instead.
+ * ONE DELIBERATE DEPARTURE.  When neither MEKE%Kh nor MEKE%Kh_diff is allocated, the reference sets Kh_here = max(0, MEKE_Kh) once
+ * before each face loop (:683, :703 firstprivate) and the CFL limiter of :695 | :710 overwrites it: once the limiter has fired at
+ * one face its result is carried to every later face of a serial sweep, or of one thread's share with OpenMP, so the reference's
+ * answer there depends on the traversal order and on the layout.  The device forms max(0, MEKE_Kh) at every face and limits it
+ * there.  The two agree wherever the limiter does not fire in that arm; with MEKE%Kh given the reference resets Kh_here at every
+ * face and there is no difference.
+ * Not carried: EKE_SOURCE = file | dbclient, MEKE%Kh_diff, the DEBUG checksums, the id_MEKE_equilibrium diagnostic.               */
+int mom6x_step_forward_MEKE(mom6x_ctx *ctx, double *MEKE, const double *h, const double *SN_u, const double *SN_v,
+                            const double *Kv_bbl_u, const double *Kv_bbl_v, const double *bbl_thick_u, const double *bbl_thick_v,
+                            double dt, const double *hu, const double *hv, const double *Rd_dx_h, const double *GM_src,
+                            const double *mom_src, const double *mom_src_bh, const double *GME_snk, double *Kh, double *Ku, double *Au,
+                            double *Le, double *src, double *src_adv, double *src_mom_K4, double *src_btm_drag, double *src_GM,
+                            double *src_mom_lp, double *src_mom_bh, double *decay, double *Kh_u, double *Kh_v, double *LmixScale,
+                            double *LRhines, double *LEady, double *Ue, double *Ub, double *Ut, double *gamma_b, double *gamma_t);
 
 /* ------------------------------------------------------------------------- */
 /* MOM_dynamics_split_RK2                                                    */

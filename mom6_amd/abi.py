@@ -351,6 +351,55 @@ def mixedlayer_restrat_params_default(GV=None, omega=7.2921e-5, **kw):
     return p
 
 
+class MEKEParams(C.Structure):
+    """mom6x_MEKE_params; the MEKE_CS members of the EKE_SOURCE = prog arm of step_forward_MEKE (MOM_MEKE.F90:54-168)."""
+    _fields_ = [("MEKE_damping", C.c_double), ("MEKE_Cd_scale", C.c_double), ("MEKE_Cb", C.c_double), ("MEKE_min_gamma", C.c_double),
+                ("MEKE_Ct", C.c_double), ("MEKE_GMcoeff", C.c_double), ("MEKE_GEOMETRIC", C.c_int), ("MEKE_GEOMETRIC_alpha", C.c_double),
+                ("MEKE_equilibrium_alt", C.c_int), ("MEKE_equilibrium_restoring", C.c_int), ("MEKE_restoring_rate", C.c_double),
+                ("MEKE_FrCoeff", C.c_double), ("MEKE_bhFrCoeff", C.c_double), ("MEKE_GMECoeff", C.c_double), ("MEKE_BGsrc", C.c_double),
+                ("MEKE_Kh", C.c_double), ("MEKE_K4", C.c_double), ("MEKE_dtScale", C.c_double), ("MEKE_positive", C.c_int),
+                ("MEKE_KhCoeff", C.c_double), ("MEKE_Uscale", C.c_double), ("GM_src_alt", C.c_int), ("MEKE_min_depth_tot", C.c_double),
+                ("visc_drag", C.c_int), ("KhMEKE_Fac", C.c_double), ("use_old_lscale", C.c_int), ("use_min_lscale", C.c_int),
+                ("lscale_maxval", C.c_double), ("Rd_as_max_scale", C.c_int), ("viscosity_coeff_Ku", C.c_double),
+                ("viscosity_coeff_Au", C.c_double), ("Lfixed", C.c_double), ("fixed_total_depth", C.c_int), ("aDeform", C.c_double),
+                ("aRhines", C.c_double), ("aEady", C.c_double), ("aFrict", C.c_double), ("aGrid", C.c_double),
+                ("MEKE_advection_factor", C.c_double), ("MEKE_advection_bug", C.c_int), ("MEKE_topographic_beta", C.c_double),
+                ("cdrag", C.c_double), ("T_to_s", C.c_double), ("L_to_m", C.c_double), ("m_s_to_L_T", C.c_double), ("cold_start", C.c_int),
+                ("eke_source_file", C.c_int), ("eke_source_dbclient", C.c_int), ("use_Kh_diff", C.c_int), ("non_Boussinesq", C.c_int),
+                ("open_bcs", C.c_int), ("debug", C.c_int)]
+
+
+MEKE_MUST_BE_0 = ("eke_source_file", "eke_source_dbclient", "use_Kh_diff", "non_Boussinesq", "open_bcs", "debug")
+
+
+def MEKE_params_default(GV=None, **kw):
+    """MEKE_init :1400-1604 defaults (EKE_SOURCE = prog, Boussinesq, unscaled units): MEKE_DAMPING = 0, MEKE_CD_SCALE = 0, MEKE_CB = 25,
+    MEKE_MIN_GAMMA2 = 1e-4, MEKE_CT = 50, MEKE_GMCOEFF = MEKE_FRCOEFF = MEKE_BHFRCOEFF = MEKE_GMECOEFF = -1, MEKE_GEOMETRIC off with
+    alpha 0.05, MEKE_RESTORING_TIMESCALE = 1e6 s, MEKE_BGSRC = 0, MEKE_KH = MEKE_K4 = -1, MEKE_DTSCALE = 1, MEKE_KHCOEFF = 1,
+    MEKE_USCALE = 0, MEKE_MIN_DEPTH_TOT = 1 m, MEKE_VISC_DRAG on, MEKE_KHMEKE_FAC = 0, MEKE_LSCALE_MAX_VAL = 1e7 m,
+    MEKE_FIXED_TOTAL_DEPTH on, every alpha 0, MEKE_ADVECTION_FACTOR = 0, MEKE_TOPOGRAPHIC_BETA = 0, MEKE_CDRAG = CDRAG = 0.003 in the
+    units of :1604, MEKE_COLD_START off."""
+    GV = GV if GV is not None else vgrid_default()
+    p = MEKEParams()
+    p.MEKE_damping = 0.0; p.MEKE_Cd_scale = 0.0; p.MEKE_Cb = 25.0; p.MEKE_min_gamma = 1.0e-4; p.MEKE_Ct = 50.0
+    p.MEKE_GMcoeff = -1.0; p.MEKE_GEOMETRIC = 0; p.MEKE_GEOMETRIC_alpha = 0.05; p.MEKE_equilibrium_alt = 0
+    p.MEKE_equilibrium_restoring = 0; p.MEKE_restoring_rate = 1.0 / 1.0e6
+    p.MEKE_FrCoeff = -1.0; p.MEKE_bhFrCoeff = -1.0; p.MEKE_GMECoeff = -1.0; p.MEKE_BGsrc = 0.0
+    p.MEKE_Kh = -1.0; p.MEKE_K4 = -1.0; p.MEKE_dtScale = 1.0; p.MEKE_positive = 0; p.MEKE_KhCoeff = 1.0; p.MEKE_Uscale = 0.0
+    p.GM_src_alt = 0; p.MEKE_min_depth_tot = 1.0 * GV.Z_to_H; p.visc_drag = 1; p.KhMEKE_Fac = 0.0
+    p.use_old_lscale = 0; p.use_min_lscale = 0; p.lscale_maxval = 1.0e7; p.Rd_as_max_scale = 0
+    p.viscosity_coeff_Ku = 0.0; p.viscosity_coeff_Au = 0.0; p.Lfixed = 0.0; p.fixed_total_depth = 1
+    p.aDeform = 0.0; p.aRhines = 0.0; p.aEady = 0.0; p.aFrict = 0.0; p.aGrid = 0.0
+    p.MEKE_advection_factor = 0.0; p.MEKE_advection_bug = 0; p.MEKE_topographic_beta = 0.0
+    p.cdrag = 0.003 * (1.0 * GV.Z_to_H)
+    p.T_to_s = 1.0; p.L_to_m = 1.0; p.m_s_to_L_T = 1.0; p.cold_start = 0
+    for n in MEKE_MUST_BE_0:
+        setattr(p, n, 0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 class HorViscParams(C.Structure):
     """mom6x_hor_visc_params; hor_visc_CS (MOM_hor_visc.F90:36-259)."""
     _fields_ = [("Laplacian", C.c_int), ("biharmonic", C.c_int), ("Kh", C.c_double), ("Kh_bg_min", C.c_double),
@@ -585,6 +634,11 @@ def load_library(path=None):
     for name in ("mom6x_barotropic_field", "mom6x_rk2_field"):
         if hasattr(lib, name):
             getattr(lib, name).restype = C.c_void_p
+    if hasattr(lib, "mom6x_step_forward_MEKE"):   # (39 arguments: the types are stated, not inferred from what a call happens to pass)
+        vp = C.c_void_p
+        lib.mom6x_MEKE_init.argtypes = [vp, C.POINTER(MEKEParams), vp, vp]
+        lib.mom6x_MEKE_set_initialized.argtypes = [vp, C.c_int]
+        lib.mom6x_step_forward_MEKE.argtypes = [vp] * 9 + [C.c_double] + [vp] * 29
     if path is None:
         _lib = lib
     return lib

@@ -173,6 +173,7 @@ extern "C" int mom6x_struct_size(int which) {
     case 20: return (int)sizeof(mom6x_tracer_hor_diff_params);
     case 21: return (int)sizeof(mom6x_varmix_params);
     case 22: return (int)sizeof(mom6x_mixedlayer_restrat_params);
+    case 23: return (int)sizeof(mom6x_MEKE_params);
     default: return -1;
   }
 }
@@ -249,6 +250,7 @@ extern "C" int mom6x_ctx_destroy(mom6x_ctx *c) {
   tracer_hor_diff_free(c);
   varmix_free(c);
   mixedlayer_restrat_free(c);
+  MEKE_free(c);
   comm_free(c);
   for (int m = 0; m < MOM6X_NSCR; m++) (void)hipFree(c->scr[m]);
   (void)hipFree(c->G); (void)hipFree(c->flag);
@@ -295,7 +297,12 @@ extern "C" int mom6x_ctx_sync(mom6x_ctx *c) {
   HIPCHK(hipMemcpy(&flag, c->flag, sizeof(int), hipMemcpyDeviceToHost));
   if (flag) {
     HIPCHK(hipMemset(c->flag, 0, sizeof(int)));
-    mom6x_set_error("device-side numeric error flag = %d (NaN or negative thickness)", flag);
+    if (flag & MOM6X_FLAG_MEKE_EQUILIBRIUM)
+      mom6x_set_error("device-side numeric error flag = %d (bit %d: MEKE_equilibrium found no bracket below 2e17 m2 s-2 or did not "
+                      "converge in 200 bisections, MOM_MEKE.F90:1095, :1133; other bits: NaN or negative thickness)", flag,
+                      MOM6X_FLAG_MEKE_EQUILIBRIUM);
+    else
+      mom6x_set_error("device-side numeric error flag = %d (NaN or negative thickness)", flag);
     return MOM6X_ENUMERIC;
   }
   return MOM6X_OK;

@@ -387,6 +387,43 @@ class Dycore:
         assert dh.numel() == n and out.numel() == n
         check(self.lib, self.lib.mom6x_mixedlayer_restrat_mu(self.ctx, _ptr(sigma), _ptr(dh), _ptr(out), C.c_int(n)))
 
+    # -- MOM_MEKE ------------------------------------------------------------------------------
+    def MEKE_init(self, params, dF_dx=None, dF_dy=None):
+        """MEKE_init (MOM_MEKE.F90:1329) for the EKE_SOURCE = prog arm; dF_dx, dF_dy: G%dF_dx, G%dF_dy, HOST planes of the tile
+        (required unless use_old_lscale)."""
+        self.MEKE_params = params
+        hp = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        dF_dx, dF_dy = hp(dF_dx), hp(dF_dy)
+        assert all(a is None or a.size == self.dims.slab for a in (dF_dx, dF_dy)), "need a 2-D plane of the tile"
+        cp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(self.lib, self.lib.mom6x_MEKE_init(self.ctx, C.byref(params), cp(dF_dx), cp(dF_dy)))
+
+    def MEKE_set_initialized(self, initialized=True):
+        """MEKE%MEKE came from a restart file (query_initialized, MOM_MEKE.F90:1720): the next step does not call MEKE_equilibrium."""
+        check(self.lib, self.lib.mom6x_MEKE_set_initialized(self.ctx, C.c_int(1 if initialized else 0)))
+
+    MEKE_DIAGS = ("src", "src_adv", "src_mom_K4", "src_btm_drag", "src_GM", "src_mom_lp", "src_mom_bh", "decay", "Kh_u", "Kh_v",
+                  "LmixScale", "LRhines", "LEady", "Ue", "Ub", "Ut", "gamma_b", "gamma_t")
+
+    def step_forward_MEKE(self, MEKE, h, SN_u, SN_v, dt, Kv_bbl_u=None, Kv_bbl_v=None, bbl_thick_u=None, bbl_thick_v=None, hu=None,
+                          hv=None, Rd_dx_h=None, GM_src=None, mom_src=None, mom_src_bh=None, GME_snk=None, Kh=None, Ku=None, Au=None,
+                          Le=None, **diags):
+        """step_forward_MEKE (MOM_MEKE.F90:174): MEKE, Kh, Ku, Au, Le in place, their halos included; the keyword arguments of
+        MEKE_DIAGS are the diagnostics the reference posts."""
+        assert set(diags) <= set(self.MEKE_DIAGS), sorted(set(diags) - set(self.MEKE_DIAGS))
+        # the kernels index whole planes and whole 3-D arrays: a smaller buffer would be read and written past its end
+        n2 = self.dims.slab
+        planes = (MEKE, SN_u, SN_v, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Rd_dx_h, GM_src, mom_src, mom_src_bh, GME_snk, Kh, Ku,
+                  Au, Le) + tuple(diags.values())
+        for a in planes:
+            assert a is None or a.numel() == n2, "need a 2-D plane of the tile"
+        for a in (h, hu, hv):
+            assert a is None or a.numel() == n2 * self.dims.nk, "need a 3-D array of the tile"
+        check(self.lib, self.lib.mom6x_step_forward_MEKE(
+            self.ctx, _ptr(MEKE), _ptr(h), _ptr(SN_u), _ptr(SN_v), _ptr(Kv_bbl_u), _ptr(Kv_bbl_v), _ptr(bbl_thick_u), _ptr(bbl_thick_v),
+            C.c_double(dt), _ptr(hu), _ptr(hv), _ptr(Rd_dx_h), _ptr(GM_src), _ptr(mom_src), _ptr(mom_src_bh), _ptr(GME_snk), _ptr(Kh),
+            _ptr(Ku), _ptr(Au), _ptr(Le), *[_ptr(diags.get(n)) for n in self.MEKE_DIAGS]))
+
     def vertvisc_field(self, name):
         """CS%a_u / a_v / h_u / h_v of the device vertvisc_CS as a torch view."""
         which = ["a_u", "a_v", "h_u", "h_v"].index(name)
