@@ -351,6 +351,14 @@ static VertviscForm vertvisc_form() {
   return form;
 }
 
+// The coefficient walk compiled for the common switch set (CoefWalk::layer<true>) where a run's constants allow it, the general one
+// otherwise.  MOM6X_VV_WALK=general, read once per process: always the general one (tests/test_vertvisc_walk_gpu.py).
+static bool vertvisc_walk_lean(const mom6x_vertvisc_params &P, const mom6x_vgrid &GV) {
+  static const bool general_env = [] { const char *e = getenv("MOM6X_VV_WALK"); return e && !strcmp(e, "general"); }();
+  return !general_env && !P.harmonic_visc && P.bottomdraglaw && P.harm_BL_val == 0.0 && !(P.Kvml_invZ2 > 0.0) && GV.H_to_Z == 1.0 &&
+         GV.dZ_subroundoff == GV.H_subroundoff;
+}
+
 // The layer counts the on-chip column kernels are built for (anything deeper walks through HBM): 75 as such (the headline's), any
 // other count up to the bound with uniform tests on the layer index (mom6x_dev.h COLS_NK_BOUND, COLS_NK_DISPATCH).
 static bool vertvisc_cols_usable(int nk, const double *Ray, const DirectStress &S) {
@@ -424,9 +432,51 @@ struct CoefWalk {
     zh = 0.; zcol0 = -bathy0; zcol1 = -bathy1;
     z_i_below = 0.;          // z_i(k+1): the interface below the layer being worked on
     dz_vel_below = 0.;       // dz_vel(k+1)
+    botfn_below = 1.;        // botfn(0): the bottom interface's coupling has its own expression and does not read it
   }
+  // LEAN (vertvisc_walk_lean): harmonic_visc off, bottomdraglaw on, harm_BL_val == 0, no KV_ML_INVZ2, H_to_Z == 1 and dz_neglect ==
+  // h_neglect, all constants of a run.  Then dz IS h (1.0 * h and the same neglect: dz_harm, dz_arith and the blend dz_vel are h_harm,
+  // h_arith and hvel in every bit), and in the upwinding arm z2_wt is exactly 1 (zh * I_Hbbl < 2 * 0 only where zh * I_Hbbl < 0 already
+  // chose h_harm), so its z2 = 1.0 * (dmax(zh, z_clear) * I_Hbbl) is this layer's z_i_top: the operand the coupling of the layer above
+  // reads as z_i_below.  One botfn per layer, carried up, serves both sites; three divisions per layer where the general form has five.
+  double botfn_below;        // LEAN: botfn(z_i(k+1))
+  template <bool LEAN>
   __device__ __forceinline__ void layer(int K, int nz, double h0, double h1, double uk, double z_t, bool have_Kv_add, double Kv_add,
                                         double &h_u_out, double &a_out) {
+    if (LEAN) {
+      const double h_harm = 2. * h0 * h1 / (h0 + h1 + h_neglect);
+      const double h_arith = 0.5 * (h1 + h0);
+      const double h_delta = h1 - h0;
+      zcol0 = zcol0 + h0; zcol1 = zcol1 + h1;
+      zh = zh + h_harm;
+      const double z_clear = dmax(zcol0, zcol1) + Dmin;
+      const double z2 = dmax(zh, z_clear) * I_Hbbl;                // z_i_top
+      const double botfn_top = 1. / (1. + 0.09 * z2 * z2 * z2 * z2 * z2 * z2);
+      double hvel = h_arith;
+      if (uk * h_delta > 0.) {
+        if (zh * I_Hbbl < 0.) hvel = h_harm;                       // (negative thicknesses: as the general form has them)
+        else hvel = (1. - botfn_top) * h_arith + botfn_top * h_harm;
+      }
+      h_u_out = hvel + h_neglect;
+      double a_cpl;
+      if (K == nz) {
+        const double dhc = hvel * 0.5;
+        a_cpl = kv_bbl / ((dmin(dhc, bbl_thick) + hn) + I_amax * kv_bbl);
+      } else {
+        double Kv_tot = CS.Kv;
+        if (have_Kv_add) Kv_tot = Kv_tot + Kv_add;
+        const double botfn = botfn_below;
+        Kv_tot = Kv_tot + (kv_bbl - CS.Kv) * botfn;
+        const double dhc = 0.5 * (dz_vel_below + hvel);
+        double h_shear;
+        if (dhc > bbl_thick) h_shear = ((1. - botfn) * dhc + botfn * bbl_thick) + hn;
+        else h_shear = dhc + hn;
+        a_cpl = Kv_tot / (h_shear + (I_amax * Kv_tot));
+      }
+      a_out = dmin(a_cpl_max, a_cpl);
+      botfn_below = botfn_top; dz_vel_below = hvel;
+      return;
+    }
     const double dz0 = H_to_Z * h0, dz1 = H_to_Z * h1;
     const double h_harm = 2. * h0 * h1 / (h0 + h1 + h_neglect);
     const double h_arith = 0.5 * (h1 + h0);
@@ -513,7 +563,7 @@ struct CoefWalk {
 // MODE selects the velocity the upwinding looks at: 0: u as given; 1: the predictor estimate of :591-598,
 // mask*(u + dtx*u_bc); 2: that of :681-694 / :957-966, mask*(u + dtx*(u_bc + u_abt)) -- formed on the fly with the
 // reference's expression, so the step never has to write and re-read up/vp just for this routine.
-template <int DIR, int MODE>
+template <int DIR, int MODE, bool LEAN>
 __global__ void __launch_bounds__(256)
 k_vertvisc_coef(Dm d, const double *__restrict__ G, mom6x_vertvisc_params CS, const double *u, double *u_out,
                 const double *__restrict__ u_bc, const double *__restrict__ u_abt, double dtx,
@@ -583,7 +633,7 @@ k_vertvisc_coef(Dm d, const double *__restrict__ G, mom6x_vertvisc_params CS, co
       if (Kv_shear) Kv_add = 0.5 * (Kv_shear[x + (size_t)K * slab] + Kv_shear[y + (size_t)K * slab]);
     }
     double hu, a;
-    W.layer(K, nz, h0, h1, uk, z_t, Kv_shear != nullptr, Kv_add, hu, a);
+    W.layer<LEAN>(K, nz, h0, h1, uk, z_t, Kv_shear != nullptr, Kv_add, hu, a);
     h_out[c] = hu;                                                 // CS%h_u :1868-1872
     a_out[x + (size_t)K * slab] = a;                               // CS%a_u :1863-1867
   }
@@ -641,7 +691,7 @@ __device__ __forceinline__ void cc_file_switch(int p, double (&aa)[NK + 1], cons
 // pair moves 12-13; MODE 1: u, u_bc, h in, visc_rem out = 4 against 8.  The same expressions in the same order as the kernels it
 // replaces (CoefWalk; the sweeps are copies): bit-identical.  KV_ML_INVZ2 (a top-down pre-pass through a_u), Rayleigh drag and the
 // direct-stress option stay with the separate kernels.
-template <int DIR, int MODE, bool REM, bool WRITE_COEF, int NKT>
+template <int DIR, int MODE, bool REM, bool WRITE_COEF, int NKT, bool LEAN>
 __global__ void __launch_bounds__(64)
 k_vertvisc_coef_cols(Dm d, const double *__restrict__ G, mom6x_vertvisc_params CS, const double *u_in, const double *__restrict__ u_bc,
                      double dtx, const double *__restrict__ h, const double *__restrict__ Kv_bbl, const double *__restrict__ bbl_thick_in,
@@ -731,7 +781,7 @@ k_vertvisc_coef_cols(Dm d, const double *__restrict__ G, mom6x_vertvisc_params C
         double Kv_add = 0.0;
         if (K < nk && Kv_shear) Kv_add = 0.5 * (Kv_shear[x + (size_t)K * slab] + Kv_shear[y + (size_t)K * slab]);
         double hu, a;
-        W.layer(K, nk, q_h0[b][m], q_h1[b][m], uk, 0.0, Kv_shear != nullptr, Kv_add, hu, a);
+        W.layer<LEAN>(K, nk, q_h0[b][m], q_h1[b][m], uk, 0.0, Kv_shear != nullptr, Kv_add, hu, a);
         t_a[b][m] = a;
         if (k == nk - 1) a_bot = a;                  // a_u at the bottom interface (aa[nk]): the walk's first layer
         // between the passes: h_u in LDS and the estimate through the result array -- or, when h_u is written anyway, the estimate
@@ -855,13 +905,16 @@ static int vertvisc_coef_launch(mom6x_ctx *c, int mode, const double *u, const d
   const double a_cpl_max = 1.0e37 * GV.Z_to_H;
   const double I_amax = (S.P.answer_date < 20190101) ? (1.0e-10 * GV.H_to_Z) * dt : 0.0;
   const dim3 gu = grid3(nxa(d.ni + 1, -1), d.nj, 1, b), gv = grid3(d.ni, d.nj + 1, 1, b);
-#define VVC(M)                                                                                                                  \
-  KLAUNCH(c, "k_vertvisc_coef<0>", (k_vertvisc_coef<0, M>), gu, b, d, c->G, S.P, u, u_out, u_bc, u_abt, dtx, h, S.Kv_bbl_u, S.bbl_thick_u, \
+  const bool lean = vertvisc_walk_lean(S.P, GV);
+#define VVC_AS(M, L)                                                                                                            \
+  KLAUNCH(c, "k_vertvisc_coef<0>", (k_vertvisc_coef<0, M, L>), gu, b, d, c->G, S.P, u, u_out, u_bc, u_abt, dtx, h, S.Kv_bbl_u, S.bbl_thick_u, \
           S.Kv_shear, S.own_a_u, S.own_h_u, GV.H_to_Z, GV.H_subroundoff, GV.dZ_subroundoff, a_cpl_max, I_amax, LAu);           \
-  KLAUNCH(c, "k_vertvisc_coef<1>", (k_vertvisc_coef<1, M>), gv, b, d, c->G, S.P, v, v_out, v_bc, v_abt, dtx, h, S.Kv_bbl_v, S.bbl_thick_v, \
+  KLAUNCH(c, "k_vertvisc_coef<1>", (k_vertvisc_coef<1, M, L>), gv, b, d, c->G, S.P, v, v_out, v_bc, v_abt, dtx, h, S.Kv_bbl_v, S.bbl_thick_v, \
           S.Kv_shear, S.own_a_v, S.own_h_v, GV.H_to_Z, GV.H_subroundoff, GV.dZ_subroundoff, a_cpl_max, I_amax, LAv)
+#define VVC(M) do { if (lean) { VVC_AS(M, true); } else { VVC_AS(M, false); } } while (0)
   if (mode == 0) { VVC(0); } else if (mode == 1) { VVC(1); } else if (mode == 2) { VVC(2); } else { VVC(3); }
 #undef VVC
+#undef VVC_AS
   HIPCHK(hipGetLastError());
   return MOM6X_OK;
 }
@@ -888,14 +941,15 @@ static int vertvisc_coef_cols_launch(mom6x_ctx *c, int mode, const double *u_in,
   const double dt_Rho0 = dt / GV.H_to_RZ, HR = GV.H_to_RZ;
   const dim3 bc(64, 1, 1);
   const dim3 gu((unsigned)((nxa(d.ni + 1, -1) + 63) / 64), (unsigned)d.nj, 1), gv((unsigned)((d.ni + 63) / 64), (unsigned)(d.nj + 1), 1);
-  const bool rem = (vr_u != nullptr);
-#define VCS(DIR, M, R, WC, NKT, g, uin, ubc, LA, uo, vro, tau, taub, Kb, bt, ao, ho)                                                  \
-  KLAUNCH_LDS(c, DIR ? "k_vertvisc_coef_cols<1>" : "k_vertvisc_coef_cols<0>", (k_vertvisc_coef_cols<DIR, M, R, WC, NKT>), g, bc,       \
+  const bool rem = (vr_u != nullptr), lean = vertvisc_walk_lean(S.P, GV);
+#define VCS(DIR, M, R, WC, NKT, L, g, uin, ubc, LA, uo, vro, tau, taub, Kb, bt, ao, ho)                                                  \
+  KLAUNCH_LDS(c, DIR ? "k_vertvisc_coef_cols<1>" : "k_vertvisc_coef_cols<0>", (k_vertvisc_coef_cols<DIR, M, R, WC, NKT, L>), g, bc,    \
               (size_t)NK_OF(NKT) * 64 * sizeof(double), d, c->G, S.P, uin, ubc,                                                       \
               dtx, h, Kb, bt, S.Kv_shear, ao, ho, GV.H_to_Z, GV.H_subroundoff, GV.dZ_subroundoff, a_cpl_max, I_amax, LA, uo, vro, tau, dt, dt_Rho0, HR, taub)
-#define VCS2(M, R, WC, NKT) do { \
-    VCS(0, M, R, WC, NKT, gu, u_in, u_bc, LAu, u, vr_u, taux, taux_bot, S.Kv_bbl_u, S.bbl_thick_u, S.own_a_u, S.own_h_u); \
-    VCS(1, M, R, WC, NKT, gv, v_in, v_bc, LAv, v, vr_v, tauy, tauy_bot, S.Kv_bbl_v, S.bbl_thick_v, S.own_a_v, S.own_h_v); } while (0)
+#define VCS2L(M, R, WC, NKT, L) do { \
+    VCS(0, M, R, WC, NKT, L, gu, u_in, u_bc, LAu, u, vr_u, taux, taux_bot, S.Kv_bbl_u, S.bbl_thick_u, S.own_a_u, S.own_h_u); \
+    VCS(1, M, R, WC, NKT, L, gv, v_in, v_bc, LAv, v, vr_v, tauy, tauy_bot, S.Kv_bbl_v, S.bbl_thick_v, S.own_a_v, S.own_h_v); } while (0)
+#define VCS2(M, R, WC, NKT) do { if (lean) VCS2L(M, R, WC, NKT, true); else VCS2L(M, R, WC, NKT, false); } while (0)
 #define VCS_ALL(NKT) do {                                                                                                               \
     if (mode == 1) VCS2(1, true, false, NKT);   /* (nobody sees the coefficients of :602-609: :737 replaces them) */                    \
     else if (rem && keep_coef) VCS2(3, true, true, NKT);                                                                                \
@@ -905,6 +959,7 @@ static int vertvisc_coef_cols_launch(mom6x_ctx *c, int mode, const double *u_in,
   COLS_NK_DISPATCH(d.nk, VCS_ALL);
 #undef VCS_ALL
 #undef VCS2
+#undef VCS2L
 #undef VCS
   HIPCHK(hipGetLastError());
   return MOM6X_OK;
