@@ -26,6 +26,7 @@ program check_abi
   type(mom6x_tracer_hor_diff_params) :: thd
   type(mom6x_varmix_params) :: vm
   type(mom6x_mixedlayer_restrat_params) :: mle
+  type(mom6x_set_diffusivity_params) :: sd
   integer :: nbad, rc
   nbad = 0
   call chk(0, int(c_sizeof(d)), "mom6x_dims")
@@ -51,6 +52,7 @@ program check_abi
   call chk(20, int(c_sizeof(thd)), "mom6x_tracer_hor_diff_params")
   call chk(21, int(c_sizeof(vm)), "mom6x_varmix_params")
   call chk(22, int(c_sizeof(mle)), "mom6x_mixedlayer_restrat_params")
+  call chk(25, int(c_sizeof(sd)), "mom6x_set_diffusivity_params")
   if (mom6x_abi_version() /= MOM6X_ABI_BUILT_FOR) then
     print '(a,i0,a,i0)', "ABI version: library ", mom6x_abi_version(), ", fortran/mom6x_c_api.F90 ", MOM6X_ABI_BUILT_FOR ; nbad = nbad + 1
   endif

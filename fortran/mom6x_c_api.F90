@@ -12,6 +12,7 @@ module mom6x_c_api
   public :: mom6x_coriolis_params, mom6x_pgf_params, mom6x_eos_params, mom6x_rk2_params, mom6x_rk2_hooks
   public :: mom6x_PressureForce_set_tv, mom6x_vertvisc_params, mom6x_vertvisc_init, mom6x_vertvisc_set_visc, mom6x_vertvisc_coef
   public :: mom6x_set_visc_params, mom6x_set_visc_init, mom6x_set_viscous_BBL
+  public :: mom6x_set_diffusivity_params, mom6x_set_diffusivity_init, mom6x_set_BBL_TKE, mom6x_set_diffusivity, mom6x_set_diffusivity_field
   public :: mom6x_thickness_diffuse_params, mom6x_thickness_diffuse_init, mom6x_thickness_diffuse
   public :: mom6x_tracer_hor_diff_params, mom6x_tracer_hor_diff_init, mom6x_tracer_hordiff, mom6x_tracer_hordiff_tile
   public :: mom6x_varmix_params, mom6x_varmix_init, mom6x_calc_slope_functions
@@ -111,6 +112,30 @@ module mom6x_c_api
     real(c_double) :: Rad_Earth, L_to_Z, L_to_H
     integer(c_int) :: nkml, open_bcs, ice_shelf, SpV_avg
   end type mom6x_set_visc_params
+
+  type, bind(C) :: mom6x_set_diffusivity_params   !< set_diffusivity_CS and its bkgnd_mixing_cs (MOM_set_diffusivity.F90:57-228, MOM_bkgnd_mixing.F90:40-100), the members set_BBL_TKE and the ALE-coordinate path of set_diffusivity read
+    real(c_double) :: Kd, Kd_min, Kd_max, Kd_add, Kv, Kd_smooth, FluxRi_max, omega
+    integer(c_int) :: answer_date, bottomdraglaw
+    real(c_double) :: cdrag, BBL_effic, ePBL_BBL_effic
+    integer(c_int) :: ePBL_BBL_mstar
+    real(c_double) :: BBL_mixing_max_decay
+    integer(c_int) :: use_LOTW_BBL_diffusivity, LOTW_BBL_use_omega
+    real(c_double) :: von_Karm
+    integer(c_int) :: LOTW_BBL_answer_date
+    real(c_double) :: dissip_min, dissip_N0, dissip_N1, dissip_Kd_min
+    integer(c_int) :: double_diffusion
+    real(c_double) :: Max_Rrho_salt_fingers, Max_salt_diff_salt_fingers, Kv_molecular
+    integer(c_int) :: use_Kd_shear, physical_OBL_scheme
+    real(c_double) :: Kd_tot_ml, Hmix
+    integer(c_int) :: Kd_via_Kdml_bug
+    real(c_double) :: prandtl_bkgnd
+    integer(c_int) :: Henyey_IGW_background
+    real(c_double) :: N0_2Omega, Henyey_max_lat
+    integer(c_int) :: Kd_tanh_lat_fn
+    real(c_double) :: Kd_tanh_lat_scale, g_Earth_Z_T2, Z_to_H_fill, m2_s_to_HZ_T, s_to_T, RL2_T2_to_Pa
+    integer(c_int) :: ML_radiation, use_tidal_mixing, use_int_tides, use_CVMix_ddiff, Bryan_Lewis_diffusivity
+    integer(c_int) :: horiz_varying_background, user_change_diff, nkml, SpV_avg, open_bcs
+  end type mom6x_set_diffusivity_params
 
   type, bind(C) :: mom6x_thickness_diffuse_params   !< thickness_diffuse_CS (MOM_thickness_diffuse.F90:41-128), the members thickness_diffuse reads
     integer(c_int) :: thickness_diffuse
@@ -382,6 +407,35 @@ module mom6x_c_api
         Ray_u, Ray_v) bind(C, name="mom6x_set_viscous_BBL")
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx, u, v, h, T, S, p_surf, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, Ray_u, Ray_v
+    end function
+    !> set_diffusivity_init (MOM_set_diffusivity.F90:2262) with bkgnd_mixing_init; eos: c_loc(an eos_params) or c_null_ptr; Rlay:
+    !! c_loc of GV%Rlay on the host (read without an EOS) or c_null_ptr; geoLatT: c_loc of G%geoLatT as a host plane of the tile in
+    !! the pitched layout (read with HENYEY_IGW_BACKGROUND or KD_TANH_LAT_FN) or c_null_ptr
+    integer(c_int) function mom6x_set_diffusivity_init(ctx, p, eos, Rlay, geoLatT) bind(C, name="mom6x_set_diffusivity_init")
+      import :: c_ptr, c_int, mom6x_set_diffusivity_params
+      type(c_ptr), value :: ctx ; type(mom6x_set_diffusivity_params), intent(in) :: p
+      type(c_ptr), value :: eos, Rlay, geoLatT
+    end function
+    !> the module's device arrays: which = 0 the Kd_sfc plane of calculate_bkgnd_mixing
+    type(c_ptr) function mom6x_set_diffusivity_field(ctx, which) bind(C, name="mom6x_set_diffusivity_field")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx ; integer(c_int), value :: which
+    end function
+    !> set_BBL_TKE (MOM_set_diffusivity.F90:1947): device pointers; BBL_meanKE_loss_sqrtCd may be c_null_ptr
+    integer(c_int) function mom6x_set_BBL_TKE(ctx, u, v, h, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, ustar_BBL, BBL_meanKE_loss, &
+        BBL_meanKE_loss_sqrtCd) bind(C, name="mom6x_set_BBL_TKE")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, u, v, h, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, ustar_BBL, BBL_meanKE_loss, BBL_meanKE_loss_sqrtCd
+    end function
+    !> set_diffusivity (MOM_set_diffusivity.F90:243): device pointers, c_null_ptr for what is absent (include/mom6x.h says which may be)
+    integer(c_int) function mom6x_set_diffusivity(ctx, u, v, h, T, S, p_surf, tv_p_surf, Kd_shear, ustar_BBL, BBL_meanKE_loss, &
+        ustar_tidal, BBL_tidal_dis, Ray_u, Ray_v, dt, Kd_int, Kd_lay, Kd_extra_T, Kd_extra_S, Kv_slow, Kv_shear, N2_3d, Kd_BBL, &
+        Kd_bkgnd, Kv_bkgnd, KT_extra, KS_extra) bind(C, name="mom6x_set_diffusivity")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, u, v, h, T, S, p_surf, tv_p_surf, Kd_shear, ustar_BBL, BBL_meanKE_loss, ustar_tidal, BBL_tidal_dis
+      type(c_ptr), value :: Ray_u, Ray_v, Kd_int, Kd_lay, Kd_extra_T, Kd_extra_S, Kv_slow, Kv_shear, N2_3d, Kd_BBL, Kd_bkgnd, Kv_bkgnd
+      type(c_ptr), value :: KT_extra, KS_extra
+      real(c_double), value :: dt
     end function
     integer(c_int) function mom6x_thickness_diffuse_init(ctx, p, eos, khth2d) bind(C, name="mom6x_thickness_diffuse_init")
       import :: c_ptr, c_int, mom6x_thickness_diffuse_params

@@ -359,7 +359,8 @@ int  mom6x_device_count(void);
  * 5 coriolis_params, 6 pgf_params, 7 rk2_params, 8 rk2_hooks, 9 eos_params, 10 vertvisc_params, 11 hor_visc_params,
  * 12 remapping_params, 13 regrid_zstar_params, 14 chksum_result, 15 sum_output_params, 16 energy_sums, 17 regrid_rho_params,
  * 18 set_visc_params, 19 thickness_diffuse_params, 20 tracer_hor_diff_params, 21 varmix_params,
- * 22 mixedlayer_restrat_params, 23 MEKE_params): lets ctypes / ISO_C_BINDING mirrors be checked at start-up.  */
+ * 22 mixedlayer_restrat_params, 23 MEKE_params, 25 set_diffusivity_params; 24 is not assigned and returns -1): lets ctypes /
+ * ISO_C_BINDING mirrors be checked at start-up.  */
 int  mom6x_struct_size(int which);
 
 /* Create a context for one tile on HIP device `device`.  `metrics_host` is a
@@ -1025,6 +1026,122 @@ int mom6x_step_forward_MEKE(mom6x_ctx *ctx, double *MEKE, const double *h, const
                             double *LRhines, double *LEady, double *Ue, double *Ub, double *Ut, double *gamma_b, double *gamma_t);
 
 /* ------------------------------------------------------------------------- */
+/* MOM_set_diffusivity: set_BBL_TKE and set_diffusivity (diapycnal diffusivities, the ALE-coordinate path)                       */
+/* set_diffusivity_CS (src/parameterizations/vertical/MOM_set_diffusivity.F90:57-228; set_diffusivity_init :2262-2700) and the
+ * bkgnd_mixing_cs it owns (MOM_bkgnd_mixing.F90:40-100; bkgnd_mixing_init :107-320): the members that set_BBL_TKE (:1947-2152),
+ * set_diffusivity (:243-868), find_N2 (:1095), double_diffusion (:1279), add_LOTW_BBL_diffusivity (:1606) and the `else` arm of
+ * calculate_bkgnd_mixing (MOM_bkgnd_mixing.F90:450-516) read on a Boussinesq grid in general coordinates.  Values are in the
+ * reference's scaled units, as its get_param calls leave them; GV%H_to_Z, Z_to_H, H_to_RZ, RZ_to_H, g_Earth, H_subroundoff and
+ * dZ_subroundoff are the context's (mom6x_vgrid).  Logicals are ints.  The members marked "must be 0" are refused with
+ * MOM6X_EUNSUPPORTED.                                                                                                           */
+typedef struct mom6x_set_diffusivity_params {
+  double Kd;                    /* KD (0, :2508-2512) [H Z T-1]: the fill of Kd_int, Kd_lay (:370-371) and the background            */
+  double Kd_min;                /* KD_MIN (0.01*KD, :2513) [H Z T-1]: the floor of Kd_sfc (MOM_bkgnd_mixing.F90:457, :465)           */
+  double Kd_max;                /* KD_MAX (-1, :2516) [H Z T-1]: Kd_wall where no TKE is consumed (:1771); > 0 with the law of the wall */
+  double Kd_add;                /* KD_ADD (0, :2529) [H Z T-1]: added to every interface and layer (:698-701, :732-736)              */
+  double Kv;                    /* KV (none, :2503) [H Z T-1]: the fill of visc%Kv_slow (:374)                                       */
+  double Kd_smooth;             /* KD_SMOOTH (1e-6, :2536) [H Z T-1]: kappa_dt_fill = Kd_smooth*dt (:354)                            */
+  double FluxRi_max;            /* FLUX_RI_MAX (0.2, :2339): the floors (:693, :721) and dissip_N2 (:2569)                           */
+  double omega;                 /* OMEGA (7.2921e-5, :2344) [T-1]: Omega2 (:356), N2_min of the law of the wall (:1667)              */
+  int    answer_date;           /* SET_DIFF_ANSWER_DATE (99991231, :2350): < 20190101 takes kappa_dt_fill of :352                    */
+  int    bottomdraglaw;         /* BOTTOMDRAGLAW (T, :2417); F: set_BBL_TKE zeroes its planes (:2007), no bottom-drag mixing         */
+  double cdrag;                 /* CDRAG (0.003, :2423): cdrag_sqrt of set_BBL_TKE (:2021)                                           */
+  double BBL_effic;             /* BBL_EFFIC (0.2, :2427) times US%L_to_Z**2: TKE_column (:1709), the Rayleigh term (:1733)          */
+  double ePBL_BBL_effic;        /* EPBL_BBL_EFFIC (0, :2431): only in the early return of set_BBL_TKE (:2007)                        */
+  int    ePBL_BBL_mstar;        /* EPBL_BBL_USE_MSTAR (F, :2433): likewise                                                           */
+  double BBL_mixing_max_decay;  /* BBL_MIXING_MAX_DECAY (200 m, :2435) [H]: IMax_decay = 1/it when > 0, else 0 (:2441-2442)          */
+  int    use_LOTW_BBL_diffusivity; /* USE_LOTW_BBL_DIFFUSIVITY (F, :2448); F with BOTTOMDRAGLAW and BBL_EFFIC > 0 is refused         */
+  int    LOTW_BBL_use_omega;    /* LOTW_BBL_USE_OMEGA (T, :2453): N2_min = omega**2 (:1667)                                          */
+  double von_Karm;              /* VON_KARMAN_BBL (VON_KARMAN_CONST = 0.41, :2456-2461)                                              */
+  int    LOTW_BBL_answer_date;  /* LOTW_BBL_ANSWER_DATE (20190101, :2466): > 20240630 takes dz_above (:1712-1717, :1745)             */
+  double dissip_min;            /* DISSIPATION_MIN (0, :2548) [R Z2 T-3 scaled as :2551]                                             */
+  double dissip_N0;             /* DISSIPATION_N0 (0, :2552)                                                                         */
+  double dissip_N1;             /* DISSIPATION_N1 (0, :2557)                                                                         */
+  double dissip_Kd_min;         /* DISSIPATION_KD_MIN (0, :2562) [H Z T-1]; limit_dissipation and dissip_N2 are derived (:2566-2570) */
+  int    double_diffusion;      /* DOUBLE_DIFFUSION (F, :2626): needs an EOS and Kd_extra_T, Kd_extra_S                              */
+  double Max_Rrho_salt_fingers; /* MAX_RRHO_SALT_FINGERS (1.9, :2632)                                                                */
+  double Max_salt_diff_salt_fingers; /* MAX_SALT_DIFF_SALT_FINGERS (1e-4, :2635) [H Z T-1]                                            */
+  double Kv_molecular;          /* KV_MOLECULAR (1.5e-6, :2638) [H Z T-1]                                                            */
+  int    use_Kd_shear;          /* useKappaShear .or. use_CVMix_shear (:2656, :2663): the host hands in visc%Kd_shear (:571-581)       */
+  int    physical_OBL_scheme;   /* a physically based boundary layer scheme is on (MOM_bkgnd_mixing.F90:157): no Hmix ramp (:475)    */
+  double Kd_tot_ml;             /* KD_ML_TOT | KDML (KD, MOM_bkgnd_mixing.F90:171-181) [H Z T-1]; /= Kd brings the ramp of :475-499  */
+  double Hmix;                  /* HMIX_FIXED (none, MOM_bkgnd_mixing.F90:191) [H]                                                   */
+  int    Kd_via_Kdml_bug;       /* KD_BACKGROUND_VIA_KDML_BUG (F, MOM_bkgnd_mixing.F90:312): the two outer arms leave Kd_lay alone   */
+  double prandtl_bkgnd;         /* PRANDTL_BKGND (1, MOM_bkgnd_mixing.F90:252): Kv_bkgnd (:514)                                      */
+  int    Henyey_IGW_background; /* HENYEY_IGW_BACKGROUND (F, MOM_bkgnd_mixing.F90:267): Kd_sfc of :452-459, needs geoLatT            */
+  double N0_2Omega;             /* HENYEY_N0_2OMEGA (20, MOM_bkgnd_mixing.F90:280)                                                   */
+  double Henyey_max_lat;        /* HENYEY_MAX_LAT (95, MOM_bkgnd_mixing.F90:287) [degN]                                              */
+  int    Kd_tanh_lat_fn;        /* KD_TANH_LAT_FN (F, MOM_bkgnd_mixing.F90:293): Kd_sfc of :460-467, needs geoLatT                   */
+  double Kd_tanh_lat_scale;     /* KD_TANH_LAT_SCALE (0, MOM_bkgnd_mixing.F90:300)                                                   */
+  double g_Earth_Z_T2;          /* GV%g_Earth_Z_T2 (g_Earth) [Z T-2]: G_Rho0 of find_N2 (:1152)                                      */
+  double Z_to_H_fill;           /* US%Z_to_m*GV%m_to_H (1): kap_dt_x2 of vert_fill_TS (MOM_isopycnal_slopes.F90:655)                 */
+  double m2_s_to_HZ_T;          /* GV%m2_s_to_HZ_T (1): kappa_dt_fill of :352                                                        */
+  double s_to_T;                /* US%s_to_T (1): likewise                                                                           */
+  double RL2_T2_to_Pa;          /* US%RL2_T2_to_Pa (1): the pressure handed to the equation of state (MOM_EOS.F90 calculate_density_derivs_1d) */
+  int    ML_radiation;          /* ML_RADIATION (F, :2363; add_MLrad_diffusivity): must be 0                                         */
+  int    use_tidal_mixing;      /* tidal_mixing_init (:2360: INT_TIDE_DISSIPATION, LEE_WAVE_DISSIPATION, USE_CVMix_TIDAL): must be 0 */
+  int    use_int_tides;         /* INTERNAL_TIDES (F, :2496; get_lowmode_diffusivity): must be 0                                     */
+  int    use_CVMix_ddiff;       /* USE_CVMIX_DDIFF (:2666): must be 0                                                                */
+  int    Bryan_Lewis_diffusivity;  /* BRYAN_LEWIS_DIFFUSIVITY (F, MOM_bkgnd_mixing.F90:201): must be 0                               */
+  int    horiz_varying_background; /* HORIZ_VARYING_BACKGROUND (F, MOM_bkgnd_mixing.F90:227): must be 0                              */
+  int    user_change_diff;      /* USER_CHANGE_DIFFUSIVITY (F, :2545): must be 0                                                     */
+  int    nkml;                  /* GV%nkml, a bulk mixed layer (:2332): must be 0                                                    */
+  int    SpV_avg;               /* tv%SpV_avg allocated, non-Boussinesq (:1690, thickness_to_dz): must be 0                          */
+  int    open_bcs;              /* open boundary conditions (set_BBL_TKE :1992-1997): must be 0                                      */
+} mom6x_set_diffusivity_params;
+/* set_diffusivity_init :2262 with bkgnd_mixing_init for the members above: checks them, keeps them, derives IMax_decay,
+ * limit_dissipation and dissip_N2, allocates the seven work arrays of the column kernel (nk + 1 levels each) and forms the
+ * Kd_sfc plane.  eos: tv%eqn_of_state (NULL: layers of constant density, dRho_int from Rlay).  Rlay: GV%Rlay, a HOST array of
+ * nk values, read without an EOS only.  geoLatT: G%geoLatT [degrees], a HOST plane of the tile in the pitched layout, read with
+ * HENYEY_IGW_BACKGROUND or KD_TANH_LAT_FN only (required then; the metric block carries no latitude).
+ * MOM6X_EUNSUPPORTED, naming the setting: every "must be 0" member, and BOTTOMDRAGLAW with BBL_EFFIC > 0 but without
+ * USE_LOTW_BBL_DIFFUSIVITY (add_drag_diffusivity with find_TKE_to_Kd and set_density_ratios, the layered-mode physics).
+ * MOM6X_EINVAL: USE_LOTW_BBL_DIFFUSIVITY with KD_MAX <= 0 (:2533), DOUBLE_DIFFUSION without an EOS (the reference leaves the
+ * arrays unset), an EOS with nk < 2, both latitude functions at once (MOM_bkgnd_mixing.F90:305), a missing Rlay or geoLatT. */
+int mom6x_set_diffusivity_init(mom6x_ctx *ctx, const mom6x_set_diffusivity_params *p, const mom6x_eos_params *eos,
+                               const double *Rlay, const double *geoLatT);
+/* Device arrays of the module: which = 0 the Kd_sfc plane of calculate_bkgnd_mixing :452-472 (one plane, formed over the whole
+ * array at init; the constant KD without a latitude function).  NULL before init or for another index.                        */
+double *mom6x_set_diffusivity_field(mom6x_ctx *ctx, int which);
+/* set_BBL_TKE(u, v, h, tv, fluxes, visc, G, GV, US, CS, OBC) :1947 on the context's stream, one launch, no host synchronisation.
+ * Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v: the planes mom6x_set_viscous_BBL leaves on the device.
+ * Read: h at i = isc-1..iec+1, j = jsc-1..jec+1 (ONE valid halo point), bottom-up over bbl_thick; u, Kv_bbl_u, bbl_thick_u at
+ * I = isc-1..iec, j = jsc..jec; v, Kv_bbl_v, bbl_thick_v at i = isc..iec, J = jsc-1..jec (what mom6x_set_viscous_BBL writes).
+ * Written on the computational domain: ustar_BBL, BBL_meanKE_loss (visc%ustar_BBL, visc%BBL_meanKE_loss) and, when given,
+ * BBL_meanKE_loss_sqrtCd.  Without BOTTOMDRAGLAW, or with BBL_EFFIC <= 0, EPBL_BBL_EFFIC <= 0 and no EPBL_BBL_USE_MSTAR, the
+ * planes that are given are zeroed there and nothing is read (:2007-2019).                                                  */
+int mom6x_set_BBL_TKE(mom6x_ctx *ctx, const double *u, const double *v, const double *h, const double *Kv_bbl_u,
+                      const double *Kv_bbl_v, const double *bbl_thick_u, const double *bbl_thick_v, double *ustar_BBL,
+                      double *BBL_meanKE_loss, double *BBL_meanKE_loss_sqrtCd);
+/* set_diffusivity(u, v, h, u_h, v_h, tv, fluxes, optics, visc, dt, Kd_int, G, GV, US, CS, VBF, Kd_lay, Kd_extra_T, Kd_extra_S) :243
+ * on the context's stream: two launches, no allocation, no host synchronisation, no halo exchange.
+ * Inputs.  h, T, S (tv%T, tv%S, with an EOS): 3-D.  p_surf: fluxes%p_surf (find_N2 :1161), tv_p_surf: tv%p_surf
+ * (double_diffusion :1326): two separately nullable planes.  Kd_shear: visc%Kd_shear (nk + 1 levels), required with use_Kd_shear.
+ * ustar_BBL, BBL_meanKE_loss: the planes of mom6x_set_BBL_TKE, required with the law of the wall.  ustar_tidal, BBL_tidal_dis:
+ * fluxes%ustar_tidal, fluxes%BBL_tidal_dis, nullable planes.  Ray_u, Ray_v: visc%Ray_u, visc%Ray_v (3-D, nullable, together):
+ * when given the law of the wall adds the Rayleigh-drag term :1732-1737 and reads u and v, otherwise u and v may be NULL.
+ * Outputs.  Kd_int (nk + 1 levels) is required.  Nullable: Kd_lay (nk levels); Kd_extra_T and Kd_extra_S (nk + 1, together,
+ * required with DOUBLE_DIFFUSION, :360-363); Kv_slow, Kv_shear (visc%Kv_slow, visc%Kv_shear, nk + 1).  Nullable diagnostics,
+ * nk + 1 levels each: N2_3d, Kd_BBL, Kd_bkgnd, Kv_bkgnd, KT_extra, KS_extra (dd%...).
+ * Read: everything at the computational domain only (i = isc..iec, j = jsc..jec), u and Ray_u also at I = isc-1, v and Ray_v
+ * at J = jsc-1, CoriolisBu at the four corners.
+ * Written over the WHOLE array, halos included (:369-374, :452-453): Kd_int = Kd_lay = KD, Kd_extra_T = Kd_extra_S = 0,
+ * Kv_slow = KV, and Kv_shear = 0 unless use_Kd_shear.  Then on the computational domain: Kd_int and Kd_lay at every level;
+ * Kd_extra_T, Kd_extra_S at K = 2..nz with DOUBLE_DIFFUSION; Kv_slow, N2_3d, Kd_bkgnd, Kv_bkgnd at every interface; KT_extra,
+ * KS_extra at every interface with DOUBLE_DIFFUSION; Kd_BBL at K = 2..nz when the law of the wall runs.  A diagnostic plane is
+ * otherwise left alone (the reference allocates its own with zeros: the caller's K = 1 and K = nz+1 planes of Kd_BBL and the
+ * halos keep what the caller put there).
+ * Not carried: Calculate_kappa_shear and CVMix shear (the host may hand in visc%Kd_shear), ML_RADIATION, tidal mixing,
+ * INTERNAL_TIDES, USE_CVMIX_DDIFF, the Bryan-Lewis and horizontally varying backgrounds, USER_CHANGE_DIFFUSIVITY,
+ * add_drag_diffusivity, dRho_int_unfilt and find_rho_bottom (nothing on this path reads them), the Kd_Work diagnostics and VBF. */
+int mom6x_set_diffusivity(mom6x_ctx *ctx, const double *u, const double *v, const double *h, const double *T, const double *S,
+                          const double *p_surf, const double *tv_p_surf, const double *Kd_shear, const double *ustar_BBL,
+                          const double *BBL_meanKE_loss, const double *ustar_tidal, const double *BBL_tidal_dis,
+                          const double *Ray_u, const double *Ray_v, double dt, double *Kd_int, double *Kd_lay,
+                          double *Kd_extra_T, double *Kd_extra_S, double *Kv_slow, double *Kv_shear, double *N2_3d,
+                          double *Kd_BBL, double *Kd_bkgnd, double *Kv_bkgnd, double *KT_extra, double *KS_extra);
+
+/* ------------------------------------------------------------------------- */
 /* MOM_dynamics_split_RK2                                                    */
 
 /* Host callbacks for the callees of step_MOM_dyn_split_RK2 that are NOT on the ported hot path
@@ -1128,9 +1245,10 @@ int mom6x_tracer_vertdiff_sink(mom6x_ctx *ctx, const double *h_old, const double
 int mom6x_tracer_vertdiff_Eulerian_sink(mom6x_ctx *ctx, const double *h_old, const double *ent, double dt, double *tr,
                                         const double *sfc_flux, const double *btm_flux, double *btm_reservoir,
                                         double sink_rate, int convert_flux);
-/* diabatic (MOM_diabatic_driver.F90:277) is a host-side dispatcher over mixing physics that is out of
- * scope; its only device-relevant behaviour is the early return for GV%ke == 1 (:330) -- the solvers
- * above are what it (and the tracer packages, e.g. DOME_tracer.F90:338) call.                       */
+/* diabatic (MOM_diabatic_driver.F90:277) is a host-side dispatcher.  Of what it calls, set_BBL_TKE and set_diffusivity
+ * (mom6x_set_BBL_TKE, mom6x_set_diffusivity: the ALE-coordinate path) and the solvers above are on the device, so a resident
+ * run forms ent = dt*Kd_int/dz there; kappa shear, the boundary layer schemes, tidal mixing and the surface fluxes stay with
+ * the host.  Its early return for GV%ke == 1 (:330) is below.                                        */
 int mom6x_diabatic_is_trivial(const mom6x_ctx *ctx);
 
 /* ------------------------------------------------------------------------- */

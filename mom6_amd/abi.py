@@ -400,6 +400,60 @@ def MEKE_params_default(GV=None, **kw):
     return p
 
 
+class SetDiffusivityParams(C.Structure):
+    """mom6x_set_diffusivity_params; set_diffusivity_CS and its bkgnd_mixing_cs (MOM_set_diffusivity.F90:57-228,
+    MOM_bkgnd_mixing.F90:40-100) as set_BBL_TKE and the ALE-coordinate path of set_diffusivity read them."""
+    _fields_ = [("Kd", C.c_double), ("Kd_min", C.c_double), ("Kd_max", C.c_double), ("Kd_add", C.c_double), ("Kv", C.c_double),
+                ("Kd_smooth", C.c_double), ("FluxRi_max", C.c_double), ("omega", C.c_double), ("answer_date", C.c_int),
+                ("bottomdraglaw", C.c_int), ("cdrag", C.c_double), ("BBL_effic", C.c_double), ("ePBL_BBL_effic", C.c_double),
+                ("ePBL_BBL_mstar", C.c_int), ("BBL_mixing_max_decay", C.c_double), ("use_LOTW_BBL_diffusivity", C.c_int),
+                ("LOTW_BBL_use_omega", C.c_int), ("von_Karm", C.c_double), ("LOTW_BBL_answer_date", C.c_int),
+                ("dissip_min", C.c_double), ("dissip_N0", C.c_double), ("dissip_N1", C.c_double), ("dissip_Kd_min", C.c_double),
+                ("double_diffusion", C.c_int), ("Max_Rrho_salt_fingers", C.c_double), ("Max_salt_diff_salt_fingers", C.c_double),
+                ("Kv_molecular", C.c_double), ("use_Kd_shear", C.c_int), ("physical_OBL_scheme", C.c_int), ("Kd_tot_ml", C.c_double),
+                ("Hmix", C.c_double), ("Kd_via_Kdml_bug", C.c_int), ("prandtl_bkgnd", C.c_double), ("Henyey_IGW_background", C.c_int),
+                ("N0_2Omega", C.c_double), ("Henyey_max_lat", C.c_double), ("Kd_tanh_lat_fn", C.c_int),
+                ("Kd_tanh_lat_scale", C.c_double), ("g_Earth_Z_T2", C.c_double), ("Z_to_H_fill", C.c_double),
+                ("m2_s_to_HZ_T", C.c_double), ("s_to_T", C.c_double), ("RL2_T2_to_Pa", C.c_double),
+                ("ML_radiation", C.c_int), ("use_tidal_mixing", C.c_int), ("use_int_tides", C.c_int), ("use_CVMix_ddiff", C.c_int),
+                ("Bryan_Lewis_diffusivity", C.c_int), ("horiz_varying_background", C.c_int), ("user_change_diff", C.c_int),
+                ("nkml", C.c_int), ("SpV_avg", C.c_int), ("open_bcs", C.c_int)]
+
+
+SET_DIFFUSIVITY_MUST_BE_0 = ("ML_radiation", "use_tidal_mixing", "use_int_tides", "use_CVMix_ddiff", "Bryan_Lewis_diffusivity",
+                             "horiz_varying_background", "user_change_diff", "nkml", "SpV_avg", "open_bcs")
+
+
+def set_diffusivity_params_default(GV=None, Kv=1.0e-4, Hmix=20.0, **kw):
+    """set_diffusivity_init :2262-2700 and bkgnd_mixing_init defaults (Boussinesq, unscaled units): KD = 0 and with it KD_MIN and
+    KD_ML_TOT, KD_MAX = -1, KD_ADD = 0, KD_SMOOTH = 1e-6, FLUX_RI_MAX = 0.2, OMEGA = 7.2921e-5, the newest answers but
+    LOTW_BBL_ANSWER_DATE = 20190101, BOTTOMDRAGLAW on with CDRAG = 0.003, BBL_MIXING_MAX_DECAY = 200 m, LOTW_BBL_USE_OMEGA on,
+    von Karman 0.41, no dissipation floors, no double diffusion (MAX_RRHO_SALT_FINGERS = 1.9, MAX_SALT_DIFF_SALT_FINGERS = 1e-4,
+    KV_MOLECULAR = 1.5e-6), PRANDTL_BKGND = 1, no latitude function (HENYEY_N0_2OMEGA = 20, HENYEY_MAX_LAT = 95).  KV and
+    HMIX_FIXED have no default in MOM6 (fail_if_missing).  Two departures, both because the reference's own defaults select a path
+    that is not on the device: BBL_EFFIC = 0 instead of 0.2 (with USE_LOTW_BBL_DIFFUSIVITY = F that is add_drag_diffusivity), and a
+    physically based boundary layer scheme is assumed (an OM4 run has ePBL), so that KD_ML_TOT plays no part."""
+    GV = GV if GV is not None else vgrid_default()
+    p = SetDiffusivityParams()
+    p.Kd = 0.0; p.Kd_min = 0.0; p.Kd_max = -1.0; p.Kd_add = 0.0; p.Kv = Kv; p.Kd_smooth = 1.0e-6
+    p.FluxRi_max = 0.2; p.omega = 7.2921e-5; p.answer_date = 99991231
+    p.bottomdraglaw = 1; p.cdrag = 0.003; p.BBL_effic = 0.0; p.ePBL_BBL_effic = 0.0; p.ePBL_BBL_mstar = 0
+    p.BBL_mixing_max_decay = 200.0 * GV.Z_to_H; p.use_LOTW_BBL_diffusivity = 0; p.LOTW_BBL_use_omega = 1; p.von_Karm = 0.41
+    p.LOTW_BBL_answer_date = 20190101
+    p.dissip_min = 0.0; p.dissip_N0 = 0.0; p.dissip_N1 = 0.0; p.dissip_Kd_min = 0.0
+    p.double_diffusion = 0; p.Max_Rrho_salt_fingers = 1.9; p.Max_salt_diff_salt_fingers = 1.0e-4; p.Kv_molecular = 1.5e-6
+    p.use_Kd_shear = 0; p.physical_OBL_scheme = 1; p.Kd_tot_ml = 0.0; p.Hmix = Hmix; p.Kd_via_Kdml_bug = 0; p.prandtl_bkgnd = 1.0
+    p.Henyey_IGW_background = 0; p.N0_2Omega = 20.0; p.Henyey_max_lat = 95.0; p.Kd_tanh_lat_fn = 0; p.Kd_tanh_lat_scale = 0.0
+    p.g_Earth_Z_T2 = GV.g_Earth; p.Z_to_H_fill = GV.Z_to_H; p.m2_s_to_HZ_T = 1.0; p.s_to_T = 1.0; p.RL2_T2_to_Pa = 1.0
+    for n in SET_DIFFUSIVITY_MUST_BE_0:
+        setattr(p, n, 0)
+    if "Kd" in kw:                                  # KD_MIN and KD_ML_TOT default from KD (:2513, MOM_bkgnd_mixing.F90:171)
+        p.Kd_min = 0.01 * kw["Kd"]; p.Kd_tot_ml = kw["Kd"]
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 class HorViscParams(C.Structure):
     """mom6x_hor_visc_params; hor_visc_CS (MOM_hor_visc.F90:36-259)."""
     _fields_ = [("Laplacian", C.c_int), ("biharmonic", C.c_int), ("Kh", C.c_double), ("Kh_bg_min", C.c_double),
@@ -639,6 +693,13 @@ def load_library(path=None):
         lib.mom6x_MEKE_init.argtypes = [vp, C.POINTER(MEKEParams), vp, vp]
         lib.mom6x_MEKE_set_initialized.argtypes = [vp, C.c_int]
         lib.mom6x_step_forward_MEKE.argtypes = [vp] * 9 + [C.c_double] + [vp] * 29
+    if hasattr(lib, "mom6x_set_diffusivity"):     # (28 arguments, stated like the MEKE step's)
+        vp = C.c_void_p
+        lib.mom6x_set_diffusivity_init.argtypes = [vp, C.POINTER(SetDiffusivityParams), C.POINTER(EOSParams), vp, vp]
+        lib.mom6x_set_diffusivity_field.argtypes = [vp, C.c_int]
+        lib.mom6x_set_diffusivity_field.restype = vp
+        lib.mom6x_set_BBL_TKE.argtypes = [vp] * 11
+        lib.mom6x_set_diffusivity.argtypes = [vp] * 15 + [C.c_double] + [vp] * 12
     if path is None:
         _lib = lib
     return lib

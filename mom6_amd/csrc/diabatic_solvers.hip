@@ -281,6 +281,7 @@ extern "C" int mom6x_tracer_vertdiff_Eulerian_sink(mom6x_ctx *c, const double *h
   return mom6x_tracer_vertdiff_sink(c, h_old, ent, ent + c->dims.slab, dt, tr, sfc_flux, btm_flux, btm_reservoir, sink_rate, convert_flux);
 }
 // diabatic(u, v, h, tv, BLD, fluxes, visc, ADp, CDp, dt, Time_end, G, GV, US, CS, ...)  diabatic_driver.F90:277
-// Only the part of the dispatcher that is on the ported path: with GV%ke == 1 it returns immediately (:330),
-// otherwise the host's mixing-coefficient physics (out of scope) supplies ea/eb or ent and calls the solvers above.
+// The dispatcher stays with the host.  With GV%ke == 1 it returns immediately (:330); otherwise set_BBL_TKE and set_diffusivity
+// (set_diffusivity.hip, the ALE-coordinate path) give Kd_int on the device, the caller forms ea/eb or ent from it and calls the
+// solvers above; kappa shear, the boundary layer schemes and tidal mixing are still the host's.
 extern "C" int mom6x_diabatic_is_trivial(const mom6x_ctx *c) { return (c && c->dims.nk == 1) ? 1 : 0; }

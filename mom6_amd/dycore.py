@@ -387,6 +387,50 @@ class Dycore:
         assert dh.numel() == n and out.numel() == n
         check(self.lib, self.lib.mom6x_mixedlayer_restrat_mu(self.ctx, _ptr(sigma), _ptr(dh), _ptr(out), C.c_int(n)))
 
+    # -- MOM_set_diffusivity -------------------------------------------------------------------
+    def set_diffusivity_init(self, params, eos=None, Rlay=None, geoLatT=None):
+        """set_diffusivity_init (MOM_set_diffusivity.F90:2262) with bkgnd_mixing_init; eos: tv%eqn_of_state (None: GV%Rlay, a HOST
+        array of nk values); geoLatT: G%geoLatT, a HOST plane of the tile, with HENYEY_IGW_BACKGROUND or KD_TANH_LAT_FN."""
+        self.set_diffusivity_params = params
+        self.set_diffusivity_eos = eos
+
+        def cp(a, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            assert a.shape == shape, (a.shape, shape)
+            self._keep.append(a)
+            return a.ctypes.data_as(C.c_void_p)
+        check(self.lib, self.lib.mom6x_set_diffusivity_init(self.ctx, C.byref(params), C.byref(eos) if eos is not None else None,
+                                                            cp(Rlay, (self.dims.nk,)), cp(geoLatT, self.dims.shape2())))
+
+    def set_diffusivity_field(self, name="Kd_sfc"):
+        """The module's device arrays as torch views: "Kd_sfc", the plane of calculate_bkgnd_mixing (MOM_bkgnd_mixing.F90:452-472)."""
+        which = ["Kd_sfc"].index(name)
+        p = self.lib.mom6x_set_diffusivity_field(self.ctx, which)
+        return _view(p, self.dims.shape2(), self.device)
+
+    def set_BBL_TKE(self, u, v, h, Kv_bbl_u, Kv_bbl_v, bbl_thick_u, bbl_thick_v, ustar_BBL, BBL_meanKE_loss, BBL_meanKE_loss_sqrtCd=None):
+        """set_BBL_TKE (MOM_set_diffusivity.F90:1947) from the planes of set_viscous_BBL into visc%ustar_BBL, visc%BBL_meanKE_loss."""
+        check(self.lib, self.lib.mom6x_set_BBL_TKE(self.ctx, _ptr(u), _ptr(v), _ptr(h), _ptr(Kv_bbl_u), _ptr(Kv_bbl_v), _ptr(bbl_thick_u),
+                                                   _ptr(bbl_thick_v), _ptr(ustar_BBL), _ptr(BBL_meanKE_loss),
+                                                   _ptr(BBL_meanKE_loss_sqrtCd)))
+
+    SET_DIFFUSIVITY_IN = ("p_surf", "tv_p_surf", "Kd_shear", "ustar_BBL", "BBL_meanKE_loss", "ustar_tidal", "BBL_tidal_dis", "Ray_u",
+                          "Ray_v")
+    SET_DIFFUSIVITY_OUT = ("Kd_lay", "Kd_extra_T", "Kd_extra_S", "Kv_slow", "Kv_shear", "N2_3d", "Kd_BBL", "Kd_bkgnd", "Kv_bkgnd",
+                           "KT_extra", "KS_extra")
+
+    def set_diffusivity(self, h, dt, Kd_int, u=None, v=None, T=None, S=None, **planes):
+        """set_diffusivity (MOM_set_diffusivity.F90:243): Kd_int and, as keyword arguments, the optional inputs SET_DIFFUSIVITY_IN
+        (fluxes%p_surf, tv%p_surf, visc%Kd_shear, visc%ustar_BBL, ...) and outputs SET_DIFFUSIVITY_OUT (Kd_lay, Kd_extra_T, ...,
+        the diagnostics of dd%)."""
+        known = self.SET_DIFFUSIVITY_IN + self.SET_DIFFUSIVITY_OUT
+        assert set(planes) <= set(known), sorted(set(planes) - set(known))
+        check(self.lib, self.lib.mom6x_set_diffusivity(
+            self.ctx, _ptr(u), _ptr(v), _ptr(h), _ptr(T), _ptr(S), *[_ptr(planes.get(n)) for n in self.SET_DIFFUSIVITY_IN],
+            C.c_double(dt), _ptr(Kd_int), *[_ptr(planes.get(n)) for n in self.SET_DIFFUSIVITY_OUT]))
+
     # -- MOM_MEKE ------------------------------------------------------------------------------
     def MEKE_init(self, params, dF_dx=None, dF_dy=None):
         """MEKE_init (MOM_MEKE.F90:1329) for the EKE_SOURCE = prog arm; dF_dx, dF_dy: G%dF_dx, G%dF_dy, HOST planes of the tile
