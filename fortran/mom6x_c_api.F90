@@ -13,6 +13,8 @@ module mom6x_c_api
   public :: mom6x_PressureForce_set_tv, mom6x_vertvisc_params, mom6x_vertvisc_init, mom6x_vertvisc_set_visc, mom6x_vertvisc_coef
   public :: mom6x_set_visc_params, mom6x_set_visc_init, mom6x_set_viscous_BBL
   public :: mom6x_set_diffusivity_params, mom6x_set_diffusivity_init, mom6x_set_BBL_TKE, mom6x_set_diffusivity, mom6x_set_diffusivity_field
+  public :: mom6x_diabatic_aux_params, mom6x_surface_fluxes, mom6x_diabatic_aux_init, mom6x_applyBoundaryFluxesInOut
+  public :: mom6x_diabatic_aux_status
   public :: mom6x_thickness_diffuse_params, mom6x_thickness_diffuse_init, mom6x_thickness_diffuse
   public :: mom6x_tracer_hor_diff_params, mom6x_tracer_hor_diff_init, mom6x_tracer_hordiff, mom6x_tracer_hordiff_tile
   public :: mom6x_varmix_params, mom6x_varmix_init, mom6x_calc_slope_functions
@@ -136,6 +138,21 @@ module mom6x_c_api
     integer(c_int) :: ML_radiation, use_tidal_mixing, use_int_tides, use_CVMix_ddiff, Bryan_Lewis_diffusivity
     integer(c_int) :: horiz_varying_background, user_change_diff, nkml, SpV_avg, open_bcs
   end type mom6x_set_diffusivity_params
+
+  type, bind(C) :: mom6x_diabatic_aux_params   !< diabatic_aux_CS (MOM_diabatic_aux.F90:43-98) and the members of tv, US and optics_type (MOM_opacity.F90:25-61) that applyBoundaryFluxesInOut, extractFluxes1d and absorbRemainingSW read
+    real(c_double) :: C_p, g_Earth_Z_T2, RL2_T2_to_Pa, ppt_to_S, rivermix_depth, dSalt_frac_max, PenSW_flux_absorb, PenSW_absorb_Invlen
+    integer(c_int) :: optics_answer_date, do_rivermix, use_river_heat_content, use_calving_heat_content, ignore_fluxes_over_land
+    integer(c_int) :: do_brine_plume, enthalpy_from_coupler, SpV_avg, nkml
+  end type mom6x_diabatic_aux_params
+
+  type, bind(C) :: mom6x_surface_fluxes   !< the members of `forcing` (MOM_forcing_type.F90:80-256) that applyBoundaryFluxesInOut touches: device planes, c_null_ptr where the reference's pointer is not associated
+    type(c_ptr) :: sw, lw, latent, sens, evap, lprec, fprec, vprec, lrunoff, frunoff, lrunoff_glc, frunoff_glc, seaice_melt
+    type(c_ptr) :: seaice_melt_heat, heat_added, salt_flux
+    type(c_ptr) :: heat_content_lrunoff, heat_content_lrunoff_glc, heat_content_frunoff, heat_content_frunoff_glc
+    type(c_ptr) :: netMassIn, netMassOut, heat_content_massin, heat_content_massout
+    type(c_ptr) :: heat_content_lprec, heat_content_fprec, heat_content_vprec, heat_content_cond
+    type(c_ptr) :: TempxPmE
+  end type mom6x_surface_fluxes
 
   type, bind(C) :: mom6x_thickness_diffuse_params   !< thickness_diffuse_CS (MOM_thickness_diffuse.F90:41-128), the members thickness_diffuse reads
     integer(c_int) :: thickness_diffuse
@@ -436,6 +453,28 @@ module mom6x_c_api
       type(c_ptr), value :: Ray_u, Ray_v, Kd_int, Kd_lay, Kd_extra_T, Kd_extra_S, Kv_slow, Kv_shear, N2_3d, Kd_BBL, Kd_bkgnd, Kv_bkgnd
       type(c_ptr), value :: KT_extra, KS_extra
       real(c_double), value :: dt
+    end function
+    !> diabatic_aux_init (MOM_diabatic_aux.F90:1349) for applyBoundaryFluxesInOut; eos: c_loc(an eos_params) or c_null_ptr
+    integer(c_int) function mom6x_diabatic_aux_init(ctx, p, eos) bind(C, name="mom6x_diabatic_aux_init")
+      import :: c_ptr, c_int, mom6x_diabatic_aux_params
+      type(c_ptr), value :: ctx ; type(mom6x_diabatic_aux_params), intent(in) :: p
+      type(c_ptr), value :: eos
+    end function
+    !> applyBoundaryFluxesInOut (MOM_diabatic_aux.F90:682): fluxes is c_loc(a mom6x_surface_fluxes) or c_null_ptr; the arrays are
+    !! device pointers, c_null_ptr for what is absent (include/mom6x.h says which may be)
+    integer(c_int) function mom6x_applyBoundaryFluxesInOut(ctx, dt, fluxes, nsw, opacity_band, sw_pen_band, h, T, S, tv_p_surf, &
+        aggregate_FW_forcing, evap_CFL_limit, minimum_forcing_depth, cTKE, dSV_dT, dSV_dS, SkinBuoyFlux, createdH, penSW_diag, &
+        penSWflux_diag, nonpenSW_diag) bind(C, name="mom6x_applyBoundaryFluxesInOut")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, fluxes, opacity_band, sw_pen_band, h, T, S, tv_p_surf, cTKE, dSV_dT, dSV_dS, SkinBuoyFlux
+      type(c_ptr), value :: createdH, penSW_diag, penSWflux_diag, nonpenSW_diag
+      real(c_double), value :: dt, evap_CFL_limit, minimum_forcing_depth
+      integer(c_int), value :: nsw, aggregate_FW_forcing
+    end function
+    !> the counts since the last call (groundings, columns left with a negative thickness, fluxes over land); synchronises
+    integer(c_int) function mom6x_diabatic_aux_status(ctx, groundings, negative_h, land_fluxes) bind(C, name="mom6x_diabatic_aux_status")
+      import :: c_ptr, c_int, c_long
+      type(c_ptr), value :: ctx ; integer(c_long), intent(out) :: groundings, negative_h, land_fluxes
     end function
     integer(c_int) function mom6x_thickness_diffuse_init(ctx, p, eos, khth2d) bind(C, name="mom6x_thickness_diffuse_init")
       import :: c_ptr, c_int, mom6x_thickness_diffuse_params

@@ -1142,6 +1142,93 @@ int mom6x_set_diffusivity(mom6x_ctx *ctx, const double *u, const double *v, cons
                           double *Kd_BBL, double *Kd_bkgnd, double *Kv_bkgnd, double *KT_extra, double *KS_extra);
 
 /* ------------------------------------------------------------------------- */
+/* MOM_diabatic_aux: applyBoundaryFluxesInOut (surface heat, salt and water into h, tv%T, tv%S)                                  */
+/* diabatic_aux_CS (src/parameterizations/vertical/MOM_diabatic_aux.F90:43-98; diabatic_aux_init :1349), the members of tv, US
+ * and optics_type (MOM_opacity.F90:25-61) that applyBoundaryFluxesInOut (:682-1346) and its callees extractFluxes1d
+ * (src/core/MOM_forcing_type.F90:447-948) and absorbRemainingSW (MOM_opacity.F90:600-867) read on a Boussinesq grid.  Values
+ * are in the reference's scaled units; GV%g_Earth, Rho0, Angstrom_H, H_subroundoff, H_to_Z, H_to_RZ and RZ_to_H are the
+ * context's (mom6x_vgrid).  Logicals are ints.  The members marked "must be 0" are refused with MOM6X_EUNSUPPORTED.           */
+typedef struct mom6x_diabatic_aux_params {
+  double C_p;                   /* tv%C_p [Q C-1]: I_Cp, I_Cp_Hconvert (MOM_forcing_type.F90:554-555) and the heat-content diagnostics */
+  double g_Earth_Z_T2;          /* GV%g_Earth_Z_T2 [Z T-2]: g_Hconv2 (:810, MOM_opacity.F90:713-717), GoRho (:821), RivermixConst (:1045) */
+  double RL2_T2_to_Pa;          /* US%RL2_T2_to_Pa (1): the pressure handed to the equation of state                                 */
+  double ppt_to_S;              /* US%ppt_to_S (1): net_salt (MOM_forcing_type.F90:813)                                              */
+  double rivermix_depth;        /* RIVERMIX_DEPTH (0, :1423) [Z]: read with DO_RIVERMIX                                              */
+  double dSalt_frac_max;        /* the largest fraction of a layer's salt that a step may take out (SALT_EXTRACTION_LIMIT, 0.9999, :1400-1404; :1122) */
+  double PenSW_flux_absorb;     /* PEN_SW_FLUX_ABSORB (2.5e-11, MOM_opacity.F90:1172) [C H T-1]: min_SW_heat = PenSW_flux_absorb*dt (MOM_opacity.F90:704)       */
+  double PenSW_absorb_Invlen;   /* 1/(PEN_SW_ABSORB_MINTHICK + H_subroundoff) (MOM_opacity.F90:1184) [H-1]: I_Habs (:705)                             */
+  int    optics_answer_date;    /* OPTICS_ANSWER_DATE (MOM_opacity.F90:1165): < 20190101 takes MOM_opacity.F90:714 and :744            */
+  int    do_rivermix;           /* DO_RIVERMIX (F, :1418): the river TKE source :1033-1054 (with energetics)                         */
+  int    use_river_heat_content;   /* USE_RIVER_HEAT_CONTENT (F, :1431): MOM_forcing_type.F90:718-735; needs heat_content_lrunoff, _glc */
+  int    use_calving_heat_content; /* USE_CALVING_HEAT_CONTENT (F, :1435): MOM_forcing_type.F90:739-756; needs heat_content_frunoff, _glc */
+  int    ignore_fluxes_over_land;  /* IGNORE_FLUXES_OVER_LAND (F, :1412): a flux over land (:1178) is not counted                    */
+  int    do_brine_plume;        /* DO_BRINE_PLUME (F, :1444): must be 0 (needs the mixed layer depth of the boundary layer scheme)   */
+  int    enthalpy_from_coupler; /* fluxes%heat_content_evap associated, do_enthalpy = .false. (MOM_forcing_type.F90:551): must be 0  */
+  int    SpV_avg;               /* tv%SpV_avg allocated, non-Boussinesq (:903, :1046): must be 0                                     */
+  int    nkml;                  /* GV%nkml, a bulk mixed layer (its own bulkmixedlayer applies the fluxes): must be 0                */
+} mom6x_diabatic_aux_params;
+/* The members of `forcing` (MOM_forcing_type.F90:80-256) that the routine touches, as DEVICE planes of the tile, NULL where the
+ * reference's pointer is not associated.  Fluxes are in [R Z T-1] (water, salt) and [Q R Z T-1] (heat).
+ * Required inputs (extractFluxes1d's fatal errors :567-587 and the sums :626-635): sw .. seaice_melt.
+ * Nullable inputs: seaice_melt_heat (:694), heat_added (:711), salt_flux (:812).  heat_content_lrunoff, _lrunoff_glc, _frunoff,
+ * _frunoff_glc are INPUTS with USE_RIVER_HEAT_CONTENT | USE_CALVING_HEAT_CONTENT (required then) and diagnostics written at
+ * :902-920 without.
+ * Nullable outputs, written on the computational domain: netMassIn, netMassOut (:976-982, 0 over land); heat_content_massin,
+ * heat_content_massout (set at :823-849, accumulated at MOM_diabatic_aux.F90:1021-1027 and :1134-1140); heat_content_lprec,
+ * _fprec, _vprec, _cond (:858-900).  TempxPmE (tv%TempxPmE) is accumulated into (:729-755, MOM_diabatic_aux.F90:1028, :1141):
+ * the caller zeroes it.                                                                                                       */
+typedef struct mom6x_surface_fluxes {
+  const double *sw, *lw, *latent, *sens, *evap, *lprec, *fprec, *vprec, *lrunoff, *frunoff, *lrunoff_glc, *frunoff_glc, *seaice_melt;
+  const double *seaice_melt_heat, *heat_added, *salt_flux;
+  double *heat_content_lrunoff, *heat_content_lrunoff_glc, *heat_content_frunoff, *heat_content_frunoff_glc;
+  double *netMassIn, *netMassOut, *heat_content_massin, *heat_content_massout;
+  double *heat_content_lprec, *heat_content_fprec, *heat_content_vprec, *heat_content_cond;
+  double *TempxPmE;
+} mom6x_surface_fluxes;
+/* diabatic_aux_init :1349 for the members above: checks them, keeps them with the equation of state and allocates the three
+ * device counters of mom6x_diabatic_aux_status.  eos: tv%eqn_of_state, NULL without one (then neither the energetics nor
+ * SkinBuoyFlux can be asked for).
+ * MOM6X_EUNSUPPORTED, naming the setting: every "must be 0" member and a non-Boussinesq context.  MOM6X_EINVAL: an unknown
+ * EQN_OF_STATE form, C_p <= 0.                                                                                                */
+int mom6x_diabatic_aux_init(mom6x_ctx *ctx, const mom6x_diabatic_aux_params *p, const mom6x_eos_params *eos);
+/* applyBoundaryFluxesInOut(CS, G, GV, US, dt, fluxes, optics, nsw, h, tv, aggregate_FW_forcing, evap_CFL_limit,
+ * minimum_forcing_depth, cTKE, dSV_dT, dSV_dS, SkinBuoyFlux) :682 with extractFluxes1d (MOM_forcing_type.F90:447, do_enthalpy)
+ * and absorbRemainingSW (MOM_opacity.F90:600; adjustAbsorptionProfile = .false., absorbAllSW = .true., no eps, ksort, htot,
+ * Ttot) on the context's stream: at most two launches, no allocation, no host synchronisation, no halo exchange.  One lane per
+ * column; the derivatives :886-895, steps A and B :1001-1175 and the downward loop of absorbRemainingSW run as ONE top-down
+ * walk, which gives the reference's results bit for bit (the steps couple layers only through per-column scalars).
+ * fluxes: NULL, or one whose sw is NULL, is .not.associated(fluxes%sw): with energetics only the derivatives and the fills are
+ * made, otherwise only the fills (:814, :900).
+ * nsw: the number of bands of penetrating shortwave, 0..4.  opacity_band: optics%opacity_band as nsw 3-D arrays, band-major
+ * (band n at offset n * (nk * slab)), in [H-1]: the caller has applied opacity_scale = GV%H_to_Z (:904).  sw_pen_band:
+ * optics%sw_pen_band as nsw planes, band-major.  Both are required with nsw > 0.
+ * h, T, S (tv%T, tv%S): 3-D, rewritten in place on the computational domain.  tv_p_surf: tv%p_surf, a nullable plane.
+ * Energetics (calculate_energetics, :806) are on when cTKE, dSV_dT and dSV_dS are all given; SkinBuoyFlux (a plane) turns
+ * calculate_buoyancy on; both need an equation of state, the energetics one of LINEAR, WRIGHT, WRIGHT_FULL, WRIGHT_REDUCED,
+ * ROQUET_SPV (the forms whose specific-volume derivatives are on the device; the others are MOM6X_EUNSUPPORTED by name).
+ * Nullable diagnostics: createdH (CS%createdH, a plane [H T-1]: 0, or less what grounded over dt, :1202), penSW_diag (nk
+ * levels), penSWflux_diag (nk + 1 levels, needs penSW_diag), nonpenSW_diag (a plane) (:1213-1272).
+ * Written over the WHOLE array, halos included (:808-809): cTKE = 0 and SkinBuoyFlux = 0.  Everything else is written on the
+ * computational domain only: dSV_dT, dSV_dS and every other array keep the caller's halo.  Land columns of the computational
+ * domain do what the reference does with them: no step A or B, but the derivatives and the shortwave absorption run.
+ * WHERE THE DEVICE DEPARTS FROM THE REFERENCE: it cannot stop.  A negative layer thickness after step B (:1163, FATAL in the
+ * reference) leaves T and S of that layer as they were and is counted; a flux over land without IGNORE_FLUXES_OVER_LAND
+ * (:1178, FATAL) is counted; a grounding (:1193, a WARNING) is counted and goes into createdH.  mom6x_diabatic_aux_status
+ * reads the counts.  Results equal the reference's wherever the reference would have run to completion.
+ * MOM6X_EINVAL: a required plane missing, nsw > 0 without the optics arrays, energetics or SkinBuoyFlux without an equation of
+ * state, USE_RIVER_HEAT_CONTENT | USE_CALVING_HEAT_CONTENT without their heat-content planes, dt <= 0.  MOM6X_EUNSUPPORTED:
+ * nsw > 4, energetics with UNESCO, ROQUET_RHO or JACKETT_06.
+ * Not carried: DO_BRINE_PLUME, enthalpy from the coupler (fluxes%heat_content_evap), non-Boussinesq mode, the bulk mixed layer. */
+int mom6x_applyBoundaryFluxesInOut(mom6x_ctx *ctx, double dt, const mom6x_surface_fluxes *fluxes, int nsw,
+                                   const double *opacity_band, const double *sw_pen_band, double *h, double *T, double *S,
+                                   const double *tv_p_surf, int aggregate_FW_forcing, double evap_CFL_limit,
+                                   double minimum_forcing_depth, double *cTKE, double *dSV_dT, double *dSV_dS, double *SkinBuoyFlux,
+                                   double *createdH, double *penSW_diag, double *penSWflux_diag, double *nonpenSW_diag);
+/* Synchronises the context's stream and returns how many columns, since the last status call, grounded (:1193), were left with
+ * a negative thickness (:1163) and had a flux over land without IGNORE_FLUXES_OVER_LAND (:1178).  Each pointer may be NULL.   */
+int mom6x_diabatic_aux_status(mom6x_ctx *ctx, long *groundings, long *negative_h, long *land_fluxes);
+
+/* ------------------------------------------------------------------------- */
 /* MOM_dynamics_split_RK2                                                    */
 
 /* Host callbacks for the callees of step_MOM_dyn_split_RK2 that are NOT on the ported hot path
@@ -1246,9 +1333,10 @@ int mom6x_tracer_vertdiff_Eulerian_sink(mom6x_ctx *ctx, const double *h_old, con
                                         const double *sfc_flux, const double *btm_flux, double *btm_reservoir,
                                         double sink_rate, int convert_flux);
 /* diabatic (MOM_diabatic_driver.F90:277) is a host-side dispatcher.  Of what it calls, set_BBL_TKE and set_diffusivity
- * (mom6x_set_BBL_TKE, mom6x_set_diffusivity: the ALE-coordinate path) and the solvers above are on the device, so a resident
- * run forms ent = dt*Kd_int/dz there; kappa shear, the boundary layer schemes, tidal mixing and the surface fluxes stay with
- * the host.  Its early return for GV%ke == 1 (:330) is below.                                        */
+ * (mom6x_set_BBL_TKE, mom6x_set_diffusivity: the ALE-coordinate path), applyBoundaryFluxesInOut (mom6x_applyBoundaryFluxesInOut:
+ * the surface fluxes) and the solvers above are on the device, so a resident, forced run forms ent = dt*Kd_int/dz there and
+ * keeps h, T and S there; kappa shear, the boundary layer schemes (energetic_PBL now has its inputs cTKE, dSV_dT, dSV_dS and
+ * SkinBuoyFlux on the device) and tidal mixing stay with the host.  Its early return for GV%ke == 1 (:330) is below.  */
 int mom6x_diabatic_is_trivial(const mom6x_ctx *ctx);
 
 /* ------------------------------------------------------------------------- */

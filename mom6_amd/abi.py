@@ -454,6 +454,55 @@ def set_diffusivity_params_default(GV=None, Kv=1.0e-4, Hmix=20.0, **kw):
     return p
 
 
+class DiabaticAuxParams(C.Structure):
+    """mom6x_diabatic_aux_params; diabatic_aux_CS (MOM_diabatic_aux.F90:43-98) and the members of tv, US and optics_type
+    (MOM_opacity.F90:25-61) that applyBoundaryFluxesInOut, extractFluxes1d and absorbRemainingSW read."""
+    _fields_ = [("C_p", C.c_double), ("g_Earth_Z_T2", C.c_double), ("RL2_T2_to_Pa", C.c_double), ("ppt_to_S", C.c_double),
+                ("rivermix_depth", C.c_double), ("dSalt_frac_max", C.c_double), ("PenSW_flux_absorb", C.c_double),
+                ("PenSW_absorb_Invlen", C.c_double), ("optics_answer_date", C.c_int), ("do_rivermix", C.c_int),
+                ("use_river_heat_content", C.c_int), ("use_calving_heat_content", C.c_int), ("ignore_fluxes_over_land", C.c_int),
+                ("do_brine_plume", C.c_int), ("enthalpy_from_coupler", C.c_int), ("SpV_avg", C.c_int), ("nkml", C.c_int)]
+
+
+DIABATIC_AUX_MUST_BE_0 = ("do_brine_plume", "enthalpy_from_coupler", "SpV_avg", "nkml")
+
+
+def diabatic_aux_params_default(GV=None, **kw):
+    """diabatic_aux_init (MOM_diabatic_aux.F90:1392-1452) and opacity_init (MOM_opacity.F90:1162-1184) defaults, Boussinesq and
+    unscaled: C_P = 3991.86795711963, SALT_EXTRACTION_LIMIT = 0.9999, no river mixing, no river or calving heat content, fluxes
+    over land are checked, the newest optics answers with PEN_SW_FLUX_ABSORB = 2.5e-11 and PEN_SW_ABSORB_MINTHICK = 1 m."""
+    GV = GV if GV is not None else vgrid_default()
+    p = DiabaticAuxParams()
+    p.C_p = 3991.86795711963; p.g_Earth_Z_T2 = GV.g_Earth; p.RL2_T2_to_Pa = 1.0; p.ppt_to_S = 1.0
+    p.rivermix_depth = 0.0; p.dSalt_frac_max = 0.9999
+    p.optics_answer_date = 99991231
+    p.PenSW_flux_absorb = 2.5e-11
+    p.do_rivermix = 0; p.use_river_heat_content = 0; p.use_calving_heat_content = 0; p.ignore_fluxes_over_land = 0
+    for n in DIABATIC_AUX_MUST_BE_0:
+        setattr(p, n, 0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    if "PenSW_absorb_Invlen" not in kw:            # PEN_SW_ABSORB_MINTHICK defaults from the answer date (MOM_opacity.F90:1179-1184)
+        p.PenSW_absorb_Invlen = 1.0 / ((0.001 if p.optics_answer_date < 20190101 else 1.0) + GV.H_subroundoff)
+    return p
+
+
+SURFACE_FLUXES_IN = ("sw", "lw", "latent", "sens", "evap", "lprec", "fprec", "vprec", "lrunoff", "frunoff", "lrunoff_glc",
+                     "frunoff_glc", "seaice_melt")
+SURFACE_FLUXES_IN_NULLABLE = ("seaice_melt_heat", "heat_added", "salt_flux")
+SURFACE_FLUXES_RUNOFF_HEAT = ("heat_content_lrunoff", "heat_content_lrunoff_glc", "heat_content_frunoff", "heat_content_frunoff_glc")
+SURFACE_FLUXES_OUT = ("netMassIn", "netMassOut", "heat_content_massin", "heat_content_massout", "heat_content_lprec",
+                      "heat_content_fprec", "heat_content_vprec", "heat_content_cond")
+SURFACE_FLUXES_INOUT = ("TempxPmE",)
+SURFACE_FLUXES_NAMES = (SURFACE_FLUXES_IN + SURFACE_FLUXES_IN_NULLABLE + SURFACE_FLUXES_RUNOFF_HEAT + SURFACE_FLUXES_OUT +
+                        SURFACE_FLUXES_INOUT)
+
+
+class SurfaceFluxes(C.Structure):
+    """mom6x_surface_fluxes: the members of `forcing` that applyBoundaryFluxesInOut touches, as device planes (None: not associated)."""
+    _fields_ = [(n, C.c_void_p) for n in SURFACE_FLUXES_NAMES]
+
+
 class HorViscParams(C.Structure):
     """mom6x_hor_visc_params; hor_visc_CS (MOM_hor_visc.F90:36-259)."""
     _fields_ = [("Laplacian", C.c_int), ("biharmonic", C.c_int), ("Kh", C.c_double), ("Kh_bg_min", C.c_double),
@@ -700,6 +749,12 @@ def load_library(path=None):
         lib.mom6x_set_diffusivity_field.restype = vp
         lib.mom6x_set_BBL_TKE.argtypes = [vp] * 11
         lib.mom6x_set_diffusivity.argtypes = [vp] * 15 + [C.c_double] + [vp] * 12
+    if hasattr(lib, "mom6x_applyBoundaryFluxesInOut"):     # (21 arguments, stated like the MEKE step's)
+        vp = C.c_void_p
+        lib.mom6x_diabatic_aux_init.argtypes = [vp, C.POINTER(DiabaticAuxParams), C.POINTER(EOSParams)]
+        lib.mom6x_applyBoundaryFluxesInOut.argtypes = ([vp, C.c_double, C.POINTER(SurfaceFluxes), C.c_int] + [vp] * 6 +
+                                                       [C.c_int, C.c_double, C.c_double] + [vp] * 8)
+        lib.mom6x_diabatic_aux_status.argtypes = [vp] + [C.POINTER(C.c_long)] * 3
     if path is None:
         _lib = lib
     return lib

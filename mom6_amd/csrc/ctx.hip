@@ -175,6 +175,8 @@ extern "C" int mom6x_struct_size(int which) {
     case 22: return (int)sizeof(mom6x_mixedlayer_restrat_params);
     case 23: return (int)sizeof(mom6x_MEKE_params);
     case 25: return (int)sizeof(mom6x_set_diffusivity_params);
+    case 27: return (int)sizeof(mom6x_diabatic_aux_params);
+    case 28: return (int)sizeof(mom6x_surface_fluxes);
     default: return -1;
   }
 }
@@ -253,6 +255,7 @@ extern "C" int mom6x_ctx_destroy(mom6x_ctx *c) {
   mixedlayer_restrat_free(c);
   MEKE_free(c);
   set_diffusivity_free(c);
+  diabatic_aux_free(c);
   comm_free(c);
   for (int m = 0; m < MOM6X_NSCR; m++) (void)hipFree(c->scr[m]);
   (void)hipFree(c->G); (void)hipFree(c->flag);

@@ -614,6 +614,43 @@ __device__ __forceinline__ void eos_density_derivs(const EOS &E, double T, doubl
   }
 }
 
+// calculate_specific_vol_derivs(T, S, pressure, dSV_dT, dSV_dS, EOS) (MOM_EOS.F90:1039 calc_spec_vol_derivs_1d -> the form's
+// calculate_specvol_derivs_elem), operation for operation: EOS_LINEAR MOM_EOS_linear.F90:164-181 (E needs Rho_T0_S0, dRho_dT,
+// dRho_dS, dRho_dp), WRIGHT MOM_EOS_Wright.F90:270-296, WRIGHT_FULL MOM_EOS_Wright_full.F90:275-301, WRIGHT_REDUCED
+// MOM_EOS_Wright_red.F90:277-304, ROQUET_SPV MOM_EOS_Roquet_SpV.F90:352-423.  The other forms are not carried
+// (eos_specvol_form_known); press is in Pa (the caller has applied RL2_T2_to_Pa).
+inline bool eos_specvol_form_known(int form) {
+  return form == MOM6X_EOS_LINEAR || form == MOM6X_EOS_WRIGHT || form == MOM6X_EOS_WRIGHT_FULL || form == MOM6X_EOS_WRIGHT_REDUCED ||
+         form == MOM6X_EOS_ROQUET_SPV;
+}
+template <int FORM, class EOS>
+__device__ __forceinline__ void eos_specvol_derivs(const EOS &E, double T, double S, double press, double &dSV_dT, double &dSV_dS) {
+  static_assert(FORM == MOM6X_EOS_LINEAR || FORM == MOM6X_EOS_WRIGHT || FORM == MOM6X_EOS_WRIGHT_FULL ||
+                FORM == MOM6X_EOS_WRIGHT_REDUCED || FORM == MOM6X_EOS_ROQUET_SPV, "eos_specvol_derivs: form not carried");
+  if (FORM == MOM6X_EOS_LINEAR) {
+    const double rho = E.Rho_T0_S0 + ((E.dRho_dT * T + E.dRho_dS * S) + E.dRho_dp * press);
+    const double I_rho2 = 1.0 / (rho * rho);
+    dSV_dT = -E.dRho_dT * I_rho2;
+    dSV_dS = -E.dRho_dS * I_rho2;
+  } else if (FORM == MOM6X_EOS_ROQUET_SPV) {
+    roquet::roquet_spv_derivs(T, S, press, &dSV_dT, &dSV_dS);
+  } else {
+    typedef WC<FORM> W;
+    double al0, p0, lambda;
+    wright_coefs<FORM>(T, S, al0, p0, lambda);
+    const double I_denom = 1.0 / (press + p0);
+    if (FORM == MOM6X_EOS_WRIGHT) {
+      dSV_dT = (W::a1 + I_denom * (W::c1 + T * ((2.0 * W::c2 + 3.0 * W::c3 * T)) + W::c5 * S)) -
+               ((I_denom * I_denom) * lambda) * (W::b1 + T * ((2.0 * W::b2 + 3.0 * W::b3 * T)) + W::b5 * S);
+      dSV_dS = (W::a2 + I_denom * (W::c4 + W::c5 * T)) - ((I_denom * I_denom) * lambda) * (W::b4 + W::b5 * T);
+    } else {
+      dSV_dT = W::a1 + I_denom * ((W::c1 + (T * (2.0 * W::c2 + 3.0 * W::c3 * T) + W::c5 * S)) -
+                                  (I_denom * lambda) * (W::b1 + (T * (2.0 * W::b2 + 3.0 * W::b3 * T) + W::b5 * S)));
+      dSV_dS = W::a2 + I_denom * ((W::c4 + W::c5 * T) - (I_denom * lambda) * (W::b4 + W::b5 * T));
+    }
+  }
+}
+
 // The kernels templated on the EOS form (set_visc.hip, thickness_diffuse.hip, lateral_mixing_coeffs.hip): CALL(F) with F the
 // literal 1..8 of `form`, so that CALL can put #F into the label it gives KLAUNCH.  An init call holds `form` to eos_form_known.
 inline bool eos_form_known(const mom6x_eos_params *e) { return e->form >= MOM6X_EOS_LINEAR && e->form <= MOM6X_EOS_ROQUET_SPV; }

@@ -431,6 +431,41 @@ class Dycore:
             self.ctx, _ptr(u), _ptr(v), _ptr(h), _ptr(T), _ptr(S), *[_ptr(planes.get(n)) for n in self.SET_DIFFUSIVITY_IN],
             C.c_double(dt), _ptr(Kd_int), *[_ptr(planes.get(n)) for n in self.SET_DIFFUSIVITY_OUT]))
 
+    # -- MOM_diabatic_aux ----------------------------------------------------------------------
+    def diabatic_aux_init(self, params, eos=None):
+        """diabatic_aux_init (MOM_diabatic_aux.F90:1349) for applyBoundaryFluxesInOut; eos: tv%eqn_of_state (None: neither the
+        energetics nor SkinBuoyFlux can be asked for)."""
+        self.diabatic_aux_params = params
+        self.diabatic_aux_eos = eos
+        check(self.lib, self.lib.mom6x_diabatic_aux_init(self.ctx, C.byref(params), C.byref(eos) if eos is not None else None))
+
+    APPLY_FLUXES_OUT = ("cTKE", "dSV_dT", "dSV_dS", "SkinBuoyFlux", "createdH", "penSW_diag", "penSWflux_diag", "nonpenSW_diag")
+
+    def applyBoundaryFluxesInOut(self, dt, fluxes, h, T, S, nsw=0, opacity_band=None, sw_pen_band=None, tv_p_surf=None,
+                                 aggregate_FW_forcing=True, evap_CFL_limit=0.8, minimum_forcing_depth=0.001, **out):
+        """applyBoundaryFluxesInOut (MOM_diabatic_aux.F90:682).  fluxes: a dict of device planes by the names of
+        abi.SURFACE_FLUXES_NAMES (None, or without "sw": fluxes%sw is not associated); opacity_band: nsw 3-D arrays, band-major,
+        in [H-1]; sw_pen_band: nsw planes; as keyword arguments the outputs APPLY_FLUXES_OUT (cTKE, dSV_dT and dSV_dS together
+        turn the energetics on, SkinBuoyFlux the buoyancy flux; the rest are diagnostics)."""
+        assert set(out) <= set(self.APPLY_FLUXES_OUT), sorted(set(out) - set(self.APPLY_FLUXES_OUT))
+        F = None
+        if fluxes is not None:
+            assert set(fluxes) <= set(abi.SURFACE_FLUXES_NAMES), sorted(set(fluxes) - set(abi.SURFACE_FLUXES_NAMES))
+            F = abi.SurfaceFluxes()
+            for n in abi.SURFACE_FLUXES_NAMES:
+                p = _ptr(fluxes.get(n))
+                setattr(F, n, p.value if p is not None else None)
+        check(self.lib, self.lib.mom6x_applyBoundaryFluxesInOut(
+            self.ctx, C.c_double(dt), C.byref(F) if F is not None else None, C.c_int(nsw), _ptr(opacity_band), _ptr(sw_pen_band),
+            _ptr(h), _ptr(T), _ptr(S), _ptr(tv_p_surf), C.c_int(1 if aggregate_FW_forcing else 0), C.c_double(evap_CFL_limit),
+            C.c_double(minimum_forcing_depth), *[_ptr(out.get(n)) for n in self.APPLY_FLUXES_OUT]))
+
+    def diabatic_aux_status(self):
+        """(groundings, columns left with a negative thickness, fluxes over land) since the last call; synchronises."""
+        n = [C.c_long(0), C.c_long(0), C.c_long(0)]
+        check(self.lib, self.lib.mom6x_diabatic_aux_status(self.ctx, *[C.byref(v) for v in n]))
+        return tuple(int(v.value) for v in n)
+
     # -- MOM_MEKE ------------------------------------------------------------------------------
     def MEKE_init(self, params, dF_dx=None, dF_dy=None):
         """MEKE_init (MOM_MEKE.F90:1329) for the EKE_SOURCE = prog arm; dF_dx, dF_dy: G%dF_dx, G%dF_dy, HOST planes of the tile
