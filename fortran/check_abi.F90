@@ -29,6 +29,7 @@ program check_abi
   type(mom6x_set_diffusivity_params) :: sd
   type(mom6x_diabatic_aux_params) :: da
   type(mom6x_surface_fluxes) :: sf
+  type(mom6x_energetic_PBL_params) :: ep
   integer :: nbad, rc
   nbad = 0
   call chk(0, int(c_sizeof(d)), "mom6x_dims")
@@ -57,6 +58,7 @@ program check_abi
   call chk(25, int(c_sizeof(sd)), "mom6x_set_diffusivity_params")
   call chk(27, int(c_sizeof(da)), "mom6x_diabatic_aux_params")
   call chk(28, int(c_sizeof(sf)), "mom6x_surface_fluxes")
+  call chk(30, int(c_sizeof(ep)), "mom6x_energetic_PBL_params")
   if (mom6x_abi_version() /= MOM6X_ABI_BUILT_FOR) then
     print '(a,i0,a,i0)', "ABI version: library ", mom6x_abi_version(), ", fortran/mom6x_c_api.F90 ", MOM6X_ABI_BUILT_FOR ; nbad = nbad + 1
   endif

@@ -15,6 +15,7 @@ module mom6x_c_api
   public :: mom6x_set_diffusivity_params, mom6x_set_diffusivity_init, mom6x_set_BBL_TKE, mom6x_set_diffusivity, mom6x_set_diffusivity_field
   public :: mom6x_diabatic_aux_params, mom6x_surface_fluxes, mom6x_diabatic_aux_init, mom6x_applyBoundaryFluxesInOut
   public :: mom6x_diabatic_aux_status
+  public :: mom6x_energetic_PBL_params, mom6x_energetic_PBL_init, mom6x_energetic_PBL, mom6x_energetic_PBL_get_MLD, mom6x_ePBL_augment_Kd
   public :: mom6x_thickness_diffuse_params, mom6x_thickness_diffuse_init, mom6x_thickness_diffuse
   public :: mom6x_tracer_hor_diff_params, mom6x_tracer_hor_diff_init, mom6x_tracer_hordiff, mom6x_tracer_hordiff_tile
   public :: mom6x_varmix_params, mom6x_varmix_init, mom6x_calc_slope_functions
@@ -144,6 +145,16 @@ module mom6x_c_api
     integer(c_int) :: optics_answer_date, do_rivermix, use_river_heat_content, use_calving_heat_content, ignore_fluxes_over_land
     integer(c_int) :: do_brine_plume, enthalpy_from_coupler, SpV_avg, nkml
   end type mom6x_diabatic_aux_params
+
+  type, bind(C) :: mom6x_energetic_PBL_params   !< what energetic_PBL_init (MOM_energetic_PBL.F90:3729-4429) leaves in energetic_PBL_CS (:38-276) for the surface boundary layer, with the members of GV and US that energetic_PBL and ePBL_column read
+    real(c_double) :: omega, omega_frac, Ekman_scale_coef, vonKar, MKE_to_TKE_effic, TKE_decay, fixed_mstar, mstar_cap, mstar_coef, C_Ek
+    real(c_double) :: RH18_mstar_cn1, RH18_mstar_cn2, RH18_mstar_cn3, RH18_mstar_cs1, RH18_mstar_cs2, nstar, mstar_convect_coef
+    real(c_double) :: transLay_scale, MLD_tol, min_mix_len, MixLenExponent, wstar_ustar_coef, vstar_scale_fac, vstar_surf_fac
+    real(c_double) :: ustar_min, g_Earth_Z_T2, m_to_Z, T_to_s, ePBL_BBL_effic, ePBL_tidal_effic
+    integer(c_int) :: answer_date, orig_PE_calc, mstar_scheme, Use_MLD_iteration, MLD_iteration_guess, MLD_bisection, MLD_iter_bug
+    integer(c_int) :: max_MLD_its, wT_scheme, TKE_diagnostics, has_eos, ePBL_BBL_use_mstar, use_LT, eqdisc, eqdisc_v0, eqdisc_v0h
+    integer(c_int) :: direct_calc, options_diff, pert_epbl, ustar_shelf, tau_mag, SpV_avg
+  end type mom6x_energetic_PBL_params
 
   type, bind(C) :: mom6x_surface_fluxes   !< the members of `forcing` (MOM_forcing_type.F90:80-256) that applyBoundaryFluxesInOut touches: device planes, c_null_ptr where the reference's pointer is not associated
     type(c_ptr) :: sw, lw, latent, sens, evap, lprec, fprec, vprec, lrunoff, frunoff, lrunoff_glc, frunoff_glc, seaice_melt
@@ -475,6 +486,34 @@ module mom6x_c_api
     integer(c_int) function mom6x_diabatic_aux_status(ctx, groundings, negative_h, land_fluxes) bind(C, name="mom6x_diabatic_aux_status")
       import :: c_ptr, c_int, c_long
       type(c_ptr), value :: ctx ; integer(c_long), intent(out) :: groundings, negative_h, land_fluxes
+    end function
+    !> energetic_PBL_init (MOM_energetic_PBL.F90:3729)
+    integer(c_int) function mom6x_energetic_PBL_init(ctx, p) bind(C, name="mom6x_energetic_PBL_init")
+      import :: c_ptr, c_int, mom6x_energetic_PBL_params
+      type(c_ptr), value :: ctx ; type(mom6x_energetic_PBL_params), intent(in) :: p
+    end function
+    !> energetic_PBL (MOM_energetic_PBL.F90:326): the arrays are device pointers, c_null_ptr for what is absent (u, v without
+    !! MKE_to_TKE_effic > 0 and every output after ML_depth; include/mom6x.h)
+    integer(c_int) function mom6x_energetic_PBL(ctx, h, u, v, T, S, dSV_dT, dSV_dS, TKE_forced, ustar, buoy_flux, dt, Kd_int, ML_depth, &
+        Velocity_Scale, Mixing_Length, diag_TKE_wind, diag_TKE_MKE, diag_TKE_conv, diag_TKE_forcing, diag_TKE_mixing, &
+        diag_TKE_mech_decay, diag_TKE_conv_decay, mstar_sfc, ustar_diag, OBL_its) bind(C, name="mom6x_energetic_PBL")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, h, u, v, T, S, dSV_dT, dSV_dS, TKE_forced, ustar, buoy_flux, Kd_int, ML_depth, Velocity_Scale
+      type(c_ptr), value :: Mixing_Length, diag_TKE_wind, diag_TKE_MKE, diag_TKE_conv, diag_TKE_forcing, diag_TKE_mixing
+      type(c_ptr), value :: diag_TKE_mech_decay, diag_TKE_conv_decay, mstar_sfc, ustar_diag, OBL_its
+      real(c_double), value :: dt
+    end function
+    !> energetic_PBL_get_MLD (MOM_energetic_PBL.F90:3707): MLD = scale * ML_depth
+    integer(c_int) function mom6x_energetic_PBL_get_MLD(ctx, ML_depth, MLD, scale) bind(C, name="mom6x_energetic_PBL_get_MLD")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, ML_depth, MLD ; real(c_double), value :: scale
+    end function
+    !> the driver's loop MOM_diabatic_driver.F90:1570-1581 and visc%h_ML = GV%Z_to_H * MLD (:1565)
+    integer(c_int) function mom6x_ePBL_augment_Kd(ctx, Kd_ePBL, Kd_shear, Kv_shear, Kd_heat, Kd_salt, ePBL_is_additive, ePBL_Prandtl, &
+        MLD, h_ML) bind(C, name="mom6x_ePBL_augment_Kd")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, Kd_ePBL, Kd_shear, Kv_shear, Kd_heat, Kd_salt, MLD, h_ML
+      integer(c_int), value :: ePBL_is_additive ; real(c_double), value :: ePBL_Prandtl
     end function
     integer(c_int) function mom6x_thickness_diffuse_init(ctx, p, eos, khth2d) bind(C, name="mom6x_thickness_diffuse_init")
       import :: c_ptr, c_int, mom6x_thickness_diffuse_params

@@ -1229,6 +1229,100 @@ int mom6x_applyBoundaryFluxesInOut(mom6x_ctx *ctx, double dt, const mom6x_surfac
 int mom6x_diabatic_aux_status(mom6x_ctx *ctx, long *groundings, long *negative_h, long *land_fluxes);
 
 /* ------------------------------------------------------------------------- */
+/* MOM_energetic_PBL: energetic_PBL (the ePBL surface boundary layer scheme), between applyBoundaryFluxesInOut and the tridiagonal
+ * solve of diabatic_ALE (src/parameterizations/vertical/MOM_diabatic_driver.F90:1559-1581).                                     */
+enum mom6x_epbl_mstar_scheme { MOM6X_EPBL_MSTAR_CONSTANT = 0, MOM6X_EPBL_MSTAR_OM4 = 2, MOM6X_EPBL_MSTAR_REICHL_H18 = 3 };   /* MOM_energetic_PBL.F90:279-282 */
+enum mom6x_epbl_wT_scheme { MOM6X_EPBL_WT_CUBE_ROOT_TKE = 0, MOM6X_EPBL_WT_REICHL_H18 = 1 };                                 /* :288-290 */
+/* What energetic_PBL_init (src/parameterizations/vertical/MOM_energetic_PBL.F90:3729-4429) leaves in energetic_PBL_CS (:38-276)
+ * for the surface boundary layer, scaled as CS holds it, with the members of GV and US that energetic_PBL and ePBL_column read.
+ * GV%Rho0, H_to_Z, Z_to_H, H_to_RZ, H_subroundoff and dZ_subroundoff are the context's (mom6x_vgrid).  Logicals are ints.  The
+ * members marked "must be 0" are refused with MOM6X_EUNSUPPORTED.                                                              */
+typedef struct mom6x_energetic_PBL_params {
+  double omega;              /* OMEGA [T-1]                                                                                      */
+  double omega_frac;         /* ML_OMEGA_FRAC: absf :662-669                                                                     */
+  double Ekman_scale_coef;   /* EKMAN_SCALE_COEF                                                                                 */
+  double vonKar;             /* VON_KARMAN_CONST                                                                                 */
+  double MKE_to_TKE_effic;   /* MKE_TO_TKE_EFFIC * US%L_to_Z**2: > 0 needs u and v                                               */
+  double TKE_decay;          /* TKE_DECAY (2.5)                                                                                  */
+  double fixed_mstar;        /* MSTAR, EPBL_MSTAR_SCHEME = CONSTANT                                                              */
+  double mstar_cap;          /* MSTAR_CAP (-1: none), OM4                                                                        */
+  double mstar_coef, C_Ek;   /* MSTAR2_COEF1, MSTAR2_COEF2, OM4                                                                  */
+  double RH18_mstar_cn1, RH18_mstar_cn2, RH18_mstar_cn3, RH18_mstar_cs1, RH18_mstar_cs2;   /* REICHL_H18                        */
+  double nstar;              /* NSTAR                                                                                            */
+  double mstar_convect_coef; /* MSTAR_CONV_ADJ                                                                                   */
+  double transLay_scale;     /* EPBL_TRANSITION_SCALE                                                                            */
+  double MLD_tol;            /* EPBL_MLD_TOLERANCE [Z]                                                                           */
+  double min_mix_len;        /* EPBL_MIN_MIX_LEN [Z]                                                                             */
+  double MixLenExponent;     /* MIX_LEN_EXPONENT                                                                                 */
+  double wstar_ustar_coef;   /* WSTAR_USTAR_COEF                                                                                 */
+  double vstar_scale_fac;    /* EPBL_VEL_SCALE_FACTOR                                                                            */
+  double vstar_surf_fac;     /* VSTAR_SURF_FAC                                                                                   */
+  double ustar_min;          /* 2e-4*omega*(Angstrom_Z + dZ_subroundoff) (:4328) [Z T-1]                                         */
+  double g_Earth_Z_T2;       /* GV%g_Earth_Z_T2 [Z T-2]: dPres :1194                                                             */
+  double m_to_Z, T_to_s;     /* US%m_to_Z, US%T_to_s (1): dMLD_min, dMLD_max :1221 and the answers before 20240101               */
+  double ePBL_BBL_effic;     /* EPBL_BBL_EFFIC: must be 0 (ePBL_BBL_column is not on the device)                                 */
+  double ePBL_tidal_effic;   /* EPBL_BBL_TIDAL_EFFIC: must be 0                                                                  */
+  int    answer_date;        /* EPBL_ANSWER_DATE: < 20190101, < 20240101 (A**(1./3.)) or later (cuberoot)                        */
+  int    orig_PE_calc;       /* EPBL_ORIGINAL_PE_CALC (T): find_PE_chg_orig, else find_PE_chg                                    */
+  int    mstar_scheme;       /* enum mom6x_epbl_mstar_scheme                                                                     */
+  int    Use_MLD_iteration;  /* USE_MLD_ITERATION (T)                                                                            */
+  int    MLD_iteration_guess;/* MLD_ITERATION_GUESS (F): the first guess is ML_depth of the call before                          */
+  int    MLD_bisection;      /* EPBL_MLD_BISECTION (F)                                                                           */
+  int    MLD_iter_bug;       /* EPBL_MLD_ITER_BUG                                                                                */
+  int    max_MLD_its;        /* EPBL_MLD_MAX_ITS (20); 1 without USE_MLD_ITERATION (:3999)                                       */
+  int    wT_scheme;          /* enum mom6x_epbl_wT_scheme                                                                        */
+  int    TKE_diagnostics;    /* CS%TKE_diagnostics: the seven diag_TKE_* planes are formed                                       */
+  int    has_eos;            /* associated(tv%eqn_of_state) (:512): what dSV_dT and dSV_dS came from                             */
+  int    ePBL_BBL_use_mstar; /* EPBL_BBL_USE_MSTAR: must be 0                                                                    */
+  int    use_LT;             /* USE_LA_LI2016 | EPBL_LT, Langmuir turbulence (needs MOM_wave_interface): must be 0               */
+  int    eqdisc, eqdisc_v0, eqdisc_v0h;   /* EPBL_EQD_DIFFUSIVITY_SHAPE, _VELOCITY, _VELOCITY_H: must be 0                      */
+  int    direct_calc;        /* DIRECT_EPBL_MIXING_CALC: must be 0                                                               */
+  int    options_diff;       /* EPBL_OPTIONS_DIFF: must be 0                                                                     */
+  int    pert_epbl;          /* stoch_CS%pert_epbl, stochastic perturbations: must be 0                                          */
+  int    ustar_shelf;        /* fluxes%ustar_shelf and frac_shelf_h associated (:656): must be 0                                 */
+  int    tau_mag;            /* fluxes%tau_mag in place of fluxes%ustar (:635-643): must be 0                                    */
+  int    SpV_avg;            /* tv%SpV_avg allocated, non-Boussinesq: must be 0                                                  */
+} mom6x_energetic_PBL_params;
+/* energetic_PBL_init :3729: checks the members, keeps them and allocates the work array of hb_hs (nk + 1 levels).
+ * A refused or invalid call leaves no module behind, also where an earlier call had succeeded.
+ * MOM6X_EUNSUPPORTED, naming the setting: every "must be 0" member, a non-Boussinesq context, and TKE_diagnostics together with
+ * MKE_to_TKE_effic > 0 (that instantiation of the kernel does not fit a lane's registers).  MOM6X_EINVAL: an unknown scheme,
+ * max_MLD_its < 1.                                                                                                     */
+int mom6x_energetic_PBL_init(mom6x_ctx *ctx, const mom6x_energetic_PBL_params *p);
+/* energetic_PBL(h_3d, u_3d, v_3d, tv, fluxes, visc, dt, Kd_int, G, GV, US, CS, stoch_CS, dSV_dT, dSV_dS, TKE_forced, buoy_flux)
+ * :326-884 with ePBL_column :890-1950, find_mstar :3519-3613, find_PE_chg_orig :3365-3516, find_PE_chg :3072-3213, cuberoot
+ * (src/framework/MOM_intrinsic_functions.F90:48-114) and the Boussinesq thickness_to_dz, in one launch on the context's stream (a second,
+ * small one with diag_TKE_* planes): no allocation, no host synchronisation, no halo exchange.  One lane per column of the computational domain; the lanes of a
+ * wavefront leave the mixed-layer-depth iteration together, after the slowest of them.
+ * h, T, S (tv%T, tv%S), dSV_dT, dSV_dS, TKE_forced: 3-D, only read.  ustar (fluxes%ustar), buoy_flux: planes, only read.
+ * u, v: the C-GRID velocities; the kernel forms u_h, v_h with the no-mixing arm of find_uv_at_h (MOM_diabatic_aux.F90:546-571,
+ * :606-611).  Read only with MKE_to_TKE_effic > 0, NULL otherwise.
+ * Kd_int: nk + 1 levels, written on the computational domain, 0 in land columns (:819-823).
+ * ML_depth: CS%ML_depth [Z], the caller's resident plane: read with MLD_iteration_guess (:673), written on the computational
+ * domain always (0 over land).
+ * Nullable outputs, on the computational domain (0 over land): Velocity_Scale, Mixing_Length (nk + 1 levels); the seven
+ * diag_TKE_* planes (with TKE_diagnostics only; diag_TKE_MKE is then always 0, since TKE_diagnostics excludes MKE conversion); mstar_sfc; ustar_diag (diag_ustar :645: fluxes%ustar before ustar_min); OBL_its
+ * (eCD%OBL_its as a real, the per-column value behind CS%sum_its).
+ * MOM6X_EINVAL: a required array missing, MKE_to_TKE_effic > 0 without u and v, no equation of state (has_eos = 0), a diag_TKE_*
+ * plane without TKE_diagnostics, dt <= 0.
+ * Not carried: bottom-boundary-layer ePBL (ePBL_BBL_column), Langmuir turbulence, the equation-discovery switches,
+ * DIRECT_EPBL_MIXING_CALC, EPBL_OPTIONS_DIFF, stochastic perturbations, ustar_shelf, tau_mag, non-Boussinesq mode.             */
+int mom6x_energetic_PBL(mom6x_ctx *ctx, const double *h, const double *u, const double *v, const double *T, const double *S,
+                        const double *dSV_dT, const double *dSV_dS, const double *TKE_forced, const double *ustar,
+                        const double *buoy_flux, double dt, double *Kd_int, double *ML_depth, double *Velocity_Scale,
+                        double *Mixing_Length, double *diag_TKE_wind, double *diag_TKE_MKE, double *diag_TKE_conv,
+                        double *diag_TKE_forcing, double *diag_TKE_mixing, double *diag_TKE_mech_decay, double *diag_TKE_conv_decay,
+                        double *mstar_sfc, double *ustar_diag, double *OBL_its);
+/* energetic_PBL_get_MLD(CS, MLD, G, US, m_to_MLD_units) :3707: MLD = scale * ML_depth on the computational domain.            */
+int mom6x_energetic_PBL_get_MLD(mom6x_ctx *ctx, const double *ML_depth, double *MLD, double scale);
+/* The driver's loop MOM_diabatic_driver.F90:1570-1581 over levels 2..nk of the computational domain: with ePBL_is_additive
+ * Kv_shear += ePBL_Prandtl*Kd_ePBL and Kd_add = Kd_ePBL, otherwise Kv_shear = max(Kv_shear, ePBL_Prandtl*Kd_ePBL) and Kd_add =
+ * max(Kd_ePBL - Kd_shear, 0.) (Kd_shear is read in this arm only); Kd_heat += Kd_add, Kd_salt += Kd_add.  MLD and h_ML, both
+ * or neither: visc%h_ML = GV%Z_to_H * MLD (:1565, the Boussinesq convert_MLD_to_ML_thickness).                                  */
+int mom6x_ePBL_augment_Kd(mom6x_ctx *ctx, const double *Kd_ePBL, const double *Kd_shear, double *Kv_shear, double *Kd_heat,
+                          double *Kd_salt, int ePBL_is_additive, double ePBL_Prandtl, const double *MLD, double *h_ML);
+
+/* ------------------------------------------------------------------------- */
 /* MOM_dynamics_split_RK2                                                    */
 
 /* Host callbacks for the callees of step_MOM_dyn_split_RK2 that are NOT on the ported hot path

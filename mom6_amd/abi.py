@@ -503,6 +503,56 @@ class SurfaceFluxes(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in SURFACE_FLUXES_NAMES]
 
 
+EPBL_MSTAR_CONSTANT, EPBL_MSTAR_OM4, EPBL_MSTAR_REICHL_H18 = 0, 2, 3   # enum mom6x_epbl_mstar_scheme (MOM_energetic_PBL.F90:279-282)
+EPBL_WT_CUBE_ROOT_TKE, EPBL_WT_REICHL_H18 = 0, 1                     # enum mom6x_epbl_wT_scheme (:288-290)
+
+
+class EnergeticPBLParams(C.Structure):
+    """mom6x_energetic_PBL_params; what energetic_PBL_init (MOM_energetic_PBL.F90:3729-4429) leaves in energetic_PBL_CS (:38-276)
+    for the surface boundary layer, with the members of GV and US that energetic_PBL and ePBL_column read."""
+    _fields_ = ([(n, C.c_double) for n in (
+        "omega", "omega_frac", "Ekman_scale_coef", "vonKar", "MKE_to_TKE_effic", "TKE_decay", "fixed_mstar", "mstar_cap", "mstar_coef",
+        "C_Ek", "RH18_mstar_cn1", "RH18_mstar_cn2", "RH18_mstar_cn3", "RH18_mstar_cs1", "RH18_mstar_cs2", "nstar", "mstar_convect_coef",
+        "transLay_scale", "MLD_tol", "min_mix_len", "MixLenExponent", "wstar_ustar_coef", "vstar_scale_fac", "vstar_surf_fac",
+        "ustar_min", "g_Earth_Z_T2", "m_to_Z", "T_to_s", "ePBL_BBL_effic", "ePBL_tidal_effic")] +
+                [(n, C.c_int) for n in (
+                    "answer_date", "orig_PE_calc", "mstar_scheme", "Use_MLD_iteration", "MLD_iteration_guess", "MLD_bisection",
+                    "MLD_iter_bug", "max_MLD_its", "wT_scheme", "TKE_diagnostics", "has_eos", "ePBL_BBL_use_mstar", "use_LT", "eqdisc",
+                    "eqdisc_v0", "eqdisc_v0h", "direct_calc", "options_diff", "pert_epbl", "ustar_shelf", "tau_mag", "SpV_avg")])
+
+
+ENERGETIC_PBL_MUST_BE_0 = ("ePBL_BBL_effic", "ePBL_tidal_effic", "ePBL_BBL_use_mstar", "use_LT", "eqdisc", "eqdisc_v0", "eqdisc_v0h",
+                           "direct_calc", "options_diff", "pert_epbl", "ustar_shelf", "tau_mag", "SpV_avg")
+
+
+def energetic_PBL_params_default(GV=None, **kw):
+    """energetic_PBL_init (MOM_energetic_PBL.F90:3767-4328) defaults, Boussinesq and unscaled: OMEGA = 7.2921e-5, ML_OMEGA_FRAC = 0,
+    the newest answers, EPBL_ORIGINAL_PE_CALC = True, TKE_DECAY = 2.5, EPBL_MSTAR_SCHEME = CONSTANT with MSTAR = 1.2, NSTAR = 0.2,
+    USE_MLD_ITERATION with EPBL_TRANSITION_SCALE = 0.1, a tolerance of 1 m, at most 20 iterations and EPBL_MLD_ITER_BUG as
+    ENABLE_BUGS_BY_DEFAULT has it, MIX_LEN_EXPONENT = 2, EPBL_VEL_SCALE_SCHEME = CUBE_ROOT_TKE; ustar_min as :4328.  A given
+    Use_MLD_iteration = 0 sets max_MLD_its = 1 (:3999)."""
+    GV = GV if GV is not None else vgrid_default()
+    p = EnergeticPBLParams()
+    p.omega = 7.2921e-5; p.omega_frac = 0.0; p.Ekman_scale_coef = 1.0; p.vonKar = 0.41; p.MKE_to_TKE_effic = 0.0; p.TKE_decay = 2.5
+    p.fixed_mstar = 1.2; p.mstar_cap = -1.0; p.mstar_coef = 0.3; p.C_Ek = 0.085
+    p.RH18_mstar_cn1 = 0.275; p.RH18_mstar_cn2 = 8.0; p.RH18_mstar_cn3 = -5.0; p.RH18_mstar_cs1 = 0.2; p.RH18_mstar_cs2 = 0.4
+    p.nstar = 0.2; p.mstar_convect_coef = 0.0; p.transLay_scale = 0.1; p.MLD_tol = 1.0; p.min_mix_len = 0.0; p.MixLenExponent = 2.0
+    p.wstar_ustar_coef = 1.0; p.vstar_scale_fac = 1.0; p.vstar_surf_fac = 1.2
+    p.g_Earth_Z_T2 = GV.g_Earth; p.m_to_Z = 1.0; p.T_to_s = 1.0
+    p.answer_date = 99991231; p.orig_PE_calc = 1; p.mstar_scheme = EPBL_MSTAR_CONSTANT; p.Use_MLD_iteration = 1
+    p.MLD_iteration_guess = 0; p.MLD_bisection = 0; p.MLD_iter_bug = 1; p.max_MLD_its = 20; p.wT_scheme = EPBL_WT_CUBE_ROOT_TKE
+    p.TKE_diagnostics = 0; p.has_eos = 1
+    for n in ENERGETIC_PBL_MUST_BE_0:
+        setattr(p, n, 0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    if "ustar_min" not in kw:                      # Angstrom_Z = H_to_Z * Angstrom_H
+        p.ustar_min = 2e-4 * p.omega * (GV.H_to_Z * GV.Angstrom_H + GV.dZ_subroundoff)
+    if not p.Use_MLD_iteration:
+        p.max_MLD_its = 1
+    return p
+
+
 class HorViscParams(C.Structure):
     """mom6x_hor_visc_params; hor_visc_CS (MOM_hor_visc.F90:36-259)."""
     _fields_ = [("Laplacian", C.c_int), ("biharmonic", C.c_int), ("Kh", C.c_double), ("Kh_bg_min", C.c_double),
@@ -755,6 +805,12 @@ def load_library(path=None):
         lib.mom6x_applyBoundaryFluxesInOut.argtypes = ([vp, C.c_double, C.POINTER(SurfaceFluxes), C.c_int] + [vp] * 6 +
                                                        [C.c_int, C.c_double, C.c_double] + [vp] * 8)
         lib.mom6x_diabatic_aux_status.argtypes = [vp] + [C.POINTER(C.c_long)] * 3
+    if hasattr(lib, "mom6x_energetic_PBL"):       # (26 arguments, stated like the MEKE step's)
+        vp = C.c_void_p
+        lib.mom6x_energetic_PBL_init.argtypes = [vp, C.POINTER(EnergeticPBLParams)]
+        lib.mom6x_energetic_PBL.argtypes = [vp] * 11 + [C.c_double] + [vp] * 14
+        lib.mom6x_energetic_PBL_get_MLD.argtypes = [vp, vp, vp, C.c_double]
+        lib.mom6x_ePBL_augment_Kd.argtypes = [vp] * 6 + [C.c_int, C.c_double, vp, vp]
     if path is None:
         _lib = lib
     return lib

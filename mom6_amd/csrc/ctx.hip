@@ -177,6 +177,7 @@ extern "C" int mom6x_struct_size(int which) {
     case 25: return (int)sizeof(mom6x_set_diffusivity_params);
     case 27: return (int)sizeof(mom6x_diabatic_aux_params);
     case 28: return (int)sizeof(mom6x_surface_fluxes);
+    case 30: return (int)sizeof(mom6x_energetic_PBL_params);
     default: return -1;
   }
 }
@@ -256,6 +257,7 @@ extern "C" int mom6x_ctx_destroy(mom6x_ctx *c) {
   MEKE_free(c);
   set_diffusivity_free(c);
   diabatic_aux_free(c);
+  energetic_PBL_free(c);
   comm_free(c);
   for (int m = 0; m < MOM6X_NSCR; m++) (void)hipFree(c->scr[m]);
   (void)hipFree(c->G); (void)hipFree(c->flag);

@@ -38,6 +38,40 @@ __device__ __forceinline__ double fmax1(double a, double b) { return (b > a) ? b
 __device__ __forceinline__ double fmin1(double a, double b) { return (b < a) ? b : a; }
 __device__ __forceinline__ double dsign(double a, double b) { return (b >= 0.0) ? fabs(a) : -fabs(a); }
 
+// cuberoot of MOM_intrinsic_functions.F90:48-114 with rescale_cbrt (:118-159) and descale (:163-184): the argument's fraction is moved
+// into [0.125, 1) by an integer power of 8, two Halley steps on a fraction num / den, one division, one Newton step, and the exponent
+// put back.  Pure arithmetic in the reference's order: bit for bit, and exact under a scaling of x by 8**n.
+__device__ __forceinline__ double dev_cuberoot(double x) {
+  if ((x >= 0.0) == (x <= 0.0)) return x;   // 0 or NaN
+  long long xb = __double_as_longlong(x);
+  const long long s_a = (xb >> 63) & 1ll;
+  const long long e_a = ((xb >> 52) & 0x7FFll) - 1023ll;
+  long long e_mod = e_a % 3ll; if (e_mod < 0) e_mod += 3ll;   // modulo(): floor
+  const long long e_r = (e_a - e_mod) / 3ll + 1ll;
+  xb = (xb & 0x000FFFFFFFFFFFFFll) | ((e_mod - 3ll + 1023ll) << 52);
+  const double asx = __longlong_as_double(xb);
+  const double r0 = 0.707106;
+  const double r0_3 = r0 * r0 * r0;
+  double num = r0 * (r0_3 + 2.0 * asx);
+  double den = 2.0 * r0_3 + asx;
+#pragma unroll
+  for (int itt = 0; itt < 2; ++itt) {
+    const double num_prev = num, den_prev = den;
+    const double np_3 = num_prev * num_prev * num_prev;
+    const double dp_3 = den_prev * den_prev * den_prev;
+    num = num_prev * (np_3 + 2.0 * asx * dp_3);
+    den = den_prev * (2.0 * np_3 + asx * dp_3);
+  }
+  double root_asx = num / den;
+  const double ra_3 = root_asx * root_asx * root_asx;
+  root_asx = root_asx - (ra_3 - asx) / (3.0 * (root_asx * root_asx));
+  long long rb = __double_as_longlong(root_asx);
+  const long long e = (rb >> 52) & 0x7FFll;
+  rb = (rb & ~(0x7FFll << 52)) | (((e_r + e) & 0x7FFll) << 52);
+  rb = (rb & 0x7FFFFFFFFFFFFFFFll) | (s_a << 63);
+  return __longlong_as_double(rb);
+}
+
 // a bit of the context's device-side error flag (mom6x_ctx::flag) with a message of its own in mom6x_ctx_sync: MEKE_equilibrium left a
 // column at one of the reference's two `stop`s (MOM_MEKE.F90:1095 the bracket, :1133 more than 200 bisections)
 #define MOM6X_FLAG_MEKE_EQUILIBRIUM 64
@@ -68,7 +102,7 @@ enum Scr { SCR_q = 0, SCR_KE, SCR_absv, SCR_e, SCR_c1, SCR_t0, SCR_t1, SCR_t2, S
 // the module's parameter copy, its caller-owned pointers, the device arrays it allocates and an `init` flag where a setter may come
 // before the init call.  The context only owns them: a typed pointer each, null until the module is first touched.
 struct ContState; struct BTState; struct CorState; struct PgfState; struct VvState; struct HvState; struct RK2State; struct AleState;
-struct TAState; struct DiagState; struct SvState; struct TdState; struct ThdState; struct VmState; struct MleState; struct MekeState; struct SdState; struct DaState;
+struct TAState; struct DiagState; struct SvState; struct TdState; struct ThdState; struct VmState; struct MleState; struct MekeState; struct SdState; struct DaState; struct EpblState;
 struct Comm;   // halo.hip: tile layout + RCCL communicator (null: single tile, wrap only)
 
 // u_bc_accel = (CAu + PFu) + diffu of the RK2 predictor (RK2.F90:565-572) formed by the pressure-force kernel that has just made
@@ -99,7 +133,7 @@ struct mom6x_ctx {
   long long n_exchanges, n_exchange_bytes;
   // the modules' states
   ContState *cont; BTState *bts; CorState *cor; PgfState *pgf; VvState *vv; HvState *hv; RK2State *rk2; AleState *ale;
-  TAState *ta; DiagState *diag; SvState *sv; TdState *td; ThdState *thd; VmState *vm; MleState *mle; MekeState *meke; SdState *sd; DaState *da; Comm *comm;
+  TAState *ta; DiagState *diag; SvState *sv; TdState *td; ThdState *thd; VmState *vm; MleState *mle; MekeState *meke; SdState *sd; DaState *da; EpblState *epbl; Comm *comm;
 };
 // Each frees every device pointer its struct owns, deletes the struct and nulls the context's pointer (a null pointer: nothing to
 // do).  mom6x_ctx_destroy calls them all; apart from them it frees only what mom6x_ctx_create allocated.
@@ -108,7 +142,8 @@ void PressureForce_free(mom6x_ctx *c);  void vertvisc_free(mom6x_ctx *c);       
 void rk2_state_free(mom6x_ctx *c);   void ALE_free(mom6x_ctx *c);               void ta_state_free(mom6x_ctx *c);
 void diag_sums_free(mom6x_ctx *c);   void set_visc_free(mom6x_ctx *c);          void thickness_diffuse_free(mom6x_ctx *c);
 void tracer_hor_diff_free(mom6x_ctx *c);  void varmix_free(mom6x_ctx *c);       void mixedlayer_restrat_free(mom6x_ctx *c);
-void MEKE_free(mom6x_ctx *c);  void set_diffusivity_free(mom6x_ctx *c);  void diabatic_aux_free(mom6x_ctx *c);  void comm_free(mom6x_ctx *c);
+void MEKE_free(mom6x_ctx *c);  void set_diffusivity_free(mom6x_ctx *c);  void diabatic_aux_free(mom6x_ctx *c);  void energetic_PBL_free(mom6x_ctx *c);
+void comm_free(mom6x_ctx *c);
 // The widths of one group pass (create_group_pass(..., halo=)).  w: rows / columns of halo filled for its 3-D fields (0: the context's
 // halo); wf[0 .. nwf - 1]: the widths of single 3-D fields (0 entries and fields beyond nwf: w).  The default is what every pass but the
 // RK2 step's own asks for; the step sends the reference's own 2-3 rows instead of NIHALO = 4 (RK2.F90:484-495).

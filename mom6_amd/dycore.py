@@ -466,6 +466,35 @@ class Dycore:
         check(self.lib, self.lib.mom6x_diabatic_aux_status(self.ctx, *[C.byref(v) for v in n]))
         return tuple(int(v.value) for v in n)
 
+    # -- MOM_energetic_PBL ---------------------------------------------------------------------
+    def energetic_PBL_init(self, params):
+        """energetic_PBL_init (MOM_energetic_PBL.F90:3729): abi.energetic_PBL_params_default(...)."""
+        self.energetic_PBL_params = params
+        check(self.lib, self.lib.mom6x_energetic_PBL_init(self.ctx, C.byref(params)))
+
+    ENERGETIC_PBL_OUT = ("Velocity_Scale", "Mixing_Length", "diag_TKE_wind", "diag_TKE_MKE", "diag_TKE_conv", "diag_TKE_forcing",
+                         "diag_TKE_mixing", "diag_TKE_mech_decay", "diag_TKE_conv_decay", "mstar_sfc", "ustar_diag", "OBL_its")
+
+    def energetic_PBL(self, h, T, S, dSV_dT, dSV_dS, TKE_forced, ustar, buoy_flux, dt, Kd_int, ML_depth, u=None, v=None, **out):
+        """energetic_PBL (MOM_energetic_PBL.F90:326): Kd_int (nk + 1 levels) and ML_depth (CS%ML_depth, the caller's resident
+        plane) from device arrays; u, v: the C-grid velocities, with MKE_to_TKE_effic > 0 only; as keyword arguments the
+        nullable outputs ENERGETIC_PBL_OUT."""
+        assert set(out) <= set(self.ENERGETIC_PBL_OUT), sorted(set(out) - set(self.ENERGETIC_PBL_OUT))
+        check(self.lib, self.lib.mom6x_energetic_PBL(
+            self.ctx, _ptr(h), _ptr(u), _ptr(v), _ptr(T), _ptr(S), _ptr(dSV_dT), _ptr(dSV_dS), _ptr(TKE_forced), _ptr(ustar),
+            _ptr(buoy_flux), C.c_double(dt), _ptr(Kd_int), _ptr(ML_depth), *[_ptr(out.get(n)) for n in self.ENERGETIC_PBL_OUT]))
+
+    def energetic_PBL_get_MLD(self, ML_depth, MLD, scale=1.0):
+        """energetic_PBL_get_MLD (:3707): MLD = scale * ML_depth on the computational domain."""
+        check(self.lib, self.lib.mom6x_energetic_PBL_get_MLD(self.ctx, _ptr(ML_depth), _ptr(MLD), C.c_double(scale)))
+
+    def ePBL_augment_Kd(self, Kd_ePBL, Kv_shear, Kd_heat, Kd_salt, Kd_shear=None, ePBL_is_additive=True, ePBL_Prandtl=1.0, MLD=None,
+                        h_ML=None):
+        """The driver's loop MOM_diabatic_driver.F90:1570-1581 and, with MLD and h_ML, visc%h_ML = GV%Z_to_H * MLD (:1565)."""
+        check(self.lib, self.lib.mom6x_ePBL_augment_Kd(self.ctx, _ptr(Kd_ePBL), _ptr(Kd_shear), _ptr(Kv_shear), _ptr(Kd_heat),
+                                                       _ptr(Kd_salt), C.c_int(1 if ePBL_is_additive else 0), C.c_double(ePBL_Prandtl),
+                                                       _ptr(MLD), _ptr(h_ML)))
+
     # -- MOM_MEKE ------------------------------------------------------------------------------
     def MEKE_init(self, params, dF_dx=None, dF_dy=None):
         """MEKE_init (MOM_MEKE.F90:1329) for the EKE_SOURCE = prog arm; dF_dx, dF_dy: G%dF_dx, G%dF_dy, HOST planes of the tile

@@ -1,0 +1,961 @@
+"""energetic_PBL (src/parameterizations/vertical/MOM_energetic_PBL.F90:326-884) restated in python, one column at a time and in
+the reference's own loop order, with ePBL_column (:890-1950), find_mstar (:3519-3613), find_PE_chg_orig (:3365-3516), find_PE_chg
+(:3072-3213), cuberoot (src/framework/MOM_intrinsic_functions.F90:48-184), the Boussinesq thickness_to_dz, the no-mixing arm of
+find_uv_at_h (MOM_diabatic_aux.F90:546-571, :606-611) and the driver's loop over Kd_ePBL (MOM_diabatic_driver.F90:1570-1581).
+The checker of mom6_amd/csrc/energetic_PBL.hip; never the product.
+
+Arithmetic is python's float (IEEE double, no fused multiply-add); sqrt is math.sqrt, correctly rounded.  exp, log and pow come
+from the `math=` argument (class Libm), which counts the calls of each: a case of CASES_EXACT makes none.
+
+Integer powers are written out as products, in the order the kernel uses too:
+  x**2 = x*x;  x**3 = (x*x)*x;  UStar**5 = ((u*u)*(u*u))*u.
+MAX(a, b) and MIN(a, b) return the FIRST argument on a tie (fmax1 / fmin1 of mom6x_dev.h): MAX(0., -0.) is +0.
+
+What the reference holds in arrays over k but uses only at k, k-1 and k-2 is held in scalars here as in the kernel (hp_a, the
+four dX_to_dY_a, dTe, dSe | Te, Se, Kddt_h(K-1), pres_Z); hb_hs keeps its bottom-up sum (:1206-1211) in a list."""
+import math as _math
+import struct
+
+import numpy as np
+
+from mom6_amd import abi
+
+G = abi.G
+
+BRANCHES = ("land", "ustar_min", "omega_ge1", "omega_frac", "omega_0", "first_guess_stored", "first_guess_half",
+            "mstar_const", "mstar_om4_new", "mstar_om4_old", "mstar_rh18_new", "mstar_rh18_old", "mstar_cap", "mstar_N_pos",
+            "conv_red_new", "conv_red_new_zero", "conv_red_old", "mech_old_fixed",
+            "forcing1_neg", "forcing1_neg_clip", "forcing1_pos",
+            "shape_one", "shape_quadratic", "shape_pow", "shape_guess_le0", "shape_clip0",
+            "decay_exp", "conv_add", "nstar_fc", "sw_deplete", "sw_reduce",
+            "stable_exhausted", "tke_here_le0", "vstar_croot", "vstar_rh18", "vstar_croot_old", "vstar_rh18_old", "kd_no_iter",
+            "min_mix_len", "mke",
+            "unstable_max_le0", "unstable_max_le0_tke0", "unstable_max_le0_fallback", "unstable_max_le0_keep", "unstable_nonmono",
+            "unstable_by_slope", "enough", "tot_zero", "newton", "newt_step", "falsepos_step", "newton_maxitt",
+            "colht_neg", "disconnect", "connected_deepen", "nk1",
+            "converged", "too_shallow", "too_deep", "bug_shallow", "bug_converged", "bug_deep", "max_its",
+            "bisection", "false_position", "mld_found", "bisect_fallback")
+
+
+class Libm:
+    """exp, log and pow with call counts.  ulp: every result is moved that many units in the last place (a negative number: down);
+    pattern: a numpy Generator, then each result is moved by +ulp or -ulp at random."""
+    def __init__(self, ulp=0, rng=None):
+        self.counts = dict(exp=0, log=0, pow=0)
+        self.ulp = ulp
+        self.rng = rng
+
+    def _move(self, y):
+        if not self.ulp or y == 0.0 or y != y or y in (_math.inf, -_math.inf):
+            return y
+        n = self.ulp
+        if self.rng is not None:
+            n = n if self.rng.integers(0, 2) else -n
+        to = _math.inf if n > 0 else -_math.inf
+        for _ in range(abs(n)):
+            y = _math.nextafter(y, to)
+        return y
+
+    def exp(self, x):
+        self.counts["exp"] += 1
+        return self._move(_math.exp(x))
+
+    def log(self, x):
+        self.counts["log"] += 1
+        return self._move(_math.log(x))
+
+    def pow(self, x, y):
+        self.counts["pow"] += 1
+        return self._move(_math.pow(x, y))
+
+
+def fmax1(a, b):
+    return b if b > a else a
+
+
+def fmin1(a, b):
+    return b if b < a else a
+
+
+def cuberoot(x):
+    """MOM_intrinsic_functions.F90:48-114 with rescale_cbrt :118-159 and descale :163-184."""
+    if (x >= 0.0) == (x <= 0.0):
+        return x
+    xb = struct.unpack("<q", struct.pack("<d", x))[0]
+    s_a = (xb >> 63) & 1
+    e_a = ((xb >> 52) & 0x7FF) - 1023
+    e_mod = e_a % 3                        # modulo(): floor
+    e_div = (e_a - e_mod) // 3
+    e_r = e_div + 1
+    e_x = e_mod - 3
+    xb = (xb & ((1 << 52) - 1)) | ((e_x + 1023) << 52)    # mvbits of 12 bits: the sign bit is cleared
+    asx = struct.unpack("<d", struct.pack("<q", xb))[0]
+    r0 = 0.707106
+    r0_3 = r0 * r0 * r0
+    num = r0 * (r0_3 + 2.0 * asx)
+    den = 2.0 * r0_3 + asx
+    for _ in range(2):
+        num_prev = num; den_prev = den
+        np_3 = num_prev * num_prev * num_prev
+        dp_3 = den_prev * den_prev * den_prev
+        num = num_prev * (np_3 + 2.0 * asx * dp_3)
+        den = den_prev * (2.0 * np_3 + asx * dp_3)
+    root_asx = num / den
+    ra_3 = root_asx * root_asx * root_asx
+    root_asx = root_asx - (ra_3 - asx) / (3.0 * (root_asx * root_asx))
+    rb = struct.unpack("<q", struct.pack("<d", root_asx))[0]
+    e = (rb >> 52) & 0x7FF
+    rb = (rb & ~(0x7FF << 52)) | (((e_r + e) & 0x7FF) << 52)
+    rb = (rb & ((1 << 63) - 1)) | (s_a << 63)
+    if rb >= (1 << 63):
+        rb -= 1 << 64
+    return struct.unpack("<d", struct.pack("<q", rb))[0]
+
+
+def find_mstar(CS, B, UStar, BLD, absf, m, br):
+    """find_mstar :3519-3613 without Langmuir turbulence, the surface scheme."""
+    T_to_s = CS.T_to_s
+    old = CS.answer_date < 20190101
+    u2 = UStar * UStar
+    u3 = u2 * UStar
+    if CS.mstar_scheme == abi.EPBL_MSTAR_CONSTANT:
+        br["mstar_const"] += 1
+        mstar = CS.fixed_mstar
+    elif CS.mstar_scheme == abi.EPBL_MSTAR_OM4:
+        if old:
+            br["mstar_om4_old"] += 1
+            mstar_S = CS.mstar_coef * _math.sqrt(fmax1(0.0, B) / u2 / (absf + 1.e-10 * T_to_s))
+            mstar_N = CS.C_Ek * m.log(fmax1(1., UStar / (absf + 1.e-10 * T_to_s) / BLD))
+        else:
+            br["mstar_om4_new"] += 1
+            mstar_S = CS.mstar_coef * _math.sqrt(fmax1(0.0, B) / (u2 * fmax1(absf, 1.e-20 * T_to_s)))
+            mstar_N = 0.0
+            if UStar > absf * BLD:
+                br["mstar_N_pos"] += 1
+                mstar_N = CS.C_Ek * m.log(UStar / (absf * BLD))
+        mstar = fmax1(mstar_S, fmin1(1.25, mstar_N))
+        if CS.mstar_cap > 0.0:
+            br["mstar_cap"] += 1
+            mstar = fmin1(CS.mstar_cap, mstar)
+    else:
+        if old:
+            br["mstar_rh18_old"] += 1
+            mstar_N = CS.RH18_mstar_cn1 * (1.0 - 1.0 / (1. + CS.RH18_mstar_cn2 * m.exp(CS.RH18_mstar_cn3 * BLD * absf / UStar)))
+        else:
+            br["mstar_rh18_new"] += 1
+            MSN_term = CS.RH18_mstar_cn2 * m.exp(CS.RH18_mstar_cn3 * BLD * absf / UStar)
+            mstar_N = (CS.RH18_mstar_cn1 * MSN_term) / (1. + MSN_term)
+        mb = fmax1(0.0, B)
+        u5 = (u2 * u2) * UStar
+        mstar_S = CS.RH18_mstar_cs1 * m.pow((mb * mb) * BLD / (u5 * fmax1(absf, 1.e-20 * T_to_s)), CS.RH18_mstar_cs2)
+        mstar = mstar_N + mstar_S
+    if old:
+        br["conv_red_old"] += 1
+        eps = 1.e-10 * ((T_to_s * T_to_s) * T_to_s) * (CS.m_to_Z * CS.m_to_Z)
+        mstar_Conv_Red = 1. - CS.mstar_convect_coef * (-fmin1(0.0, B) + eps) / ((-fmin1(0.0, B) + eps) + 2.0 * mstar * u3 / BLD)
+    else:
+        MSCR_term1 = -(BLD * fmin1(0.0, B))
+        MSCR_term2 = 2.0 * mstar * u3
+        if abs(MSCR_term2) > 0.0:
+            br["conv_red_new"] += 1
+            mstar_Conv_Red = ((1. - CS.mstar_convect_coef) * MSCR_term1 + MSCR_term2) / (MSCR_term1 + MSCR_term2)
+        else:
+            br["conv_red_new_zero"] += 1
+            mstar_Conv_Red = 1. - CS.mstar_convect_coef
+    return mstar * mstar_Conv_Red
+
+
+def find_PE_chg_orig(Kddt_h, h_k, b_den_1, dTe_term, dSe_term, dT_km1_t2, dS_km1_t2, dT_to_dPE_k, dS_to_dPE_k, dT_to_dPEa, dS_to_dPEa,
+                     pres_Z, dT_to_dColHt_k, dS_to_dColHt_k, dT_to_dColHta, dS_to_dColHta, br=None):
+    """find_PE_chg_orig :3365-3516: (PE_chg, dPEc_dKd, dPE_max, dPEc_dKd_0), every optional output formed."""
+    b1 = 1.0 / (b_den_1 + Kddt_h)
+    b1Kd = Kddt_h * b1
+    I_Kr_denom = 1.0 / (h_k * b_den_1 + (b_den_1 + h_k) * Kddt_h)
+    dT_k = (Kddt_h * I_Kr_denom) * dTe_term
+    dS_k = (Kddt_h * I_Kr_denom) * dSe_term
+    dT_km1 = b1Kd * (dT_k + dT_km1_t2)
+    dS_km1 = b1Kd * (dS_k + dS_km1_t2)
+    PE_chg = (dT_to_dPE_k * dT_k + dT_to_dPEa * dT_km1) + (dS_to_dPE_k * dS_k + dS_to_dPEa * dS_km1)
+    ColHt_chg = (dT_to_dColHt_k * dT_k + dT_to_dColHta * dT_km1) + (dS_to_dColHt_k * dS_k + dS_to_dColHta * dS_km1)
+    if ColHt_chg < 0.0:
+        if br is not None:
+            br["colht_neg"] += 1
+        PE_chg = PE_chg - pres_Z * ColHt_chg
+    dKr_dKd = (h_k * b_den_1) * (I_Kr_denom * I_Kr_denom)
+    ddT_k_dKd = dKr_dKd * dTe_term
+    ddS_k_dKd = dKr_dKd * dSe_term
+    ddT_km1_dKd = ((b1 * b1) * b_den_1) * (dT_k + dT_km1_t2) + b1Kd * ddT_k_dKd
+    ddS_km1_dKd = ((b1 * b1) * b_den_1) * (dS_k + dS_km1_t2) + b1Kd * ddS_k_dKd
+    dPEc_dKd = (dT_to_dPE_k * ddT_k_dKd + dT_to_dPEa * ddT_km1_dKd) + (dS_to_dPE_k * ddS_k_dKd + dS_to_dPEa * ddS_km1_dKd)
+    dColHt_dKd = (dT_to_dColHt_k * ddT_k_dKd + dT_to_dColHta * ddT_km1_dKd) + (dS_to_dColHt_k * ddS_k_dKd + dS_to_dColHta * ddS_km1_dKd)
+    if dColHt_dKd < 0.0:
+        dPEc_dKd = dPEc_dKd - pres_Z * dColHt_dKd
+    dPE_max = (dT_to_dPEa * dT_km1_t2 + dS_to_dPEa * dS_km1_t2) + \
+        ((dT_to_dPE_k + dT_to_dPEa) * dTe_term + (dS_to_dPE_k + dS_to_dPEa) * dSe_term) / (b_den_1 + h_k)
+    dColHt_max = (dT_to_dColHta * dT_km1_t2 + dS_to_dColHta * dS_km1_t2) + \
+        ((dT_to_dColHt_k + dT_to_dColHta) * dTe_term + (dS_to_dColHt_k + dS_to_dColHta) * dSe_term) / (b_den_1 + h_k)
+    if dColHt_max < 0.0:
+        dPE_max = dPE_max - pres_Z * dColHt_max
+    dPEc_dKd_0 = (dT_to_dPEa * dT_km1_t2 + dS_to_dPEa * dS_km1_t2) / (b_den_1) + \
+        (dT_to_dPE_k * dTe_term + dS_to_dPE_k * dSe_term) / (h_k * b_den_1)
+    dColHt_dKd = (dT_to_dColHta * dT_km1_t2 + dS_to_dColHta * dS_km1_t2) / (b_den_1) + \
+        (dT_to_dColHt_k * dTe_term + dS_to_dColHt_k * dSe_term) / (h_k * b_den_1)
+    if dColHt_dKd < 0.0:
+        dPEc_dKd_0 = dPEc_dKd_0 - pres_Z * dColHt_dKd
+    return PE_chg, dPEc_dKd, dPE_max, dPEc_dKd_0
+
+
+def find_PE_chg(Kddt_h0, dKddt_h, hp_a, hp_b, Th_a, Sh_a, Th_b, Sh_b, dT_to_dPE_a, dS_to_dPE_a, dT_to_dPE_b, dS_to_dPE_b, pres_Z,
+                dT_to_dColHt_a, dS_to_dColHt_a, dT_to_dColHt_b, dS_to_dColHt_b, br=None):
+    """find_PE_chg :3072-3213: (PE_chg, dPEc_dKd, dPE_max, dPEc_dKd_0)."""
+    hps = hp_a + hp_b
+    bdt1 = hp_a * hp_b + Kddt_h0 * hps
+    dT_c = hp_a * Th_b - hp_b * Th_a
+    dS_c = hp_a * Sh_b - hp_b * Sh_a
+    PEc_core = hp_b * (dT_to_dPE_a * dT_c + dS_to_dPE_a * dS_c) - hp_a * (dT_to_dPE_b * dT_c + dS_to_dPE_b * dS_c)
+    ColHt_core = hp_b * (dT_to_dColHt_a * dT_c + dS_to_dColHt_a * dS_c) - hp_a * (dT_to_dColHt_b * dT_c + dS_to_dColHt_b * dS_c)
+    y1_3 = dKddt_h / (bdt1 * (bdt1 + dKddt_h * hps))
+    PE_chg = PEc_core * y1_3
+    ColHt_chg = ColHt_core * y1_3
+    if ColHt_chg < 0.0:
+        if br is not None:
+            br["colht_neg"] += 1
+        PE_chg = PE_chg - pres_Z * ColHt_chg
+    t = bdt1 + dKddt_h * hps
+    y1_4 = 1.0 / (t * t)
+    dPEc_dKd = PEc_core * y1_4
+    ColHt_chg = ColHt_core * y1_4
+    if ColHt_chg < 0.0:
+        dPEc_dKd = dPEc_dKd - pres_Z * ColHt_chg
+    y1_3 = 1.0 / (bdt1 * hps)
+    dPE_max = PEc_core * y1_3
+    ColHt_chg = ColHt_core * y1_3
+    if ColHt_chg < 0.0:
+        dPE_max = dPE_max - pres_Z * ColHt_chg
+    y1_4 = 1.0 / (bdt1 * bdt1)
+    dPEc_dKd_0 = PEc_core * y1_4
+    ColHt_chg = ColHt_core * y1_4
+    if ColHt_chg < 0.0:
+        dPEc_dKd_0 = dPEc_dKd_0 - pres_Z * ColHt_chg
+    return PE_chg, dPEc_dKd, dPE_max, dPEc_dKd_0
+
+
+def _vstar(CS, SpV, TKE_here, conv_PErel, dztot, MLD_guess, u_star, m, br):
+    """:1525-1541 (and its twin :1600-1616)."""
+    if CS.answer_date < 20240101:
+        vus = CS.m_to_Z * CS.T_to_s
+        if CS.wT_scheme == abi.EPBL_WT_CUBE_ROOT_TKE:
+            br["vstar_croot_old"] += 1
+            return CS.vstar_scale_fac * vus * m.pow(SpV * TKE_here, 1.0 / 3.0)
+        br["vstar_rh18_old"] += 1
+        Surface_Scale = fmax1(0.05, 1.0 - dztot / MLD_guess)
+        return CS.vstar_scale_fac * Surface_Scale * (CS.vstar_surf_fac * u_star + vus * m.pow(CS.wstar_ustar_coef * conv_PErel * SpV, 1.0 / 3.0))
+    if CS.wT_scheme == abi.EPBL_WT_CUBE_ROOT_TKE:
+        br["vstar_croot"] += 1
+        return CS.vstar_scale_fac * cuberoot(SpV * TKE_here)
+    br["vstar_rh18"] += 1
+    Surface_Scale = fmax1(0.05, 1.0 - dztot / MLD_guess)
+    return (CS.vstar_scale_fac * Surface_Scale) * (CS.vstar_surf_fac * u_star + cuberoot((CS.wstar_ustar_coef * conv_PErel) * SpV))
+
+
+def ePBL_column(CS, GV, h, dz, u, v, T0, S0, dSV_dT, dSV_dS, SpV_dt, TKE_forcing, B_flux, absf, u_star, mech_TKE_in, dt, MLD_io, m, br,
+                trace=None):
+    """ePBL_column :890-1950 on python lists.  Returns (Kd, mixvel, mixlen, MLD, eCD); eCD: dTKE_conv, dTKE_forcing, dTKE_wind,
+    dTKE_mixing, dTKE_MKE, dTKE_mech_decay, dTKE_conv_decay, mstar, OBL_its.  trace: a list that gets, per MLD iteration, a tuple
+    (arms at the interfaces, the outer decision)."""
+    nz = len(h)
+    orig = bool(CS.orig_PE_calc)
+    diag = bool(CS.TKE_diagnostics)
+    use_mke = CS.MKE_to_TKE_effic > 0.0
+    g_Z = CS.g_Earth_Z_T2
+    I_dtdiag = 1.0 / dt
+    max_itt = 20
+    dz_tt_min = 0.0
+    MLD_guess = MLD_io
+    Kd = [0.0] * (nz + 1); mixvel = [0.0] * (nz + 1); mixlen = [0.0] * (nz + 1)
+    dz_sum = GV.dZ_subroundoff
+    for k in range(nz):
+        dz_sum = dz_sum + dz[k]
+    I_dzsum = 0.0
+    if dz_sum > 0.0:
+        I_dzsum = 1.0 / dz_sum
+    dz_bot = 0.0
+    hb_hs = [0.0] * (nz + 1)
+    for k in range(nz - 1, -1, -1):
+        dz_bot = dz_bot + dz[k]
+        hb_hs[k] = dz_bot * I_dzsum
+    MLD_output = dz[0]
+    max_MLD = 0.0
+    for k in range(nz):
+        max_MLD = max_MLD + dz[k]
+    min_MLD = 0.0
+    dMLD_min = -1.0 * CS.m_to_Z; dMLD_max = 1.0 * CS.m_to_Z
+    if MLD_guess <= min_MLD:
+        br["first_guess_half"] += 1
+        MLD_guess = 0.5 * (min_MLD + max_MLD)
+    else:
+        br["first_guess_stored"] += 1
+    h_dz_int = GV.Z_to_H
+    eCD = dict(dTKE_conv=0.0, dTKE_forcing=0.0, dTKE_wind=0.0, dTKE_mixing=0.0, dTKE_MKE=0.0, dTKE_mech_decay=0.0, dTKE_conv_decay=0.0)
+    if nz == 1:
+        br["nk1"] += 1
+    OBL_it = 0
+    mstar_total = 0.0
+    while OBL_it < CS.max_MLD_its:
+        OBL_it += 1
+        arms = []
+        MLD_output = dz[0]
+        sfc_connected = True
+        mstar_total = find_mstar(CS, B_flux, u_star, MLD_guess, absf, m, br)
+        if (CS.answer_date < 20190101) and (CS.mstar_scheme == abi.EPBL_MSTAR_CONSTANT):
+            br["mech_old_fixed"] += 1
+            mech_TKE = (dt * mstar_total * GV.Rho0) * ((u_star * u_star) * u_star)
+        else:
+            mech_TKE = mstar_total * mech_TKE_in
+        if diag:
+            eCD["dTKE_conv"] = 0.0; eCD["dTKE_mixing"] = 0.0
+            eCD["dTKE_MKE"] = 0.0; eCD["dTKE_mech_decay"] = 0.0; eCD["dTKE_conv_decay"] = 0.0
+            eCD["dTKE_wind"] = mech_TKE * I_dtdiag
+            if TKE_forcing[0] <= 0.0:
+                eCD["dTKE_forcing"] = fmax1(-mech_TKE, TKE_forcing[0]) * I_dtdiag
+            else:
+                eCD["dTKE_forcing"] = CS.nstar * TKE_forcing[0] * I_dtdiag
+        if TKE_forcing[0] <= 0.0:
+            br["forcing1_neg"] += 1
+            mech_TKE = mech_TKE + TKE_forcing[0]
+            if mech_TKE < 0.0:
+                br["forcing1_neg_clip"] += 1
+                mech_TKE = 0.0
+            conv_PErel = 0.0
+        else:
+            br["forcing1_pos"] += 1
+            conv_PErel = TKE_forcing[0]
+        for K in range(nz + 1):
+            mixvel[K] = 0.0; mixlen[K] = 0.0
+        # the mixing shape function :1293-1324, formed at each interface below
+        if (not CS.Use_MLD_iteration) or (CS.transLay_scale >= 1.0) or (CS.transLay_scale < 0.0):
+            shape = 0; br["shape_one"] += 1
+        elif MLD_guess <= 0.0:
+            shape = 1; br["shape_guess_le0"] += 1
+        else:
+            shape = 2
+            I_MLD = 1.0 / MLD_guess
+        dz_rsum = 0.0
+        Kd[0] = 0.0
+        Kddt_h_prev = 0.0                   # Kddt_h(K-1)
+        hp_a = h[0]                         # hp_a(k-1) and the four dX_to_dY_a(k-1)
+        dMass = GV.H_to_RZ * h[0]
+        dPres = g_Z * dMass
+        pres_Z = 0.0
+        dT_to_dPE_a = (dMass * (pres_Z + 0.5 * dPres)) * dSV_dT[0]
+        dS_to_dPE_a = (dMass * (pres_Z + 0.5 * dPres)) * dSV_dS[0]
+        dT_to_dColHt_a = dMass * dSV_dT[0]
+        dS_to_dColHt_a = dMass * dSV_dS[0]
+        dT_to_dColHt_km1 = dT_to_dColHt_a; dS_to_dColHt_km1 = dS_to_dColHt_a      # dX_to_dColHt(k-1)
+        pres_Z = pres_Z + dPres             # pres_Z(2)
+        htot = h[0]; dztot = dz[0]
+        uhtot = u[0] * h[0] if use_mke else 0.0
+        vhtot = v[0] * h[0] if use_mke else 0.0
+        dTe_km2 = 0.0; dSe_km2 = 0.0        # dTe(k-2), dSe(k-2)
+        Te_km2 = 0.0; Se_km2 = 0.0          # Te(k-2), Se(k-2)
+        PE_chg = 0.0
+        for k in range(1, nz):              # interface K = k + 1 of the reference, between layers k-1 and k (0-based)
+            # the layer below: dX_to_dPE(k), dX_to_dColHt(k) :1192-1201
+            dMass = GV.H_to_RZ * h[k]
+            dPres = g_Z * dMass
+            dT_to_dPE = (dMass * (pres_Z + 0.5 * dPres)) * dSV_dT[k]
+            dS_to_dPE = (dMass * (pres_Z + 0.5 * dPres)) * dSV_dS[k]
+            dT_to_dColHt = dMass * dSV_dT[k]
+            dS_to_dColHt = dMass * dSV_dS[k]
+            # MixLen_shape(K)
+            if shape == 0:
+                MixLen_shape = 1.0
+            elif shape == 1:
+                MixLen_shape = CS.transLay_scale if CS.transLay_scale > 0.0 else 1.0
+            else:
+                dz_rsum = dz_rsum + dz[k - 1]
+                x = fmax1(0.0, (MLD_guess - dz_rsum) * I_MLD)
+                if x == 0.0:
+                    br["shape_clip0"] += 1
+                if CS.MixLenExponent == 2.0:
+                    br["shape_quadratic"] += 1
+                    MixLen_shape = CS.transLay_scale + (1.0 - CS.transLay_scale) * (x * x)
+                else:
+                    br["shape_pow"] += 1
+                    MixLen_shape = CS.transLay_scale + (1.0 - CS.transLay_scale) * m.pow(x, CS.MixLenExponent)
+            Idecay_len_TKE = (CS.TKE_decay * absf / u_star) * GV.H_to_Z
+            exp_kh = 1.0
+            if Idecay_len_TKE > 0.0:
+                br["decay_exp"] += 1
+                exp_kh = m.exp(-h[k - 1] * Idecay_len_TKE)
+            if diag:
+                eCD["dTKE_mech_decay"] = eCD["dTKE_mech_decay"] + (exp_kh - 1.0) * mech_TKE * I_dtdiag
+            mech_TKE = mech_TKE * exp_kh
+            if TKE_forcing[k] > 0.0:
+                br["conv_add"] += 1
+                conv_PErel = conv_PErel + TKE_forcing[k]
+                if diag:
+                    eCD["dTKE_forcing"] = eCD["dTKE_forcing"] + CS.nstar * TKE_forcing[k] * I_dtdiag
+            nstar_FC = CS.nstar
+            if CS.nstar * conv_PErel > 0.0:
+                br["nstar_fc"] += 1
+                t = absf * dztot
+                nstar_FC = CS.nstar * conv_PErel / (conv_PErel + 0.2 * _math.sqrt(0.5 * dt * GV.Rho0 * ((t * t) * t) * conv_PErel))
+            tot_TKE = mech_TKE + nstar_FC * conv_PErel
+            sw = "-"
+            if TKE_forcing[k] < 0.0:
+                if TKE_forcing[k] + tot_TKE < 0.0:
+                    br["sw_deplete"] += 1; sw = "D"
+                    if diag:
+                        eCD["dTKE_mixing"] = eCD["dTKE_mixing"] + tot_TKE * I_dtdiag
+                        eCD["dTKE_forcing"] = eCD["dTKE_forcing"] - tot_TKE * I_dtdiag
+                        eCD["dTKE_conv_decay"] = eCD["dTKE_conv_decay"] + (CS.nstar - nstar_FC) * conv_PErel * I_dtdiag
+                    tot_TKE = 0.0; mech_TKE = 0.0; conv_PErel = 0.0
+                else:
+                    br["sw_reduce"] += 1; sw = "R"
+                    TKE_reduc = (tot_TKE + TKE_forcing[k]) / tot_TKE
+                    if diag:
+                        eCD["dTKE_mixing"] = eCD["dTKE_mixing"] - TKE_forcing[k] * I_dtdiag
+                        eCD["dTKE_forcing"] = eCD["dTKE_forcing"] + TKE_forcing[k] * I_dtdiag
+                        eCD["dTKE_conv_decay"] = eCD["dTKE_conv_decay"] + (1.0 - TKE_reduc) * (CS.nstar - nstar_FC) * conv_PErel * I_dtdiag
+                    tot_TKE = TKE_reduc * tot_TKE
+                    mech_TKE = TKE_reduc * mech_TKE
+                    conv_PErel = TKE_reduc * conv_PErel
+            if orig:
+                if k == 1:
+                    dTe_t2 = 0.0; dSe_t2 = 0.0
+                else:
+                    dTe_t2 = Kddt_h_prev * ((T0[k - 2] - T0[k - 1]) + dTe_km2)
+                    dSe_t2 = Kddt_h_prev * ((S0[k - 2] - S0[k - 1]) + dSe_km2)
+            dt_h = dt / fmax1(0.5 * (dz[k - 1] + dz[k]), 1e-15 * dz_sum)
+            Convectively_stable = (0.0 <= ((dT_to_dColHt + dT_to_dColHt_km1) * (T0[k - 1] - T0[k]) +
+                                           (dS_to_dColHt + dS_to_dColHt_km1) * (S0[k - 1] - S0[k])))
+            if ((mech_TKE + conv_PErel) <= 0.0) and Convectively_stable:
+                br["stable_exhausted"] += 1; arm = "S"
+                tot_TKE = 0.0; mech_TKE = 0.0; conv_PErel = 0.0
+                Kd[k] = 0.0; Kddt_h = 0.0
+                sfc_disconnect = True
+                b1 = 1.0 / hp_a
+                if orig:
+                    dTe_km1 = b1 * (dTe_t2)
+                    dSe_km1 = b1 * (dSe_t2)
+                hp_a_new = h[k]
+                dT_to_dPE_a = dT_to_dPE; dS_to_dPE_a = dS_to_dPE
+                dT_to_dColHt_a = dT_to_dColHt; dS_to_dColHt_a = dS_to_dColHt
+            else:
+                sfc_disconnect = False
+                if orig:
+                    if k == 1:
+                        dT_km1_t2 = (T0[k] - T0[k - 1])
+                        dS_km1_t2 = (S0[k] - S0[k - 1])
+                    else:
+                        dT_km1_t2 = (T0[k] - T0[k - 1]) - (Kddt_h_prev / hp_a) * ((T0[k - 2] - T0[k - 1]) + dTe_km2)
+                        dS_km1_t2 = (S0[k] - S0[k - 1]) - (Kddt_h_prev / hp_a) * ((S0[k - 2] - S0[k - 1]) + dSe_km2)
+                    dTe_term = dTe_t2 + hp_a * (T0[k - 1] - T0[k])
+                    dSe_term = dSe_t2 + hp_a * (S0[k - 1] - S0[k])
+                else:
+                    if k <= 1:
+                        Th_a = h[k - 1] * T0[k - 1]; Sh_a = h[k - 1] * S0[k - 1]
+                    else:
+                        Th_a = h[k - 1] * T0[k - 1] + Kddt_h_prev * Te_km2
+                        Sh_a = h[k - 1] * S0[k - 1] + Kddt_h_prev * Se_km2
+                    Th_b = h[k] * T0[k]; Sh_b = h[k] * S0[k]
+
+                def pe(Kddt):
+                    if orig:
+                        return find_PE_chg_orig(Kddt, h[k], hp_a, dTe_term, dSe_term, dT_km1_t2, dS_km1_t2, dT_to_dPE, dS_to_dPE,
+                                                dT_to_dPE_a, dS_to_dPE_a, pres_Z, dT_to_dColHt, dS_to_dColHt, dT_to_dColHt_a,
+                                                dS_to_dColHt_a, br)
+                    return find_PE_chg(0.0, Kddt, hp_a, h[k], Th_a, Sh_a, Th_b, Sh_b, dT_to_dPE_a, dS_to_dPE_a, dT_to_dPE, dS_to_dPE,
+                                       pres_Z, dT_to_dColHt_a, dS_to_dColHt_a, dT_to_dColHt, dS_to_dColHt, br)
+
+                if use_mke and (htot * h[k] > 0.0):
+                    br["mke"] += 1
+                    du = uhtot - u[k] * htot; dv = vhtot - v[k] * htot
+                    dMKE_max = (GV.H_to_RZ * CS.MKE_to_TKE_effic) * 0.5 * (h[k] / ((htot + h[k]) * htot)) * ((du * du) + (dv * dv))
+                    MKE2_Hharm = (htot + h[k] + 2.0 * GV.H_subroundoff) / ((htot + GV.H_subroundoff) * (h[k] + GV.H_subroundoff))
+                else:
+                    dMKE_max = 0.0
+                    MKE2_Hharm = 0.0
+                dz_tt = dztot + dz_tt_min
+                TKE_here = mech_TKE + CS.wstar_ustar_coef * conv_PErel
+                if TKE_here > 0.0:
+                    vstar = _vstar(CS, SpV_dt, TKE_here, conv_PErel, dztot, MLD_guess, u_star, m, br)
+                    hbs_here = fmin1(hb_hs[k], MixLen_shape)
+                    ml = ((dz_tt * hbs_here) * vstar) / ((CS.Ekman_scale_coef * absf) * (dz_tt * hbs_here) + vstar)
+                    if not (ml > CS.min_mix_len):
+                        br["min_mix_len"] += 1
+                    mixlen[k] = fmax1(CS.min_mix_len, ml)
+                    if not CS.Use_MLD_iteration:
+                        br["kd_no_iter"] += 1
+                        Kd_guess0 = (h_dz_int * vstar) * CS.vonKar * ((dz_tt * hbs_here) * vstar) / \
+                            ((CS.Ekman_scale_coef * absf) * (dz_tt * hbs_here) + vstar)
+                    else:
+                        Kd_guess0 = (h_dz_int * vstar) * CS.vonKar * mixlen[k]
+                else:
+                    br["tke_here_le0"] += 1
+                    vstar = 0.0; Kd_guess0 = 0.0
+                mixvel[k] = vstar
+                Kddt_h_g0 = Kd_guess0 * dt_h
+                PE_chg_g0, _d, PE_chg_max, dPEc_dKd_Kd0 = pe(Kddt_h_g0)
+                convectively_unstable = (PE_chg_g0 < 0.0) or ((vstar == 0.0) and (dPEc_dKd_Kd0 < 0.0))
+                if use_mke:
+                    MKE_src = dMKE_max * (1.0 - m.exp(-Kddt_h_g0 * MKE2_Hharm))
+                else:
+                    MKE_src = 0.0
+                if convectively_unstable:
+                    if not (PE_chg_g0 < 0.0):
+                        br["unstable_by_slope"] += 1
+                    if PE_chg_max <= 0.0:
+                        br["unstable_max_le0"] += 1; arm = "U"
+                        TKE_here = mech_TKE + CS.wstar_ustar_coef * (conv_PErel - PE_chg_max)
+                        if TKE_here > 0.0:
+                            vstar = _vstar(CS, SpV_dt, TKE_here, conv_PErel, dztot, MLD_guess, u_star, m, br)
+                            hbs_here = fmin1(hb_hs[k], MixLen_shape)
+                            mixlen[k] = fmax1(CS.min_mix_len, ((dz_tt * hbs_here) * vstar) /
+                                              ((CS.Ekman_scale_coef * absf) * (dz_tt * hbs_here) + vstar))
+                            if not CS.Use_MLD_iteration:
+                                Kd[k] = (h_dz_int * vstar) * CS.vonKar * ((dz_tt * hbs_here) * vstar) / \
+                                    ((CS.Ekman_scale_coef * absf) * (dz_tt * hbs_here) + vstar)
+                            else:
+                                Kd[k] = (h_dz_int * vstar) * CS.vonKar * mixlen[k]
+                        else:
+                            br["unstable_max_le0_tke0"] += 1; arm += "0"
+                            vstar = 0.0; Kd[k] = 0.0
+                        mixvel[k] = vstar
+                        dPE_conv = pe(Kd[k] * dt_h)[0]
+                        if dPE_conv > 0.0:
+                            br["unstable_max_le0_fallback"] += 1; arm += "f"
+                            Kd[k] = Kd_guess0; dPE_conv = PE_chg_g0
+                        else:
+                            br["unstable_max_le0_keep"] += 1
+                            if use_mke:
+                                MKE_src = dMKE_max * (1.0 - m.exp(-(Kd[k] * dt_h) * MKE2_Hharm))
+                            else:
+                                MKE_src = 0.0
+                    else:
+                        br["unstable_nonmono"] += 1; arm = "N"
+                        Kd[k] = Kd_guess0; dPE_conv = PE_chg_g0
+                    conv_PErel = conv_PErel - dPE_conv
+                    mech_TKE = mech_TKE + MKE_src
+                    if diag:
+                        eCD["dTKE_conv"] = eCD["dTKE_conv"] - CS.nstar * dPE_conv * I_dtdiag
+                        eCD["dTKE_MKE"] = eCD["dTKE_MKE"] + MKE_src * I_dtdiag
+                    if sfc_connected:
+                        br["connected_deepen"] += 1
+                        MLD_output = MLD_output + dz[k]
+                elif tot_TKE + (MKE_src - PE_chg_g0) >= 0.0:
+                    br["enough"] += 1; arm = "E"
+                    Kd[k] = Kd_guess0
+                    tot_TKE = tot_TKE + MKE_src
+                    TKE_reduc = 0.0
+                    if tot_TKE > 0.0:
+                        TKE_reduc = (tot_TKE - PE_chg_g0) / tot_TKE
+                    if diag:
+                        eCD["dTKE_mixing"] = eCD["dTKE_mixing"] - PE_chg_g0 * I_dtdiag
+                        eCD["dTKE_MKE"] = eCD["dTKE_MKE"] + MKE_src * I_dtdiag
+                        eCD["dTKE_conv_decay"] = eCD["dTKE_conv_decay"] + (1.0 - TKE_reduc) * (CS.nstar - nstar_FC) * conv_PErel * I_dtdiag
+                    tot_TKE = TKE_reduc * tot_TKE
+                    mech_TKE = TKE_reduc * (mech_TKE + MKE_src)
+                    conv_PErel = TKE_reduc * conv_PErel
+                    if sfc_connected:
+                        br["connected_deepen"] += 1
+                        MLD_output = MLD_output + dz[k]
+                elif tot_TKE == 0.0:
+                    br["tot_zero"] += 1; arm = "Z"
+                    Kd[k] = 0.0
+                    tot_TKE = 0.0; conv_PErel = 0.0; mech_TKE = 0.0
+                    sfc_disconnect = True
+                else:
+                    br["newton"] += 1; arm = "I"
+                    Kddt_h_max = Kddt_h_g0; Kddt_h_min = 0.0
+                    TKE_left_max = tot_TKE + (MKE_src - PE_chg_g0)
+                    TKE_left_min = tot_TKE
+                    Kddt_h_guess = tot_TKE * Kddt_h_max / fmax1(PE_chg_g0 - MKE_src, Kddt_h_max * (dPEc_dKd_Kd0 - dMKE_max * MKE2_Hharm))
+                    steps = ""
+                    for itt in range(1, max_itt + 1):
+                        PE_chg, dPEc_dKd, _a, _b = pe(Kddt_h_guess)
+                        if use_mke:
+                            MKE_src = dMKE_max * (1.0 - m.exp(-MKE2_Hharm * Kddt_h_guess))
+                            dMKE_src_dK = dMKE_max * MKE2_Hharm * m.exp(-MKE2_Hharm * Kddt_h_guess)
+                        else:
+                            MKE_src = 0.0; dMKE_src_dK = 0.0
+                        TKE_left = tot_TKE + (MKE_src - PE_chg)
+                        if TKE_left >= 0.0:
+                            Kddt_h_min = Kddt_h_guess; TKE_left_min = TKE_left
+                        else:
+                            Kddt_h_max = Kddt_h_guess; TKE_left_max = TKE_left
+                        use_Newt = True
+                        if dPEc_dKd - dMKE_src_dK <= 0.0:
+                            use_Newt = False
+                        else:
+                            dKddt_h_Newt = TKE_left / (dPEc_dKd - dMKE_src_dK)
+                            Kddt_h_Newt = Kddt_h_guess + dKddt_h_Newt
+                            if (Kddt_h_Newt > Kddt_h_max) or (Kddt_h_Newt < Kddt_h_min):
+                                use_Newt = False
+                        if use_Newt:
+                            br["newt_step"] += 1; steps += "n"
+                            Kddt_h_next = Kddt_h_guess + dKddt_h_Newt
+                            dKddt_h = dKddt_h_Newt
+                        else:
+                            br["falsepos_step"] += 1; steps += "f"
+                            Kddt_h_next = (TKE_left_max * Kddt_h_min - Kddt_h_max * TKE_left_min) / (TKE_left_max - TKE_left_min)
+                            dKddt_h = Kddt_h_next - Kddt_h_guess
+                        if (abs(dKddt_h) < 1e-9 * Kddt_h_guess) or (itt == max_itt):
+                            if itt == max_itt:
+                                br["newton_maxitt"] += 1
+                            break
+                        else:
+                            Kddt_h_guess = Kddt_h_next
+                    arm += steps
+                    Kd[k] = Kddt_h_guess / dt_h
+                    if diag:
+                        eCD["dTKE_mixing"] = eCD["dTKE_mixing"] - (tot_TKE + MKE_src) * I_dtdiag
+                        eCD["dTKE_MKE"] = eCD["dTKE_MKE"] + MKE_src * I_dtdiag
+                        eCD["dTKE_conv_decay"] = eCD["dTKE_conv_decay"] + (CS.nstar - nstar_FC) * conv_PErel * I_dtdiag
+                    if sfc_connected:
+                        MLD_output = MLD_output + (PE_chg / (PE_chg_g0)) * dz[k]
+                    tot_TKE = 0.0; mech_TKE = 0.0; conv_PErel = 0.0
+                    sfc_disconnect = True
+                Kddt_h = Kd[k] * dt_h
+                b1 = 1.0 / (hp_a + Kddt_h)
+                c1 = Kddt_h * b1
+                if orig:
+                    dTe_km1 = b1 * (Kddt_h * (T0[k] - T0[k - 1]) + dTe_t2)
+                    dSe_km1 = b1 * (Kddt_h * (S0[k] - S0[k - 1]) + dSe_t2)
+                hp_a_new = h[k] + (hp_a * b1) * Kddt_h
+                dT_to_dPE_a = dT_to_dPE + c1 * dT_to_dPE_a
+                dS_to_dPE_a = dS_to_dPE + c1 * dS_to_dPE_a
+                dT_to_dColHt_a = dT_to_dColHt + c1 * dT_to_dColHt_a
+                dS_to_dColHt_a = dS_to_dColHt + c1 * dS_to_dColHt_a
+            arms.append(sw + arm)
+            if sfc_disconnect:
+                if sfc_connected:
+                    br["disconnect"] += 1
+                if use_mke:
+                    uhtot = u[k] * h[k]; vhtot = v[k] * h[k]
+                htot = h[k]
+                dztot = dz[k]
+                sfc_connected = False
+            else:
+                if use_mke:
+                    uhtot = uhtot + u[k] * h[k]; vhtot = vhtot + v[k] * h[k]
+                htot = htot + h[k]
+                dztot = dztot + dz[k]
+            if not orig:                    # calc_Te
+                if k == 1:
+                    Te_km1 = b1 * (h[0] * T0[0])
+                    Se_km1 = b1 * (h[0] * S0[0])
+                else:
+                    Te_km1 = b1 * (h[k - 1] * T0[k - 1] + Kddt_h_prev * Te_km2)
+                    Se_km1 = b1 * (h[k - 1] * S0[k - 1] + Kddt_h_prev * Se_km2)
+                Te_km2 = Te_km1; Se_km2 = Se_km1
+            else:
+                dTe_km2 = dTe_km1; dSe_km2 = dSe_km1
+            hp_a = hp_a_new
+            Kddt_h_prev = Kddt_h
+            dT_to_dColHt_km1 = dT_to_dColHt; dS_to_dColHt_km1 = dS_to_dColHt
+            pres_Z = pres_Z + dPres
+        Kd[nz] = 0.0
+        if OBL_it >= CS.max_MLD_its:
+            br["max_its"] += 1
+            if trace is not None:
+                trace.append((tuple(arms), "max"))
+            break
+        MLD_found = MLD_output
+        done = False
+        if CS.MLD_iter_bug:
+            if MLD_found - MLD_guess > CS.MLD_tol:
+                br["bug_shallow"] += 1; dec = "bs"
+                min_MLD = MLD_guess; dMLD_min = MLD_found - MLD_guess
+            elif abs(MLD_found - MLD_guess) < CS.MLD_tol:
+                br["bug_converged"] += 1; dec = "bc"
+                done = True
+            else:
+                br["bug_deep"] += 1; dec = "bd"
+                max_MLD = MLD_guess; dMLD_max = MLD_found - MLD_guess
+        else:
+            if abs(MLD_found - MLD_guess) < CS.MLD_tol:
+                br["converged"] += 1; dec = "c"
+                done = True
+            elif MLD_found > MLD_guess:
+                br["too_shallow"] += 1; dec = "s"
+                min_MLD = MLD_guess; dMLD_min = MLD_found - MLD_guess
+            else:
+                br["too_deep"] += 1; dec = "d"
+                max_MLD = MLD_guess; dMLD_max = MLD_found - MLD_guess
+        if done:
+            if trace is not None:
+                trace.append((tuple(arms), dec))
+            break
+        if CS.MLD_bisection:
+            br["bisection"] += 1; dec += "B"
+            MLD_guess = 0.5 * (min_MLD + max_MLD)
+        else:
+            if (dMLD_min > 0.0) and (dMLD_max < 0.0) and (OBL_it > 2) and ((OBL_it - 1) % 4 > 0):
+                br["false_position"] += 1; dec += "F"
+                MLD_guess = (dMLD_min * max_MLD - dMLD_max * min_MLD) / (dMLD_min - dMLD_max)
+            elif (MLD_found > min_MLD) and (MLD_found < max_MLD):
+                br["mld_found"] += 1; dec += "M"
+                MLD_guess = MLD_found
+            else:
+                br["bisect_fallback"] += 1; dec += "H"
+                MLD_guess = 0.5 * (min_MLD + max_MLD)
+        if trace is not None:
+            trace.append((tuple(arms), dec))
+    eCD["OBL_its"] = min(OBL_it, CS.max_MLD_its)
+    eCD["mstar"] = mstar_total
+    return Kd, mixvel, mixlen, MLD_output, eCD
+
+
+TKE_DIAGS = ("diag_TKE_wind", "diag_TKE_MKE", "diag_TKE_conv", "diag_TKE_forcing", "diag_TKE_mixing", "diag_TKE_mech_decay",
+             "diag_TKE_conv_decay")
+_ECD = dict(diag_TKE_wind="dTKE_wind", diag_TKE_MKE="dTKE_MKE", diag_TKE_conv="dTKE_conv", diag_TKE_forcing="dTKE_forcing",
+            diag_TKE_mixing="dTKE_mixing", diag_TKE_mech_decay="dTKE_mech_decay", diag_TKE_conv_decay="dTKE_conv_decay")
+DIAG_3D = ("Velocity_Scale", "Mixing_Length")
+DIAG_2D = TKE_DIAGS + ("mstar_sfc", "ustar_diag", "OBL_its")
+
+
+def energetic_PBL(d, M, GV, CS, h, u, v, T, S, dSV_dT, dSV_dS, TKE_forced, ustar, buoy_flux, dt, Kd_int, ML_depth, math=None,
+                  counts=None, traces=None, **diag):
+    """energetic_PBL :326-884 on the arrays of a tile; Kd_int, ML_depth and the diagnostics given by name are written on the
+    computational domain.  traces: a dict that gets {(j, i): trace} of the wet columns."""
+    m = math if math is not None else Libm()
+    br = counts if counts is not None else dict.fromkeys(BRANCHES, 0)
+    nz = d.nk
+    assert set(diag) <= set(DIAG_3D + DIAG_2D), sorted(diag)
+    use_mke = CS.MKE_to_TKE_effic > 0.0
+    I_rho0dt = 1.0 / (GV.Rho0 * dt)
+    if CS.answer_date < 20240101:
+        Z_to_m = 1.0 / CS.m_to_Z; s_to_T = 1.0 / CS.T_to_s
+        SpV_dt = (((Z_to_m * Z_to_m) * Z_to_m) * ((s_to_T * s_to_T) * s_to_T)) * (1.0 / (dt * GV.Rho0))
+    else:
+        SpV_dt = I_rho0dt
+    mask = M[G["mask2dT"]]; f = M[G["CoriolisBu"]]
+    aCu = M[G["areaCu"]]; aCv = M[G["areaCv"]]; IaT = M[G["IareaT"]]
+    for jl in range(d.nj):
+        for il in range(d.ni):
+            j = jl + d.joff; i = il + d.ioff
+            if not (mask[j, i] > 0.0):
+                br["land"] += 1
+                Kd_int[:, j, i] = 0.0
+                ML_depth[j, i] = 0.0
+                for n in diag:
+                    diag[n][..., j, i] = 0.0
+                continue
+            hc = [float(x) + GV.H_subroundoff for x in h[:, j, i]]
+            dzc = [GV.H_to_Z * float(x) + GV.dZ_subroundoff for x in h[:, j, i]]
+            if use_mke:
+                a_w = a_e = a_s = a_n = 0.0
+                sum_area = float(aCu[j, i - 1]) + float(aCu[j, i])
+                if sum_area > 0.0:
+                    Idenom = _math.sqrt(0.5 * float(IaT[j, i]) / sum_area)
+                    a_w = float(aCu[j, i - 1]) * Idenom; a_e = float(aCu[j, i]) * Idenom
+                sum_area = float(aCv[j - 1, i]) + float(aCv[j, i])
+                if sum_area > 0.0:
+                    Idenom = _math.sqrt(0.5 * float(IaT[j, i]) / sum_area)
+                    a_s = float(aCv[j - 1, i]) * Idenom; a_n = float(aCv[j, i]) * Idenom
+                uc = [(a_e * float(u[k, j, i])) + (a_w * float(u[k, j, i - 1])) for k in range(nz)]
+                vc = [(a_n * float(v[k, j, i])) + (a_s * float(v[k, j - 1, i])) for k in range(nz)]
+            else:
+                uc = vc = None
+            u_star = float(ustar[j, i])
+            ustar_raw = u_star
+            mech_TKE = dt * GV.Rho0 * ((u_star * u_star) * u_star)
+            if u_star < CS.ustar_min:
+                br["ustar_min"] += 1
+                u_star = CS.ustar_min
+            if CS.omega_frac >= 1.0:
+                br["omega_ge1"] += 1
+                absf = 2.0 * CS.omega
+            else:
+                absf = 0.25 * ((abs(float(f[j, i])) + abs(float(f[j - 1, i - 1]))) + (abs(float(f[j - 1, i])) + abs(float(f[j, i - 1]))))
+                if CS.omega_frac > 0.0:
+                    br["omega_frac"] += 1
+                    absf = _math.sqrt(CS.omega_frac * 4.0 * (CS.omega * CS.omega) + (1.0 - CS.omega_frac) * (absf * absf))
+                else:
+                    br["omega_0"] += 1
+            MLD_io = -1.0
+            if CS.MLD_iteration_guess and (ML_depth[j, i] > 0.0):
+                MLD_io = float(ML_depth[j, i])
+            tr = [] if traces is not None else None
+            Kd, mixvel, mixlen, MLD, eCD = ePBL_column(
+                CS, GV, hc, dzc, uc, vc, T[:, j, i].tolist(), S[:, j, i].tolist(), dSV_dT[:, j, i].tolist(), dSV_dS[:, j, i].tolist(),
+                SpV_dt, TKE_forced[:, j, i].tolist(), float(buoy_flux[j, i]), absf, u_star, mech_TKE, dt, MLD_io, m, br, tr)
+            if traces is not None:
+                traces[(jl, il)] = tuple(tr)
+            Kd_int[:, j, i] = Kd
+            ML_depth[j, i] = MLD
+            for n in diag:
+                if n == "Velocity_Scale":
+                    diag[n][:, j, i] = mixvel
+                elif n == "Mixing_Length":
+                    diag[n][:, j, i] = mixlen
+                elif n in _ECD:
+                    diag[n][j, i] = 0.0 + eCD[_ECD[n]]
+                elif n == "mstar_sfc":
+                    diag[n][j, i] = eCD["mstar"]
+                elif n == "ustar_diag":
+                    diag[n][j, i] = ustar_raw
+                else:
+                    diag[n][j, i] = float(eCD["OBL_its"])
+    return br
+
+
+def get_MLD(d, ML_depth, MLD, scale=1.0):
+    """energetic_PBL_get_MLD :3707-3725."""
+    o = (slice(d.joff, d.joff + d.nj), slice(d.ioff, d.ioff + d.ni))
+    MLD[o] = scale * ML_depth[o]
+
+
+def augment_Kd(d, GV, Kd_ePBL, Kd_shear, Kv_shear, Kd_heat, Kd_salt, ePBL_is_additive, ePBL_Prandtl, MLD=None, h_ML=None):
+    """MOM_diabatic_driver.F90:1570-1581, levels 2..nk on the computational domain, and visc%h_ML = GV%Z_to_H * MLD (the
+    Boussinesq convert_MLD_to_ML_thickness)."""
+    o = (slice(d.joff, d.joff + d.nj), slice(d.ioff, d.ioff + d.ni))
+    for K in range(1, d.nk):
+        Ke = Kd_ePBL[K][o]
+        if ePBL_is_additive:
+            add = Ke
+            Kv_shear[K][o] = Kv_shear[K][o] + ePBL_Prandtl * Ke
+        else:
+            x = Ke - Kd_shear[K][o]
+            add = np.where(0.0 > x, 0.0, x)        # MAX(x, 0.): the first argument on a tie
+            a = Kv_shear[K][o]; b = ePBL_Prandtl * Ke
+            Kv_shear[K][o] = np.where(b > a, b, a)
+        Kd_heat[K][o] = Kd_heat[K][o] + add
+        Kd_salt[K][o] = Kd_salt[K][o] + add
+    if h_ML is not None:
+        h_ML[o] = GV.Z_to_H * MLD[o]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# Shared cases of tests/test_energetic_PBL_cpu.py and tests/test_energetic_PBL_gpu.py
+
+def _ij(d):
+    il = (np.arange(d.pitch) - d.ioff + d.i_glob0)[None, :] * np.ones(d.shape2(), int)
+    jl = (np.arange(d.shape2()[0]) - d.joff + d.j_glob0)[:, None] * np.ones(d.shape2(), int)
+    return il, jl
+
+
+def inputs(d, M, GV, seed=3, dt=3600.0, strat=1.0, shear=None, weak_sources=True, h_scale=None):
+    """h, u, v, T, S, dSV_dT, dSV_dS, TKE_forced, ustar, buoy_flux on a tile, laid in global coordinates.  T falls and S rises with
+    depth (stable) except, in bands of columns, an inversion two interfaces down (an unstable interior below a quiet layer), an
+    inversion at the first interface, and columns of uniform T and S.  Some columns have vanished layers.  ustar is 0.002 .. 0.02
+    m s-1, 0 in a patch (below ustar_min) and large in another; buoy_flux and TKE_forced have both signs; in a band TKE_forced of
+    the second layer takes more than the column has, in another the surface layer does.  shear: u and v are multiplied by it and
+    change sign from layer to layer (up to 1.1 m s-1 with 5), so that homogenizing a layer with the water above releases mean
+    kinetic energy of the size of the TKE; h_scale: every thickness is multiplied by it (0.01: layers of metres, where that
+    energy is of the size of the potential-energy change too): together the cases where Newton's step leaves its bracket.  weak_sources = False makes
+    TKE_forced of the interior layers a sink wherever it was a source of up to 0.01 J m-2: below a layer that took all the
+    energy such a source starts a solve for a diffusivity at roundoff, and with mean kinetic energy as a second source its step
+    count depends on the last bits of exp (the libm cases with MKE conversion, see the screen)."""
+    from mom6_amd import synth
+    nk = d.nk
+    h, u, v = synth.make_state(d, M, seed=20250909 + seed, u_max=0.3, h_pert=0.01)
+    il, jl = _ij(d)
+    wetp = M[G["mask2dT"]] > 0.0
+    sf = lambda n, **kw: synth.smooth_field(d, seed + n, ox=0.5, oy=0.5, **kw)
+    if h_scale is not None:
+        h *= h_scale
+    if shear is not None:
+        for k in range(nk):
+            u[k] *= shear * (-1.0) ** k; v[k] *= shear * (-1.0) ** k
+    if nk > 2:
+        h[nk - 2] = np.where(wetp & (il % 7 == 3), 0.0, h[nk - 2])
+        h[1] = np.where(wetp & (il % 13 == 5), 0.0, h[1])
+    pT, pS = sf(10), sf(11)
+    T = np.zeros_like(h); S = np.zeros_like(h)
+    for k in range(nk):
+        zf = k / max(nk - 1, 1)
+        T[k] = 20.0 - strat * 15.0 * zf + 0.8 * pT * (1.0 - 0.5 * zf)
+        S[k] = 34.5 + strat * 1.0 * zf + 0.2 * pS * (1.0 - 0.5 * zf)
+    if nk > 3:                                                     # an inversion below a quiet layer
+        sel = (il % 5 == 1)
+        T[3] = np.where(sel, T[2] + 0.5, T[3])
+    if nk > 1:
+        T[1] = np.where(il % 9 == 4, T[0] + 0.3, T[1])             # unstable at the first interface
+    uni = (jl % 6 == 2) & (il % 4 == 0)                            # uniform T and S
+    for k in range(nk):
+        T[k] = np.where(uni, 12.0, T[k]); S[k] = np.where(uni, 35.0, S[k])
+    dSV_dT = np.stack([(2.0e-4 / 1035.0) * (1.0 + 0.3 * sf(20 + k % 3)) * (1.0 - 0.3 * k / max(nk, 1)) for k in range(nk)])
+    dSV_dS = np.stack([-(7.6e-4 / 1035.0) * (1.0 + 0.1 * sf(24 + k % 2)) for k in range(nk)])
+    TKE = np.stack([0.02 * sf(30 + k % 4) - 0.01 for k in range(nk)])
+    if not weak_sources:
+        TKE = -np.abs(TKE)
+    TKE[0] = 1.5 * sf(40)
+    TKE[0] = np.where((il % 8 == 6) & (jl % 2 == 0), -500.0, TKE[0])
+    if nk > 1:
+        TKE[1] = np.where(il % 10 == 7, -300.0, TKE[1])
+        TKE[1] = np.where(il % 10 == 2, 0.4, TKE[1])
+    ustar = 0.011 + 0.009 * sf(50)
+    ustar = np.where((il >= 4) & (il <= 7) & (jl >= 4) & (jl <= 6), 0.0, ustar)
+    ustar = np.where((il >= 12) & (il <= 15) & (jl >= 9) & (jl <= 11), 0.06, ustar)
+    bf = 2.0e-7 * sf(51)
+    bf = np.where((il % 6 == 0), 0.0, bf)
+    bf = np.where((il % 12 == 3), -0.0, bf)
+    out = dict(h=h, u=u, v=v, T=T, S=S, dSV_dT=dSV_dT, dSV_dS=dSV_dS, TKE_forced=TKE, ustar=ustar, buoy_flux=bf)
+    return {n: np.ascontiguousarray(a, dtype=np.float64) for n, a in out.items()}
+
+
+_EXACT = dict(TKE_decay=0.0, answer_date=20240101)
+_ALL_DIAG = DIAG_3D + DIAG_2D
+# case -> (params members, options).  Options: diag (the nullable outputs handed in), ncalls, dt, inp (keyword arguments of inputs())
+CASES = {
+    "croot_orig": (dict(_EXACT), dict(diag=("OBL_its",))),
+    "croot_new": (dict(_EXACT, orig_PE_calc=0, MLD_iter_bug=0, TKE_diagnostics=1), dict(diag=_ALL_DIAG)),
+    "rh18_orig": (dict(_EXACT, wT_scheme=abi.EPBL_WT_REICHL_H18, transLay_scale=0.0, omega_frac=0.5, MLD_iter_bug=0, TKE_diagnostics=1),
+                  dict(diag=_ALL_DIAG)),
+    "rh18_new_bisect": (dict(_EXACT, wT_scheme=abi.EPBL_WT_REICHL_H18, orig_PE_calc=0, MLD_bisection=1, omega_frac=1.0),
+                        dict(diag=("OBL_its", "mstar_sfc", "ustar_diag"))),
+    "no_iter": (dict(_EXACT, Use_MLD_iteration=0, nstar=0.0), dict(diag=("Velocity_Scale", "Mixing_Length", "OBL_its"))),
+    "no_iter_new": (dict(_EXACT, Use_MLD_iteration=0, orig_PE_calc=0, TKE_diagnostics=1), dict(diag=TKE_DIAGS + ("OBL_its",), inp=dict(strat=0.02))),
+    "translay1": (dict(_EXACT, transLay_scale=1.0, min_mix_len=3.0, max_MLD_its=3), dict(diag=("Mixing_Length", "OBL_its"))),
+    "guess": (dict(_EXACT, MLD_iteration_guess=1, MLD_tol=0.25), dict(diag=("OBL_its",), ncalls=2, inp=dict(strat=0.05))),
+    "mstar0": (dict(_EXACT, fixed_mstar=0.0, max_MLD_its=2), dict(diag=("OBL_its", "mstar_sfc"))),
+    "weak": (dict(_EXACT, MLD_tol=0.01, MLD_iter_bug=0), dict(diag=("OBL_its",), inp=dict(strat=0.01))),
+    # the cases with exp, log or pow
+    "decay": (dict(answer_date=20240101), dict(diag=("OBL_its",))),
+    "om4": (dict(mstar_scheme=abi.EPBL_MSTAR_OM4, mstar_cap=1.1, mstar_convect_coef=0.5, TKE_diagnostics=1), dict(diag=_ALL_DIAG)),
+    "om4_old": (dict(mstar_scheme=abi.EPBL_MSTAR_OM4, mstar_convect_coef=0.5, answer_date=20181231), dict(diag=("OBL_its", "mstar_sfc"))),
+    "rh18m": (dict(mstar_scheme=abi.EPBL_MSTAR_REICHL_H18, mstar_convect_coef=0.3, wT_scheme=abi.EPBL_WT_REICHL_H18, orig_PE_calc=0),
+              dict(diag=("OBL_its", "mstar_sfc"))),
+    "rh18m_old": (dict(mstar_scheme=abi.EPBL_MSTAR_REICHL_H18, answer_date=20181231, wT_scheme=abi.EPBL_WT_REICHL_H18),
+                  dict(diag=("OBL_its", "mstar_sfc"))),
+    "mke": (dict(_EXACT, MKE_to_TKE_effic=0.05), dict(diag=("OBL_its", "Velocity_Scale"))),
+    "mke_shear": (dict(_EXACT, MKE_to_TKE_effic=0.5), dict(diag=("OBL_its", "Velocity_Scale"), inp=dict(shear=5.0, weak_sources=False, h_scale=0.01))),
+    "date2023": (dict(TKE_decay=0.0, answer_date=20231231, orig_PE_calc=0), dict(diag=("OBL_its", "Velocity_Scale"))),
+    "const_old": (dict(TKE_decay=0.0, answer_date=20181231), dict(diag=("OBL_its",))),
+    "exp1": (dict(_EXACT, MixLenExponent=1.0), dict(diag=("OBL_its", "Mixing_Length"))),
+}
+CASES_LIBM = ("decay", "om4", "om4_old", "rh18m", "rh18m_old", "mke", "mke_shear", "date2023", "const_old", "exp1")
+CASES_EXACT = tuple(n for n in CASES if n not in CASES_LIBM)
+
+
+def case(name, GV):
+    """(params, options)"""
+    mods, opt = CASES[name]
+    opt = dict(dict(diag=(), ncalls=1, dt=3600.0, inp={}), **opt)
+    return abi.energetic_PBL_params_default(GV, **mods), opt
+
+
+def case_inputs(d, M, GV, opt, **kw):
+    return inputs(d, M, GV, dt=opt["dt"], **dict(opt["inp"], **kw))
+
+
+def outputs(d, opt, fill=np.nan):
+    out = dict(Kd_int=np.full(d.shape3(d.nk + 1), fill), ML_depth=np.full(d.shape2(), fill))
+    for n in opt["diag"]:
+        out[n] = np.full(d.shape3(d.nk + 1) if n in DIAG_3D else d.shape2(), fill)
+    return out
+
+
+def run(d, M, GV, P, opt, inp, fill=np.nan, math=None, counts=None, traces=None, ncalls=None):
+    """energetic_PBL of a case `ncalls` times in a row on the same outputs.  Returns (outputs by name, counts)."""
+    counts = counts if counts is not None else dict.fromkeys(BRANCHES, 0)
+    out = outputs(d, opt, fill)
+    need_uv = P.MKE_to_TKE_effic > 0.0
+    for _ in range(ncalls or opt["ncalls"]):
+        energetic_PBL(d, M, GV, P, inp["h"], inp["u"] if need_uv else None, inp["v"] if need_uv else None, inp["T"], inp["S"],
+                      inp["dSV_dT"], inp["dSV_dS"], inp["TKE_forced"], inp["ustar"], inp["buoy_flux"], opt["dt"], math=math,
+                      counts=counts, traces=traces, **out)
+    return out, counts
