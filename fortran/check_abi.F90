@@ -30,6 +30,8 @@ program check_abi
   type(mom6x_diabatic_aux_params) :: da
   type(mom6x_surface_fluxes) :: sf
   type(mom6x_energetic_PBL_params) :: ep
+  type(mom6x_frazil_params) :: fz
+  type(mom6x_geothermal_params) :: geo
   integer :: nbad, rc
   nbad = 0
   call chk(0, int(c_sizeof(d)), "mom6x_dims")
@@ -59,6 +61,8 @@ program check_abi
   call chk(27, int(c_sizeof(da)), "mom6x_diabatic_aux_params")
   call chk(28, int(c_sizeof(sf)), "mom6x_surface_fluxes")
   call chk(30, int(c_sizeof(ep)), "mom6x_energetic_PBL_params")
+  call chk(32, int(c_sizeof(fz)), "mom6x_frazil_params")
+  call chk(33, int(c_sizeof(geo)), "mom6x_geothermal_params")
   if (mom6x_abi_version() /= MOM6X_ABI_BUILT_FOR) then
     print '(a,i0,a,i0)', "ABI version: library ", mom6x_abi_version(), ", fortran/mom6x_c_api.F90 ", MOM6X_ABI_BUILT_FOR ; nbad = nbad + 1
   endif

@@ -15,6 +15,8 @@ module mom6x_c_api
   public :: mom6x_set_diffusivity_params, mom6x_set_diffusivity_init, mom6x_set_BBL_TKE, mom6x_set_diffusivity, mom6x_set_diffusivity_field
   public :: mom6x_diabatic_aux_params, mom6x_surface_fluxes, mom6x_diabatic_aux_init, mom6x_applyBoundaryFluxesInOut
   public :: mom6x_diabatic_aux_status
+  public :: mom6x_frazil_params, mom6x_make_frazil_init, mom6x_make_frazil, mom6x_adjust_salt
+  public :: mom6x_geothermal_params, mom6x_geothermal_init, mom6x_geothermal_in_place
   public :: mom6x_energetic_PBL_params, mom6x_energetic_PBL_init, mom6x_energetic_PBL, mom6x_energetic_PBL_get_MLD, mom6x_ePBL_augment_Kd
   public :: mom6x_thickness_diffuse_params, mom6x_thickness_diffuse_init, mom6x_thickness_diffuse
   public :: mom6x_tracer_hor_diff_params, mom6x_tracer_hor_diff_init, mom6x_tracer_hordiff, mom6x_tracer_hordiff_tile
@@ -155,6 +157,13 @@ module mom6x_c_api
     integer(c_int) :: max_MLD_its, wT_scheme, TKE_diagnostics, has_eos, ePBL_BBL_use_mstar, use_LT, eqdisc, eqdisc_v0, eqdisc_v0h
     integer(c_int) :: direct_calc, options_diff, pert_epbl, ustar_shelf, tau_mag, SpV_avg
   end type mom6x_energetic_PBL_params
+  type, bind(C) :: mom6x_frazil_params   !< what make_frazil (MOM_diabatic_aux.F90:110-230) reads of diabatic_aux_CS, tv and tv%eqn_of_state (calculate_TFreeze, MOM_EOS.F90:664-744)
+    real(c_double) :: C_p, RL2_T2_to_Pa, S_to_ppt, degC_to_C, TFr_S0_P0, dTFr_dS, dTFr_dp
+    integer(c_int) :: form_of_TFreeze, reclaim_frazil, pressure_dependent_frazil, use_conT_absS
+  end type mom6x_frazil_params
+  type, bind(C) :: mom6x_geothermal_params   !< what geothermal_in_place (MOM_geothermal.F90:364-535) reads of geothermal_CS, tv, GV and US
+    real(c_double) :: C_p, geothermal_thick, g_Earth_Z_T2, RL2_T2_to_Pa
+  end type mom6x_geothermal_params
 
   type, bind(C) :: mom6x_surface_fluxes   !< the members of `forcing` (MOM_forcing_type.F90:80-256) that applyBoundaryFluxesInOut touches: device planes, c_null_ptr where the reference's pointer is not associated
     type(c_ptr) :: sw, lw, latent, sens, evap, lprec, fprec, vprec, lrunoff, frunoff, lrunoff_glc, frunoff_glc, seaice_melt
@@ -514,6 +523,34 @@ module mom6x_c_api
       import :: c_ptr, c_int, c_double
       type(c_ptr), value :: ctx, Kd_ePBL, Kd_shear, Kv_shear, Kd_heat, Kd_salt, MLD, h_ML
       integer(c_int), value :: ePBL_is_additive ; real(c_double), value :: ePBL_Prandtl
+    end function
+    !> what make_frazil reads, and its pressure work array with PRESSURE_DEPENDENT_FRAZIL
+    integer(c_int) function mom6x_make_frazil_init(ctx, p) bind(C, name="mom6x_make_frazil_init")
+      import :: c_ptr, c_int, mom6x_frazil_params
+      type(c_ptr), value :: ctx ; type(mom6x_frazil_params), intent(in) :: p
+    end function
+    !> make_frazil (MOM_diabatic_aux.F90:110): the arrays are device pointers, p_surf c_null_ptr when absent
+    integer(c_int) function mom6x_make_frazil(ctx, h, T, S, frazil, p_surf, halo) bind(C, name="mom6x_make_frazil")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, h, T, S, frazil, p_surf ; integer(c_int), value :: halo
+    end function
+    !> adjust_salt (MOM_diabatic_aux.F90:339) with S_min = tv%min_salinity
+    integer(c_int) function mom6x_adjust_salt(ctx, h, S, salt_deficit, min_salinity) bind(C, name="mom6x_adjust_salt")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, h, S, salt_deficit ; real(c_double), value :: min_salinity
+    end function
+    !> geothermal_init (MOM_geothermal.F90:538): geo_heat is a HOST plane of the tile, eos is c_loc(an eos_params) or c_null_ptr
+    integer(c_int) function mom6x_geothermal_init(ctx, p, geo_heat, eos) bind(C, name="mom6x_geothermal_init")
+      import :: c_ptr, c_int, mom6x_geothermal_params
+      type(c_ptr), value :: ctx ; type(mom6x_geothermal_params), intent(in) :: p
+      type(c_ptr), value :: geo_heat, eos
+    end function
+    !> geothermal_in_place (MOM_geothermal.F90:364): the arrays are device pointers, c_null_ptr for what is absent
+    integer(c_int) function mom6x_geothermal_in_place(ctx, h, T, S, dt, internal_heat, BFlx_geothermal, dTdt_diag, heat_tend_diag, halo) &
+        bind(C, name="mom6x_geothermal_in_place")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, h, T, S, internal_heat, BFlx_geothermal, dTdt_diag, heat_tend_diag
+      real(c_double), value :: dt ; integer(c_int), value :: halo
     end function
     integer(c_int) function mom6x_thickness_diffuse_init(ctx, p, eos, khth2d) bind(C, name="mom6x_thickness_diffuse_init")
       import :: c_ptr, c_int, mom6x_thickness_diffuse_params

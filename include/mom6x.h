@@ -359,7 +359,8 @@ int  mom6x_device_count(void);
  * 5 coriolis_params, 6 pgf_params, 7 rk2_params, 8 rk2_hooks, 9 eos_params, 10 vertvisc_params, 11 hor_visc_params,
  * 12 remapping_params, 13 regrid_zstar_params, 14 chksum_result, 15 sum_output_params, 16 energy_sums, 17 regrid_rho_params,
  * 18 set_visc_params, 19 thickness_diffuse_params, 20 tracer_hor_diff_params, 21 varmix_params,
- * 22 mixedlayer_restrat_params, 23 MEKE_params, 25 set_diffusivity_params; 24 is not assigned and returns -1): lets ctypes /
+ * 22 mixedlayer_restrat_params, 23 MEKE_params, 25 set_diffusivity_params, 27 diabatic_aux_params, 28 surface_fluxes, 30 energetic_PBL_params, 32 frazil_params,
+ * 33 geothermal_params; 24, 26, 29 and 31 are not assigned and return -1): lets ctypes /
  * ISO_C_BINDING mirrors be checked at start-up.  */
 int  mom6x_struct_size(int which);
 
@@ -1227,6 +1228,80 @@ int mom6x_applyBoundaryFluxesInOut(mom6x_ctx *ctx, double dt, const mom6x_surfac
 /* Synchronises the context's stream and returns how many columns, since the last status call, grounded (:1193), were left with
  * a negative thickness (:1163) and had a flux over land without IGNORE_FLUXES_OVER_LAND (:1178).  Each pointer may be NULL.   */
 int mom6x_diabatic_aux_status(mom6x_ctx *ctx, long *groundings, long *negative_h, long *land_fluxes);
+
+/* ------------------------------------------------------------------------- */
+/* The in-place modifiers of tv%T and tv%S around the column physics of diabatic (MOM_diabatic_driver.F90): make_frazil before
+ * and after it (:371-391, :437-444), geothermal_in_place as the first call of diabatic_ALE (:1373), adjust_salt just before the
+ * tridiagonal solve (:1633).  Each is one lane per column on the context's stream with no allocation, no host synchronisation and
+ * no halo exchange, and gives the reference's results bit for bit.                                                            */
+enum mom6x_tfreeze_form { MOM6X_TFREEZE_LINEAR = 1, MOM6X_TFREEZE_MILLERO = 2, MOM6X_TFREEZE_TEOS10 = 3,
+                          MOM6X_TFREEZE_TEOSPOLY = 4 };   /* MOM_EOS.F90:184-187; TFREEZE_FORM = LINEAR, MILLERO_78, TEOS10, TEOS_POLY */
+/* What make_frazil (src/parameterizations/vertical/MOM_diabatic_aux.F90:110-230) reads of diabatic_aux_CS, tv and of
+ * tv%eqn_of_state for calculate_TFreeze (src/equation_of_state/MOM_EOS.F90:664-744).  GV%H_to_RZ, g_Earth, Angstrom_H and
+ * H_subroundoff are the context's.  Logicals are ints.                                                                        */
+typedef struct mom6x_frazil_params {
+  double C_p;                       /* tv%C_p [Q C-1]: hc = (C_p*H_to_RZ)*h (:179, :202)                                       */
+  double RL2_T2_to_Pa;              /* EOS%RL2_T2_to_Pa (1) } with both 1 the freezing point is taken from S and the pressure  */
+  double S_to_ppt;                  /* EOS%S_to_ppt (1)     } as they are (MOM_EOS.F90:699), otherwise from their products (:715-716) */
+  double degC_to_C;                 /* EOS%degC_to_C (1): applied to the freezing point when it is not 1 (:740)                */
+  double TFr_S0_P0;                 /* TFREEZE_S0_P0 (0.0) [degC]       }                                                     */
+  double dTFr_dS;                   /* DTFREEZE_DS (-0.054) [degC ppt-1] } TFREEZE_FORM = LINEAR (MOM_TFreeze.F90:82)         */
+  double dTFr_dp;                   /* DTFREEZE_DP (0.0) [degC Pa-1]    }                                                     */
+  int    form_of_TFreeze;           /* enum mom6x_tfreeze_form; TEOS10 needs the GSW library: MOM6X_EUNSUPPORTED               */
+  int    reclaim_frazil;            /* RECLAIM_FRAZIL (T): the arm on layer 1 (:167-189)                                       */
+  int    pressure_dependent_frazil; /* PRESSURE_DEPENDENT_FRAZIL (F): the mid-layer pressures (:158-165) instead of 0          */
+  int    use_conT_absS;             /* EOS%use_conT_absS (gsw_sp_from_sr, gsw_ct_from_pt, MOM_EOS.F90:687-694, :733): must be 0 */
+} mom6x_frazil_params;
+/* Keeps the members above; with pressure_dependent_frazil it allocates the routine's `pressure` work array (nk levels), without
+ * it nothing.  MOM6X_EUNSUPPORTED, naming the setting: TFREEZE_FORM = TEOS10, use_conT_absS.  MOM6X_EINVAL: an unknown
+ * form_of_TFreeze, C_p <= 0.                                                                                                  */
+int mom6x_make_frazil_init(mom6x_ctx *ctx, const mom6x_frazil_params *p);
+/* make_frazil(h, tv, G, GV, US, CS, p_surf, halo) :110-230.  h, T (tv%T), S (tv%S): 3-D; frazil (tv%frazil): a plane; p_surf:
+ * a nullable plane, read with pressure_dependent_frazil only; halo: 0 .. the context's halo, the width by which the
+ * computational domain is widened (anything else is MOM6X_EINVAL).  One launch, one lane per column of that range, in the
+ * reference's order: the mid-layer pressures top-down into the work array (:160-163, with the switch only); the reclaim arm on
+ * layer 1 (:167-189), which has no land mask in the reference and none here; the walk from layer nk up to 1 in wet columns
+ * (:191-220), where a layer with T >= 0 and no heat pending reads neither S nor h nor a pressure (:194-195); and
+ * frazil = frazil + fraz_col in every column of the range, land included (:221-223), which turns a stored -0 into +0.
+ * Reads h, S, p_surf; rewrites T and frazil inside the range only.  tv%frazil_was_reset (:226) is the host's flag.            */
+int mom6x_make_frazil(mom6x_ctx *ctx, const double *h, double *T, const double *S, double *frazil, const double *p_surf, int halo);
+/* adjust_salt(h, tv, G, GV, CS) :339-390 with S_min = tv%min_salinity: needs no init call.  h, S (tv%S): 3-D; salt_deficit
+ * (tv%salt_deficit): a plane.  The computational domain only; wet columns are walked from layer nk up to 1, where a layer with
+ * S >= S_min and no deficit pending reads no h (:366-367); the thin-layer test is h <= 10*Angstrom_H (:369, no H_subroundoff)
+ * and the absorbing arm tests <= 0 (:375); salt_deficit = salt_deficit + salt_add_col in every column of the domain (:384-386).
+ * Reads h; rewrites S and salt_deficit on the computational domain only.                                                      */
+int mom6x_adjust_salt(mom6x_ctx *ctx, const double *h, double *S, double *salt_deficit, double min_salinity);
+/* What geothermal_in_place (src/parameterizations/vertical/MOM_geothermal.F90:364-535) reads of geothermal_CS, tv, GV and US.
+ * GV%H_to_RZ, g_Earth, Rho0, Angstrom_H and H_subroundoff are the context's.                                                  */
+typedef struct mom6x_geothermal_params {
+  double C_p;                /* tv%C_p [Q C-1]: Irho_cp (:416), I_Cp (:421), the heat tendency (:523)                          */
+  double geothermal_thick;   /* GEOTHERMAL_THICKNESS (0.1 m, :579) [H]                                                         */
+  double g_Earth_Z_T2;       /* GV%g_Earth_Z_T2 [Z T-2]: BFlx_geothermal (:458)                                                */
+  double RL2_T2_to_Pa;       /* US%RL2_T2_to_Pa (1): the bottom pressure handed to the equation of state                       */
+} mom6x_geothermal_params;
+/* geothermal_init :538 for the in-place mode.  geo_heat_host_plane: CS%geo_heat [Q R Z T-1], a HOST plane of the tile as the
+ * caller has scaled and masked it (:600-606), copied to the device once.  eos: tv%eqn_of_state, NULL without one (then
+ * BFlx_geothermal cannot be asked for).  MOM6X_EUNSUPPORTED: a non-Boussinesq context (:444-451).  MOM6X_EINVAL: a null
+ * argument, an unknown EQN_OF_STATE form, C_p <= 0.  Not carried: geothermal_entraining (:41-359, the layered mode) has no
+ * entry point.                                                                                                                */
+int mom6x_geothermal_init(mom6x_ctx *ctx, const mom6x_geothermal_params *p, const double *geo_heat_host_plane,
+                          const mom6x_eos_params *eos);
+/* geothermal_in_place(h, tv, dt, G, GV, US, CS, BFlx_geothermal, halo) :364-535.  h, T (tv%T), S (tv%S): 3-D; internal_heat
+ * (tv%internal_heat) and BFlx_geothermal: nullable planes; dTdt_diag (internal_heat_temp_tendency) and heat_tend_diag
+ * (internal_heat_heat_tendency, the product at :523): nullable, nk levels, either without the other; halo as in make_frazil.
+ * One lane per column of the widened domain.  With BFlx_geothermal the lane sums H_to_pres*h top-down (:441-443) and takes
+ * the bottom layer's density derivatives, from any EQN_OF_STATE form, at RL2_T2_to_Pa times that pressure (:455-458; as the
+ * reference's EOS domain has it, they are 0 in the columns of the i halo); this needs an equation of state and S.  Without it
+ * the column of h is not summed.  The walk from the bottom (:482-507) reads and writes only the layers that take heat.
+ * Written over the WHOLE array, halos included: BFlx_geothermal = 0 (:434), dTdt_diag = 0 and heat_tend_diag = 0 (:436);
+ * inside the range heat_tend_diag is the product :523 of every layer.  T and internal_heat are rewritten inside the range only.
+ * WHERE THE DEVICE DEPARTS FROM THE REFERENCE: the reference skips a whole j-row of its tile when no column of it is heated
+ * (:476), and with it that row's internal_heat = internal_heat + H_to_RZ*(...) (:509-512).  For an unheated column the addend
+ * is +0, so the skip shows only in an internal_heat of -0, and it depends on the tile layout in the reference itself.  The
+ * device makes the addition in every column of the range.
+ * MOM6X_EINVAL: dt <= 0, a halo outside 0 .. the context's, null h or T, BFlx_geothermal without an equation of state or S.  */
+int mom6x_geothermal_in_place(mom6x_ctx *ctx, const double *h, double *T, const double *S, double dt, double *internal_heat,
+                              double *BFlx_geothermal, double *dTdt_diag, double *heat_tend_diag, int halo);
 
 /* ------------------------------------------------------------------------- */
 /* MOM_energetic_PBL: energetic_PBL (the ePBL surface boundary layer scheme), between applyBoundaryFluxesInOut and the tridiagonal

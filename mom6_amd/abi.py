@@ -503,7 +503,45 @@ class SurfaceFluxes(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in SURFACE_FLUXES_NAMES]
 
 
-EPBL_MSTAR_CONSTANT, EPBL_MSTAR_OM4, EPBL_MSTAR_REICHL_H18 = 0, 2, 3   # enum mom6x_epbl_mstar_scheme (MOM_energetic_PBL.F90:279-282)
+TFREEZE_LINEAR, TFREEZE_MILLERO, TFREEZE_TEOS10, TFREEZE_TEOSPOLY = 1, 2, 3, 4   # enum mom6x_tfreeze_form (MOM_EOS.F90:184-187)
+
+
+class FrazilParams(C.Structure):
+    """mom6x_frazil_params: what make_frazil (MOM_diabatic_aux.F90:110-230) reads of diabatic_aux_CS, tv and tv%eqn_of_state
+    (calculate_TFreeze, MOM_EOS.F90:664-744)."""
+    _fields_ = ([(n, C.c_double) for n in ("C_p", "RL2_T2_to_Pa", "S_to_ppt", "degC_to_C", "TFr_S0_P0", "dTFr_dS", "dTFr_dp")] +
+                [(n, C.c_int) for n in ("form_of_TFreeze", "reclaim_frazil", "pressure_dependent_frazil", "use_conT_absS")])
+
+
+def frazil_params_default(**kw):
+    """diabatic_aux_init (MOM_diabatic_aux.F90:1392-1410) and EOS_init (MOM_EOS.F90:1540-1575) defaults, unscaled:
+    C_P = 3991.86795711963, RECLAIM_FRAZIL = True, PRESSURE_DEPENDENT_FRAZIL = False, TFREEZE_FORM = LINEAR with
+    TFREEZE_S0_P0 = 0, DTFREEZE_DS = -0.054, DTFREEZE_DP = 0."""
+    p = FrazilParams()
+    p.C_p = 3991.86795711963; p.RL2_T2_to_Pa = 1.0; p.S_to_ppt = 1.0; p.degC_to_C = 1.0
+    p.TFr_S0_P0 = 0.0; p.dTFr_dS = -0.054; p.dTFr_dp = 0.0
+    p.form_of_TFreeze = TFREEZE_LINEAR; p.reclaim_frazil = 1; p.pressure_dependent_frazil = 0; p.use_conT_absS = 0
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+class GeothermalParams(C.Structure):
+    """mom6x_geothermal_params: what geothermal_in_place (MOM_geothermal.F90:364-535) reads of geothermal_CS, tv, GV and US."""
+    _fields_ = [(n, C.c_double) for n in ("C_p", "geothermal_thick", "g_Earth_Z_T2", "RL2_T2_to_Pa")]
+
+
+def geothermal_params_default(GV=None, **kw):
+    """geothermal_init (MOM_geothermal.F90:579) defaults, Boussinesq and unscaled: GEOTHERMAL_THICKNESS = 0.1 m."""
+    GV = GV if GV is not None else vgrid_default()
+    p = GeothermalParams()
+    p.C_p = 3991.86795711963; p.geothermal_thick = 0.1 * GV.Z_to_H; p.g_Earth_Z_T2 = GV.g_Earth; p.RL2_T2_to_Pa = 1.0
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+EPBL_MSTAR_CONSTANT, EPBL_MSTAR_OM4, EPBL_MSTAR_REICHL_H18 = 0, 2, 3  # enum mom6x_epbl_mstar_scheme (MOM_energetic_PBL.F90:279-282)
 EPBL_WT_CUBE_ROOT_TKE, EPBL_WT_REICHL_H18 = 0, 1                     # enum mom6x_epbl_wT_scheme (:288-290)
 
 
@@ -811,6 +849,13 @@ def load_library(path=None):
         lib.mom6x_energetic_PBL.argtypes = [vp] * 11 + [C.c_double] + [vp] * 14
         lib.mom6x_energetic_PBL_get_MLD.argtypes = [vp, vp, vp, C.c_double]
         lib.mom6x_ePBL_augment_Kd.argtypes = [vp] * 6 + [C.c_int, C.c_double, vp, vp]
+    if hasattr(lib, "mom6x_make_frazil"):
+        vp = C.c_void_p
+        lib.mom6x_make_frazil_init.argtypes = [vp, C.POINTER(FrazilParams)]
+        lib.mom6x_make_frazil.argtypes = [vp] * 6 + [C.c_int]
+        lib.mom6x_adjust_salt.argtypes = [vp] * 4 + [C.c_double]
+        lib.mom6x_geothermal_init.argtypes = [vp, C.POINTER(GeothermalParams), vp, C.POINTER(EOSParams)]
+        lib.mom6x_geothermal_in_place.argtypes = [vp] * 4 + [C.c_double] + [vp] * 4 + [C.c_int]
     if path is None:
         _lib = lib
     return lib

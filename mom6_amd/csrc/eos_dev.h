@@ -651,6 +651,41 @@ __device__ __forceinline__ void eos_specvol_derivs(const EOS &E, double T, doubl
   }
 }
 
+// calculate_TFreeze(S, pressure, T_fr, EOS) for one point: calculate_TFreeze_1d (MOM_EOS.F90:664-744) without use_conT_absS
+// (TFreeze_S = S, :696), over TFREEZE_FORM = LINEAR (MOM_TFreeze.F90:82), MILLERO_78 (:129) and TEOS_POLY (:196-200) in the
+// reference's parenthesisation.  E: RL2_T2_to_Pa, S_to_ppt, degC_to_C, TFr_S0_P0, dTFr_dS, dTFr_dp, form_of_TFreeze, and `zero`, 0.0 as
+// a run-time value: max(S, 0.0) against the literal would be compiled to v_max_f64, which loses the sign of S = -0 (DaK::zero).
+template <class EOS>
+__device__ __forceinline__ double eos_TFreeze(const EOS &E, double S, double pressure) {
+  double Sa = S, pres = pressure;
+  if (!((E.RL2_T2_to_Pa == 1.0) && (E.S_to_ppt == 1.0))) {   // :713-717
+    pres = E.RL2_T2_to_Pa * pressure;
+    Sa = E.S_to_ppt * S;
+  }
+  double T_fr;
+  if (E.form_of_TFreeze == MOM6X_TFREEZE_LINEAR) {
+    T_fr = (E.TFr_S0_P0 + E.dTFr_dS * Sa) + E.dTFr_dp * pres;
+  } else if (E.form_of_TFreeze == MOM6X_TFREEZE_MILLERO) {
+    const double cS1 = -0.0575, cS3_2 = 1.710523e-3, cS2 = -2.154996e-4, dTFr_dp = -7.75e-8;
+    T_fr = Sa * (cS1 + (cS3_2 * sqrt(fmax1(Sa, E.zero)) + cS2 * Sa)) + dTFr_dp * pres;
+  } else {   // TEOS_POLY; TFab: the S**(a/2) * P**b term
+    const double TF00 = 0.017947064327968736, TF20 = -6.076099099929818e-2, TF30 = 4.883198653547851e-3, TF40 = -1.188081601230542e-3,
+                 TF50 = 1.334658511480257e-4, TF60 = -8.722761043208607e-6, TF70 = 2.082038908808201e-7, TF01 = -7.389420998107497e-8,
+                 TF21 = -9.891538123307282e-11, TF31 = -8.987150128406496e-13, TF41 = 1.054318231187074e-12,
+                 TF51 = 3.850133554097069e-14, TF61 = -2.079022768390933e-14, TF71 = 1.242891021876471e-15,
+                 TF02 = -2.110913185058476e-16, TF22 = 3.831132432071728e-19, TF32 = 1.065556599652796e-19,
+                 TF42 = -2.078616693017569e-20, TF52 = 1.596435439942262e-21, TF03 = 2.295491578006229e-25,
+                 TF23 = -7.997496801694032e-27, TF33 = 8.756340772729538e-28, TF43 = 1.338002171109174e-29;
+    const double rS = sqrt(fmax1(Sa, E.zero));
+    T_fr = (TF00 + Sa * (TF20 + rS * (TF30 + rS * (TF40 + rS * (TF50 + rS * (TF60 + rS * TF70)))))) +
+           pres * ((TF01 + Sa * (TF21 + rS * (TF31 + rS * (TF41 + rS * (TF51 + rS * (TF61 + rS * TF71)))))) +
+                   pres * ((TF02 + Sa * (TF22 + rS * (TF32 + rS * (TF42 + rS * TF52)))) +
+                           pres * (TF03 + Sa * (TF23 + rS * (TF33 + rS * TF43)))));
+  }
+  if (E.degC_to_C != 1.0) T_fr = E.degC_to_C * T_fr;   // :740
+  return T_fr;
+}
+
 // The kernels templated on the EOS form (set_visc.hip, thickness_diffuse.hip, lateral_mixing_coeffs.hip): CALL(F) with F the
 // literal 1..8 of `form`, so that CALL can put #F into the label it gives KLAUNCH.  An init call holds `form` to eos_form_known.
 inline bool eos_form_known(const mom6x_eos_params *e) { return e->form >= MOM6X_EOS_LINEAR && e->form <= MOM6X_EOS_ROQUET_SPV; }

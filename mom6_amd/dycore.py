@@ -466,6 +466,39 @@ class Dycore:
         check(self.lib, self.lib.mom6x_diabatic_aux_status(self.ctx, *[C.byref(v) for v in n]))
         return tuple(int(v.value) for v in n)
 
+    # -- make_frazil, adjust_salt (MOM_diabatic_aux), geothermal_in_place (MOM_geothermal) -------
+    def make_frazil_init(self, params):
+        """What make_frazil reads (abi.frazil_params_default(...)); allocates its pressure work array with
+        pressure_dependent_frazil."""
+        self.frazil_params = params
+        check(self.lib, self.lib.mom6x_make_frazil_init(self.ctx, C.byref(params)))
+
+    def make_frazil(self, h, T, S, frazil, p_surf=None, halo=0):
+        """make_frazil (MOM_diabatic_aux.F90:110): T and the plane frazil are rewritten on the computational domain widened by
+        halo; p_surf is read with pressure_dependent_frazil only."""
+        check(self.lib, self.lib.mom6x_make_frazil(self.ctx, _ptr(h), _ptr(T), _ptr(S), _ptr(frazil), _ptr(p_surf), C.c_int(halo)))
+
+    def adjust_salt(self, h, S, salt_deficit, min_salinity):
+        """adjust_salt (MOM_diabatic_aux.F90:339): S and the plane salt_deficit are rewritten on the computational domain."""
+        check(self.lib, self.lib.mom6x_adjust_salt(self.ctx, _ptr(h), _ptr(S), _ptr(salt_deficit), C.c_double(min_salinity)))
+
+    def geothermal_init(self, params, geo_heat, eos=None):
+        """geothermal_init (MOM_geothermal.F90:538) for the in-place mode; geo_heat: CS%geo_heat, a HOST plane of the tile as
+        scaled and masked by the caller; eos: tv%eqn_of_state (None: BFlx_geothermal cannot be asked for)."""
+        self.geothermal_params = params
+        g = np.ascontiguousarray(geo_heat, dtype=np.float64)
+        assert g.size == self.dims.slab, "need a 2-D plane of the tile"
+        check(self.lib, self.lib.mom6x_geothermal_init(self.ctx, C.byref(params), g.ctypes.data_as(C.c_void_p),
+                                                       C.byref(eos) if eos is not None else None))
+
+    def geothermal_in_place(self, h, T, S, dt, internal_heat=None, BFlx_geothermal=None, dTdt_diag=None, heat_tend_diag=None,
+                            halo=0):
+        """geothermal_in_place (MOM_geothermal.F90:364): T is rewritten on the computational domain widened by halo; the
+        planes internal_heat and BFlx_geothermal and the nk-level diagnostics are optional."""
+        check(self.lib, self.lib.mom6x_geothermal_in_place(
+            self.ctx, _ptr(h), _ptr(T), _ptr(S), C.c_double(dt), _ptr(internal_heat), _ptr(BFlx_geothermal), _ptr(dTdt_diag),
+            _ptr(heat_tend_diag), C.c_int(halo)))
+
     # -- MOM_energetic_PBL ---------------------------------------------------------------------
     def energetic_PBL_init(self, params):
         """energetic_PBL_init (MOM_energetic_PBL.F90:3729): abi.energetic_PBL_params_default(...)."""
