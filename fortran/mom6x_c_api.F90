@@ -17,6 +17,7 @@ module mom6x_c_api
   public :: mom6x_diabatic_aux_status
   public :: mom6x_frazil_params, mom6x_make_frazil_init, mom6x_make_frazil, mom6x_adjust_salt
   public :: mom6x_geothermal_params, mom6x_geothermal_init, mom6x_geothermal_in_place
+  public :: mom6x_opacity_params, mom6x_opacity_init, mom6x_set_pen_shortwave, mom6x_opacity_status
   public :: mom6x_energetic_PBL_params, mom6x_energetic_PBL_init, mom6x_energetic_PBL, mom6x_energetic_PBL_get_MLD, mom6x_ePBL_augment_Kd
   public :: mom6x_thickness_diffuse_params, mom6x_thickness_diffuse_init, mom6x_thickness_diffuse
   public :: mom6x_tracer_hor_diff_params, mom6x_tracer_hor_diff_init, mom6x_tracer_hordiff, mom6x_tracer_hordiff_tile
@@ -164,6 +165,11 @@ module mom6x_c_api
   type, bind(C) :: mom6x_geothermal_params   !< what geothermal_in_place (MOM_geothermal.F90:364-535) reads of geothermal_CS, tv, GV and US
     real(c_double) :: C_p, geothermal_thick, g_Earth_Z_T2, RL2_T2_to_Pa
   end type mom6x_geothermal_params
+  type, bind(C) :: mom6x_opacity_params   !< what opacity_init (MOM_opacity.F90:1041-1315) reads into opacity_CS and optics_type for set_opacity
+    real(c_double) :: pen_sw_scale, pen_sw_scale_2nd, sw_1st_exp_ratio, pen_sw_frac, blue_frac, opacity_land_value
+    real(c_double) :: manizza_coef(6), manizza_power(3), morel_coef(6), morel_pen_coef(6), Z_to_m, m_to_Z
+    integer(c_int) :: opacity_scheme, nbands
+  end type mom6x_opacity_params
 
   type, bind(C) :: mom6x_surface_fluxes   !< the members of `forcing` (MOM_forcing_type.F90:80-256) that applyBoundaryFluxesInOut touches: device planes, c_null_ptr where the reference's pointer is not associated
     type(c_ptr) :: sw, lw, latent, sens, evap, lprec, fprec, vprec, lrunoff, frunoff, lrunoff_glc, frunoff_glc, seaice_melt
@@ -551,6 +557,24 @@ module mom6x_c_api
       import :: c_ptr, c_int, c_double
       type(c_ptr), value :: ctx, h, T, S, internal_heat, BFlx_geothermal, dTdt_diag, heat_tend_diag
       real(c_double), value :: dt ; integer(c_int), value :: halo
+    end function
+    !> opacity_init (MOM_opacity.F90:1041): the band-count rules, the coefficients per band, the Ohlmann table
+    integer(c_int) function mom6x_opacity_init(ctx, p) bind(C, name="mom6x_opacity_init")
+      import :: c_ptr, c_int, mom6x_opacity_params
+      type(c_ptr), value :: ctx ; type(mom6x_opacity_params), intent(in) :: p
+    end function
+    !> set_pen_shortwave (MOM_diabatic_aux.F90:621) with set_opacity (MOM_opacity.F90:118): the arrays are device pointers, c_null_ptr for what is absent
+    integer(c_int) function mom6x_set_pen_shortwave(ctx, sw, sw_vis_dir, sw_vis_dif, sw_nir_dir, sw_nir_dif, chl_2d, chl_3d, opacity_scale, &
+        opacity_band, sw_pen_band, SW_pen, SW_vis_pen, opac_diag) bind(C, name="mom6x_set_pen_shortwave")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, sw, sw_vis_dir, sw_vis_dif, sw_nir_dir, sw_nir_dif, chl_2d, chl_3d
+      real(c_double), value :: opacity_scale
+      type(c_ptr), value :: opacity_band, sw_pen_band, SW_pen, SW_vis_pen, opac_diag
+    end function
+    !> the wet points with negative chlorophyll since the last call (the reference's fatal error); synchronises
+    integer(c_int) function mom6x_opacity_status(ctx, negative_chl) bind(C, name="mom6x_opacity_status")
+      import :: c_ptr, c_int, c_long
+      type(c_ptr), value :: ctx ; integer(c_long), intent(out) :: negative_chl
     end function
     integer(c_int) function mom6x_thickness_diffuse_init(ctx, p, eos, khth2d) bind(C, name="mom6x_thickness_diffuse_init")
       import :: c_ptr, c_int, mom6x_thickness_diffuse_params

@@ -360,7 +360,7 @@ int  mom6x_device_count(void);
  * 12 remapping_params, 13 regrid_zstar_params, 14 chksum_result, 15 sum_output_params, 16 energy_sums, 17 regrid_rho_params,
  * 18 set_visc_params, 19 thickness_diffuse_params, 20 tracer_hor_diff_params, 21 varmix_params,
  * 22 mixedlayer_restrat_params, 23 MEKE_params, 25 set_diffusivity_params, 27 diabatic_aux_params, 28 surface_fluxes, 30 energetic_PBL_params, 32 frazil_params,
- * 33 geothermal_params; 24, 26, 29 and 31 are not assigned and return -1): lets ctypes /
+ * 33 geothermal_params, 34 opacity_params; 24, 26, 29 and 31 are not assigned and return -1): lets ctypes /
  * ISO_C_BINDING mirrors be checked at start-up.  */
 int  mom6x_struct_size(int which);
 
@@ -1302,6 +1302,68 @@ int mom6x_geothermal_init(mom6x_ctx *ctx, const mom6x_geothermal_params *p, cons
  * MOM6X_EINVAL: dt <= 0, a halo outside 0 .. the context's, null h or T, BFlx_geothermal without an equation of state or S.  */
 int mom6x_geothermal_in_place(mom6x_ctx *ctx, const double *h, double *T, const double *S, double dt, double *internal_heat,
                               double *BFlx_geothermal, double *dTdt_diag, double *heat_tend_diag, int halo);
+
+/* ------------------------------------------------------------------------- */
+/* The shortwave optics: set_pen_shortwave (src/parameterizations/vertical/MOM_diabatic_aux.F90:621-677) with set_opacity
+ * (src/parameterizations/vertical/MOM_opacity.F90:118-240), called in diabatic_ALE before applyBoundaryFluxesInOut
+ * (MOM_diabatic_driver.F90).  They produce the optics%opacity_band and optics%sw_pen_band that
+ * mom6x_applyBoundaryFluxesInOut reads, from the shortwave planes of `forcing` and, at most, one field of chlorophyll.           */
+enum mom6x_opacity_scheme { MOM6X_OPACITY_MANIZZA_05 = 1, MOM6X_OPACITY_MOREL_88 = 2, MOM6X_OPACITY_SINGLE_EXP = 3,
+                            MOM6X_OPACITY_DOUBLE_EXP = 4, MOM6X_OPACITY_OHLMANN_03 = 5 };   /* MOM_opacity.F90:105-106 */
+/* What opacity_init (MOM_opacity.F90:1041-1315) reads into opacity_CS and optics_type for set_opacity.  GV%Angstrom_Z is taken
+ * as H_to_Z*Angstrom_H of the context (the same length in a Boussinesq model), GV%dZ_subroundoff is the context's.              */
+typedef struct mom6x_opacity_params {
+  double pen_sw_scale;        /* PEN_SW_SCALE (0.0) [Z]: :157, :166, :182                                                       */
+  double pen_sw_scale_2nd;    /* PEN_SW_SCALE_2ND (0.0) [Z]: DOUBLE_EXP, :163                                                   */
+  double sw_1st_exp_ratio;    /* SW_1ST_EXP_RATIO (0.0): DOUBLE_EXP, :174-175                                                   */
+  double pen_sw_frac;         /* PEN_SW_FRAC (0.0): SINGLE_EXP, :190                                                            */
+  double blue_frac;           /* BLUE_FRAC_SW (0.5): MANIZZA_05, :369-372                                                       */
+  double opacity_land_value;  /* OPACITY_LAND_VALUE (10 m-1) [Z-1]: :439, :454, :466                                            */
+  double manizza_coef[6];     /* OPACITY_VALUES_MANIZZA (0.0232, 0.074, 0.225, 0.037, 2.86, 0.0) [Z-1]: coef_1, coef_2 per band */
+  double manizza_power[3];    /* CHOROPHYLL_POWER_MANIZZA (0.674, 0.629, 0.0)                                                   */
+  double morel_coef[6];       /* OPACITY_VALUES_MOREL (7.925, -6.644, 3.662, -1.815, -0.218, 0.502) [Z]: :490-492               */
+  double morel_pen_coef[6];   /* SW_PEN_FRAC_COEFS_MOREL (0.321, 0.008, 0.132, 0.038, -0.017, -0.007): :510-512                 */
+  double Z_to_m;              /* US%Z_to_m (1): the Ohlmann opacities, :469                                                     */
+  double m_to_Z;              /* US%m_to_Z (1): the length of the opacity diagnostic, :228                                      */
+  int    opacity_scheme;      /* enum mom6x_opacity_scheme: OPACITY_SCHEME with VAR_PEN_SW, EXP_OPACITY_SCHEME without          */
+  int    nbands;              /* PEN_SW_NBANDS (1): 0 .. 4                                                                      */
+} mom6x_opacity_params;
+/* What opacity_init does with the parameters, on the host: the band-count rules (:1151-1160: DOUBLE_EXP and OHLMANN_03 need 2
+ * bands, SINGLE_EXP 1); the coefficients of MANIZZA_05 per band, band 3's for the bands from 4 on (:1246-1254); chl_dep_bands
+ * and the fold of a chlorophyll coefficient whose power is 0 into the constant (:1256-1269); with OHLMANN_03 the table of 401
+ * entries (init_ohlmann_table :1321-1430), uploaded once.  It allocates one device counter.  nbands = 0 is accepted where the
+ * rules allow it, and mom6x_set_pen_shortwave then does nothing.  MOM6X_EINVAL: a null argument, an unknown scheme, a negative
+ * nbands, a broken band-count rule.  MOM6X_EUNSUPPORTED, naming the setting: more than 4 bands (the limit of
+ * mom6x_applyBoundaryFluxesInOut), a non-Boussinesq context (the SpV_avg scaling of extract_optics_slice :555).  Not carried:
+ * sumSWoverBands, the band wavelengths, and the once-only warning of :310-318 (the host knows which pointers it passes).       */
+int mom6x_opacity_init(mom6x_ctx *ctx, const mom6x_opacity_params *p);
+/* set_pen_shortwave(optics, fluxes, G, GV, US, CS, opacity, tracer_flow_CSp) MOM_diabatic_aux.F90:621-677 with set_opacity
+ * MOM_opacity.F90:118-240, opacity_from_chl :245-477, opacity_morel and SW_pen_frac_morel :481-513, lookup_ohlmann_swpen and
+ * lookup_ohlmann_opacity :1433-1485, and the product of extract_optics_slice :559.  All arrays are device pointers.
+ * sw (fluxes%sw), sw_vis_dir, sw_vis_dif, sw_nir_dir, sw_nir_dif: planes, NULL where the reference's pointer is not associated.
+ * chl_2d: the plane time_interp_external gave the host (CHL_FROM_FILE); chl_3d: the model's own chlorophyll, nk levels
+ * (get_chl_from_model); both NULL: the exponential arm :152-193.  opacity_band: nbands 3-D arrays, band n at offset
+ * n*nk*slab; sw_pen_band: nbands planes, band n at offset n*slab: the layout mom6x_applyBoundaryFluxesInOut reads, so the two
+ * pointers pass straight on.  The value stored in opacity_band is opacity_scale*opacity, the single product of :559: the caller
+ * passes GV%H_to_Z, and with 1.0 the array is optics%opacity_band itself.  Nullable diagnostics: SW_pen (:197-206) and
+ * SW_vis_pen (:207-226, bands 1 and 2 only under MANIZZA_05), planes; opac_diag, nbands 3-D arrays laid out as opacity_band, of
+ * tanh(op_diag_len*op)/op_diag_len from the unscaled opacity (:227-237).
+ * One launch on the context's stream, one lane per column, no allocation, no host synchronisation, no halo exchange.  Every
+ * output is written on the computational domain only; the caller's halo is kept.  With chl_2d or without chlorophyll the
+ * opacity of a column is evaluated once and stored at every layer (the reference evaluates the same expression nk times).
+ * WHERE THE DEVICE DEPARTS FROM THE REFERENCE: a negative chlorophyll at a wet point (mask2dT > 0) is FATAL in the reference
+ * (MOM_diabatic_aux.F90:649, MOM_opacity.F90:328, :338).  The device cannot stop: it counts such points
+ * (mom6x_opacity_status) and stores there what the formulas give; everywhere else the results are the reference's.
+ * MOM6X_EINVAL: a call before init; both chl_2d and chl_3d; MANIZZA_05, MOREL_88 or OHLMANN_03 without chlorophyll; SINGLE_EXP
+ * or DOUBLE_EXP with it; OHLMANN_03 with neither sw nor all four band planes, or with the visible pair but not the near-infrared
+ * one (:410 and the dereference at :406); nbands > 0 with a null opacity_band or sw_pen_band.                                  */
+int mom6x_set_pen_shortwave(mom6x_ctx *ctx, const double *sw, const double *sw_vis_dir, const double *sw_vis_dif,
+                            const double *sw_nir_dir, const double *sw_nir_dif, const double *chl_2d, const double *chl_3d,
+                            double opacity_scale, double *opacity_band, double *sw_pen_band, double *SW_pen, double *SW_vis_pen,
+                            double *opac_diag);
+/* Synchronises the stream.  *negative_chl: the wet points (mask2dT > 0) with negative chlorophyll since the last status call,
+ * one per (i,j) for chl_2d and one per cell for chl_3d.  The pointer may be NULL.                                              */
+int mom6x_opacity_status(mom6x_ctx *ctx, long *negative_chl);
 
 /* ------------------------------------------------------------------------- */
 /* MOM_energetic_PBL: energetic_PBL (the ePBL surface boundary layer scheme), between applyBoundaryFluxesInOut and the tridiagonal

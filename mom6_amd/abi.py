@@ -541,6 +541,40 @@ def geothermal_params_default(GV=None, **kw):
     return p
 
 
+OPACITY_MANIZZA_05, OPACITY_MOREL_88, OPACITY_SINGLE_EXP, OPACITY_DOUBLE_EXP, OPACITY_OHLMANN_03 = 1, 2, 3, 4, 5   # enum mom6x_opacity_scheme (MOM_opacity.F90:105-106)
+
+
+class OpacityParams(C.Structure):
+    """mom6x_opacity_params: what opacity_init (MOM_opacity.F90:1041-1315) reads into opacity_CS and optics_type for set_opacity."""
+    _fields_ = ([(n, C.c_double) for n in ("pen_sw_scale", "pen_sw_scale_2nd", "sw_1st_exp_ratio", "pen_sw_frac", "blue_frac",
+                                           "opacity_land_value")] +
+                [("manizza_coef", C.c_double * 6), ("manizza_power", C.c_double * 3), ("morel_coef", C.c_double * 6),
+                 ("morel_pen_coef", C.c_double * 6), ("Z_to_m", C.c_double), ("m_to_Z", C.c_double),
+                 ("opacity_scheme", C.c_int), ("nbands", C.c_int)])
+
+
+def opacity_params_default(**kw):
+    """opacity_init (MOM_opacity.F90:1104-1106, :1125-1145, :1193, :1198, :1205, :1210, :1287) defaults, unscaled, with
+    VAR_PEN_SW = True: OPACITY_SCHEME = MANIZZA_05, PEN_SW_NBANDS = 1, BLUE_FRAC_SW = 0.5, PEN_SW_SCALE = PEN_SW_SCALE_2ND =
+    SW_1ST_EXP_RATIO = PEN_SW_FRAC = 0, OPACITY_LAND_VALUE = 10 m-1 and the Manizza and Morel coefficients.  Array members take
+    a sequence.  SINGLE_EXP carries sw_1st_exp_ratio = 1 in the reference (:1141); it is not read by that scheme."""
+    p = OpacityParams()
+    p.pen_sw_scale = 0.0; p.pen_sw_scale_2nd = 0.0; p.sw_1st_exp_ratio = 0.0; p.pen_sw_frac = 0.0; p.blue_frac = 0.5
+    p.opacity_land_value = 10.0
+    p.manizza_coef[:] = (0.0232, 0.074, 0.225, 0.037, 2.86, 0.0)
+    p.manizza_power[:] = (0.674, 0.629, 0.0)
+    p.morel_coef[:] = (7.925, -6.644, 3.662, -1.815, -0.218, 0.502)
+    p.morel_pen_coef[:] = (0.321, 0.008, 0.132, 0.038, -0.017, -0.007)
+    p.Z_to_m = 1.0; p.m_to_Z = 1.0
+    p.opacity_scheme = OPACITY_MANIZZA_05; p.nbands = 1
+    for k, v in kw.items():
+        if k in ("manizza_coef", "manizza_power", "morel_coef", "morel_pen_coef"):
+            getattr(p, k)[:] = tuple(v)
+        else:
+            setattr(p, k, v)
+    return p
+
+
 EPBL_MSTAR_CONSTANT, EPBL_MSTAR_OM4, EPBL_MSTAR_REICHL_H18 = 0, 2, 3  # enum mom6x_epbl_mstar_scheme (MOM_energetic_PBL.F90:279-282)
 EPBL_WT_CUBE_ROOT_TKE, EPBL_WT_REICHL_H18 = 0, 1                     # enum mom6x_epbl_wT_scheme (:288-290)
 
@@ -856,6 +890,11 @@ def load_library(path=None):
         lib.mom6x_adjust_salt.argtypes = [vp] * 4 + [C.c_double]
         lib.mom6x_geothermal_init.argtypes = [vp, C.POINTER(GeothermalParams), vp, C.POINTER(EOSParams)]
         lib.mom6x_geothermal_in_place.argtypes = [vp] * 4 + [C.c_double] + [vp] * 4 + [C.c_int]
+    if hasattr(lib, "mom6x_set_pen_shortwave"):
+        vp = C.c_void_p
+        lib.mom6x_opacity_init.argtypes = [vp, C.POINTER(OpacityParams)]
+        lib.mom6x_set_pen_shortwave.argtypes = [vp] * 8 + [C.c_double] + [vp] * 5
+        lib.mom6x_opacity_status.argtypes = [vp, C.POINTER(C.c_long)]
     if path is None:
         _lib = lib
     return lib

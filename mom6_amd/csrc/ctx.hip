@@ -180,6 +180,7 @@ extern "C" int mom6x_struct_size(int which) {
     case 30: return (int)sizeof(mom6x_energetic_PBL_params);
     case 32: return (int)sizeof(mom6x_frazil_params);
     case 33: return (int)sizeof(mom6x_geothermal_params);
+    case 34: return (int)sizeof(mom6x_opacity_params);
     default: return -1;
   }
 }
@@ -261,6 +262,7 @@ extern "C" int mom6x_ctx_destroy(mom6x_ctx *c) {
   diabatic_aux_free(c);
   energetic_PBL_free(c);
   diabatic_TS_free(c);
+  opacity_free(c);
   comm_free(c);
   for (int m = 0; m < MOM6X_NSCR; m++) (void)hipFree(c->scr[m]);
   (void)hipFree(c->G); (void)hipFree(c->flag);

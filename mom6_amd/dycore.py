@@ -499,6 +499,28 @@ class Dycore:
             self.ctx, _ptr(h), _ptr(T), _ptr(S), C.c_double(dt), _ptr(internal_heat), _ptr(BFlx_geothermal), _ptr(dTdt_diag),
             _ptr(heat_tend_diag), C.c_int(halo)))
 
+    # -- set_pen_shortwave (MOM_diabatic_aux) with set_opacity (MOM_opacity) ----------------------
+    def opacity_init(self, params):
+        """opacity_init (MOM_opacity.F90:1041) with the parameters of abi.opacity_params_default(...): the band-count rules, the
+        coefficients per band and, with OHLMANN_03, the lookup table."""
+        self.opacity_params = params
+        check(self.lib, self.lib.mom6x_opacity_init(self.ctx, C.byref(params)))
+
+    def set_pen_shortwave(self, opacity_band, sw_pen_band, sw=None, sw_vis_dir=None, sw_vis_dif=None, sw_nir_dir=None,
+                          sw_nir_dif=None, chl_2d=None, chl_3d=None, opacity_scale=1.0, SW_pen=None, SW_vis_pen=None, opac_diag=None):
+        """set_pen_shortwave (MOM_diabatic_aux.F90:621) with set_opacity (MOM_opacity.F90:118): opacity_band (nbands 3-D arrays,
+        band-major, times opacity_scale) and sw_pen_band (nbands planes) are written on the computational domain, in the layout
+        applyBoundaryFluxesInOut reads; the shortwave planes, the chlorophyll and the diagnostics are optional."""
+        check(self.lib, self.lib.mom6x_set_pen_shortwave(
+            self.ctx, _ptr(sw), _ptr(sw_vis_dir), _ptr(sw_vis_dif), _ptr(sw_nir_dir), _ptr(sw_nir_dif), _ptr(chl_2d), _ptr(chl_3d),
+            C.c_double(opacity_scale), _ptr(opacity_band), _ptr(sw_pen_band), _ptr(SW_pen), _ptr(SW_vis_pen), _ptr(opac_diag)))
+
+    def opacity_status(self):
+        """The wet points with negative chlorophyll since the last call (the reference's fatal error); synchronises."""
+        n = C.c_long(0)
+        check(self.lib, self.lib.mom6x_opacity_status(self.ctx, C.byref(n)))
+        return int(n.value)
+
     # -- MOM_energetic_PBL ---------------------------------------------------------------------
     def energetic_PBL_init(self, params):
         """energetic_PBL_init (MOM_energetic_PBL.F90:3729): abi.energetic_PBL_params_default(...)."""
