@@ -1387,7 +1387,7 @@ typedef struct mom6x_energetic_PBL_params {
   double RH18_mstar_cn1, RH18_mstar_cn2, RH18_mstar_cn3, RH18_mstar_cs1, RH18_mstar_cs2;   /* REICHL_H18                        */
   double nstar;              /* NSTAR                                                                                            */
   double mstar_convect_coef; /* MSTAR_CONV_ADJ                                                                                   */
-  double transLay_scale;     /* EPBL_TRANSITION_SCALE                                                                            */
+  double transLay_scale;     /* EPBL_TRANSITION_SCALE (outside (0, 1) with Use_MLD_iteration the reference stops, :3969; taken here) */
   double MLD_tol;            /* EPBL_MLD_TOLERANCE [Z]                                                                           */
   double min_mix_len;        /* EPBL_MIN_MIX_LEN [Z]                                                                             */
   double MixLenExponent;     /* MIX_LEN_EXPONENT                                                                                 */

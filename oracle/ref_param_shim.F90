@@ -1,0 +1,310 @@
+!> ORACLE SUPPORT (test infrastructure only): bind(C) doors into the reference's parameterization modules, compiled where
+!! they lie against the stand-ins of oracle/ref_standins.F90 into oracle/_ref/libref_param.so (see oracle/Makefile):
+!! MOM_EOS_Wright.F90, MOM_EOS_Wright_full.F90, MOM_EOS_Wright_red.F90, MOM_EOS_linear.F90, MOM_intrinsic_functions.F90,
+!! MOM_opacity.F90 and MOM_energetic_PBL.F90, with MOM_unit_scaling.F90 and MOM_string_functions.F90.
+!! tests/ref_param.py loads the library and holds the parameter-name maps; tests/test_ref_parity_cpu.py holds the python
+!! restatements under tests/ to these doors.  Nothing of the reference is copied here.
+!!
+!! Arrays come in the project's pitched tile layout: a plane is [nj_mem, ni_mem] in C order, which is (ni_mem, nj_mem) here, so
+!! the data domain is isd = jsd = 1, ied = ni_mem, jed = nj_mem, and idx = (isc, iec, jsc, jec) names the computational domain
+!! (1-based).  Planes at vorticity points have the same extents (IsdB = 1), the point (I, J) lying north-east of (i, j).
+!! vgr = (Rho0, g_Earth_Z_T2, Angstrom_H, Angstrom_Z, H_subroundoff, dZ_subroundoff, H_to_Z, Z_to_H, H_to_RZ, RZ_to_H, H_to_m,
+!! m_to_H, H_to_MKS, HZ_T_to_m2_s).  Every door that runs a module returns the number of FATAL messages it met.
+module ref_param_shim
+  use, intrinsic :: iso_c_binding
+  use MOM_error_handler, only : standin_fatal_count
+  use MOM_file_parser, only : param_file_type, standin_clear_params, standin_set_real, standin_set_int, standin_set_char, &
+                              standin_set_reals
+  use MOM_diag_mediator, only : diag_ctrl, time_type, standin_clear_diags, standin_want_diag, standin_diag_size, standin_get_diag
+  use MOM_grid, only : ocean_grid_type
+  use MOM_verticalGrid, only : verticalGrid_type
+  use MOM_unit_scaling, only : unit_scale_type, unit_scaling_init, unit_scaling_end
+  use MOM_variables, only : thermo_var_ptrs, vertvisc_type
+  use MOM_EOS, only : EOS_type
+  use MOM_forcing_type, only : forcing
+  use MOM_wave_interface, only : wave_parameters_CS
+  use MOM_stochastics, only : stochastic_CS
+  use MOM_EOS_Wright, only : buggy_Wright_EOS
+  use MOM_EOS_Wright_full, only : Wright_full_EOS
+  use MOM_EOS_Wright_red, only : Wright_red_EOS
+  use MOM_EOS_linear, only : linear_EOS
+  use MOM_EOS_base_type, only : EOS_base
+  use MOM_intrinsic_functions, only : cuberoot, invcosh
+  use MOM_opacity, only : optics_type, opacity_CS, opacity_init, set_opacity, opacity_end, absorbRemainingSW, sumSWoverBands
+  use MOM_energetic_PBL, only : energetic_PBL_CS, energetic_PBL_init, energetic_PBL, energetic_PBL_get_MLD, energetic_PBL_end
+  implicit none
+contains
+  function fstr(s) result(f)
+    character(kind=c_char), intent(in) :: s(*) ; character(len=:), allocatable :: f ; integer :: n, m
+    n = 0
+    do while (s(n+1) /= c_null_char) ; n = n + 1 ; enddo
+    allocate(character(len=n) :: f)
+    do m = 1, n ; f(m:m) = s(m) ; enddo
+  end function fstr
+
+  ! ---- the parameter table, the diagnostics asked for and the capture store ----
+  subroutine ref_param_clear() bind(C, name="ref_param_clear")
+    call standin_clear_params() ; call standin_clear_diags() ; standin_fatal_count = 0
+  end subroutine
+  subroutine ref_set_real(name, value) bind(C, name="ref_set_real")
+    character(kind=c_char), intent(in) :: name(*) ; real(c_double), value :: value
+    call standin_set_real(fstr(name), value)
+  end subroutine
+  subroutine ref_set_reals(name, n, values) bind(C, name="ref_set_reals")
+    character(kind=c_char), intent(in) :: name(*) ; integer(c_int), value :: n ; real(c_double), intent(in) :: values(n)
+    call standin_set_reals(fstr(name), values)
+  end subroutine
+  subroutine ref_set_int(name, value) bind(C, name="ref_set_int")
+    character(kind=c_char), intent(in) :: name(*) ; integer(c_int), value :: value
+    call standin_set_int(fstr(name), int(value))
+  end subroutine
+  subroutine ref_set_char(name, value) bind(C, name="ref_set_char")
+    character(kind=c_char), intent(in) :: name(*), value(*)
+    call standin_set_char(fstr(name), fstr(value))
+  end subroutine
+  subroutine ref_want_diag(name) bind(C, name="ref_want_diag")
+    character(kind=c_char), intent(in) :: name(*)
+    call standin_want_diag(fstr(name))
+  end subroutine
+  integer(c_int) function ref_diag_size(name) bind(C, name="ref_diag_size")
+    character(kind=c_char), intent(in) :: name(*)
+    ref_diag_size = standin_diag_size(fstr(name))
+  end function
+  subroutine ref_get_diag(name, n, out) bind(C, name="ref_get_diag")
+    character(kind=c_char), intent(in) :: name(*) ; integer(c_int), value :: n ; real(c_double), intent(inout) :: out(n)
+    call standin_get_diag(fstr(name), out)
+  end subroutine
+
+  ! ---- equations of state and intrinsic functions ----
+  subroutine eos_points(eos, n, T, S, p, rho_ref, rho, rho_anom, spv, drho_dT, drho_dS, dSV_dT, dSV_dS, rho_c, drho_dp)
+    class(EOS_base), intent(in) :: eos ; integer, intent(in) :: n
+    real, intent(in) :: T(n), S(n), p(n), rho_ref
+    real, intent(out) :: rho(n), rho_anom(n), spv(n), drho_dT(n), drho_dS(n), dSV_dT(n), dSV_dS(n), rho_c(n), drho_dp(n)
+    integer :: i
+    do i = 1, n
+      rho(i) = eos%density_elem(T(i), S(i), p(i))
+      rho_anom(i) = eos%density_anomaly_elem(T(i), S(i), p(i), rho_ref)
+      spv(i) = eos%spec_vol_elem(T(i), S(i), p(i))
+      call eos%calculate_density_derivs_elem(T(i), S(i), p(i), drho_dT(i), drho_dS(i))
+      call eos%calculate_specvol_derivs_elem(T(i), S(i), p(i), dSV_dT(i), dSV_dS(i))
+      call eos%calculate_compress_elem(T(i), S(i), p(i), rho_c(i), drho_dp(i))
+    enddo
+  end subroutine eos_points
+  !> src/equation_of_state/MOM_EOS_Wright.F90 (the default WRIGHT): density_elem, density_anomaly_elem, spec_vol_elem,
+  !! calculate_density_derivs_elem, calculate_specvol_derivs_elem and calculate_compress_elem of n points.
+  subroutine ref_WRIGHT(n, T, S, p, rho_ref, rho, rho_anom, spv, drho_dT, drho_dS, dSV_dT, dSV_dS, rho_c, drho_dp) &
+      bind(C, name="ref_WRIGHT")
+    integer(c_int), value :: n ; real(c_double), intent(in) :: T(n), S(n), p(n) ; real(c_double), value :: rho_ref
+    real(c_double), intent(out) :: rho(n), rho_anom(n), spv(n), drho_dT(n), drho_dS(n), dSV_dT(n), dSV_dS(n), rho_c(n), drho_dp(n)
+    type(buggy_Wright_EOS) :: eos
+    call eos_points(eos, int(n), T, S, p, rho_ref, rho, rho_anom, spv, drho_dT, drho_dS, dSV_dT, dSV_dS, rho_c, drho_dp)
+  end subroutine
+  !> src/equation_of_state/MOM_EOS_Wright_full.F90 likewise.
+  subroutine ref_WRIGHT_FULL(n, T, S, p, rho_ref, rho, rho_anom, spv, drho_dT, drho_dS, dSV_dT, dSV_dS, rho_c, drho_dp) &
+      bind(C, name="ref_WRIGHT_FULL")
+    integer(c_int), value :: n ; real(c_double), intent(in) :: T(n), S(n), p(n) ; real(c_double), value :: rho_ref
+    real(c_double), intent(out) :: rho(n), rho_anom(n), spv(n), drho_dT(n), drho_dS(n), dSV_dT(n), dSV_dS(n), rho_c(n), drho_dp(n)
+    type(Wright_full_EOS) :: eos
+    call eos_points(eos, int(n), T, S, p, rho_ref, rho, rho_anom, spv, drho_dT, drho_dS, dSV_dT, dSV_dS, rho_c, drho_dp)
+  end subroutine
+  !> src/equation_of_state/MOM_EOS_Wright_red.F90 likewise.
+  subroutine ref_WRIGHT_REDUCED(n, T, S, p, rho_ref, rho, rho_anom, spv, drho_dT, drho_dS, dSV_dT, dSV_dS, rho_c, drho_dp) &
+      bind(C, name="ref_WRIGHT_REDUCED")
+    integer(c_int), value :: n ; real(c_double), intent(in) :: T(n), S(n), p(n) ; real(c_double), value :: rho_ref
+    real(c_double), intent(out) :: rho(n), rho_anom(n), spv(n), drho_dT(n), drho_dS(n), dSV_dT(n), dSV_dS(n), rho_c(n), drho_dp(n)
+    type(Wright_red_EOS) :: eos
+    call eos_points(eos, int(n), T, S, p, rho_ref, rho, rho_anom, spv, drho_dT, drho_dS, dSV_dT, dSV_dS, rho_c, drho_dp)
+  end subroutine
+  !> src/equation_of_state/MOM_EOS_linear.F90 likewise, the coefficients set through set_params_linear (:255).
+  subroutine ref_LINEAR(n, T, S, p, rho_ref, coef, rho, rho_anom, spv, drho_dT, drho_dS, dSV_dT, dSV_dS, rho_c, drho_dp) &
+      bind(C, name="ref_LINEAR")
+    integer(c_int), value :: n ; real(c_double), intent(in) :: T(n), S(n), p(n), coef(4) ; real(c_double), value :: rho_ref
+    real(c_double), intent(out) :: rho(n), rho_anom(n), spv(n), drho_dT(n), drho_dS(n), dSV_dT(n), dSV_dS(n), rho_c(n), drho_dp(n)
+    type(linear_EOS) :: eos
+    call eos%set_params_linear(Rho_T0_S0=coef(1), dRho_dT=coef(2), dRho_dS=coef(3), dRho_dp=coef(4))
+    call eos_points(eos, int(n), T, S, p, rho_ref, rho, rho_anom, spv, drho_dT, drho_dS, dSV_dT, dSV_dS, rho_c, drho_dp)
+  end subroutine
+  !> src/framework/MOM_intrinsic_functions.F90: cuberoot :48 and invcosh :32.
+  subroutine ref_cuberoot(n, x, y) bind(C, name="ref_cuberoot")
+    integer(c_int), value :: n ; real(c_double), intent(in) :: x(n) ; real(c_double), intent(out) :: y(n) ; integer :: i
+    do i = 1, n ; y(i) = cuberoot(x(i)) ; enddo
+  end subroutine
+  subroutine ref_invcosh(n, x, y) bind(C, name="ref_invcosh")
+    integer(c_int), value :: n ; real(c_double), intent(in) :: x(n) ; real(c_double), intent(out) :: y(n) ; integer :: i
+    do i = 1, n ; y(i) = invcosh(x(i)) ; enddo
+  end subroutine
+
+  ! ---- the grid, the vertical grid and the unit scaling of a door ----
+  subroutine setup(ni_mem, nj_mem, idx, nk, vgr, mask, cor, pf, G, GV, US)
+    integer, intent(in) :: ni_mem, nj_mem, idx(4), nk ; real, intent(in) :: vgr(14), mask(ni_mem, nj_mem)
+    type(c_ptr), intent(in) :: cor ; type(param_file_type), intent(in) :: pf
+    type(ocean_grid_type), intent(inout) :: G ; type(verticalGrid_type), intent(inout) :: GV ; type(unit_scale_type), pointer :: US
+    real, pointer :: f(:,:)
+    G%isd = 1 ; G%ied = ni_mem ; G%jsd = 1 ; G%jed = nj_mem ; G%IsdB = 1 ; G%IedB = ni_mem ; G%JsdB = 1 ; G%JedB = nj_mem
+    G%isc = idx(1) ; G%iec = idx(2) ; G%jsc = idx(3) ; G%jec = idx(4)
+    G%IscB = G%isc - 1 ; G%IecB = G%iec ; G%JscB = G%jsc - 1 ; G%JecB = G%jec
+    G%HI%isd = G%isd ; G%HI%ied = G%ied ; G%HI%jsd = G%jsd ; G%HI%jed = G%jed ; G%HI%isc = G%isc ; G%HI%iec = G%iec
+    G%HI%jsc = G%jsc ; G%HI%jec = G%jec ; G%HI%IsdB = G%IsdB ; G%HI%IedB = G%IedB ; G%HI%JsdB = G%JsdB ; G%HI%JedB = G%JedB
+    G%HI%IscB = G%IscB ; G%HI%IecB = G%IecB ; G%HI%JscB = G%JscB ; G%HI%JecB = G%JecB
+    allocate(G%mask2dT(ni_mem, nj_mem), G%CoriolisBu(ni_mem, nj_mem), G%geoLonT(ni_mem, nj_mem), G%geoLatT(ni_mem, nj_mem))
+    G%mask2dT(:,:) = mask(:,:) ; G%CoriolisBu(:,:) = 0.0 ; G%geoLonT(:,:) = 0.0 ; G%geoLatT(:,:) = 0.0
+    if (c_associated(cor)) then
+      call c_f_pointer(cor, f, (/ ni_mem, nj_mem /)) ; G%CoriolisBu(:,:) = f(:,:)
+    endif
+    GV%ke = nk ; GV%Boussinesq = .true.
+    GV%Rho0 = vgr(1) ; GV%g_Earth_Z_T2 = vgr(2) ; GV%Angstrom_H = vgr(3) ; GV%Angstrom_Z = vgr(4) ; GV%H_subroundoff = vgr(5)
+    GV%dZ_subroundoff = vgr(6) ; GV%H_to_Z = vgr(7) ; GV%Z_to_H = vgr(8) ; GV%H_to_RZ = vgr(9) ; GV%RZ_to_H = vgr(10)
+    GV%H_to_m = vgr(11) ; GV%m_to_H = vgr(12) ; GV%H_to_MKS = vgr(13) ; GV%HZ_T_to_m2_s = vgr(14)
+    US => NULL()
+    call unit_scaling_init(pf, US)   ! the reference's own, from the *_RESCALE_POWER entries of the table
+  end subroutine setup
+  subroutine plane(p, ni_mem, nj_mem, f)
+    type(c_ptr), intent(in) :: p ; integer, intent(in) :: ni_mem, nj_mem ; real, pointer :: f(:,:)
+    f => NULL()
+    if (c_associated(p)) call c_f_pointer(p, f, (/ ni_mem, nj_mem /))
+  end subroutine plane
+
+  !> opacity_init (MOM_opacity.F90:1019) through the table, then set_opacity (:118) on whole arrays.  The shortwave planes and the
+  !! chlorophyll arrays are C pointers, null for "not associated" / "not present".  opacity_band [nbands, nk, nj_mem, ni_mem] and
+  !! sw_pen_band [nbands, nj_mem, ni_mem] get optics%opacity_band and optics%sw_pen_band; nbands_out gets optics%nbands.  The
+  !! diagnostics asked for with ref_want_diag (SW_pen, SW_vis_pen, opac_1 ...) are read back with ref_get_diag.
+  integer(c_int) function ref_opacity(ni_mem, nj_mem, idx, nk, vgr, mask, sw, vis_dir, vis_dif, nir_dir, nir_dif, chl_2d, chl_3d, &
+                                      nb_max, nbands_out, opacity_band, sw_pen_band) bind(C, name="ref_opacity")
+    integer(c_int), value :: ni_mem, nj_mem, nk, nb_max ; integer(c_int), intent(in) :: idx(4)
+    real(c_double), intent(in) :: vgr(14), mask(ni_mem, nj_mem)
+    type(c_ptr), value :: sw, vis_dir, vis_dif, nir_dir, nir_dif, chl_2d, chl_3d
+    integer(c_int), intent(out) :: nbands_out
+    real(c_double), intent(inout) :: opacity_band(ni_mem, nj_mem, nk, nb_max), sw_pen_band(ni_mem, nj_mem, nb_max)
+    type(ocean_grid_type) :: G ; type(verticalGrid_type) :: GV ; type(unit_scale_type), pointer :: US
+    type(param_file_type) :: pf ; type(diag_ctrl), target :: diag ; type(time_type), target :: Time
+    type(opacity_CS) :: CS ; type(optics_type) :: optics
+    real, pointer, dimension(:,:) :: p_sw, p_vd, p_vf, p_nd, p_nf, c2
+    real, pointer :: c3(:,:,:)
+    integer :: i, j, k, n
+    standin_fatal_count = 0
+    call setup(int(ni_mem), int(nj_mem), int(idx), int(nk), vgr, mask, c_null_ptr, pf, G, GV, US)
+    call opacity_init(Time, G, GV, US, pf, diag, CS, optics)
+    nbands_out = optics%nbands
+    if (standin_fatal_count == 0 .and. optics%nbands <= nb_max) then
+      call plane(sw, int(ni_mem), int(nj_mem), p_sw) ; call plane(vis_dir, int(ni_mem), int(nj_mem), p_vd)
+      call plane(vis_dif, int(ni_mem), int(nj_mem), p_vf) ; call plane(nir_dir, int(ni_mem), int(nj_mem), p_nd)
+      call plane(nir_dif, int(ni_mem), int(nj_mem), p_nf) ; call plane(chl_2d, int(ni_mem), int(nj_mem), c2)
+      c3 => NULL() ; if (c_associated(chl_3d)) call c_f_pointer(chl_3d, c3, (/ int(ni_mem), int(nj_mem), int(nk) /))
+      if (associated(c2)) then
+        call set_opacity(optics, p_sw, p_vd, p_vf, p_nd, p_nf, G, GV, US, CS, chl_2d=c2)
+      elseif (associated(c3)) then
+        call set_opacity(optics, p_sw, p_vd, p_vf, p_nd, p_nf, G, GV, US, CS, chl_3d=c3)
+      else
+        call set_opacity(optics, p_sw, p_vd, p_vf, p_nd, p_nf, G, GV, US, CS)
+      endif
+      do n = 1, optics%nbands
+        do k = 1, nk ; do j = 1, nj_mem ; do i = 1, ni_mem
+          opacity_band(i,j,k,n) = optics%opacity_band(n,i,j,k)
+        enddo ; enddo ; enddo
+        do j = G%jsc, G%jec ; do i = G%isc, G%iec
+          sw_pen_band(i,j,n) = optics%sw_pen_band(n,i,j)
+        enddo ; enddo
+      enddo
+    endif
+    call opacity_end(CS, optics)
+    call unit_scaling_end(US)
+    ref_opacity = standin_fatal_count
+  end function
+
+  !> absorbRemainingSW (MOM_opacity.F90:600) on one j-row of ni points and nk layers, with the optional TKE and dSV_dT (C
+  !! pointers, null: absent).  optics carries nbands, answer_date, PenSW_flux_absorb and PenSW_absorb_Invlen, which is all that
+  !! the routine reads of it.  h, T, TKE, dSV_dT are [nk, ni]; opacity_band [nk, ni, nsw_mem] and Pen_SW_bnd [ni, nsw_mem] with
+  !! nsw_mem = max(nsw, 1), the band first as in the reference.
+  integer(c_int) function ref_absorbRemainingSW(ni, nk, vgr, nsw, answer_date, PenSW_flux_absorb, PenSW_absorb_Invlen, h, &
+        opacity_band, dt, H_limit_fluxes, adjustAbsorptionProfile, absorbAllSW, T, Pen_SW_bnd, TKE, dSV_dT) &
+        bind(C, name="ref_absorbRemainingSW")
+    integer(c_int), value :: ni, nk, nsw, answer_date, adjustAbsorptionProfile, absorbAllSW
+    real(c_double), intent(in) :: vgr(14), h(ni, nk), opacity_band(max(1,nsw), ni, nk)
+    real(c_double), value :: PenSW_flux_absorb, PenSW_absorb_Invlen, dt, H_limit_fluxes
+    real(c_double), intent(inout) :: T(ni, nk), Pen_SW_bnd(max(1,nsw), ni)
+    type(c_ptr), value :: TKE, dSV_dT
+    type(ocean_grid_type) :: G ; type(verticalGrid_type) :: GV ; type(unit_scale_type), pointer :: US
+    type(param_file_type) :: pf ; type(optics_type) :: optics
+    real :: mask(ni, 1)
+    real, pointer :: p_TKE(:,:), p_dSV(:,:)
+    standin_fatal_count = 0
+    mask(:,:) = 1.0
+    call setup(int(ni), 1, (/ 1, int(ni), 1, 1 /), int(nk), vgr, mask, c_null_ptr, pf, G, GV, US)
+    optics%nbands = nsw ; optics%answer_date = answer_date
+    optics%PenSW_flux_absorb = PenSW_flux_absorb ; optics%PenSW_absorb_Invlen = PenSW_absorb_Invlen
+    if (c_associated(TKE) .and. c_associated(dSV_dT)) then
+      call c_f_pointer(TKE, p_TKE, (/ int(ni), int(nk) /)) ; call c_f_pointer(dSV_dT, p_dSV, (/ int(ni), int(nk) /))
+      call absorbRemainingSW(G, GV, US, h, opacity_band, int(nsw), optics, 1, dt, H_limit_fluxes, &
+                             (adjustAbsorptionProfile /= 0), (absorbAllSW /= 0), T, Pen_SW_bnd, TKE=p_TKE, dSV_dT=p_dSV)
+    else
+      call absorbRemainingSW(G, GV, US, h, opacity_band, int(nsw), optics, 1, dt, H_limit_fluxes, &
+                             (adjustAbsorptionProfile /= 0), (absorbAllSW /= 0), T, Pen_SW_bnd)
+    endif
+    call unit_scaling_end(US)
+    ref_absorbRemainingSW = standin_fatal_count
+  end function
+
+  !> sumSWoverBands (MOM_opacity.F90:873) on one j-row: h, dz [nk, ni]; opacity_band [nk, ni, nsw_mem] goes into
+  !! optics%opacity_band of the row; iPen_SW_bnd [ni, nsw_mem]; netPen [nk + 1, ni].
+  integer(c_int) function ref_sumSWoverBands(ni, nk, vgr, nsw, answer_date, PenSW_flux_absorb, PenSW_absorb_Invlen, h, dz, &
+        opacity_band, dt, H_limit_fluxes, absorbAllSW, iPen_SW_bnd, netPen) bind(C, name="ref_sumSWoverBands")
+    integer(c_int), value :: ni, nk, nsw, answer_date, absorbAllSW
+    real(c_double), intent(in) :: vgr(14), h(ni, nk), dz(ni, nk), opacity_band(max(1,nsw), ni, nk), iPen_SW_bnd(max(1,nsw), ni)
+    real(c_double), value :: PenSW_flux_absorb, PenSW_absorb_Invlen, dt, H_limit_fluxes
+    real(c_double), intent(inout) :: netPen(ni, nk+1)
+    type(ocean_grid_type) :: G ; type(verticalGrid_type) :: GV ; type(unit_scale_type), pointer :: US
+    type(param_file_type) :: pf ; type(optics_type) :: optics
+    real :: mask(ni, 1)
+    integer :: i, k, n
+    standin_fatal_count = 0
+    mask(:,:) = 1.0
+    call setup(int(ni), 1, (/ 1, int(ni), 1, 1 /), int(nk), vgr, mask, c_null_ptr, pf, G, GV, US)
+    optics%nbands = nsw ; optics%answer_date = answer_date
+    optics%PenSW_flux_absorb = PenSW_flux_absorb ; optics%PenSW_absorb_Invlen = PenSW_absorb_Invlen
+    allocate(optics%opacity_band(max(1,nsw), ni, 1, nk))
+    do k = 1, nk ; do i = 1, ni ; do n = 1, max(1,nsw) ; optics%opacity_band(n,i,1,k) = opacity_band(n,i,k) ; enddo ; enddo ; enddo
+    call sumSWoverBands(G, GV, US, h, dz, int(nsw), optics, 1, dt, H_limit_fluxes, (absorbAllSW /= 0), iPen_SW_bnd, netPen)
+    call unit_scaling_end(US)
+    ref_sumSWoverBands = standin_fatal_count
+  end function
+
+  !> energetic_PBL_init (MOM_energetic_PBL.F90:3729) through the table, then energetic_PBL (:326) ncalls times on the same
+  !! control structure, then energetic_PBL_get_MLD (:3707).  3-D arrays are [nk, nj_mem, ni_mem] (Kd_int: nk + 1 interfaces).
+  !! u_h and v_h are the velocities at thickness points (read only with MKE_TO_TKE_EFFIC > 0).  Waves is null and stoch_CS has
+  !! pert_epbl false; fluxes carries ustar and ustar_gustless (both the given plane); visc is empty, since every bottom-boundary
+  !! option is off.  The diagnostics asked for with ref_want_diag are read back with ref_get_diag.
+  integer(c_int) function ref_energetic_PBL(ni_mem, nj_mem, idx, nk, vgr, mask, CoriolisBu, h, u_h, v_h, T, S, dSV_dT, dSV_dS, &
+        TKE_forced, ustar, buoy_flux, dt, ncalls, Kd_int, MLD) bind(C, name="ref_energetic_PBL")
+    integer(c_int), value :: ni_mem, nj_mem, nk, ncalls ; integer(c_int), intent(in) :: idx(4)
+    real(c_double), intent(in) :: vgr(14), mask(ni_mem, nj_mem) ; type(c_ptr), value :: CoriolisBu
+    real(c_double), intent(inout) :: h(ni_mem, nj_mem, nk)
+    real(c_double), intent(in), dimension(ni_mem, nj_mem, nk) :: u_h, v_h, dSV_dT, dSV_dS, TKE_forced
+    real(c_double), intent(inout), target :: T(ni_mem, nj_mem, nk), S(ni_mem, nj_mem, nk), ustar(ni_mem, nj_mem)
+    real(c_double), intent(in) :: buoy_flux(ni_mem, nj_mem) ; real(c_double), value :: dt
+    real(c_double), intent(inout) :: Kd_int(ni_mem, nj_mem, nk+1), MLD(ni_mem, nj_mem)
+    type(ocean_grid_type) :: G ; type(verticalGrid_type) :: GV ; type(unit_scale_type), pointer :: US
+    type(param_file_type) :: pf ; type(diag_ctrl), target :: diag ; type(time_type), target :: Time
+    type(energetic_PBL_CS) :: CS ; type(thermo_var_ptrs) :: tv ; type(forcing) :: fluxes ; type(vertvisc_type) :: visc
+    type(EOS_type), target :: eqn ; type(wave_parameters_CS), pointer :: Waves ; type(stochastic_CS), pointer :: stoch
+    real :: BBL_buoy_flux(ni_mem, nj_mem)
+    integer :: m
+    standin_fatal_count = 0
+    call setup(int(ni_mem), int(nj_mem), int(idx), int(nk), vgr, mask, CoriolisBu, pf, G, GV, US)
+    call energetic_PBL_init(Time, G, GV, US, pf, diag, CS)
+    tv%T => T ; tv%S => S ; tv%eqn_of_state => eqn
+    fluxes%ustar => ustar ; fluxes%ustar_gustless => ustar
+    Waves => NULL() ; allocate(stoch) ; stoch%pert_epbl = .false.
+    BBL_buoy_flux(:,:) = 0.0
+    if (standin_fatal_count == 0) then
+      do m = 1, ncalls
+        call energetic_PBL(h, u_h, v_h, tv, fluxes, visc, dt, Kd_int, G, GV, US, CS, stoch, dSV_dT, dSV_dS, TKE_forced, &
+                           buoy_flux, BBL_buoy_flux, Waves)
+      enddo
+      call energetic_PBL_get_MLD(CS, MLD, G, US)
+    endif
+    call energetic_PBL_end(CS)
+    deallocate(stoch)
+    call unit_scaling_end(US)
+    ref_energetic_PBL = standin_fatal_count
+  end function
+end module ref_param_shim

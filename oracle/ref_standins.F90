@@ -1,0 +1,448 @@
+!> oracle/ref_standins.F90 -- ORACLE SUPPORT (test infrastructure only), not product and not reference text.
+!!
+!! The reference's parameterization modules (MOM_opacity.F90, MOM_energetic_PBL.F90) `use` framework modules that need FMS and
+!! netCDF.  oracle/Makefile compiles those two files, and every framework file that does compile on its own, where they lie, against
+!! the interface-only stand-ins below.  The rule is that of tests/fortran_stubs/mom_stubs.F90: each module carries the name of the
+!! MOM6 module it stands for and declares ONLY the derived-type members and procedure signatures that the compiled reference files
+!! touch (names, members and argument lists are interface facts); the bodies are a few lines of bookkeeping written here.
+!!   * get_param answers from a name -> value table that the doors of ref_param_shim.F90 fill (standin_set_*), else with the
+!!     call's default= or defaults=; log_param, log_version, openParameterBlock and closeParameterBlock do nothing;
+!!   * register_diag_field returns a positive id for the names the door has asked for (standin_want_diag) and -1 otherwise;
+!!     post_data copies the posted field into a store keyed by that id, which the door reads back (standin_get_diag);
+!!   * query_averaging_enabled is true;
+!!   * MOM_error(FATAL, ...) prints and counts (standin_fatal_count); it never stops, since a stop would end the test process;
+!!   * EFP sums are plain sums (they feed a debugging printout only).
+!! Stood in for: MOM_error_handler, MOM_coms, MOM_cpu_clock, MOM_time_manager, MOM_hor_index, MOM_domains, MOM_grid,
+!! MOM_verticalGrid, MOM_file_parser, MOM_EOS (the type's name only), MOM_variables, MOM_forcing_type, MOM_diag_mediator,
+!! MOM_debugging, MOM_interface_heights, MOM_wave_interface, MOM_stochastics.
+!! The file is compiled twice: everything but MOM_wave_interface before the reference's own MOM_unit_scaling.F90, and
+!! MOM_wave_interface (whose one procedure takes a unit_scale_type) after it, with -DSTANDINS_AFTER_UNIT_SCALING.
+#ifndef STANDINS_AFTER_UNIT_SCALING
+
+module MOM_error_handler
+  implicit none ; public
+  integer, parameter :: NOTE = 0, WARNING = 1, FATAL = 2
+  integer :: standin_fatal_count = 0     !< FATAL messages since the door last cleared it
+  logical :: standin_print_warnings = .false.
+contains
+  subroutine MOM_error(level, message, all_print)
+    integer, intent(in) :: level ; character(len=*), intent(in) :: message ; logical, optional, intent(in) :: all_print
+    if (level == FATAL) then
+      standin_fatal_count = standin_fatal_count + 1
+      print '(a)', "FATAL (counted, not stopped): "//trim(message) ; flush(6)
+    elseif (level == WARNING .and. standin_print_warnings) then
+      print '(a)', "WARNING: "//trim(message)
+    endif
+  end subroutine MOM_error
+  subroutine MOM_mesg(message, verb, all_print)
+    character(len=*), intent(in) :: message ; integer, optional, intent(in) :: verb ; logical, optional, intent(in) :: all_print
+  end subroutine MOM_mesg
+  logical function is_root_pe()
+    is_root_pe = .true.
+  end function is_root_pe
+end module MOM_error_handler
+
+module MOM_coms
+  implicit none ; private
+  public :: EFP_type, real_to_EFP, EFP_to_real, EFP_sum_across_PEs, operator(+), assignment(=)
+  type :: EFP_type ; real :: v = 0.0 ; end type EFP_type   ! a plain sum: it feeds only a debugging printout
+  interface operator (+) ; module procedure EFP_plus ; end interface
+  interface assignment(=) ; module procedure EFP_assign ; end interface
+contains
+  function EFP_plus(EFP1, EFP2)
+    type(EFP_type) :: EFP_plus ; type(EFP_type), intent(in) :: EFP1, EFP2
+    EFP_plus%v = EFP1%v + EFP2%v
+  end function EFP_plus
+  subroutine EFP_assign(EFP1, EFP2)
+    type(EFP_type), intent(out) :: EFP1 ; type(EFP_type), intent(in) :: EFP2
+    EFP1%v = EFP2%v
+  end subroutine EFP_assign
+  function real_to_EFP(val, overflow)
+    real, intent(in) :: val ; logical, optional, intent(inout) :: overflow ; type(EFP_type) :: real_to_EFP
+    real_to_EFP%v = val
+  end function real_to_EFP
+  function EFP_to_real(EFP1)
+    type(EFP_type), intent(inout) :: EFP1 ; real :: EFP_to_real
+    EFP_to_real = EFP1%v
+  end function EFP_to_real
+  subroutine EFP_sum_across_PEs(EFPs, nval, errors)
+    type(EFP_type), dimension(:), intent(inout) :: EFPs ; integer, intent(in) :: nval
+    logical, dimension(:), optional, intent(out) :: errors
+    if (present(errors)) errors(:) = .false.
+  end subroutine EFP_sum_across_PEs
+end module MOM_coms
+
+module MOM_cpu_clock
+  implicit none ; public
+  integer, parameter :: CLOCK_COMPONENT = 1, CLOCK_SUBCOMPONENT = 11, CLOCK_MODULE_DRIVER = 21, CLOCK_MODULE = 31, CLOCK_ROUTINE = 41
+contains
+  integer function cpu_clock_id(name, grain)
+    character(len=*), intent(in) :: name ; integer, optional, intent(in) :: grain
+    cpu_clock_id = 1
+  end function cpu_clock_id
+  subroutine cpu_clock_begin(id) ; integer, intent(in) :: id ; end subroutine
+  subroutine cpu_clock_end(id) ; integer, intent(in) :: id ; end subroutine
+end module MOM_cpu_clock
+
+module MOM_time_manager
+  implicit none ; public
+  type :: time_type ; integer :: seconds = 0, days = 0 ; end type time_type
+end module MOM_time_manager
+
+module MOM_hor_index
+  implicit none ; public
+  type :: hor_index_type
+    integer :: isc, iec, jsc, jec, isd, ied, jsd, jed, IscB, IecB, JscB, JecB, IsdB, IedB, JsdB, JedB
+    integer :: idg_offset = 0, jdg_offset = 0
+    logical :: symmetric = .true.
+  end type hor_index_type
+end module MOM_hor_index
+
+module MOM_domains
+  implicit none ; public
+  type :: MOM_domain_type ; integer :: dummy = 0 ; end type MOM_domain_type
+  type :: group_pass_type ; integer :: dummy = 0 ; end type group_pass_type
+contains
+  subroutine create_group_pass(group, array, MOM_dom)
+    type(group_pass_type), intent(inout) :: group ; real, dimension(:,:), intent(inout) :: array
+    type(MOM_domain_type), intent(inout) :: MOM_dom
+  end subroutine create_group_pass
+  subroutine do_group_pass(group, MOM_dom)
+    type(group_pass_type), intent(inout) :: group ; type(MOM_domain_type), intent(inout) :: MOM_dom
+  end subroutine do_group_pass
+end module MOM_domains
+
+module MOM_grid
+  use MOM_hor_index, only : hor_index_type
+  implicit none ; public
+  type :: ocean_grid_type
+    type(hor_index_type) :: HI
+    integer :: isc, iec, jsc, jec, isd, ied, jsd, jed, IscB, IecB, JscB, JecB, IsdB, IedB, JsdB, JedB
+    real, allocatable, dimension(:,:) :: mask2dT, CoriolisBu, geoLonT, geoLatT
+  end type ocean_grid_type
+end module MOM_grid
+
+module MOM_verticalGrid
+  implicit none ; public
+  type :: verticalGrid_type
+    integer :: ke
+    logical :: Boussinesq = .true.
+    real :: Rho0, g_Earth_Z_T2, Angstrom_H, Angstrom_Z, H_subroundoff, dZ_subroundoff
+    real :: H_to_Z = 1., Z_to_H = 1., H_to_RZ, RZ_to_H, H_to_m = 1., m_to_H = 1., H_to_MKS = 1., HZ_T_to_m2_s = 1.
+  end type verticalGrid_type
+end module MOM_verticalGrid
+
+module MOM_file_parser
+  implicit none ; private
+  public :: param_file_type, get_param, log_param, log_version, openParameterBlock, closeParameterBlock
+  public :: standin_clear_params, standin_set_real, standin_set_int, standin_set_char, standin_set_reals
+  type :: param_file_type ; integer :: dummy = 0 ; end type param_file_type
+  integer, parameter :: NMAX = 256, AMAX = 32
+  !> the name -> value table the doors fill: one table for the process (the doors run one at a time)
+  integer :: ntab = 0
+  character(len=64) :: tab_name(NMAX) = ""
+  character(len=128) :: tab_char(NMAX) = ""
+  integer :: tab_int(NMAX) = 0, tab_len(NMAX) = 0
+  real :: tab_real(AMAX, NMAX) = 0.0
+  interface get_param
+    module procedure get_param_real, get_param_int, get_param_logical, get_param_char, get_param_real_array
+  end interface
+  interface log_param
+    module procedure log_param_real, log_param_char
+  end interface
+contains
+  subroutine standin_clear_params()
+    ntab = 0
+  end subroutine standin_clear_params
+  integer function slot(name)
+    character(len=*), intent(in) :: name ; integer :: m
+    do m = 1, ntab ; if (trim(tab_name(m)) == trim(name)) then ; slot = m ; return ; endif ; enddo
+    ntab = ntab + 1 ; slot = ntab ; tab_name(ntab) = name ; tab_len(ntab) = 0 ; tab_char(ntab) = "" ; tab_int(ntab) = 0
+  end function slot
+  integer function find(name)
+    character(len=*), intent(in) :: name ; integer :: m
+    find = 0
+    do m = 1, ntab ; if (trim(tab_name(m)) == trim(name)) then ; find = m ; return ; endif ; enddo
+  end function find
+  subroutine standin_set_real(name, value)
+    character(len=*), intent(in) :: name ; real, intent(in) :: value ; integer :: m
+    m = slot(name) ; tab_real(1, m) = value ; tab_len(m) = 1
+  end subroutine standin_set_real
+  subroutine standin_set_reals(name, values)
+    character(len=*), intent(in) :: name ; real, intent(in) :: values(:) ; integer :: m
+    m = slot(name) ; tab_len(m) = min(size(values), AMAX) ; tab_real(1:tab_len(m), m) = values(1:tab_len(m))
+  end subroutine standin_set_reals
+  subroutine standin_set_int(name, value)   ! (logicals too: 0 is false)
+    character(len=*), intent(in) :: name ; integer, intent(in) :: value ; integer :: m
+    m = slot(name) ; tab_int(m) = value
+  end subroutine standin_set_int
+  subroutine standin_set_char(name, value)
+    character(len=*), intent(in) :: name, value ; integer :: m
+    m = slot(name) ; tab_char(m) = value
+  end subroutine standin_set_char
+
+  subroutine get_param_real(CS, modulename, varname, value, desc, units, default, fail_if_missing, do_not_read, do_not_log, &
+                            debuggingParam, scale, unscaled, layoutParam, old_name)
+    type(param_file_type), intent(in) :: CS ; character(len=*), intent(in) :: modulename, varname
+    real, intent(inout) :: value ; character(len=*), optional, intent(in) :: desc, units, old_name
+    real, optional, intent(in) :: default, scale ; real, optional, intent(out) :: unscaled
+    logical, optional, intent(in) :: fail_if_missing, do_not_read, do_not_log, debuggingParam, layoutParam
+    integer :: m
+    m = find(varname)
+    if (m > 0) then ; value = tab_real(1, m)
+    elseif (present(default)) then ; value = default ; endif
+    if (present(unscaled)) unscaled = value
+    if (present(scale)) value = scale * value
+  end subroutine get_param_real
+  subroutine get_param_real_array(CS, modulename, varname, value, desc, units, default, defaults, fail_if_missing, do_not_read, &
+                                  do_not_log, debuggingParam, scale, unscaled, old_name)
+    type(param_file_type), intent(in) :: CS ; character(len=*), intent(in) :: modulename, varname
+    real, dimension(:), intent(inout) :: value ; character(len=*), optional, intent(in) :: desc, units, old_name
+    real, optional, intent(in) :: default, scale ; real, dimension(:), optional, intent(in) :: defaults
+    real, dimension(:), optional, intent(out) :: unscaled
+    logical, optional, intent(in) :: fail_if_missing, do_not_read, do_not_log, debuggingParam
+    integer :: m, n
+    m = find(varname)
+    if (m > 0) then
+      n = min(size(value), tab_len(m)) ; value(1:n) = tab_real(1:n, m)
+    elseif (present(defaults)) then
+      n = min(size(value), size(defaults)) ; value(1:n) = defaults(1:n)
+    elseif (present(default)) then ; value(:) = default ; endif
+    if (present(unscaled)) unscaled(:) = value(:)
+    if (present(scale)) value(:) = scale * value(:)
+  end subroutine get_param_real_array
+  subroutine get_param_int(CS, modulename, varname, value, desc, units, default, fail_if_missing, do_not_read, do_not_log, &
+                           debuggingParam, layoutParam, old_name)
+    type(param_file_type), intent(in) :: CS ; character(len=*), intent(in) :: modulename, varname
+    integer, intent(inout) :: value ; character(len=*), optional, intent(in) :: desc, units, old_name
+    integer, optional, intent(in) :: default
+    logical, optional, intent(in) :: fail_if_missing, do_not_read, do_not_log, debuggingParam, layoutParam
+    integer :: m
+    m = find(varname)
+    if (m > 0) then ; value = tab_int(m)
+    elseif (present(default)) then ; value = default ; endif
+  end subroutine get_param_int
+  subroutine get_param_logical(CS, modulename, varname, value, desc, units, default, fail_if_missing, do_not_read, do_not_log, &
+                               debuggingParam, layoutParam, old_name)
+    type(param_file_type), intent(in) :: CS ; character(len=*), intent(in) :: modulename, varname
+    logical, intent(inout) :: value ; character(len=*), optional, intent(in) :: desc, units, old_name
+    logical, optional, intent(in) :: default
+    logical, optional, intent(in) :: fail_if_missing, do_not_read, do_not_log, debuggingParam, layoutParam
+    integer :: m
+    m = find(varname)
+    if (m > 0) then ; value = (tab_int(m) /= 0)
+    elseif (present(default)) then ; value = default ; endif
+  end subroutine get_param_logical
+  subroutine get_param_char(CS, modulename, varname, value, desc, units, default, fail_if_missing, do_not_read, do_not_log, &
+                            debuggingParam, layoutParam, old_name)
+    type(param_file_type), intent(in) :: CS ; character(len=*), intent(in) :: modulename, varname
+    character(len=*), intent(inout) :: value ; character(len=*), optional, intent(in) :: desc, units, default, old_name
+    logical, optional, intent(in) :: fail_if_missing, do_not_read, do_not_log, debuggingParam, layoutParam
+    integer :: m
+    m = find(varname)
+    if (m > 0) then ; value = trim(tab_char(m))
+    elseif (present(default)) then ; value = default ; endif
+  end subroutine get_param_char
+
+  subroutine log_param_real(CS, modulename, varname, value, desc, units, default, debuggingParam, like_default, unscale)
+    type(param_file_type), intent(in) :: CS ; character(len=*), intent(in) :: modulename, varname ; real, intent(in) :: value
+    character(len=*), optional, intent(in) :: desc, units ; real, optional, intent(in) :: default, unscale
+    logical, optional, intent(in) :: debuggingParam, like_default
+  end subroutine log_param_real
+  subroutine log_param_char(CS, modulename, varname, value, desc, units, default, layoutParam, debuggingParam, like_default)
+    type(param_file_type), intent(in) :: CS ; character(len=*), intent(in) :: modulename, varname, value
+    character(len=*), optional, intent(in) :: desc, units, default ; logical, optional, intent(in) :: layoutParam, debuggingParam, like_default
+  end subroutine log_param_char
+  subroutine log_version(CS, modulename, version, desc, all_default, layout, debugging, log_to_all)
+    type(param_file_type), intent(in) :: CS ; character(len=*), intent(in) :: modulename, version
+    character(len=*), optional, intent(in) :: desc ; logical, optional, intent(in) :: all_default, layout, debugging, log_to_all
+  end subroutine log_version
+  subroutine openParameterBlock(CS, blockName, desc, do_not_log)
+    type(param_file_type), intent(in) :: CS ; character(len=*), intent(in) :: blockName
+    character(len=*), optional, intent(in) :: desc ; logical, optional, intent(in) :: do_not_log
+  end subroutine openParameterBlock
+  subroutine closeParameterBlock(CS)
+    type(param_file_type), intent(in) :: CS
+  end subroutine closeParameterBlock
+end module MOM_file_parser
+
+module MOM_EOS
+  implicit none ; public
+  type :: EOS_type ; integer :: form_of_EOS = 0 ; end type EOS_type
+end module MOM_EOS
+
+module MOM_variables
+  use MOM_EOS, only : EOS_type
+  implicit none ; public
+  type :: thermo_var_ptrs
+    real, pointer, dimension(:,:,:) :: T => NULL(), S => NULL()
+    type(EOS_type), pointer :: eqn_of_state => NULL()
+    real, allocatable, dimension(:,:,:) :: SpV_avg
+  end type thermo_var_ptrs
+  type :: vertvisc_type
+    real, allocatable, dimension(:,:) :: ustar_BBL, BBL_meanKE_loss, BBL_meanKE_loss_sqrtCd
+  end type vertvisc_type
+end module MOM_variables
+
+module MOM_forcing_type
+  implicit none ; public
+  type :: forcing
+    real, pointer, dimension(:,:) :: ustar => NULL(), ustar_gustless => NULL(), tau_mag => NULL(), tau_mag_gustless => NULL(), &
+                                     ustar_shelf => NULL(), frac_shelf_h => NULL(), BBL_tidal_dis => NULL()
+  end type forcing
+end module MOM_forcing_type
+
+module MOM_diag_mediator
+  use MOM_time_manager, only : time_type
+  implicit none ; private
+  public :: time_type, diag_ctrl, axes_grp, register_diag_field, post_data, query_averaging_enabled, safe_alloc_ptr, safe_alloc_alloc
+  public :: standin_clear_diags, standin_want_diag, standin_diag_size, standin_get_diag
+  type :: axes_grp ; integer :: rank = 0 ; end type axes_grp
+  type :: diag_ctrl
+    type(axes_grp) :: axesT1, axesTL, axesTi
+  end type diag_ctrl
+  integer, parameter :: NDMAX = 64
+  type :: capture ; real, allocatable :: v(:) ; end type capture
+  !> the names the door has asked for; a field's id is its place in this list; what post_data last copied for it
+  integer :: nwant = 0
+  character(len=48) :: want_name(NDMAX) = ""
+  type(capture) :: store(NDMAX)
+  interface post_data
+    module procedure post_data_2d, post_data_3d
+  end interface
+  interface safe_alloc_ptr
+    module procedure safe_alloc_ptr_2d, safe_alloc_ptr_3d
+  end interface
+  interface safe_alloc_alloc
+    module procedure safe_alloc_alloc_2d, safe_alloc_alloc_3d
+  end interface
+contains
+  subroutine standin_clear_diags()
+    integer :: m
+    do m = 1, NDMAX ; if (allocated(store(m)%v)) deallocate(store(m)%v) ; enddo
+    nwant = 0
+  end subroutine standin_clear_diags
+  subroutine standin_want_diag(name)
+    character(len=*), intent(in) :: name
+    if (nwant < NDMAX) then ; nwant = nwant + 1 ; want_name(nwant) = name ; endif
+  end subroutine standin_want_diag
+  integer function want_id(name)
+    character(len=*), intent(in) :: name ; integer :: m
+    want_id = -1
+    do m = 1, nwant ; if (trim(want_name(m)) == trim(name)) then ; want_id = m ; return ; endif ; enddo
+  end function want_id
+  !> the number of values captured for a name: 0 when nothing was posted, -1 when the name was not asked for
+  integer function standin_diag_size(name)
+    character(len=*), intent(in) :: name ; integer :: m
+    m = want_id(name) ; standin_diag_size = -1
+    if (m > 0) then ; standin_diag_size = 0 ; if (allocated(store(m)%v)) standin_diag_size = size(store(m)%v) ; endif
+  end function standin_diag_size
+  subroutine standin_get_diag(name, out)
+    character(len=*), intent(in) :: name ; real, intent(inout) :: out(:) ; integer :: m, n
+    m = want_id(name) ; if (m < 1) return ; if (.not.allocated(store(m)%v)) return
+    n = min(size(out), size(store(m)%v)) ; out(1:n) = store(m)%v(1:n)
+  end subroutine standin_get_diag
+
+  integer function register_diag_field(module_name, field_name, axes, init_time, long_name, units, conversion, cmor_long_name)
+    character(len=*), intent(in) :: module_name, field_name ; type(axes_grp), intent(in) :: axes ; type(time_type), intent(in) :: init_time
+    character(len=*), optional, intent(in) :: long_name, units, cmor_long_name ; real, optional, intent(in) :: conversion
+    register_diag_field = want_id(field_name)
+  end function register_diag_field
+  subroutine post_data_2d(diag_field_id, field, diag_cs)
+    integer, intent(in) :: diag_field_id ; real, intent(in) :: field(:,:) ; type(diag_ctrl), intent(in) :: diag_cs
+    if (diag_field_id < 1 .or. diag_field_id > NDMAX) return
+    if (allocated(store(diag_field_id)%v)) deallocate(store(diag_field_id)%v)
+    allocate(store(diag_field_id)%v(size(field))) ; store(diag_field_id)%v(:) = reshape(field, (/ size(field) /))
+  end subroutine post_data_2d
+  subroutine post_data_3d(diag_field_id, field, diag_cs)
+    integer, intent(in) :: diag_field_id ; real, intent(in) :: field(:,:,:) ; type(diag_ctrl), intent(in) :: diag_cs
+    if (diag_field_id < 1 .or. diag_field_id > NDMAX) return
+    if (allocated(store(diag_field_id)%v)) deallocate(store(diag_field_id)%v)
+    allocate(store(diag_field_id)%v(size(field))) ; store(diag_field_id)%v(:) = reshape(field, (/ size(field) /))
+  end subroutine post_data_3d
+  logical function query_averaging_enabled(diag_cs)
+    type(diag_ctrl), intent(in) :: diag_cs
+    query_averaging_enabled = .true.
+  end function query_averaging_enabled
+  subroutine safe_alloc_ptr_2d(ptr, is, ie, js, je)
+    real, dimension(:,:), pointer :: ptr ; integer, intent(in) :: is, ie, js, je
+    if (.not.associated(ptr)) then ; allocate(ptr(is:ie,js:je)) ; ptr(:,:) = 0.0 ; endif
+  end subroutine safe_alloc_ptr_2d
+  subroutine safe_alloc_ptr_3d(ptr, is, ie, js, je, nk)
+    real, dimension(:,:,:), pointer :: ptr ; integer, intent(in) :: is, ie, js, je, nk
+    if (.not.associated(ptr)) then ; allocate(ptr(is:ie,js:je,nk)) ; ptr(:,:,:) = 0.0 ; endif
+  end subroutine safe_alloc_ptr_3d
+  subroutine safe_alloc_alloc_2d(ptr, is, ie, js, je)
+    real, dimension(:,:), allocatable :: ptr ; integer, intent(in) :: is, ie, js, je
+    if (.not.allocated(ptr)) then ; allocate(ptr(is:ie,js:je)) ; ptr(:,:) = 0.0 ; endif
+  end subroutine safe_alloc_alloc_2d
+  subroutine safe_alloc_alloc_3d(ptr, is, ie, js, je, nk)
+    real, dimension(:,:,:), allocatable :: ptr ; integer, intent(in) :: is, ie, js, je, nk
+    if (.not.allocated(ptr)) then ; allocate(ptr(is:ie,js:je,nk)) ; ptr(:,:,:) = 0.0 ; endif
+  end subroutine safe_alloc_alloc_3d
+end module MOM_diag_mediator
+
+module MOM_debugging
+  use MOM_hor_index, only : hor_index_type
+  implicit none ; private
+  public :: hchksum
+  interface hchksum
+    module procedure hchksum_2d, hchksum_3d
+  end interface
+contains
+  subroutine hchksum_2d(array, mesg, HI, haloshift, unscale)
+    real, intent(in) :: array(:,:) ; character(len=*), intent(in) :: mesg ; type(hor_index_type), intent(in) :: HI
+    integer, optional, intent(in) :: haloshift ; real, optional, intent(in) :: unscale
+  end subroutine hchksum_2d
+  subroutine hchksum_3d(array, mesg, HI, haloshift, unscale)
+    real, intent(in) :: array(:,:,:) ; character(len=*), intent(in) :: mesg ; type(hor_index_type), intent(in) :: HI
+    integer, optional, intent(in) :: haloshift ; real, optional, intent(in) :: unscale
+  end subroutine hchksum_3d
+end module MOM_debugging
+
+module MOM_interface_heights
+  use MOM_grid, only : ocean_grid_type
+  use MOM_verticalGrid, only : verticalGrid_type
+  use MOM_variables, only : thermo_var_ptrs
+  implicit none ; private
+  public :: thickness_to_dz
+contains
+  !> The j-slice form, Boussinesq only: dz = GV%H_to_Z * h.  The device refuses non-Boussinesq contexts, so the specific-volume
+  !! arm of the reference's routine cannot be reached by anything compared here and is not stood in for.
+  subroutine thickness_to_dz(h, tv, dz, j, G, GV, halo_size)
+    type(ocean_grid_type), intent(in) :: G ; type(verticalGrid_type), intent(in) :: GV
+    real, dimension(G%isd:G%ied,G%jsd:G%jed,GV%ke), intent(in) :: h ; type(thermo_var_ptrs), intent(in) :: tv
+    real, dimension(G%isd:G%ied,GV%ke), intent(inout) :: dz ; integer, intent(in) :: j ; integer, optional, intent(in) :: halo_size
+    integer :: i, k
+    do k = 1, GV%ke ; do i = G%isc, G%iec ; dz(i,k) = GV%H_to_Z * h(i,j,k) ; enddo ; enddo
+  end subroutine thickness_to_dz
+end module MOM_interface_heights
+
+module MOM_stochastics
+  implicit none ; public
+  type :: stochastic_CS
+    logical :: pert_epbl = .false.
+    integer :: id_epbl1_wts = -1, id_epbl2_wts = -1
+    real, allocatable, dimension(:,:) :: epbl1_wts, epbl2_wts
+  end type stochastic_CS
+end module MOM_stochastics
+
+#else
+
+module MOM_wave_interface
+  use MOM_grid, only : ocean_grid_type
+  use MOM_verticalGrid, only : verticalGrid_type
+  use MOM_unit_scaling, only : unit_scale_type
+  implicit none ; public
+  type :: wave_parameters_CS ; integer :: dummy = 0 ; end type wave_parameters_CS
+contains
+  !> Never reached: the device refuses use_LT, and the doors leave Waves null.
+  subroutine get_Langmuir_Number(LA, G, GV, US, HBL, ustar, i, j, dz, Waves, U_H, V_H, Override_MA)
+    real, intent(out) :: LA ; type(ocean_grid_type), intent(in) :: G ; type(verticalGrid_type), intent(in) :: GV
+    type(unit_scale_type), intent(in) :: US ; real, intent(in) :: HBL, ustar ; integer, intent(in) :: i, j
+    real, dimension(GV%ke), intent(in) :: dz ; type(wave_parameters_CS), pointer :: Waves
+    real, dimension(GV%ke), optional, intent(in) :: U_H, V_H ; logical, optional, intent(in) :: Override_MA
+    LA = 0.0
+  end subroutine get_Langmuir_Number
+end module MOM_wave_interface
+#endif

@@ -716,6 +716,13 @@ DIAG_3D = ("Velocity_Scale", "Mixing_Length")
 DIAG_2D = TKE_DIAGS + ("mstar_sfc", "ustar_diag", "OBL_its")
 
 
+def reference_refuses(CS):
+    """True for what energetic_PBL_init stops on among the settings the device and this restatement take: EPBL_TRANSITION_SCALE
+    outside (0, 1) with USE_MLD_ITERATION (:3969-3972).  Found by running the compiled reference (tests/test_ref_parity_cpu.py);
+    the formulas of ePBL_column (:1293-1324) are defined for such values, and both sides here evaluate them."""
+    return bool(CS.Use_MLD_iteration) and abs(CS.transLay_scale - 0.5) >= 0.5
+
+
 def energetic_PBL(d, M, GV, CS, h, u, v, T, S, dSV_dT, dSV_dS, TKE_forced, ustar, buoy_flux, dt, Kd_int, ML_depth, math=None,
                   counts=None, traces=None, **diag):
     """energetic_PBL :326-884 on the arrays of a tile; Kd_int, ML_depth and the diagnostics given by name are written on the
@@ -910,6 +917,11 @@ CASES = {
     "no_iter": (dict(_EXACT, Use_MLD_iteration=0, nstar=0.0), dict(diag=("Velocity_Scale", "Mixing_Length", "OBL_its"))),
     "no_iter_new": (dict(_EXACT, Use_MLD_iteration=0, orig_PE_calc=0, TKE_diagnostics=1), dict(diag=TKE_DIAGS + ("OBL_its",), inp=dict(strat=0.02))),
     "translay1": (dict(_EXACT, transLay_scale=1.0, min_mix_len=3.0, max_MLD_its=3), dict(diag=("Mixing_Length", "OBL_its"))),
+    # rh18_orig and translay1 hold EPBL_TRANSITION_SCALE of 0 and 1, on which the reference's init stops (reference_refuses): the
+    # two cases below are their twins at values it runs, 2**-20 (columns still iterate to max_MLD_its) and 1 - 2**-6
+    "rh18_orig_tl": (dict(_EXACT, wT_scheme=abi.EPBL_WT_REICHL_H18, transLay_scale=2.0 ** -20, omega_frac=0.5, MLD_iter_bug=0, TKE_diagnostics=1),
+                     dict(diag=_ALL_DIAG)),
+    "translay_hi": (dict(_EXACT, transLay_scale=1.0 - 2.0 ** -6, min_mix_len=3.0, max_MLD_its=3), dict(diag=("Mixing_Length", "OBL_its"))),
     "guess": (dict(_EXACT, MLD_iteration_guess=1, MLD_tol=0.25), dict(diag=("OBL_its",), ncalls=2, inp=dict(strat=0.05))),
     "mstar0": (dict(_EXACT, fixed_mstar=0.0, max_MLD_its=2), dict(diag=("OBL_its", "mstar_sfc"))),
     "weak": (dict(_EXACT, MLD_tol=0.01, MLD_iter_bug=0), dict(diag=("OBL_its",), inp=dict(strat=0.01))),
