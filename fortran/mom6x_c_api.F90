@@ -18,6 +18,7 @@ module mom6x_c_api
   public :: mom6x_frazil_params, mom6x_make_frazil_init, mom6x_make_frazil, mom6x_adjust_salt
   public :: mom6x_geothermal_params, mom6x_geothermal_init, mom6x_geothermal_in_place
   public :: mom6x_opacity_params, mom6x_opacity_init, mom6x_set_pen_shortwave, mom6x_opacity_status
+  public :: mom6x_kappa_shear_params, mom6x_kappa_shear_init, mom6x_Calculate_kappa_shear, mom6x_kappa_shear_work_bytes
   public :: mom6x_energetic_PBL_params, mom6x_energetic_PBL_init, mom6x_energetic_PBL, mom6x_energetic_PBL_get_MLD, mom6x_ePBL_augment_Kd
   public :: mom6x_thickness_diffuse_params, mom6x_thickness_diffuse_init, mom6x_thickness_diffuse
   public :: mom6x_tracer_hor_diff_params, mom6x_tracer_hor_diff_init, mom6x_tracer_hordiff, mom6x_tracer_hordiff_tile
@@ -170,6 +171,13 @@ module mom6x_c_api
     real(c_double) :: manizza_coef(6), manizza_power(3), morel_coef(6), morel_pen_coef(6), Z_to_m, m_to_Z
     integer(c_int) :: opacity_scheme, nbands
   end type mom6x_opacity_params
+  type, bind(C) :: mom6x_kappa_shear_params   !< what kappa_shear_init (MOM_kappa_shear.F90:2070-2330) leaves in Kappa_shear_CS (:34-126), with the members of US, GV and the EOS type the routines read
+    real(c_double) :: RiNo_crit, Shearmix_rate, FRi_curvature, C_N, C_S, lambda, lambda2_N_S, lz_rescale, TKE_bg, kappa_0, kappa_seed
+    real(c_double) :: kappa_trunc, kappa_tol_err, Prandtl_turb, vel_underflow, kappa_src_max_chg, m_to_Z, T_to_s, L_to_Z, Z_to_m_m_to_H
+    real(c_double) :: g_Earth_Z_T2, RL2_T2_to_Pa, kg_m3_to_R
+    integer(c_int) :: max_RiNo_it, max_KS_it, nkml, eliminate_massless, dKdQ_iteration_bug, all_layer_TKE_bug
+    integer(c_int) :: restrictive_tolerance_check, KS_at_vertex, work_columns
+  end type mom6x_kappa_shear_params
 
   type, bind(C) :: mom6x_surface_fluxes   !< the members of `forcing` (MOM_forcing_type.F90:80-256) that applyBoundaryFluxesInOut touches: device planes, c_null_ptr where the reference's pointer is not associated
     type(c_ptr) :: sw, lw, latent, sens, evap, lprec, fprec, vprec, lrunoff, frunoff, lrunoff_glc, frunoff_glc, seaice_melt
@@ -570,6 +578,25 @@ module mom6x_c_api
       type(c_ptr), value :: ctx, sw, sw_vis_dir, sw_vis_dif, sw_nir_dir, sw_nir_dif, chl_2d, chl_3d
       real(c_double), value :: opacity_scale
       type(c_ptr), value :: opacity_band, sw_pen_band, SW_pen, SW_vis_pen, opac_diag
+    end function
+    !> kappa_shear_init (MOM_kappa_shear.F90:2070): eos is c_loc(a mom6x_eos_params) or c_null_ptr, Rlay c_loc(GV%Rlay on the HOST) or c_null_ptr; allocates the workspace
+    integer(c_int) function mom6x_kappa_shear_init(ctx, p, eos, Rlay) bind(C, name="mom6x_kappa_shear_init")
+      import :: c_ptr, c_int, mom6x_kappa_shear_params
+      type(c_ptr), value :: ctx ; type(mom6x_kappa_shear_params), intent(in) :: p ; type(c_ptr), value :: eos, Rlay
+    end function
+    !> the bytes of the workspace that mom6x_kappa_shear_init allocated
+    integer(c_long_long) function mom6x_kappa_shear_work_bytes(ctx) bind(C, name="mom6x_kappa_shear_work_bytes")
+      import :: c_ptr, c_long_long
+      type(c_ptr), value :: ctx
+    end function
+    !> Calculate_kappa_shear (MOM_kappa_shear.F90:133) from the C-grid u, v (find_uv_at_h inside; zero_mix /= 0: the arm of
+    !! MOM_diabatic_aux.F90:595-605): the arrays are device pointers, c_null_ptr for what is absent; kappa_io is not read
+    integer(c_int) function mom6x_Calculate_kappa_shear(ctx, u, v, h, T, S, p_surf, dt, zero_mix, kappa_io, tke_io, kv_io, N2_init, &
+        S2_init, N2_mean, S2_mean, KS_its) bind(C, name="mom6x_Calculate_kappa_shear")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, u, v, h, T, S, p_surf
+      real(c_double), value :: dt ; integer(c_int), value :: zero_mix
+      type(c_ptr), value :: kappa_io, tke_io, kv_io, N2_init, S2_init, N2_mean, S2_mean, KS_its
     end function
     !> the wet points with negative chlorophyll since the last call (the reference's fatal error); synchronises
     integer(c_int) function mom6x_opacity_status(ctx, negative_chl) bind(C, name="mom6x_opacity_status")

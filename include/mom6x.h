@@ -360,7 +360,7 @@ int  mom6x_device_count(void);
  * 12 remapping_params, 13 regrid_zstar_params, 14 chksum_result, 15 sum_output_params, 16 energy_sums, 17 regrid_rho_params,
  * 18 set_visc_params, 19 thickness_diffuse_params, 20 tracer_hor_diff_params, 21 varmix_params,
  * 22 mixedlayer_restrat_params, 23 MEKE_params, 25 set_diffusivity_params, 27 diabatic_aux_params, 28 surface_fluxes, 30 energetic_PBL_params, 32 frazil_params,
- * 33 geothermal_params, 34 opacity_params; 24, 26, 29 and 31 are not assigned and return -1): lets ctypes /
+ * 33 geothermal_params, 34 opacity_params, 35 kappa_shear_params; 24, 26, 29 and 31 are not assigned and return -1): lets ctypes /
  * ISO_C_BINDING mirrors be checked at start-up.  */
 int  mom6x_struct_size(int which);
 
@@ -1132,7 +1132,8 @@ int mom6x_set_BBL_TKE(mom6x_ctx *ctx, const double *u, const double *v, const do
  * KS_extra at every interface with DOUBLE_DIFFUSION; Kd_BBL at K = 2..nz when the law of the wall runs.  A diagnostic plane is
  * otherwise left alone (the reference allocates its own with zeros: the caller's K = 1 and K = nz+1 planes of Kd_BBL and the
  * halos keep what the caller put there).
- * Not carried: Calculate_kappa_shear and CVMix shear (the host may hand in visc%Kd_shear), ML_RADIATION, tidal mixing,
+ * The call of Calculate_kappa_shear (:413-444) is the host's: mom6x_Calculate_kappa_shear writes the visc%Kd_shear and
+ * visc%Kv_shear that are handed in here.  Not carried: CVMix shear (the host may hand in its visc%Kd_shear), ML_RADIATION, tidal mixing,
  * INTERNAL_TIDES, USE_CVMIX_DDIFF, the Bryan-Lewis and horizontally varying backgrounds, USER_CHANGE_DIFFUSIVITY,
  * add_drag_diffusivity, dRho_int_unfilt and find_rho_bottom (nothing on this path reads them), the Kd_Work diagnostics and VBF. */
 int mom6x_set_diffusivity(mom6x_ctx *ctx, const double *u, const double *v, const double *h, const double *T, const double *S,
@@ -1458,6 +1459,82 @@ int mom6x_energetic_PBL_get_MLD(mom6x_ctx *ctx, const double *ML_depth, double *
  * or neither: visc%h_ML = GV%Z_to_H * MLD (:1565, the Boussinesq convert_MLD_to_ML_thickness).                                  */
 int mom6x_ePBL_augment_Kd(mom6x_ctx *ctx, const double *Kd_ePBL, const double *Kd_shear, double *Kv_shear, double *Kd_heat,
                           double *Kd_salt, int ePBL_is_additive, double ePBL_Prandtl, const double *MLD, double *h_ML);
+
+/* ------------------------------------------------------------------------- */
+/* MOM_kappa_shear: Calculate_kappa_shear, the Jackson et al. (2008) shear-driven mixing (USE_JACKSON_PARAM), called by
+ * set_diffusivity (src/parameterizations/vertical/MOM_set_diffusivity.F90:413-444) after the driver's find_uv_at_h
+ * (MOM_diabatic_driver.F90:1391-1398).  It produces the visc%Kd_shear and visc%Kv_shear that mom6x_set_diffusivity reads.        */
+/* What kappa_shear_init (src/parameterizations/vertical/MOM_kappa_shear.F90:2070-2330) leaves in Kappa_shear_CS (:34-126), scaled
+ * as CS holds it, with the members of US, GV and the EOS type that Calculate_kappa_shear (:133-411), kappa_shear_column
+ * (:864-1372), calculate_projected_state (:1377-1504) and find_kappa_tke (:1507-2067) read and the context does not hold.
+ * GV%g_Earth, Rho0, H_to_Z, H_to_RZ and H_subroundoff are the context's (mom6x_vgrid).  Logicals are ints.  (struct 35)           */
+typedef struct mom6x_kappa_shear_params {
+  double RiNo_crit;          /* RINO_CRIT (0.25)                                                                                 */
+  double Shearmix_rate;      /* SHEARMIX_RATE (0.089)                                                                            */
+  double FRi_curvature;      /* FRI_CURVATURE (-0.97)                                                                            */
+  double C_N;                /* TKE_N_DECAY_CONST (0.24)                                                                         */
+  double C_S;                /* TKE_SHEAR_DECAY_CONST (0.14)                                                                     */
+  double lambda;             /* KAPPA_BUOY_SCALE_COEF (0.82)                                                                     */
+  double lambda2_N_S;        /* KAPPA_N_OVER_S_SCALE_COEF2 (0): kept in CS, read by no routine                                   */
+  double lz_rescale;         /* LZ_RESCALE (1): :1010                                                                            */
+  double TKE_bg;             /* TKE_BACKGROUND (0) [Z2 T-2]                                                                      */
+  double kappa_0;            /* KD_KAPPA_SHEAR_0 (max(KD, 1e-7 m2 s-1)) [H Z T-1]                                                */
+  double kappa_seed;         /* KD_SEED_KAPPA_SHEAR (1 m2 s-1) [H Z T-1]: the first guess :323                                   */
+  double kappa_trunc;        /* KD_TRUNC_KAPPA_SHEAR (0.01*kappa_0) [H Z T-1]                                                    */
+  double kappa_tol_err;      /* KAPPA_SHEAR_TOL_ERR (0.1)                                                                        */
+  double Prandtl_turb;       /* PRANDTL_TURB (1): kv_io :391                                                                     */
+  double vel_underflow;      /* VEL_UNDERFLOW (0) [L T-1]                                                                        */
+  double kappa_src_max_chg;  /* KAPPA_SHEAR_MAX_KAP_SRC_CHG (10): must be greater than 1                                         */
+  double m_to_Z, T_to_s;     /* US%m_to_Z, US%T_to_s (1): TKE_min :1630, the KAPPA_SHEAR_ITER_BUG arm :1860                      */
+  double L_to_Z;             /* US%L_to_Z (1): the squared shear :1484-1489                                                      */
+  double Z_to_m_m_to_H;      /* US%Z_to_m*GV%m_to_H (1): dz_massless :219                                                        */
+  double g_Earth_Z_T2;       /* GV%g_Earth_Z_T2 [Z T-2]: g_R0 :1007                                                              */
+  double RL2_T2_to_Pa;       /* EOS%RL2_T2_to_Pa (1): the pressure handed to the equation of state, MOM_EOS.F90:813               */
+  double kg_m3_to_R;         /* EOS%kg_m3_to_R (1): the density derivatives, MOM_EOS.F90:820                                     */
+  int    max_RiNo_it;        /* MAX_RINO_IT (50): the iterations of find_kappa_tke, at least 1                                   */
+  int    max_KS_it;          /* MAX_KAPPA_SHEAR_IT (13): the outer iterations of a column, at least 1                            */
+  int    nkml;               /* CS%nkml: GV%nkml with a bulk mixed layer and KAPPA_SHEAR_MERGE_ML, else 1 (:2283-2289)           */
+  int    eliminate_massless; /* KAPPA_SHEAR_ELIM_MASSLESS (T)                                                                    */
+  int    dKdQ_iteration_bug; /* KAPPA_SHEAR_ITER_BUG (F)                                                                         */
+  int    all_layer_TKE_bug;  /* KAPPA_SHEAR_ALL_LAYER_TKE_BUG (F)                                                                */
+  int    restrictive_tolerance_check;   /* USE_RESTRICTIVE_TOLERANCE_CHECK (F)                                                   */
+  int    KS_at_vertex;       /* VERTEX_SHEAR: must be 0 (Calc_kappa_shear_vertex is not on the device)                           */
+  int    work_columns;       /* the columns in flight, each with a slot of the workspace; 0: the library's default (the columns
+                              * of the tile, at most 65536).  Rounded up to whole wavefronts of 64.  A small value makes a small
+                              * grid reuse its slots (for tests)                                                                 */
+} mom6x_kappa_shear_params;
+/* kappa_shear_init :2070: checks the members, keeps them with the equation of state (tv%eqn_of_state; NULL: none) and a device
+ * copy of GV%Rlay (a HOST array of nk values; NULL: none), and allocates the workspace: 51 arrays of nk + 1 levels for each of
+ * work_columns slots, on the device.  A refused or invalid call leaves no module behind, also where an earlier call had succeeded.
+ * MOM6X_EUNSUPPORTED, naming the setting: KS_at_vertex (VERTEX_SHEAR), a non-Boussinesq context.  MOM6X_EINVAL: max_KS_it < 1,
+ * max_RiNo_it < 1, RiNo_crit <= 0, kappa_src_max_chg <= 1, work_columns < 0, nkml < 1, lambda = 0, an unknown EQN_OF_STATE form.  */
+int mom6x_kappa_shear_init(mom6x_ctx *ctx, const mom6x_kappa_shear_params *p, const mom6x_eos_params *eos, const double *Rlay);
+/* The bytes of the workspace that mom6x_kappa_shear_init allocated (0 before it). */
+long long mom6x_kappa_shear_work_bytes(mom6x_ctx *ctx);
+/* Calculate_kappa_shear(u_in, v_in, h, tv, p_surf, kappa_io, tke_io, kv_io, dt, G, GV, US, CS) :133-411 with kappa_shear_column
+ * :864-1372, calculate_projected_state :1377-1504, find_kappa_tke :1507-2067 and the Boussinesq thickness_to_dz, in one launch on
+ * the context's stream: no allocation, no host synchronisation, no halo exchange.  All arrays are device pointers.
+ * u, v: the C-GRID velocities, only read.  The kernel forms u_h, v_h as the driver's find_uv_at_h does
+ * (MOM_diabatic_driver.F90:1391-1398; MOM_diabatic_aux.F90:546-611, without ea and eb): the plain average (:607-610), or with
+ * zero_mix != 0 the arm of :595-605 with GV%H_subroundoff, which the driver takes when geothermal heating is on.
+ * h, T, S (tv%T, tv%S): 3-D, only read; p_surf: a plane or NULL.  T and S are given together (and need the equation of state
+ * given to init: calculate_density_derivs at interfaces 2..nzc with scale = -g_R0, every form of mom6x_eos_form) or both NULL (the
+ * layered arm, GV%Rlay as the state :241, :1146-1147, needs the Rlay given to init).
+ * kappa_io (visc%Kd_shear), tke_io (visc%TKE_turb), kv_io (visc%Kv_shear): nk + 1 levels, written on the computational domain
+ * only, 0 in land columns (:382-391); halos are left alone.  kappa_io is NOT READ: although the reference declares it intent(inout)
+ * ("the value from the previous timestep"), every column starts from kappa_seed (:323), and so does the device.
+ * N2_init, S2_init, N2_mean, S2_mean: nullable diagnostics of nk + 1 levels (0 in land columns).  KS_its: a nullable plane, the
+ * outer iterations (:1189) each column used, as a real (0 over land).
+ * One lane per column; a lane walks its share of the columns and reuses its slot of the workspace.  The lanes of a wavefront
+ * leave a column together, after the slowest of them; a wavefront of columns without an interface of Ri < Ri_crit (:1303) does
+ * not wait for any other.
+ * MOM6X_EINVAL: a call before init, null u, v, h, kappa_io, tke_io or kv_io, dt <= 0, T without S, T and S without an equation of
+ * state at init, no T and S when init got no Rlay.
+ * Not carried: Calc_kappa_shear_vertex (:415-860, VERTEX_SHEAR) with full_convection and the vertex averages, CVMix shear
+ * (MOM_CVMix_shear), non-Boussinesq mode, the debug checksums (:397-402), VBF%Kd_KS.                                            */
+int mom6x_Calculate_kappa_shear(mom6x_ctx *ctx, const double *u, const double *v, const double *h, const double *T, const double *S,
+                                const double *p_surf, double dt, int zero_mix, double *kappa_io, double *tke_io, double *kv_io,
+                                double *N2_init, double *S2_init, double *N2_mean, double *S2_mean, double *KS_its);
 
 /* ------------------------------------------------------------------------- */
 /* MOM_dynamics_split_RK2                                                    */

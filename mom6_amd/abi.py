@@ -625,6 +625,54 @@ def energetic_PBL_params_default(GV=None, **kw):
     return p
 
 
+class KappaShearParams(C.Structure):
+    """mom6x_kappa_shear_params; what kappa_shear_init (MOM_kappa_shear.F90:2070-2330) leaves in Kappa_shear_CS (:34-126), with the
+    members of US, GV and the EOS type that the routines read.  (`lambda` is a Python keyword: getattr(p, "lambda"), or the
+    property lambda_.)"""
+    _fields_ = ([(n, C.c_double) for n in (
+        "RiNo_crit", "Shearmix_rate", "FRi_curvature", "C_N", "C_S", "lambda", "lambda2_N_S", "lz_rescale", "TKE_bg", "kappa_0",
+        "kappa_seed", "kappa_trunc", "kappa_tol_err", "Prandtl_turb", "vel_underflow", "kappa_src_max_chg", "m_to_Z", "T_to_s",
+        "L_to_Z", "Z_to_m_m_to_H", "g_Earth_Z_T2", "RL2_T2_to_Pa", "kg_m3_to_R")] +
+                [(n, C.c_int) for n in (
+                    "max_RiNo_it", "max_KS_it", "nkml", "eliminate_massless", "dKdQ_iteration_bug", "all_layer_TKE_bug",
+                    "restrictive_tolerance_check", "KS_at_vertex", "work_columns")])
+
+    @property
+    def lambda_(self):
+        return getattr(self, "lambda")
+
+    @lambda_.setter
+    def lambda_(self, v):
+        setattr(self, "lambda", v)
+
+
+KAPPA_SHEAR_MUST_BE_0 = ("KS_at_vertex",)
+
+
+def kappa_shear_params_default(GV=None, **kw):
+    """kappa_shear_init (MOM_kappa_shear.F90:2157-2289) defaults, Boussinesq and unscaled: RINO_CRIT = 0.25, SHEARMIX_RATE = 0.089,
+    FRI_CURVATURE = -0.97, TKE_N_DECAY_CONST = 0.24, TKE_SHEAR_DECAY_CONST = 0.14, KAPPA_BUOY_SCALE_COEF = 0.82, LZ_RESCALE = 1,
+    KD_KAPPA_SHEAR_0 = 1e-7 (KD = 0), KD_SEED_KAPPA_SHEAR = 1, KAPPA_SHEAR_TOL_ERR = 0.1, MAX_RINO_IT = 50, MAX_KAPPA_SHEAR_IT = 13,
+    KAPPA_SHEAR_MAX_KAP_SRC_CHG = 10, massless layers eliminated, no bulk mixed layer (nkml = 1), every bug switch off.
+    KD_TRUNC_KAPPA_SHEAR follows kappa_0 (0.01 of it, :2185) unless given.  lambda is given as lambda_."""
+    GV = GV if GV is not None else vgrid_default()
+    p = KappaShearParams()
+    p.RiNo_crit = 0.25; p.Shearmix_rate = 0.089; p.FRi_curvature = -0.97; p.C_N = 0.24; p.C_S = 0.14; p.lambda_ = 0.82
+    p.lambda2_N_S = 0.0; p.lz_rescale = 1.0; p.TKE_bg = 0.0; p.kappa_0 = 1.0e-7; p.kappa_seed = 1.0; p.kappa_tol_err = 0.1
+    p.Prandtl_turb = 1.0; p.vel_underflow = 0.0; p.kappa_src_max_chg = 10.0
+    p.m_to_Z = 1.0; p.T_to_s = 1.0; p.L_to_Z = 1.0; p.Z_to_m_m_to_H = 1.0; p.g_Earth_Z_T2 = GV.g_Earth
+    p.RL2_T2_to_Pa = 1.0; p.kg_m3_to_R = 1.0
+    p.max_RiNo_it = 50; p.max_KS_it = 13; p.nkml = 1; p.eliminate_massless = 1; p.dKdQ_iteration_bug = 0; p.all_layer_TKE_bug = 0
+    p.restrictive_tolerance_check = 0; p.work_columns = 0
+    for n in KAPPA_SHEAR_MUST_BE_0:
+        setattr(p, n, 0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    if "kappa_trunc" not in kw:
+        p.kappa_trunc = 0.01 * p.kappa_0
+    return p
+
+
 class HorViscParams(C.Structure):
     """mom6x_hor_visc_params; hor_visc_CS (MOM_hor_visc.F90:36-259)."""
     _fields_ = [("Laplacian", C.c_int), ("biharmonic", C.c_int), ("Kh", C.c_double), ("Kh_bg_min", C.c_double),
@@ -895,6 +943,12 @@ def load_library(path=None):
         lib.mom6x_opacity_init.argtypes = [vp, C.POINTER(OpacityParams)]
         lib.mom6x_set_pen_shortwave.argtypes = [vp] * 8 + [C.c_double] + [vp] * 5
         lib.mom6x_opacity_status.argtypes = [vp, C.POINTER(C.c_long)]
+    if hasattr(lib, "mom6x_Calculate_kappa_shear"):
+        vp = C.c_void_p
+        lib.mom6x_kappa_shear_init.argtypes = [vp, C.POINTER(KappaShearParams), C.POINTER(EOSParams), vp]
+        lib.mom6x_kappa_shear_work_bytes.argtypes = [vp]
+        lib.mom6x_kappa_shear_work_bytes.restype = C.c_longlong
+        lib.mom6x_Calculate_kappa_shear.argtypes = [vp] * 7 + [C.c_double, C.c_int] + [vp] * 8
     if path is None:
         _lib = lib
     return lib

@@ -181,6 +181,7 @@ extern "C" int mom6x_struct_size(int which) {
     case 32: return (int)sizeof(mom6x_frazil_params);
     case 33: return (int)sizeof(mom6x_geothermal_params);
     case 34: return (int)sizeof(mom6x_opacity_params);
+    case 35: return (int)sizeof(mom6x_kappa_shear_params);
     default: return -1;
   }
 }
@@ -263,6 +264,7 @@ extern "C" int mom6x_ctx_destroy(mom6x_ctx *c) {
   energetic_PBL_free(c);
   diabatic_TS_free(c);
   opacity_free(c);
+  kappa_shear_free(c);
   comm_free(c);
   for (int m = 0; m < MOM6X_NSCR; m++) (void)hipFree(c->scr[m]);
   (void)hipFree(c->G); (void)hipFree(c->flag);

@@ -102,7 +102,7 @@ enum Scr { SCR_q = 0, SCR_KE, SCR_absv, SCR_e, SCR_c1, SCR_t0, SCR_t1, SCR_t2, S
 // the module's parameter copy, its caller-owned pointers, the device arrays it allocates and an `init` flag where a setter may come
 // before the init call.  The context only owns them: a typed pointer each, null until the module is first touched.
 struct ContState; struct BTState; struct CorState; struct PgfState; struct VvState; struct HvState; struct RK2State; struct AleState;
-struct TAState; struct DiagState; struct SvState; struct TdState; struct ThdState; struct VmState; struct MleState; struct MekeState; struct SdState; struct DaState; struct EpblState; struct DtsState; struct OpState;
+struct TAState; struct DiagState; struct SvState; struct TdState; struct ThdState; struct VmState; struct MleState; struct MekeState; struct SdState; struct DaState; struct EpblState; struct DtsState; struct OpState; struct KsState;
 struct Comm;   // halo.hip: tile layout + RCCL communicator (null: single tile, wrap only)
 
 // u_bc_accel = (CAu + PFu) + diffu of the RK2 predictor (RK2.F90:565-572) formed by the pressure-force kernel that has just made
@@ -133,7 +133,7 @@ struct mom6x_ctx {
   long long n_exchanges, n_exchange_bytes;
   // the modules' states
   ContState *cont; BTState *bts; CorState *cor; PgfState *pgf; VvState *vv; HvState *hv; RK2State *rk2; AleState *ale;
-  TAState *ta; DiagState *diag; SvState *sv; TdState *td; ThdState *thd; VmState *vm; MleState *mle; MekeState *meke; SdState *sd; DaState *da; EpblState *epbl; DtsState *dts; OpState *op; Comm *comm;
+  TAState *ta; DiagState *diag; SvState *sv; TdState *td; ThdState *thd; VmState *vm; MleState *mle; MekeState *meke; SdState *sd; DaState *da; EpblState *epbl; DtsState *dts; OpState *op; KsState *ks; Comm *comm;
 };
 // Each frees every device pointer its struct owns, deletes the struct and nulls the context's pointer (a null pointer: nothing to
 // do).  mom6x_ctx_destroy calls them all; apart from them it frees only what mom6x_ctx_create allocated.
@@ -142,7 +142,7 @@ void PressureForce_free(mom6x_ctx *c);  void vertvisc_free(mom6x_ctx *c);       
 void rk2_state_free(mom6x_ctx *c);   void ALE_free(mom6x_ctx *c);               void ta_state_free(mom6x_ctx *c);
 void diag_sums_free(mom6x_ctx *c);   void set_visc_free(mom6x_ctx *c);          void thickness_diffuse_free(mom6x_ctx *c);
 void tracer_hor_diff_free(mom6x_ctx *c);  void varmix_free(mom6x_ctx *c);       void mixedlayer_restrat_free(mom6x_ctx *c);
-void MEKE_free(mom6x_ctx *c);  void set_diffusivity_free(mom6x_ctx *c);  void diabatic_aux_free(mom6x_ctx *c);  void energetic_PBL_free(mom6x_ctx *c);  void diabatic_TS_free(mom6x_ctx *c);  void opacity_free(mom6x_ctx *c);
+void MEKE_free(mom6x_ctx *c);  void set_diffusivity_free(mom6x_ctx *c);  void diabatic_aux_free(mom6x_ctx *c);  void energetic_PBL_free(mom6x_ctx *c);  void diabatic_TS_free(mom6x_ctx *c);  void opacity_free(mom6x_ctx *c);  void kappa_shear_free(mom6x_ctx *c);
 void comm_free(mom6x_ctx *c);
 // The widths of one group pass (create_group_pass(..., halo=)).  w: rows / columns of halo filled for its 3-D fields (0: the context's
 // halo); wf[0 .. nwf - 1]: the widths of single 3-D fields (0 entries and fields beyond nwf: w).  The default is what every pass but the

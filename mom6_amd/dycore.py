@@ -550,6 +550,34 @@ class Dycore:
                                                        _ptr(Kd_salt), C.c_int(1 if ePBL_is_additive else 0), C.c_double(ePBL_Prandtl),
                                                        _ptr(MLD), _ptr(h_ML)))
 
+    # -- MOM_kappa_shear -----------------------------------------------------------------------
+    def kappa_shear_init(self, params, eos=None, Rlay=None):
+        """kappa_shear_init (MOM_kappa_shear.F90:2070) with abi.kappa_shear_params_default(...); eos: tv%eqn_of_state (None: none);
+        Rlay: GV%Rlay, a HOST array of nk values, for the layered arm (None: none).  Allocates the workspace."""
+        self.kappa_shear_params = params
+        rl = None
+        if Rlay is not None:
+            a = np.ascontiguousarray(Rlay, dtype=np.float64)
+            assert a.shape == (self.dims.nk,), (a.shape, self.dims.nk)
+            self._keep.append(a)
+            rl = a.ctypes.data_as(C.c_void_p)
+        check(self.lib, self.lib.mom6x_kappa_shear_init(self.ctx, C.byref(params), C.byref(eos) if eos is not None else None, rl))
+
+    def kappa_shear_work_bytes(self):
+        """The bytes of the workspace that kappa_shear_init allocated."""
+        return int(self.lib.mom6x_kappa_shear_work_bytes(self.ctx))
+
+    KAPPA_SHEAR_OUT = ("N2_init", "S2_init", "N2_mean", "S2_mean", "KS_its")
+
+    def Calculate_kappa_shear(self, u, v, h, dt, kappa_io, tke_io, kv_io, T=None, S=None, p_surf=None, zero_mix=False, **out):
+        """Calculate_kappa_shear (MOM_kappa_shear.F90:133) from the C-grid u, v (find_uv_at_h is formed inside; zero_mix: the arm
+        the driver takes with geothermal heating): visc%Kd_shear, visc%TKE_turb, visc%Kv_shear (nk + 1 levels) on the computational
+        domain; T and S both or neither (the layered arm); as keyword arguments the nullable outputs KAPPA_SHEAR_OUT."""
+        assert set(out) <= set(self.KAPPA_SHEAR_OUT), sorted(set(out) - set(self.KAPPA_SHEAR_OUT))
+        check(self.lib, self.lib.mom6x_Calculate_kappa_shear(
+            self.ctx, _ptr(u), _ptr(v), _ptr(h), _ptr(T), _ptr(S), _ptr(p_surf), C.c_double(dt), C.c_int(1 if zero_mix else 0),
+            _ptr(kappa_io), _ptr(tke_io), _ptr(kv_io), *[_ptr(out.get(n)) for n in self.KAPPA_SHEAR_OUT]))
+
     # -- MOM_MEKE ------------------------------------------------------------------------------
     def MEKE_init(self, params, dF_dx=None, dF_dy=None):
         """MEKE_init (MOM_MEKE.F90:1329) for the EKE_SOURCE = prog arm; dF_dx, dF_dy: G%dF_dx, G%dF_dy, HOST planes of the tile

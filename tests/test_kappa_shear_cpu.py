@@ -1,0 +1,248 @@
+"""What pins tests/kappa_shear_ref.py, the checker of mom6x_Calculate_kappa_shear, without a GPU.  The restatement and the kernel
+come from one reading of MOM_kappa_shear.F90, so these checks stand on something else: the reference's dimensional test (Z, L, T, H
+and R each rescaled by 2**11 leave the unscaled bits), exact invariants of the scheme (zero-thickness layers inserted, elimination
+on and off, a column at rest, kv = Prandtl*kappa, land, the unread kappa_io), the arms the case table reaches on the grids of the
+GPU tests, a floor on how much of the `shear` case really mixes, and the struct and the init rules."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from mom6_amd import abi
+from tests import helpers as H
+from tests import kappa_shear_ref as R
+
+G = abi.G
+CONFIGS = (("benchmark_small", 1), ("benchmark_small", 2), ("benchmark_small", 3), ("benchmark_small", 4), ("benchmark_small", 8),
+           ("island_basin", 4))
+# the arms the case table must reach on CONFIGS.  Of BRANCHES, left out: newton_pivot_K (:1853, a negative pivot of the kappa
+# equation in Newton's method) -- decay_term_k = h_Int*I_Ld2 - Idz*dQmdK*dKdQ went negative in none of 1300 columns with mixing
+# over layers of 1, 10 and 100 m, velocity jumps of 0.3 to 3 m s-1, tolerances of 0.1 and 0.01, steps of an hour and a day, with
+# and without KAPPA_SHEAR_ITER_BUG, while its twin for the TKE equation (:1888, newton_pivot_Q) did; no input that reaches it is
+# known.  halving_ran_out, scan_stable_invalid, no_source, newton_left_early, newton_K_Q, ke_tke_interior, the kappa_trunc_* and
+# kappa_small_* arms, itt_limit and lz_rescale are reached too but are not conditions on the inputs.
+REQUIRED = ("land", "no_mixing_exit", "pred_corr", "halved", "refine_accept", "refine_reject", "two_iterations", "last_iteration",
+            "tol_restrictive", "tol_loose", "scan_stable_arm", "newton_entered", "newton_aborted", "newton_pivot_Q", "dKdQ_bug",
+            "dKdQ_fixed", "all_layer_bug", "all_layer_avg", "merged", "kf_pos", "nzc_1", "nkml_gt1", "layered", "eos", "elim_on",
+            "elim_off", "uv_plain", "uv_zero_mix", "vel_underflow")
+
+
+def _bits(a, b, name):
+    a = np.ascontiguousarray(a); b = np.ascontiguousarray(b)
+    ne = a.view(np.int64) != b.view(np.int64)
+    assert not ne.any(), f"{name}: {int(ne.sum())} of {a.size} words differ"
+
+
+def _grid(grid, nk):
+    return getattr(H, grid)(nk=nk)[1:]
+
+
+def _own(d):
+    own = np.zeros(d.shape2(), bool); own[H.interior(d, "h")] = True
+    return own
+
+
+def test_exports_and_struct_size():
+    lib = abi.load_library()
+    for name in ("mom6x_kappa_shear_init", "mom6x_Calculate_kappa_shear", "mom6x_kappa_shear_work_bytes"):
+        assert hasattr(lib, name), name
+    assert lib.mom6x_struct_size(35) == C.sizeof(abi.KappaShearParams) == 23 * 8 + 9 * 4 + 4
+    assert lib.mom6x_abi_version() == 6
+    names = [n for n, _ in abi.KappaShearParams._fields_]
+    off = {n: getattr(abi.KappaShearParams, n).offset for n in names}
+    assert [off[n] for n in names[:23]] == [8 * k for k in range(23)]
+    assert [off[n] for n in names[23:]] == [23 * 8 + 4 * k for k in range(9)]
+    assert names[:6] == ["RiNo_crit", "Shearmix_rate", "FRi_curvature", "C_N", "C_S", "lambda"] and names[-2:] == ["KS_at_vertex", "work_columns"]
+    assert abi.KAPPA_SHEAR_MUST_BE_0 == ("KS_at_vertex",)
+    P = abi.kappa_shear_params_default()
+    assert (P.RiNo_crit, P.Shearmix_rate, P.FRi_curvature, P.C_N, P.C_S, P.lambda_) == (0.25, 0.089, -0.97, 0.24, 0.14, 0.82)
+    assert (P.max_RiNo_it, P.max_KS_it, P.nkml, P.eliminate_massless, P.work_columns) == (50, 13, 1, 1, 0)
+    assert P.kappa_trunc == 0.01 * P.kappa_0 and P.kappa_seed == 1.0 and P.kappa_src_max_chg == 10.0
+
+
+def test_init_rules_decided_on_the_host():
+    """The refusals and the invalid values of init in the restatement's twin of the rules, and the library's own answer where no
+    context is needed for it."""
+    GV = abi.vgrid_default()
+    dflt = abi.kappa_shear_params_default
+    R.init_check(dflt(GV), GV)
+    with pytest.raises(NotImplementedError, match="VERTEX_SHEAR"):
+        R.init_check(dflt(GV, KS_at_vertex=1), GV)
+    GVn = abi.vgrid_default(); GVn.Boussinesq = 0
+    with pytest.raises(NotImplementedError, match="Boussinesq"):
+        R.init_check(dflt(GVn), GVn)
+    for bad in (dict(max_KS_it=0), dict(max_RiNo_it=0), dict(RiNo_crit=0.0), dict(RiNo_crit=-0.25), dict(kappa_src_max_chg=1.0),
+                dict(work_columns=-1), dict(nkml=0)):
+        with pytest.raises(ValueError):
+            R.init_check(dflt(GV, **bad), GV)
+    lib = abi.load_library()
+    P = dflt(GV)
+    assert lib.mom6x_kappa_shear_init(None, C.byref(P), None, None) == 1                 # MOM6X_EINVAL
+    assert b"null argument" in lib.mom6x_last_error()
+    assert lib.mom6x_Calculate_kappa_shear(*([None] * 7), C.c_double(1.0), C.c_int(0), *([None] * 8)) == 1                 # MOM6X_EINVAL
+    assert b"initialized" in lib.mom6x_last_error()
+    assert lib.mom6x_kappa_shear_work_bytes(None) == 0
+
+
+# powers of (Z, L, T, H, R)
+_DIM_P = dict(TKE_bg=(2, 0, -2, 0, 0), kappa_0=(1, 0, -1, 1, 0), kappa_seed=(1, 0, -1, 1, 0), kappa_trunc=(1, 0, -1, 1, 0),
+              vel_underflow=(0, 1, -1, 0, 0), m_to_Z=(1, 0, 0, 0, 0), T_to_s=(0, 0, -1, 0, 0), L_to_Z=(1, -1, 0, 0, 0),
+              Z_to_m_m_to_H=(-1, 0, 0, 1, 0), g_Earth_Z_T2=(1, 0, -2, 0, 0), RL2_T2_to_Pa=(0, -2, 2, 0, -1), kg_m3_to_R=(0, 0, 0, 0, 1))
+_DIM_GV = dict(g_Earth=(-1, 2, -2, 0, 0), Rho0=(0, 0, 0, 0, 1), Angstrom_H=(0, 0, 0, 1, 0), H_subroundoff=(0, 0, 0, 1, 0),
+               dZ_subroundoff=(1, 0, 0, 0, 0), H_to_Z=(1, 0, 0, -1, 0), Z_to_H=(-1, 0, 0, 1, 0), H_to_RZ=(1, 0, 0, -1, 1),
+               RZ_to_H=(-1, 0, 0, 1, -1))
+_DIM_IN = dict(u=(0, 1, -1, 0, 0), v=(0, 1, -1, 0, 0), h=(0, 0, 0, 1, 0), p_surf=(0, 2, -2, 0, 1), Rlay=(0, 0, 0, 0, 1))
+_DIM_OUT = dict(kappa_io=(1, 0, -1, 1, 0), kv_io=(1, 0, -1, 1, 0), tke_io=(2, 0, -2, 0, 0), N2_init=(0, 0, -2, 0, 0),
+                S2_init=(0, 0, -2, 0, 0), N2_mean=(0, 0, -2, 0, 0), S2_mean=(0, 0, -2, 0, 0), KS_its=(0, 0, 0, 0, 0))
+_DIM_M = dict(CoriolisBu=(0, 0, -1, 0, 0), Coriolis2Bu=(0, 0, -2, 0, 0), areaCu=(0, 2, 0, 0, 0), areaCv=(0, 2, 0, 0, 0),
+              areaT=(0, 2, 0, 0, 0), IareaT=(0, -2, 0, 0, 0))
+
+
+@pytest.mark.parametrize("name", ("shear", "bugs", "layered", "nkml2", "newton"))
+def test_dimensional_rescaling(name):
+    """The reference's test.dim: Z, L, T, H and R rescaled by 2**11, one at a time and all at once with unequal powers: params,
+    vertical grid, metrics and inputs are scaled in, outputs are unscaled, and every bit is the unscaled run's.  A unit factor in
+    the wrong place (US%m_to_Z of the KAPPA_SHEAR_ITER_BUG arm :1860, L_to_Z of S2 :1484, H_to_Z of dz_h_Int) breaks it."""
+    d, M = _grid("island_basin", 4)
+    GV = abi.vgrid_default()
+    P, opt = R.case(name, GV)
+    inp = R.case_inputs(d, M, GV, opt)
+    want, counts = R.run(d, M, GV, P, opt, inp)
+    assert counts["pred_corr"] > 0
+    big = 2.0 ** 11
+    sets = [tuple(big if n == m else 1.0 for n in range(5)) for m in range(5)] + [(2.0 ** 11, 2.0 ** 5, 2.0 ** -7, 2.0 ** 9, 2.0 ** 3)]
+    for sc in sets:
+        f = lambda pw: float(np.prod([s ** p for s, p in zip(sc, pw)]))                    # noqa: E731
+        GV2 = abi.vgrid_default()
+        for n, pw in _DIM_GV.items():
+            setattr(GV2, n, getattr(GV, n) * f(pw))
+        P2, _ = R.case(name, GV)
+        for n, pw in _DIM_P.items():
+            setattr(P2, n, getattr(P, n) * f(pw))
+        M2 = M.copy()
+        for n, pw in _DIM_M.items():
+            M2[G[n]] = M[G[n]] * f(pw)
+        inp2 = {n: a * f(_DIM_IN[n]) if n in _DIM_IN else a for n, a in inp.items()}
+        got, _ = R.run(d, M2, GV2, P2, dict(opt, dt=opt["dt"] * sc[2]), inp2)
+        assert set(got) == set(want)
+        for n in want:
+            _bits(got[n] / f(_DIM_OUT[n]), want[n], f"{name}: {n} rescaled by Z, L, T, H, R = {sc}")
+
+
+def test_zero_thickness_layers_inserted_below_nkml_change_no_bit():
+    """Four layers, and the same four with layers of exactly zero thickness (and other T, S, u, v) after the first and the third
+    and at the bottom (with nkml = 2: after the second, the fourth and at the bottom): with eliminate_massless the merged sums add exact zeros, and the interfaces above each massive layer and
+    the bottom one keep their bits."""
+    d4, M = _grid("benchmark_small", 4)
+    d7, M7 = _grid("benchmark_small", 7)
+    GV = abi.vgrid_default()
+    # the massive layer in each place of the seven, and the interfaces above the massive layers with the bottom one
+    for mods, lay, keep in ((dict(), (0, None, 1, 2, None, 3, None), [0, 2, 3, 5, 7]),
+                            (dict(nkml=2), (0, 1, None, 2, None, 3, None), [0, 1, 3, 5, 7])):
+        P = abi.kappa_shear_params_default(GV, kappa_0=1.5e-5, **mods)
+        opt = dict(R.case("shear", GV)[1], diag=R.DIAG_3D + R.DIAG_2D)
+        inp4 = R.inputs(d4, M, GV, band=0.3, U0=0.8, thin=False)
+        inp7 = dict(p_surf=inp4["p_surf"], Rlay=None)
+        for n in ("u", "v", "h", "T", "S"):
+            a = np.empty((7,) + inp4[n].shape[1:])
+            for k, src in enumerate(lay):
+                if src is not None:
+                    a[k] = inp4[n][src]
+                else:
+                    a[k] = 0.0 if n == "h" else 0.7 * inp4[n][lay[k - 1]] + 0.1
+            inp7[n] = np.ascontiguousarray(a)
+        want4, c4 = R.run(d4, M, GV, P, opt, inp4)
+        want7, c7 = R.run(d7, M7, GV, P, opt, inp7)
+        assert c4["pred_corr"] > 0 and c7["merged"] > 0 and (c4["merged"] > 0) == (P.nkml > 1)
+        for n in want4:
+            if n in R.DIAG_2D:
+                _bits(want7[n], want4[n], n)
+            else:
+                _bits(want7[n][keep], want4[n], f"{mods}: {n} at the surviving interfaces")
+
+
+def test_elimination_changes_nothing_where_no_layer_is_massless():
+    d, M = _grid("benchmark_small", 8)
+    GV = abi.vgrid_default()
+    _, opt = R.case("elim_off", GV)
+    inp = R.case_inputs(d, M, GV, opt)
+    off, c0 = R.run(d, M, GV, abi.kappa_shear_params_default(GV, eliminate_massless=0), opt, inp)
+    on, c1 = R.run(d, M, GV, abi.kappa_shear_params_default(GV, eliminate_massless=1), opt, inp)
+    assert c0["pred_corr"] > 0 and c1["merged"] == 0 and c1["elim_on"] > 0 and c0["elim_off"] > 0
+    for n in off:
+        _bits(on[n], off[n], n)
+
+
+def test_a_column_at_rest_does_not_mix():
+    """u = v = 0 over stable stratification: kappa = 0 at every interface, one outer iteration, and tke is what the first
+    find_kappa_tke returned (its weight dt_rem/dt is exactly 1)."""
+    d, M = _grid("island_basin", 4)
+    GV = abi.vgrid_default()
+    P, opt = R.case("shear", GV)
+    inp = R.case_inputs(d, M, GV, opt, zero_uv=True)
+    traces = {}
+    out, c = R.run(d, M, GV, P, opt, inp, traces=traces)
+    wet = _own(d) & (M[G["mask2dT"]] > 0.0)
+    assert (out["kappa_io"][:, wet] == 0.0).all() and (out["kv_io"][:, wet] == 0.0).all()
+    assert (out["KS_its"][wet] == 1.0).all() and c["pred_corr"] == 0 and c["no_mixing_exit"] == int(wet.sum())
+    n = 0
+    for (jl, il), (nzc, its, first_tke) in traces.items():
+        if nzc == d.nk:
+            _bits(out["tke_io"][:, jl + d.joff, il + d.ioff], np.array(first_tke[1:d.nk + 2]), "tke of the first find_kappa_tke")
+            n += 1
+    assert n > 0
+
+
+def test_kv_is_prandtl_times_kappa_land_is_zero_and_kappa_io_is_not_read():
+    d, M = _grid("island_basin", 4)
+    GV = abi.vgrid_default()
+    own = _own(d)
+    land = own & ~(M[G["mask2dT"]] > 0.0)
+    assert land.any()
+    for name in ("its2", "shear"):
+        P, opt = R.case(name, GV)
+        inp = R.case_inputs(d, M, GV, opt)
+        a, c = R.run(d, M, GV, P, opt, inp, fill=np.nan)
+        b, _ = R.run(d, M, GV, P, opt, inp, fill=3.25)
+        assert c["pred_corr"] > 0
+        _bits(a["kv_io"][:, own], P.Prandtl_turb * a["kappa_io"][:, own], name + ": kv_io = Prandtl_turb * kappa_io")
+        for n in a:
+            _bits(a[n][..., own], b[n][..., own], f"{name}: {n} with two fills")
+            z = a[n][..., land]
+            assert (z == 0.0).all() and not np.signbit(z).any(), (name, n)
+            assert np.isnan(a[n][..., ~own]).all() and (b[n][..., ~own] == 3.25).all(), (name, n)
+            assert np.isfinite(a[n][..., own]).all(), (name, n)
+
+
+def _runs():
+    GV = abi.vgrid_default()
+    for grid, nk in CONFIGS:
+        d, M = _grid(grid, nk)
+        for name in R.CASES:
+            P, opt = R.case(name, GV)
+            yield grid, nk, name, d, M, GV, P, opt, R.case_inputs(d, M, GV, opt)
+
+
+def test_the_case_table_reaches_every_required_arm_and_the_shear_case_mixes():
+    """Over the case table on the grids of the GPU tests every counter of REQUIRED is non-zero.  On the case `shear` at least a
+    quarter of the wet columns have kappa > 0 at some interface and at least one in ten take two or more outer iterations, on every
+    grid with an interior interface: a comparison of that case is a comparison of mixing columns."""
+    tot = R.new_counts()
+    for grid, nk, name, d, M, GV, P, opt, inp in _runs():
+        out, counts = R.run(d, M, GV, P, opt, inp)
+        own = _own(d)
+        for n, a in out.items():
+            assert np.isfinite(a[..., own]).all() and np.isnan(a[..., ~own]).all(), (grid, nk, name, n)
+        for k, v in counts.items():
+            tot[k] += v
+        if name == "shear" and nk >= 2:
+            wet = own & (M[G["mask2dT"]] > 0.0)
+            mixed = (out["kappa_io"][:, wet] > 0.0).any(axis=0)
+            two = out["KS_its"][wet] >= 2.0
+            print(grid, nk, "shear: wet", int(wet.sum()), "mixing", int(mixed.sum()), "two or more iterations", int(two.sum()))
+            assert 4 * mixed.sum() >= wet.sum(), (grid, nk, int(mixed.sum()), int(wet.sum()))
+            assert 10 * two.sum() >= wet.sum(), (grid, nk, int(two.sum()), int(wet.sum()))
+    print("branch counts", tot)
+    for k in REQUIRED:
+        assert tot[k] > 0, (k, tot)
+    assert set(REQUIRED) <= set(R.BRANCHES)
