@@ -1507,7 +1507,11 @@ typedef struct mom6x_kappa_shear_params {
  * copy of GV%Rlay (a HOST array of nk values; NULL: none), and allocates the workspace: 51 arrays of nk + 1 levels for each of
  * work_columns slots, on the device.  A refused or invalid call leaves no module behind, also where an earlier call had succeeded.
  * MOM6X_EUNSUPPORTED, naming the setting: KS_at_vertex (VERTEX_SHEAR), a non-Boussinesq context.  MOM6X_EINVAL: max_KS_it < 1,
- * max_RiNo_it < 1, RiNo_crit <= 0, kappa_src_max_chg <= 1, work_columns < 0, nkml < 1, lambda = 0, an unknown EQN_OF_STATE form.  */
+ * max_RiNo_it < 1, RiNo_crit <= 0, kappa_src_max_chg <= 1, work_columns < 0, nkml < 1, lambda = 0, an unknown EQN_OF_STATE form.
+ * The reference's kappa_shear_init has no FATAL of its own: the compiled init takes every one of these values as given
+ * (KAPPA_BUOY_SCALE_COEF = 0 then divides by zero at :1632); GV%nkml = 0 is its spelling of nkml = 1 (:2283-2289) and
+ * work_columns is not a setting of its.  The refusals above are the device's alone; only an unknown EQN_OF_STATE is FATAL there
+ * too (MOM_EOS.F90:1591).  tests/test_ref_parity_cpu.py holds this list to the compiled init.                                   */
 int mom6x_kappa_shear_init(mom6x_ctx *ctx, const mom6x_kappa_shear_params *p, const mom6x_eos_params *eos, const double *Rlay);
 /* The bytes of the workspace that mom6x_kappa_shear_init allocated (0 before it). */
 long long mom6x_kappa_shear_work_bytes(mom6x_ctx *ctx);

@@ -26,7 +26,8 @@
 // find_kappa_tke (:1303); a wavefront of such columns goes on to its next columns at once (there is no barrier in the kernel).  In a
 // mixed wavefront the lanes that are done idle behind the slowest column until the wavefront moves on.
 //
-// x**2 is x*x.  MAX and MIN are fmax1 and fmin1; a literal 0.0 operand is the run-time K.zero (see energetic_PBL.hip).  The EOS form
+// x**2 is x*x.  MAX and MIN are fmax1 and fmin1, but N2 = MAX(0.0, ...) of :1492-1502 is dmax: with an argument of -0.0 the compiled
+// reference returns -0.0 (the case `tie`).  A literal 0.0 operand is the run-time K.zero (see energetic_PBL.hip).  The EOS form
 // is a wavefront-uniform switch inside the one kernel (EOS_FORM_DISPATCH): the kernel is not instantiated per form.
 #include "mom6x_dev.h"
 #include "eos_dev.h"
@@ -135,7 +136,7 @@ __device__ __forceinline__ void ks_proj(const Ws &W, const KsK &K, int a_kap, do
     const double I = W(A_Idzi, ks);
     um = W(ou, ks); vm = W(ov, ks); Tm = W(oT, ks); Sm = W(oS, ks);
     W(A_S2, ks) = (ks_sq(um - W(A_u, ks - 1)) + ks_sq(vm - W(A_v, ks - 1))) * ks_sq(K.L_to_Z * I);
-    W(A_N2, ks) = fmax1(K.zero, I * (W(A_dbT, ks) * (W(A_T, ks - 1) - Tm) + W(A_dbS, ks) * (W(A_S, ks - 1) - Sm)));
+    W(A_N2, ks) = dmax(K.zero, I * (W(A_dbT, ks) * (W(A_T, ks - 1) - Tm) + W(A_dbS, ks) * (W(A_S, ks - 1) - Sm)));
   } else {
     um = W(ou, 1); vm = W(ov, 1); Tm = W(oT, 1); Sm = W(oS, 1);
   }
@@ -143,13 +144,13 @@ __device__ __forceinline__ void ks_proj(const Ws &W, const KsK &K, int a_kap, do
     const double I = W(A_Idzi, k);
     const double uk = W(ou, k), vk = W(ov, k), Tk = W(oT, k), Sk = W(oS, k);
     W(A_S2, k) = (ks_sq(uk - um) + ks_sq(vk - vm)) * ks_sq(K.L_to_Z * I);
-    W(A_N2, k) = fmax1(K.zero, I * (W(A_dbT, k) * (Tm - Tk) + W(A_dbS, k) * (Sm - Sk)));
+    W(A_N2, k) = dmax(K.zero, I * (W(A_dbT, k) * (Tm - Tk) + W(A_dbS, k) * (Sm - Sk)));
     um = uk; vm = vk; Tm = Tk; Sm = Sk;
   }
   if (ke < nz) {
     const double I = W(A_Idzi, ke + 1);
     W(A_S2, ke + 1) = (ks_sq(W(A_u, ke + 1) - um) + ks_sq(W(A_v, ke + 1) - vm)) * ks_sq(K.L_to_Z * I);
-    W(A_N2, ke + 1) = fmax1(K.zero, I * (W(A_dbT, ke + 1) * (Tm - W(A_T, ke + 1)) + W(A_dbS, ke + 1) * (Sm - W(A_S, ke + 1))));
+    W(A_N2, ke + 1) = dmax(K.zero, I * (W(A_dbT, ke + 1) * (Tm - W(A_T, ke + 1)) + W(A_dbS, ke + 1) * (Sm - W(A_S, ke + 1))));
   }
 }
 

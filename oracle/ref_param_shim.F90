@@ -1,7 +1,8 @@
 !> ORACLE SUPPORT (test infrastructure only): bind(C) doors into the reference's parameterization modules, compiled where
 !! they lie against the stand-ins of oracle/ref_standins.F90 into oracle/_ref/libref_param.so (see oracle/Makefile):
 !! MOM_EOS_Wright.F90, MOM_EOS_Wright_full.F90, MOM_EOS_Wright_red.F90, MOM_EOS_linear.F90, MOM_intrinsic_functions.F90,
-!! MOM_opacity.F90 and MOM_energetic_PBL.F90, with MOM_unit_scaling.F90 and MOM_string_functions.F90.
+!! MOM_opacity.F90, MOM_energetic_PBL.F90 and MOM_kappa_shear.F90 (with the dispatcher MOM_EOS.F90 that it calls), with
+!! MOM_unit_scaling.F90 and MOM_string_functions.F90.
 !! tests/ref_param.py loads the library and holds the parameter-name maps; tests/test_ref_parity_cpu.py holds the python
 !! restatements under tests/ to these doors.  Nothing of the reference is copied here.
 !!
@@ -20,7 +21,7 @@ module ref_param_shim
   use MOM_verticalGrid, only : verticalGrid_type
   use MOM_unit_scaling, only : unit_scale_type, unit_scaling_init, unit_scaling_end
   use MOM_variables, only : thermo_var_ptrs, vertvisc_type
-  use MOM_EOS, only : EOS_type
+  use MOM_EOS, only : EOS_type, EOS_init
   use MOM_forcing_type, only : forcing
   use MOM_wave_interface, only : wave_parameters_CS
   use MOM_stochastics, only : stochastic_CS
@@ -32,6 +33,7 @@ module ref_param_shim
   use MOM_intrinsic_functions, only : cuberoot, invcosh
   use MOM_opacity, only : optics_type, opacity_CS, opacity_init, set_opacity, opacity_end, absorbRemainingSW, sumSWoverBands
   use MOM_energetic_PBL, only : energetic_PBL_CS, energetic_PBL_init, energetic_PBL, energetic_PBL_get_MLD, energetic_PBL_end
+  use MOM_kappa_shear, only : Kappa_shear_CS, kappa_shear_init, Calculate_kappa_shear
   implicit none
 contains
   function fstr(s) result(f)
@@ -306,5 +308,49 @@ contains
     deallocate(stoch)
     call unit_scaling_end(US)
     ref_energetic_PBL = standin_fatal_count
+  end function
+  !> kappa_shear_init (MOM_kappa_shear.F90:2070) and EOS_init (MOM_EOS.F90:1540) through the table, then Calculate_kappa_shear
+  !! (:133) on a whole tile.  3-D arrays are [nk, nj_mem, ni_mem], the outputs [nk + 1, nj_mem, ni_mem].  u_h and v_h are the
+  !! velocities at thickness points (find_uv_at_h lives in MOM_diabatic_aux.F90, which is not compiled).  T and S are C pointers,
+  !! null together for the layered arm (tv%T not associated), which reads GV%Rlay = Rlay(nk); p_surf is a C pointer, null for "not
+  !! associated".  vgx = (g_Earth, m2_s_to_HZ_T, HZ_T_to_m2_s, HZ_T_to_MKS) are the members of GV beyond vgr that the module reads;
+  !! nkml goes in as GV%nkml (read with KAPPA_SHEAR_MERGE_ML).  The diagnostics N2_shear_in, S2_shear_in, N2_shear_mean and
+  !! S2_shear_mean are asked for here and read back with ref_get_diag.  dt <= 0: the two inits only (for what they refuse).
+  integer(c_int) function ref_Calculate_kappa_shear(ni_mem, nj_mem, idx, nk, vgr, vgx, nkml, mask, Coriolis2Bu, Rlay, h, u_h, v_h, &
+        T, S, p_surf, dt, kappa_io, tke_io, kv_io) bind(C, name="ref_Calculate_kappa_shear")
+    integer(c_int), value :: ni_mem, nj_mem, nk, nkml ; integer(c_int), intent(in) :: idx(4)
+    real(c_double), intent(in) :: vgr(14), vgx(4), mask(ni_mem, nj_mem), Coriolis2Bu(ni_mem, nj_mem), Rlay(nk)
+    real(c_double), intent(in), dimension(ni_mem, nj_mem, nk) :: h, u_h, v_h
+    type(c_ptr), value :: T, S, p_surf ; real(c_double), value :: dt
+    real(c_double), intent(inout), dimension(ni_mem, nj_mem, nk+1) :: kappa_io, tke_io, kv_io
+    type(ocean_grid_type) :: G ; type(verticalGrid_type) :: GV ; type(unit_scale_type), pointer :: US
+    type(param_file_type) :: pf ; type(diag_ctrl), target :: diag ; type(time_type), target :: Time
+    type(Kappa_shear_CS), pointer :: CS ; type(thermo_var_ptrs) :: tv ; type(EOS_type), target :: eqn
+    real, pointer :: p_ps(:,:)
+    logical :: used
+    standin_fatal_count = 0
+    call standin_want_diag("N2_shear_in") ; call standin_want_diag("S2_shear_in")
+    call standin_want_diag("N2_shear_mean") ; call standin_want_diag("S2_shear_mean")
+    call setup(int(ni_mem), int(nj_mem), int(idx), int(nk), vgr, mask, c_null_ptr, pf, G, GV, US)
+    allocate(G%Coriolis2Bu(ni_mem, nj_mem), G%mask2dCu(ni_mem, nj_mem), G%mask2dCv(ni_mem, nj_mem), G%mask2dBu(ni_mem, nj_mem))
+    G%Coriolis2Bu(:,:) = Coriolis2Bu(:,:) ; G%mask2dCu(:,:) = 0.0 ; G%mask2dCv(:,:) = 0.0 ; G%mask2dBu(:,:) = 0.0  ! (vertex only)
+    GV%g_Earth = vgx(1) ; GV%m2_s_to_HZ_T = vgx(2) ; GV%HZ_T_to_m2_s = vgx(3) ; GV%HZ_T_to_MKS = vgx(4)
+    GV%nkml = nkml ; GV%semi_Boussinesq = .false.
+    allocate(GV%Rlay(nk)) ; GV%Rlay(:) = Rlay(:)
+    CS => NULL()
+    used = kappa_shear_init(Time, G, GV, US, pf, diag, CS)
+    if (.not.used) standin_fatal_count = standin_fatal_count + 1    ! USE_JACKSON_PARAM is part of every table
+    if (c_associated(T) .and. c_associated(S)) then
+      call c_f_pointer(T, tv%T, (/ int(ni_mem), int(nj_mem), int(nk) /))
+      call c_f_pointer(S, tv%S, (/ int(ni_mem), int(nj_mem), int(nk) /))
+      call EOS_init(pf, eqn, US)
+      tv%eqn_of_state => eqn
+    endif
+    call plane(p_surf, int(ni_mem), int(nj_mem), p_ps)
+    if (standin_fatal_count == 0 .and. dt > 0.0) &
+      call Calculate_kappa_shear(u_h, v_h, h, tv, p_ps, kappa_io, tke_io, kv_io, dt, G, GV, US, CS)
+    if (associated(CS)) deallocate(CS)
+    call unit_scaling_end(US)
+    ref_Calculate_kappa_shear = standin_fatal_count
   end function
 end module ref_param_shim

@@ -1,7 +1,8 @@
 !> oracle/ref_standins.F90 -- ORACLE SUPPORT (test infrastructure only), not product and not reference text.
 !!
-!! The reference's parameterization modules (MOM_opacity.F90, MOM_energetic_PBL.F90) `use` framework modules that need FMS and
-!! netCDF.  oracle/Makefile compiles those two files, and every framework file that does compile on its own, where they lie, against
+!! The reference's parameterization modules (MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90) `use` framework modules
+!! that need FMS and netCDF.  oracle/Makefile compiles those files, and every framework file that does compile on its own (the
+!! equation-of-state dispatcher MOM_EOS.F90 with every module it uses among them), where they lie, against
 !! the interface-only stand-ins below.  The rule is that of tests/fortran_stubs/mom_stubs.F90: each module carries the name of the
 !! MOM6 module it stands for and declares ONLY the derived-type members and procedure signatures that the compiled reference files
 !! touch (names, members and argument lists are interface facts); the bodies are a few lines of bookkeeping written here.
@@ -11,12 +12,16 @@
 !!     post_data copies the posted field into a store keyed by that id, which the door reads back (standin_get_diag);
 !!   * query_averaging_enabled is true;
 !!   * MOM_error(FATAL, ...) prints and counts (standin_fatal_count); it never stops, since a stop would end the test process;
-!!   * EFP sums are plain sums (they feed a debugging printout only).
+!!   * EFP sums are plain sums (they feed a debugging printout only);
+!!   * gsw_mod_toolbox (the TEOS-10 toolbox, a package the reference links to and does not hold) has the ten procedures that
+!!     MOM_EOS_TEOS10.F90 and MOM_TFreeze.F90 name, which answer NaN: with it those two files and MOM_EOS.F90 compile from their own
+!!     text.  No compared case selects TEOS10 or a TEOS10 freezing point, so none of the ten is ever called.
 !! Stood in for: MOM_error_handler, MOM_coms, MOM_cpu_clock, MOM_time_manager, MOM_hor_index, MOM_domains, MOM_grid,
-!! MOM_verticalGrid, MOM_file_parser, MOM_EOS (the type's name only), MOM_variables, MOM_forcing_type, MOM_diag_mediator,
-!! MOM_debugging, MOM_interface_heights, MOM_wave_interface, MOM_stochastics.
-!! The file is compiled twice: everything but MOM_wave_interface before the reference's own MOM_unit_scaling.F90, and
-!! MOM_wave_interface (whose one procedure takes a unit_scale_type) after it, with -DSTANDINS_AFTER_UNIT_SCALING.
+!! MOM_verticalGrid, MOM_file_parser, MOM_io (stdout and stderr), gsw_mod_toolbox, MOM_variables, MOM_forcing_type,
+!! MOM_diag_mediator, MOM_debugging, MOM_interface_heights, MOM_wave_interface, MOM_stochastics.  MOM_EOS is no longer among them.
+!! The file is compiled twice: what needs neither a unit_scale_type nor an EOS_type before the reference's own
+!! MOM_unit_scaling.F90 and equation-of-state files, and MOM_variables (whose thermo_var_ptrs holds an EOS_type),
+!! MOM_interface_heights and MOM_wave_interface after them, with -DSTANDINS_AFTER_UNIT_SCALING.
 #ifndef STANDINS_AFTER_UNIT_SCALING
 
 module MOM_error_handler
@@ -118,17 +123,19 @@ module MOM_grid
   type :: ocean_grid_type
     type(hor_index_type) :: HI
     integer :: isc, iec, jsc, jec, isd, ied, jsd, jed, IscB, IecB, JscB, JecB, IsdB, IedB, JsdB, JedB
-    real, allocatable, dimension(:,:) :: mask2dT, CoriolisBu, geoLonT, geoLatT
+    real, allocatable, dimension(:,:) :: mask2dT, CoriolisBu, geoLonT, geoLatT, Coriolis2Bu, mask2dCu, mask2dCv, mask2dBu
   end type ocean_grid_type
 end module MOM_grid
 
 module MOM_verticalGrid
   implicit none ; public
   type :: verticalGrid_type
-    integer :: ke
-    logical :: Boussinesq = .true.
-    real :: Rho0, g_Earth_Z_T2, Angstrom_H, Angstrom_Z, H_subroundoff, dZ_subroundoff
+    integer :: ke, nkml = 0
+    logical :: Boussinesq = .true., semi_Boussinesq = .false.
+    real :: Rho0, g_Earth, g_Earth_Z_T2, Angstrom_H, Angstrom_Z, H_subroundoff, dZ_subroundoff
     real :: H_to_Z = 1., Z_to_H = 1., H_to_RZ, RZ_to_H, H_to_m = 1., m_to_H = 1., H_to_MKS = 1., HZ_T_to_m2_s = 1.
+    real :: m2_s_to_HZ_T = 1., HZ_T_to_MKS = 1.
+    real, allocatable, dimension(:) :: Rlay
   end type verticalGrid_type
 end module MOM_verticalGrid
 
@@ -266,23 +273,52 @@ contains
   end subroutine closeParameterBlock
 end module MOM_file_parser
 
-module MOM_EOS
+module MOM_io
+  use, intrinsic :: iso_fortran_env, only : stdout => output_unit, stderr => error_unit
   implicit none ; public
-  type :: EOS_type ; integer :: form_of_EOS = 0 ; end type EOS_type
-end module MOM_EOS
+end module MOM_io
 
-module MOM_variables
-  use MOM_EOS, only : EOS_type
-  implicit none ; public
-  type :: thermo_var_ptrs
-    real, pointer, dimension(:,:,:) :: T => NULL(), S => NULL()
-    type(EOS_type), pointer :: eqn_of_state => NULL()
-    real, allocatable, dimension(:,:,:) :: SpV_avg
-  end type thermo_var_ptrs
-  type :: vertvisc_type
-    real, allocatable, dimension(:,:) :: ustar_BBL, BBL_meanKE_loss, BBL_meanKE_loss_sqrtCd
-  end type vertvisc_type
-end module MOM_variables
+module gsw_mod_toolbox
+  use, intrinsic :: ieee_arithmetic, only : ieee_value, ieee_quiet_nan
+  implicit none ; private
+  public :: gsw_sp_from_sr, gsw_sr_from_sp, gsw_pt_from_ct, gsw_ct_from_pt, gsw_rho, gsw_specvol, gsw_ct_freezing_exact
+  public :: gsw_rho_first_derivatives, gsw_rho_second_derivatives, gsw_specvol_first_derivatives
+contains
+  elemental real function gsw_sp_from_sr(sr) ; real, intent(in) :: sr
+    gsw_sp_from_sr = ieee_value(sr, ieee_quiet_nan) ; end function
+  elemental real function gsw_sr_from_sp(sp) ; real, intent(in) :: sp
+    gsw_sr_from_sp = ieee_value(sp, ieee_quiet_nan) ; end function
+  elemental real function gsw_pt_from_ct(sa, ct) ; real, intent(in) :: sa, ct
+    gsw_pt_from_ct = ieee_value(sa, ieee_quiet_nan) ; end function
+  elemental real function gsw_ct_from_pt(sa, pt) ; real, intent(in) :: sa, pt
+    gsw_ct_from_pt = ieee_value(sa, ieee_quiet_nan) ; end function
+  elemental real function gsw_rho(sa, ct, p) ; real, intent(in) :: sa, ct, p
+    gsw_rho = ieee_value(sa, ieee_quiet_nan) ; end function
+  elemental real function gsw_specvol(sa, ct, p) ; real, intent(in) :: sa, ct, p
+    gsw_specvol = ieee_value(sa, ieee_quiet_nan) ; end function
+  elemental real function gsw_ct_freezing_exact(sa, p, saturation_fraction) ; real, intent(in) :: sa, p, saturation_fraction
+    gsw_ct_freezing_exact = ieee_value(sa, ieee_quiet_nan) ; end function
+  elemental subroutine gsw_rho_first_derivatives(sa, ct, p, drho_dsa, drho_dct, drho_dp)
+    real, intent(in) :: sa, ct, p ; real, intent(out), optional :: drho_dsa, drho_dct, drho_dp
+    if (present(drho_dsa)) drho_dsa = ieee_value(sa, ieee_quiet_nan)
+    if (present(drho_dct)) drho_dct = ieee_value(sa, ieee_quiet_nan)
+    if (present(drho_dp)) drho_dp = ieee_value(sa, ieee_quiet_nan)
+  end subroutine
+  elemental subroutine gsw_rho_second_derivatives(sa, ct, p, rho_sa_sa, rho_sa_ct, rho_ct_ct, rho_sa_p, rho_ct_p)
+    real, intent(in) :: sa, ct, p ; real, intent(out), optional :: rho_sa_sa, rho_sa_ct, rho_ct_ct, rho_sa_p, rho_ct_p
+    if (present(rho_sa_sa)) rho_sa_sa = ieee_value(sa, ieee_quiet_nan)
+    if (present(rho_sa_ct)) rho_sa_ct = ieee_value(sa, ieee_quiet_nan)
+    if (present(rho_ct_ct)) rho_ct_ct = ieee_value(sa, ieee_quiet_nan)
+    if (present(rho_sa_p)) rho_sa_p = ieee_value(sa, ieee_quiet_nan)
+    if (present(rho_ct_p)) rho_ct_p = ieee_value(sa, ieee_quiet_nan)
+  end subroutine
+  elemental subroutine gsw_specvol_first_derivatives(sa, ct, p, v_sa, v_ct, v_p)
+    real, intent(in) :: sa, ct, p ; real, intent(out), optional :: v_sa, v_ct, v_p
+    if (present(v_sa)) v_sa = ieee_value(sa, ieee_quiet_nan)
+    if (present(v_ct)) v_ct = ieee_value(sa, ieee_quiet_nan)
+    if (present(v_p)) v_p = ieee_value(sa, ieee_quiet_nan)
+  end subroutine
+end module gsw_mod_toolbox
 
 module MOM_forcing_type
   implicit none ; public
@@ -299,7 +335,7 @@ module MOM_diag_mediator
   public :: standin_clear_diags, standin_want_diag, standin_diag_size, standin_get_diag
   type :: axes_grp ; integer :: rank = 0 ; end type axes_grp
   type :: diag_ctrl
-    type(axes_grp) :: axesT1, axesTL, axesTi
+    type(axes_grp) :: axesT1, axesTL, axesTi, axesBi
   end type diag_ctrl
   integer, parameter :: NDMAX = 64
   type :: capture ; real, allocatable :: v(:) ; end type capture
@@ -385,8 +421,11 @@ end module MOM_diag_mediator
 module MOM_debugging
   use MOM_hor_index, only : hor_index_type
   implicit none ; private
-  public :: hchksum
+  public :: hchksum, Bchksum
   interface hchksum
+    module procedure hchksum_2d, hchksum_3d
+  end interface
+  interface Bchksum
     module procedure hchksum_2d, hchksum_3d
   end interface
 contains
@@ -400,24 +439,6 @@ contains
   end subroutine hchksum_3d
 end module MOM_debugging
 
-module MOM_interface_heights
-  use MOM_grid, only : ocean_grid_type
-  use MOM_verticalGrid, only : verticalGrid_type
-  use MOM_variables, only : thermo_var_ptrs
-  implicit none ; private
-  public :: thickness_to_dz
-contains
-  !> The j-slice form, Boussinesq only: dz = GV%H_to_Z * h.  The device refuses non-Boussinesq contexts, so the specific-volume
-  !! arm of the reference's routine cannot be reached by anything compared here and is not stood in for.
-  subroutine thickness_to_dz(h, tv, dz, j, G, GV, halo_size)
-    type(ocean_grid_type), intent(in) :: G ; type(verticalGrid_type), intent(in) :: GV
-    real, dimension(G%isd:G%ied,G%jsd:G%jed,GV%ke), intent(in) :: h ; type(thermo_var_ptrs), intent(in) :: tv
-    real, dimension(G%isd:G%ied,GV%ke), intent(inout) :: dz ; integer, intent(in) :: j ; integer, optional, intent(in) :: halo_size
-    integer :: i, k
-    do k = 1, GV%ke ; do i = G%isc, G%iec ; dz(i,k) = GV%H_to_Z * h(i,j,k) ; enddo ; enddo
-  end subroutine thickness_to_dz
-end module MOM_interface_heights
-
 module MOM_stochastics
   implicit none ; public
   type :: stochastic_CS
@@ -428,6 +449,53 @@ module MOM_stochastics
 end module MOM_stochastics
 
 #else
+
+module MOM_variables
+  use MOM_EOS, only : EOS_type
+  implicit none ; public
+  type :: thermo_var_ptrs
+    real, pointer, dimension(:,:,:) :: T => NULL(), S => NULL()
+    type(EOS_type), pointer :: eqn_of_state => NULL()
+    real, allocatable, dimension(:,:,:) :: SpV_avg
+  end type thermo_var_ptrs
+  type :: vertvisc_type
+    real, allocatable, dimension(:,:) :: ustar_BBL, BBL_meanKE_loss, BBL_meanKE_loss_sqrtCd
+  end type vertvisc_type
+end module MOM_variables
+
+module MOM_interface_heights
+  use MOM_grid, only : ocean_grid_type
+  use MOM_verticalGrid, only : verticalGrid_type
+  use MOM_unit_scaling, only : unit_scale_type
+  use MOM_variables, only : thermo_var_ptrs
+  implicit none ; private
+  public :: thickness_to_dz
+  interface thickness_to_dz
+    module procedure thickness_to_dz_jslice, thickness_to_dz_3d
+  end interface
+contains
+  !> The j-slice form, Boussinesq only: dz = GV%H_to_Z * h.  The device refuses non-Boussinesq contexts, so the specific-volume
+  !! arm of the reference's routine cannot be reached by anything compared here and is not stood in for.
+  subroutine thickness_to_dz_jslice(h, tv, dz, j, G, GV, halo_size)
+    type(ocean_grid_type), intent(in) :: G ; type(verticalGrid_type), intent(in) :: GV
+    real, dimension(G%isd:G%ied,G%jsd:G%jed,GV%ke), intent(in) :: h ; type(thermo_var_ptrs), intent(in) :: tv
+    real, dimension(G%isd:G%ied,GV%ke), intent(inout) :: dz ; integer, intent(in) :: j ; integer, optional, intent(in) :: halo_size
+    integer :: i, k
+    do k = 1, GV%ke ; do i = G%isc, G%iec ; dz(i,k) = GV%H_to_Z * h(i,j,k) ; enddo ; enddo
+  end subroutine thickness_to_dz_jslice
+  !> The 3-D form, which only Calc_kappa_shear_vertex calls (compiled with its module, never run: the device refuses
+  !! VERTEX_SHEAR): the same body over the computational domain and halo_size points around it.
+  subroutine thickness_to_dz_3d(h, tv, dz, G, GV, US, halo_size)
+    type(ocean_grid_type), intent(in) :: G ; type(verticalGrid_type), intent(in) :: GV ; type(unit_scale_type), intent(in) :: US
+    real, dimension(G%isd:G%ied,G%jsd:G%jed,GV%ke), intent(in) :: h ; type(thermo_var_ptrs), intent(in) :: tv
+    real, dimension(G%isd:G%ied,G%jsd:G%jed,GV%ke), intent(inout) :: dz ; integer, optional, intent(in) :: halo_size
+    integer :: i, j, k, halo
+    halo = 0 ; if (present(halo_size)) halo = max(halo_size, 0)
+    do k = 1, GV%ke ; do j = G%jsc-halo, G%jec+halo ; do i = G%isc-halo, G%iec+halo
+      dz(i,j,k) = GV%H_to_Z * h(i,j,k)
+    enddo ; enddo ; enddo
+  end subroutine thickness_to_dz_3d
+end module MOM_interface_heights
 
 module MOM_wave_interface
   use MOM_grid, only : ocean_grid_type

@@ -1,13 +1,21 @@
 """Calculate_kappa_shear (src/parameterizations/vertical/MOM_kappa_shear.F90:133-411) with kappa_shear_column (:864-1372),
 calculate_projected_state (:1377-1504) and find_kappa_tke (:1507-2067), Boussinesq, and find_uv_at_h without vertical mixing
 (MOM_diabatic_aux.F90:546-571, :595-611), restated per column in plain Python from the Fortran in its statement order.  The
-arithmetic is + - * / and sqrt; x**2 is a product; MAX and MIN return their first argument on a tie.  The column's arrays are lists
+arithmetic is + - * / and sqrt; x**2 is a product; MAX and MIN return their first argument on a tie (fmax1, fmin1), except at the
+one kind of site where the tie shows, N2 = MAX(0.0, ...) of :1492-1502 with an argument of -0.0, where the compiled reference
+returns its second (dmax: N2 = -0.0; found by tests/test_ref_parity_cpu.py with the case `tie`).  The column's arrays are lists
 indexed as in the Fortran (element 0 is not used) and start as NaN, so that a read of a value the reference never set shows.
 
 The constants tke_noflux_top_BC, tke_noflux_bottom_BC and debug_soln of find_kappa_tke are .false. in the reference; their arms
 are not restated.  Density derivatives come from the oracle's EOS (tests/ref_common._derivs), which is held to the compiled Fortran.
 
-BRANCHES names the arms a case list can be held to; every run adds to a dict of counters."""
+BRANCHES names the arms a case list can be held to; every run adds to a dict of counters.
+
+What pins this file: tests/test_ref_parity_cpu.py compares it, whole arrays bit for bit, with the reference's own
+MOM_kappa_shear.F90 and MOM_EOS.F90 compiled where they lie (oracle/Makefile), on every case of CASES, through the reference's own
+kappa_shear_init, EOS_init and unit_scaling_init, and with the results recorded from them (tests/golden/ref_kshear_*.npz).  Outside
+that comparison stay find_uv_at_h below (its module is not compiled; the compiled routine is handed what it makes) and the
+iteration count KS_its (it reaches no diagnostic of the reference); tests/test_kappa_shear_cpu.py holds those."""
 import math
 
 import numpy as np
@@ -34,6 +42,11 @@ def fmax1(a, b):
 
 def fmin1(a, b):
     return b if b < a else a
+
+
+def dmax(a, b):
+    """MAX(a, b) as the compiled reference evaluates it: the second argument on a tie, which between +0 and -0 is the sign."""
+    return a if a > b else b
 
 
 def new_counts():
@@ -149,11 +162,11 @@ def calculate_projected_state(kappa, u0, v0, T0, S0, dt, nz, dz, I_dz_int, dbuoy
         S2[ke + 1] = (sq(u0[ke + 1] - u[ke]) + sq(v0[ke + 1] - v[ke])) * sq(L_to_Z * I_dz_int[ke + 1])
     N2[1] = 0.0; N2[nz + 1] = 0.0
     if ks > 1:
-        N2[ks] = fmax1(0.0, I_dz_int[ks] * (dbuoy_dT[ks] * (T0[ks - 1] - T[ks]) + dbuoy_dS[ks] * (S0[ks - 1] - Sal[ks])))
+        N2[ks] = dmax(0.0, I_dz_int[ks] * (dbuoy_dT[ks] * (T0[ks - 1] - T[ks]) + dbuoy_dS[ks] * (S0[ks - 1] - Sal[ks])))
     for K in range(ks + 1, ke + 1):
-        N2[K] = fmax1(0.0, I_dz_int[K] * (dbuoy_dT[K] * (T[K - 1] - T[K]) + dbuoy_dS[K] * (Sal[K - 1] - Sal[K])))
+        N2[K] = dmax(0.0, I_dz_int[K] * (dbuoy_dT[K] * (T[K - 1] - T[K]) + dbuoy_dS[K] * (Sal[K - 1] - Sal[K])))
     if ke < nz:
-        N2[ke + 1] = fmax1(0.0, I_dz_int[ke + 1] * (dbuoy_dT[ke + 1] * (T[ke] - T0[ke + 1]) + dbuoy_dS[ke + 1] * (Sal[ke] - S0[ke + 1])))
+        N2[ke + 1] = dmax(0.0, I_dz_int[ke + 1] * (dbuoy_dT[ke + 1] * (T[ke] - T0[ke + 1]) + dbuoy_dS[ke + 1] * (Sal[ke] - S0[ke + 1])))
 
 
 def find_kappa_tke(CS, N2, S2, kappa_in, Idz, h_Int, dz_Int, dz_h_Int, I_L2_bdry, f2, nz, K_Q, tke, kappa, br, kappa_src=None,
@@ -852,13 +865,15 @@ def _ij(d):
     return il, jl
 
 
-def inputs(d, M, GV, seed=5, band=0.15, U0=0.5, thin=True, zero_uv=False, p_surf=True, h0=10.0):
+def inputs(d, M, GV, seed=5, band=0.15, U0=0.5, thin=True, zero_uv=False, p_surf=True, h0=10.0, uniform=False):
     """u, v, h, T, S, p_surf and GV%Rlay on a tile, laid in global coordinates.  Layers of about 10 m whatever their number; T falls
     by 0.5 degC and S rises by 0.02 from layer to layer (stable), Rlay rises by 0.1 kg m-3.  u is a tanh shear layer of three
     layers' width across the middle of the column, of amplitude U0*(0.6 + 0.8*smooth) in a band of rows (the fraction `band` of
     the basin, from a quarter of the way up) and a twentieth of that elsewhere; v is -0.3 times a shifted copy: the bulk Ri across
     the middle is 0.1 to 0.3 in the band and above 25 outside.  thin: some columns have layers of exactly zero thickness, others a
-    layer of 0.1 mm in the shear layer (massless: below dz_massless, merged with weight kf > 0).  zero_uv: u = v = 0.  h0: the layer thickness in place of 10 m."""
+    layer of 0.1 mm in the shear layer (massless: below dz_massless, merged with weight kf > 0).  zero_uv: u = v = 0.  h0: the layer
+    thickness in place of 10 m.  uniform: every wet layer is exactly h0 thick, T = 16 and S = 32 everywhere (with h0 a power of two
+    and kappa_0 = 0 the differences of T and of S between layers are exact zeros)."""
     from mom6_amd import synth
     nk = d.nk
     il, jl = _ij(d)
@@ -869,6 +884,8 @@ def inputs(d, M, GV, seed=5, band=0.15, U0=0.5, thin=True, zero_uv=False, p_surf
         h[nk - 2] = np.where(il % 7 == 3, 0.0, h[nk - 2])
         h[1] = np.where(il % 13 == 5, 0.0, h[1])
         h[nk // 2] = np.where(il % 11 == 2, 1.0e-4, h[nk // 2])
+    if uniform:
+        h = np.full_like(h, h0)
     h = np.where(wetp, h, 0.0)
     j0 = int(0.25 * d.nj_glob); j1 = j0 + max(int(round(band * d.nj_glob)), 1)
     inband = (jl >= j0) & (jl < j1)
@@ -881,6 +898,8 @@ def inputs(d, M, GV, seed=5, band=0.15, U0=0.5, thin=True, zero_uv=False, p_surf
     pT, pS = sf(10), sf(11)
     T = np.stack([20.0 - 0.5 * k + 0.2 * pT for k in range(nk)])
     S = np.stack([34.5 + 0.02 * k + 0.05 * pS for k in range(nk)])
+    if uniform:
+        T = np.full_like(T, 16.0); S = np.full_like(S, 32.0)
     out = dict(u=u, v=v, h=h, T=T, S=S)
     if p_surf:
         out["p_surf"] = 1.0e4 * (1.0 + 0.5 * sf(40))
@@ -891,7 +910,7 @@ def inputs(d, M, GV, seed=5, band=0.15, U0=0.5, thin=True, zero_uv=False, p_surf
 
 _ALL_DIAG = DIAG_3D + DIAG_2D
 # case -> (params members, options).  Options: eos (an EOS form, None: the layered arm), zero_mix, diag (the nullable outputs handed
-# in), dt, inp (keyword arguments of inputs())
+# in), dt, inp (keyword arguments of inputs()), eos_mods (members of the equation of state's parameters)
 CASES = {
     "shear": (dict(kappa_0=1.5e-5), dict(zero_mix=True, diag=_ALL_DIAG, inp=dict(band=0.45, U0=0.8))),
     "plain_linear": (dict(restrictive_tolerance_check=1), dict(eos=abi.LINEAR, diag=("KS_its", "N2_init"), inp=dict(p_surf=False))),
@@ -905,18 +924,27 @@ CASES = {
     "short_dt": (dict(max_RiNo_it=3, kappa_tol_err=0.3), dict(diag=("KS_its",), dt=300.0)),
     # a tight tolerance keeps find_kappa_tke iterating: Newton's method is entered often, and leaves on a negative pivot (:1888)
     "newton": (dict(kappa_tol_err=0.01), dict(eos=None, diag=("KS_its",), inp=dict(U0=0.8, band=0.1))),
+    # no stratification at all under a linear equation of state whose density rises with T and with S, and no background
+    # diffusion: dbuoy_dT*(+0) + dbuoy_dS*(+0) is -0.0 at every interior interface, and N2 = MAX(0.0, -0.0) (:1492-1502) is a tie
+    "tie": (dict(kappa_0=0.0), dict(eos=abi.LINEAR, eos_mods=dict(dRho_dT=0.25, dRho_dS=0.75), diag=("KS_its", "N2_init", "N2_mean"),
+                                    inp=dict(uniform=True, h0=8.0, thin=False))),
 }
 
 
 def case(name, GV):
     """(params, options)"""
     mods, opt = CASES[name]
-    opt = dict(dict(eos=abi.WRIGHT, zero_mix=False, diag=(), dt=3600.0, inp={}), **opt)
+    opt = dict(dict(eos=abi.WRIGHT, eos_mods={}, zero_mix=False, diag=(), dt=3600.0, inp={}), **opt)
     return abi.kappa_shear_params_default(GV, **mods), opt
 
 
 def case_eos(opt):
-    return abi.eos_params_default(opt["eos"]) if opt["eos"] is not None else None
+    if opt["eos"] is None:
+        return None
+    eos = abi.eos_params_default(opt["eos"])
+    for n, v in opt.get("eos_mods", {}).items():
+        setattr(eos, n, v)
+    return eos
 
 
 def case_inputs(d, M, GV, opt, **kw):

@@ -1,7 +1,8 @@
 """The loader of oracle/_ref/libref_param.so -- the reference's own MOM_EOS_Wright*.F90, MOM_EOS_linear.F90,
-MOM_intrinsic_functions.F90, MOM_opacity.F90 and MOM_energetic_PBL.F90 compiled where they lie against the interface stand-ins of
-oracle/ref_standins.F90, behind the bind(C) doors of oracle/ref_param_shim.F90 -- and the one place where the members of
-abi.OpacityParams and abi.EnergeticPBLParams are mapped to the names the reference reads with get_param.  Test infrastructure:
+MOM_intrinsic_functions.F90, MOM_opacity.F90, MOM_energetic_PBL.F90 and MOM_kappa_shear.F90 (with MOM_EOS.F90) compiled where they
+lie against the interface stand-ins of oracle/ref_standins.F90, behind the bind(C) doors of oracle/ref_param_shim.F90 -- and the
+one place where the members of abi.OpacityParams, abi.EnergeticPBLParams and abi.KappaShearParams are mapped to the names the
+reference reads with get_param.  Test infrastructure:
 tests/test_ref_parity_cpu.py holds the python restatements to these doors, scripts/record_ref_parity.py records their results for
 the GPU tests.  The maps below are lists of names; nothing of the reference's text is here."""
 import ctypes as C
@@ -29,7 +30,7 @@ def lib():
     if _lib is None and available():
         _lib = C.CDLL(LIB_PATH)
         _lib.ref_diag_size.restype = C.c_int
-        for n in ("ref_opacity", "ref_energetic_PBL", "ref_absorbRemainingSW", "ref_sumSWoverBands"):
+        for n in ("ref_opacity", "ref_energetic_PBL", "ref_absorbRemainingSW", "ref_sumSWoverBands", "ref_Calculate_kappa_shear"):
             getattr(_lib, n).restype = C.c_int
     return _lib
 
@@ -341,10 +342,109 @@ def energetic_PBL(d, M, GV, P, opt, inp, ncalls=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# recorded results (tests/golden/ref_opacity_*.npz, ref_epbl_*.npz): written by scripts/record_ref_parity.py from the doors above
+# MOM_kappa_shear
+
+# member of abi.KappaShearParams -> (the name kappa_shear_init reads (MOM_kappa_shear.F90:2114-2285), kind, the unit of the member)
+KSHEAR_PARAM_NAMES = {
+    "RiNo_crit": ("RINO_CRIT", "real", ""), "Shearmix_rate": ("SHEARMIX_RATE", "real", ""), "FRi_curvature": ("FRI_CURVATURE", "real", ""),
+    "C_N": ("TKE_N_DECAY_CONST", "real", ""), "C_S": ("TKE_SHEAR_DECAY_CONST", "real", ""), "lambda": ("KAPPA_BUOY_SCALE_COEF", "real", ""),
+    "lambda2_N_S": ("KAPPA_N_OVER_S_SCALE_COEF2", "real", ""), "lz_rescale": ("LZ_RESCALE", "real", ""),
+    "TKE_bg": ("TKE_BACKGROUND", "real", "Z2 T-2"), "kappa_0": ("KD_KAPPA_SHEAR_0", "real", "H Z T-1"),
+    "kappa_seed": ("KD_SEED_KAPPA_SHEAR", "real", "H Z T-1"), "kappa_trunc": ("KD_TRUNC_KAPPA_SHEAR", "real", "H Z T-1"),
+    "kappa_tol_err": ("KAPPA_SHEAR_TOL_ERR", "real", ""), "Prandtl_turb": ("PRANDTL_TURB", "real", ""),
+    "vel_underflow": ("VEL_UNDERFLOW", "real", "L T-1"), "kappa_src_max_chg": ("KAPPA_SHEAR_MAX_KAP_SRC_CHG", "real", ""),
+    "max_RiNo_it": ("MAX_RINO_IT", "int", ""), "max_KS_it": ("MAX_KAPPA_SHEAR_IT", "int", ""),
+    "eliminate_massless": ("KAPPA_SHEAR_ELIM_MASSLESS", "bool", ""), "dKdQ_iteration_bug": ("KAPPA_SHEAR_ITER_BUG", "bool", ""),
+    "all_layer_TKE_bug": ("KAPPA_SHEAR_ALL_LAYER_TKE_BUG", "bool", ""),
+    "restrictive_tolerance_check": ("USE_RESTRICTIVE_TOLERANCE_CHECK", "bool", ""), "KS_at_vertex": ("VERTEX_SHEAR", "bool", ""),
+}
+# Not parameters: nkml (GV%nkml with KAPPA_SHEAR_MERGE_ML, :2283-2289), m_to_Z, T_to_s, L_to_Z, RL2_T2_to_Pa and kg_m3_to_R (the
+# *_RESCALE_POWERs), Z_to_m_m_to_H and g_Earth_Z_T2 (GV), work_columns (the device's workspace).  USE_JACKSON_PARAM is true.
+KSHEAR_DIAG_NAMES = {"N2_init": "N2_shear_in", "S2_init": "S2_shear_in", "N2_mean": "N2_shear_mean", "S2_mean": "S2_shear_mean"}
+KSHEAR_NOT_EXPOSED = ("KS_its",)     # the iteration count reaches no diagnostic of the reference
+KSHEAR_EOS_NAMES = {abi.WRIGHT: "WRIGHT", abi.WRIGHT_FULL: "WRIGHT_FULL", abi.WRIGHT_REDUCED: "WRIGHT_REDUCED", abi.LINEAR: "LINEAR"}
+
+
+def kshear_units(P):
+    """The unit factors of a case from the members of abi.KappaShearParams: the powers of unit_scaling_init and the factors of GV."""
+    Z_to_m = 1.0 / P.m_to_Z
+    L_to_m = P.L_to_Z * Z_to_m
+    R_to_kg_m3 = 1.0 / P.kg_m3_to_R
+    m_to_H = P.Z_to_m_m_to_H * P.m_to_Z
+    powers = dict(Z=_power_of_two(Z_to_m, "Z_to_m"), L=_power_of_two(L_to_m, "L_to_m"), T=_power_of_two(P.T_to_s, "T_to_s"),
+                  R=_power_of_two(R_to_kg_m3, "R_to_kg_m3"))
+    assert P.RL2_T2_to_Pa == R_to_kg_m3 * (L_to_m / P.T_to_s) ** 2, "RL2_T2_to_Pa is not what US derives"
+    _power_of_two(m_to_H, "m_to_H")
+    return powers, dict(m_to_H=m_to_H, m2_s_to_HZ_T=m_to_H * P.m_to_Z * P.T_to_s, Z2_T2=(P.m_to_Z * P.T_to_s) ** 2,
+                        m_s_to_L_T=P.T_to_s / L_to_m)
+
+
+def kshear_table(P, eos=None, merge_ml=True):
+    """The parameter table of a case: members in the model's units go back to the MKS values a parameter file holds."""
+    powers, f = kshear_units(P)
+    to_mks = {"": 1.0, "Z2 T-2": 1.0 / f["Z2_T2"], "H Z T-1": 1.0 / f["m2_s_to_HZ_T"], "L T-1": 1.0 / f["m_s_to_L_T"]}
+    ent = [("USE_JACKSON_PARAM", True), ("KAPPA_SHEAR_MERGE_ML", bool(merge_ml))]
+    for member, (name, kind, unit) in KSHEAR_PARAM_NAMES.items():
+        v = getattr(P, member)
+        ent.append((name, float(v) * to_mks[unit] if kind == "real" else int(v) if kind == "int" else bool(v)))
+    if eos is not None:
+        ent.append(("EQN_OF_STATE", KSHEAR_EOS_NAMES[eos.form]))
+        if eos.form == abi.LINEAR:
+            ent += [("RHO_T0_S0", float(eos.Rho_T0_S0)), ("DRHO_DT", float(eos.dRho_dT)), ("DRHO_DS", float(eos.dRho_dS)),
+                    ("DRHO_DP", float(eos.dRho_dp))]
+    return ent, powers
+
+
+def Calculate_kappa_shear(d, M, GV, P, opt, inp, eos=None, table_extra=()):
+    """kappa_shear_init and EOS_init through the table, then Calculate_kappa_shear on the whole tile, with the arguments of a case
+    of tests/kappa_shear_ref.py.  u_h and v_h are those kappa_shear_ref.find_uv_at_h makes of u and v (find_uv_at_h is not part of
+    the compiled files).  Returns kappa_io, tke_io, kv_io and the four 3-D diagnostics by the names of kappa_shear_ref.outputs
+    (planes beyond the computational domain are whatever the reference left) and the FATAL count."""
+    from tests import kappa_shear_ref as K
+    L = lib()
+    layered = opt["eos"] is None
+    eos = eos if eos is not None else K.case_eos(opt)
+    ent, powers = kshear_table(P, None if layered else eos)
+    _table(ent + list(table_extra), powers)          # (a later entry of a name replaces an earlier one)
+    _, f = kshear_units(P)
+    ni_mem, nj_mem, idx = _tile(d)
+    H_to_m = 1.0 / f["m_to_H"]
+    gv = np.array([GV.Rho0, P.g_Earth_Z_T2, GV.Angstrom_H, GV.H_to_Z * GV.Angstrom_H, GV.H_subroundoff, GV.dZ_subroundoff, GV.H_to_Z,
+                   GV.Z_to_H, GV.H_to_RZ, GV.RZ_to_H, H_to_m, f["m_to_H"], H_to_m, 1.0 / f["m2_s_to_HZ_T"]])
+    gx = np.array([GV.g_Earth, f["m2_s_to_HZ_T"], 1.0 / f["m2_s_to_HZ_T"], 1.0 / f["m2_s_to_HZ_T"]])
+    with np.errstate(all="ignore"):
+        u_h, v_h = K.find_uv_at_h(d, M, GV, inp["u"], inp["v"], inp["h"], opt["zero_mix"])
+    mask = _c(M[G["mask2dT"]]); f2 = _c(M[G["Coriolis2Bu"]])
+    a = {n: _c(inp[n]).copy() for n in ("h", "T", "S", "p_surf") if inp.get(n) is not None and not (layered and n in ("T", "S"))}
+    Rlay = _c(inp["Rlay"]) if inp.get("Rlay") is not None else np.zeros(d.nk)
+    out = {n: np.full(d.shape3(d.nk + 1), np.nan) for n in ("kappa_io", "tke_io", "kv_io")}
+    fatal = L.ref_Calculate_kappa_shear(C.c_int(ni_mem), C.c_int(nj_mem), idx, C.c_int(d.nk), _p(gv), _p(gx), C.c_int(int(P.nkml)), _p(mask),
+                                        _p(f2), _p(Rlay), _p(a["h"]), _p(_c(u_h)), _p(_c(v_h)), _p(a.get("T")), _p(a.get("S")),
+                                        _p(a.get("p_surf")), C.c_double(opt["dt"]), _p(out["kappa_io"]), _p(out["tke_io"]),
+                                        _p(out["kv_io"]))
+    if fatal:
+        return None, fatal
+    if not opt["dt"] > 0.0:             # the door ran the two inits only
+        return {}, fatal
+    for n in a:
+        assert np.array_equal(a[n], inp[n], equal_nan=True), n + " is only read"
+    for n, name in KSHEAR_DIAG_NAMES.items():
+        out[n] = _diag(name, d.shape3(d.nk + 1))
+    return out, fatal
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# recorded results (tests/golden/ref_opacity_*.npz, ref_epbl_*.npz, ref_kshear_*.npz): written by scripts/record_ref_parity.py from
+# the doors above
 
 GOLDEN_OPACITY = ("manizza_3", "morel_1", "ohlmann_1")
 GOLDEN_EPBL = ("croot_new", "rh18_orig_tl")      # (rh18_orig itself holds a setting the reference stops on: its twin)
+# (case, grid, keyword arguments) of MOM_kappa_shear; the torus gets its shape in golden_configs
+GOLDEN_KSHEAR = tuple((n, "island_basin", dict(nk=4)) for n in ("shear", "bugs", "nkml2", "layered", "newton", "tie")) + (
+    ("shear", "benchmark_small", dict(nk=8)), ("nkml2", "benchmark_small", dict(nk=8)), ("shear", "benchmark_small", dict(nk=2)),
+    ("shear", "torus", dict(nk=3)), ("layered", "torus", dict(nk=3)))
+KSHEAR_CORE = ("kappa_io", "tke_io", "kv_io")                      # in every file
+KSHEAR_DROP_ORDER = ("S2_mean", "N2_mean", "S2_init", "N2_init")   # what a file that would pass the size limit leaves out, in this order
 
 
 def edge_torus_shape():
@@ -363,6 +463,8 @@ def golden_configs():
         out.append(("epbl", name, "benchmark_small", dict(nk=3)))
         out.append(("epbl", name, "benchmark_small", dict(nk=8)))
         out.append(("epbl", name, "torus", dict(nk=3, ni=ni, nj=nj)))
+    for name, grid, kw in GOLDEN_KSHEAR:
+        out.append(("kshear", name, grid, dict(kw, ni=ni, nj=nj) if grid == "torus" else dict(kw)))
     return out
 
 
@@ -374,10 +476,14 @@ def golden_name(kind, name, grid, kw):
 def golden_setup(kind, name, grid, kw):
     """(d, M, GV, P, opt, inp) of a recorded configuration: the inputs are regenerated from the seeded case_inputs."""
     from tests import helpers as H
-    from tests import opacity_ref, epbl_ref
+    from tests import opacity_ref, epbl_ref, kappa_shear_ref
     d, M = getattr(H, grid)(**kw)[1:]
     GV = abi.vgrid_default()
-    if kind == "opacity":
+    if kind == "kshear":
+        P, opt = kappa_shear_ref.case(name, GV)
+        opt = dict(opt, diag=kappa_shear_ref.DIAG_3D + kappa_shear_ref.DIAG_2D)       # every diagnostic, whatever the case names
+        inp = kappa_shear_ref.case_inputs(d, M, GV, opt)
+    elif kind == "opacity":
         P, opt = opacity_ref.case(name)
         inp = opacity_ref.case_inputs(d, M, opt)
     else:
@@ -390,10 +496,13 @@ def sha256(a):
     return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest()
 
 
-def input_hashes(M, inp):
-    """SHA-256 of every input array of a case and of the grid planes the two modules read."""
-    h = {n: sha256(a) for n, a in inp.items()}
+def input_hashes(M, inp, kind=None):
+    """SHA-256 of every input array of a case and of the grid planes the modules read."""
+    h = {n: sha256(a) for n, a in inp.items() if a is not None}
     h["mask2dT"] = sha256(M[G["mask2dT"]]); h["CoriolisBu"] = sha256(M[G["CoriolisBu"]])
+    if kind == "kshear":
+        for n in ("Coriolis2Bu", "areaCu", "areaCv", "IareaT"):
+            h[n] = sha256(M[G[n]])
     return h
 
 
@@ -407,7 +516,7 @@ def load_golden(kind, name, grid, kw, M, inp):
     path = os.path.join(GOLDEN, golden_name(kind, name, grid, kw) + ".npz")
     with np.load(path) as z:
         got = {k: z[k] for k in z.files}
-    want = input_hashes(M, inp)
+    want = input_hashes(M, inp, kind)
     names = [str(s) for s in got.pop("input_names")]
     hashes = [str(s) for s in got.pop("input_sha256")]
     assert dict(zip(names, hashes)) == want, f"{path}: the seeded inputs are not the recorded ones"

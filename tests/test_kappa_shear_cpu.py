@@ -1,5 +1,8 @@
 """What pins tests/kappa_shear_ref.py, the checker of mom6x_Calculate_kappa_shear, without a GPU.  The restatement and the kernel
-come from one reading of MOM_kappa_shear.F90, so these checks stand on something else: the reference's dimensional test (Z, L, T, H
+come from one reading of MOM_kappa_shear.F90.  What involves the reference's own code is tests/test_ref_parity_cpu.py: the
+restatement against the compiled MOM_kappa_shear.F90 and MOM_EOS.F90, whole arrays bit for bit on every case and grid below (where
+oracle/_ref is built), and against the results recorded from it in tests/golden/ref_kshear_*.npz (always).  The checks here stand
+on something else again and need no compiled reference: the reference's dimensional test (Z, L, T, H
 and R each rescaled by 2**11 leave the unscaled bits), exact invariants of the scheme (zero-thickness layers inserted, elimination
 on and off, a column at rest, kv = Prandtl*kappa, land, the unread kappa_io), the arms the case table reaches on the grids of the
 GPU tests, a floor on how much of the `shear` case really mixes, and the struct and the init rules."""
@@ -98,6 +101,26 @@ _DIM_M = dict(CoriolisBu=(0, 0, -1, 0, 0), Coriolis2Bu=(0, 0, -2, 0, 0), areaCu=
               areaT=(0, 2, 0, 0, 0), IareaT=(0, -2, 0, 0, 0))
 
 
+RESCALE_SETS = [tuple(2.0 ** 11 if n == m else 1.0 for n in range(5)) for m in range(5)] + [(2.0 ** 11, 2.0 ** 5, 2.0 ** -7, 2.0 ** 9, 2.0 ** 3)]
+
+
+def rescaled(name, sc, M, GV, P, opt, inp):
+    """A case with Z, L, T, H and R rescaled by the factors `sc`: (metrics, vertical grid, params, options, inputs, f), where f(pw)
+    is the factor of a quantity whose powers of (Z, L, T, H, R) are pw."""
+    f = lambda pw: float(np.prod([s ** p for s, p in zip(sc, pw)]))                    # noqa: E731
+    GV2 = abi.vgrid_default()
+    for n, pw in _DIM_GV.items():
+        setattr(GV2, n, getattr(GV, n) * f(pw))
+    P2, _ = R.case(name, GV)
+    for n, pw in _DIM_P.items():
+        setattr(P2, n, getattr(P, n) * f(pw))
+    M2 = M.copy()
+    for n, pw in _DIM_M.items():
+        M2[G[n]] = M[G[n]] * f(pw)
+    inp2 = {n: a * f(_DIM_IN[n]) if n in _DIM_IN else a for n, a in inp.items()}
+    return M2, GV2, P2, dict(opt, dt=opt["dt"] * sc[2]), inp2, f
+
+
 @pytest.mark.parametrize("name", ("shear", "bugs", "layered", "nkml2", "newton"))
 def test_dimensional_rescaling(name):
     """The reference's test.dim: Z, L, T, H and R rescaled by 2**11, one at a time and all at once with unequal powers: params,
@@ -109,21 +132,9 @@ def test_dimensional_rescaling(name):
     inp = R.case_inputs(d, M, GV, opt)
     want, counts = R.run(d, M, GV, P, opt, inp)
     assert counts["pred_corr"] > 0
-    big = 2.0 ** 11
-    sets = [tuple(big if n == m else 1.0 for n in range(5)) for m in range(5)] + [(2.0 ** 11, 2.0 ** 5, 2.0 ** -7, 2.0 ** 9, 2.0 ** 3)]
-    for sc in sets:
-        f = lambda pw: float(np.prod([s ** p for s, p in zip(sc, pw)]))                    # noqa: E731
-        GV2 = abi.vgrid_default()
-        for n, pw in _DIM_GV.items():
-            setattr(GV2, n, getattr(GV, n) * f(pw))
-        P2, _ = R.case(name, GV)
-        for n, pw in _DIM_P.items():
-            setattr(P2, n, getattr(P, n) * f(pw))
-        M2 = M.copy()
-        for n, pw in _DIM_M.items():
-            M2[G[n]] = M[G[n]] * f(pw)
-        inp2 = {n: a * f(_DIM_IN[n]) if n in _DIM_IN else a for n, a in inp.items()}
-        got, _ = R.run(d, M2, GV2, P2, dict(opt, dt=opt["dt"] * sc[2]), inp2)
+    for sc in RESCALE_SETS:
+        M2, GV2, P2, opt2, inp2, f = rescaled(name, sc, M, GV, P, opt, inp)
+        got, _ = R.run(d, M2, GV2, P2, opt2, inp2)
         assert set(got) == set(want)
         for n in want:
             _bits(got[n] / f(_DIM_OUT[n]), want[n], f"{name}: {n} rescaled by Z, L, T, H, R = {sc}")
@@ -246,3 +257,18 @@ def test_the_case_table_reaches_every_required_arm_and_the_shear_case_mixes():
     for k in REQUIRED:
         assert tot[k] > 0, (k, tot)
     assert set(REQUIRED) <= set(R.BRANCHES)
+
+
+def test_the_launch_edge_grids_of_the_gpu_tests_mix():
+    """The grids of tests/test_kappa_shear_gpu.py::test_launch_shape_edges that are not among CONFIGS -- 35 columns (fewer than a
+    wavefront) and the 65 x 5 torus -- still have columns in the predictor-corrector and columns of two or more outer iterations
+    in the case `shear`: what runs at those launch shapes is not a field of columns that leave at the no-mixing exit."""
+    from tests import ref_param as RP
+    ni, nj = RP.edge_torus_shape()
+    GV = abi.vgrid_default()
+    for grid, kw in (("benchmark_small", dict(nk=4, ni=7, nj=5)), ("torus", dict(nk=3, ni=ni, nj=nj))):
+        d, M = getattr(H, grid)(**kw)[1:]
+        P, opt = R.case("shear", GV)
+        _, counts = R.run(d, M, GV, P, opt, R.case_inputs(d, M, GV, opt))
+        print(grid, kw, "pred_corr", counts["pred_corr"], "two_iterations", counts["two_iterations"])
+        assert counts["pred_corr"] > 0 and counts["two_iterations"] > 0, (grid, kw, counts)

@@ -2,8 +2,12 @@
 tests/kappa_shear_ref.py, whole arrays bit for bit: the arithmetic is + - * / and sqrt, there is no tolerance class.  Every output
 starts as NaN and the halo of every input is NaN (u and v keep the one face to the west and south); afterwards the outputs' halos
 are still NaN, their interiors finite, and the inputs are what was uploaded.  Every case of the table at 1, 2, 3, 4 and 8 layers on
-a bowl and at 4 on a basin with an island, the case `shear` at 75; slots of the workspace reused on a poisoned workspace; two calls;
-the chain into mom6x_set_diffusivity; two tiles; the refusals.  tests/test_kappa_shear_cpu.py screens the restatement."""
+a bowl and at 4 on a basin with an island, the case `shear` at 75; slots of the workspace reused on a poisoned workspace, evenly
+and at the launch-shape edges (lanes of one wavefront that walk unequal numbers of columns, a work_columns that is no multiple of
+64, a column count that is none, fewer columns than a wavefront, 75 layers with reuse); two calls; the chain into
+mom6x_set_diffusivity; two tiles; the refusals.  The restatement is held to the reference's own compiled MOM_kappa_shear.F90 by
+tests/test_ref_parity_cpu.py, and the device to its recorded results by tests/test_ref_parity_gpu.py;
+tests/test_kappa_shear_cpu.py screens the restatement without it."""
 import functools
 import threading
 
@@ -41,9 +45,9 @@ def _nan_halo(d, inp):
     return inp
 
 
-def _device(d, M, GV, P, opt, inp, fill=np.nan, ncalls=1, layout=None, pe=None, uid=None, work_columns=None):
+def _device(d, M, GV, P, opt, inp, fill=np.nan, ncalls=1, layout=None, pe=None, uid=None, work_columns=None, info=None):
     """One mom6x_kappa_shear_init, then `ncalls` calls on the same device arrays.  Returns the outputs by name and the exchanges
-    made; the inputs are compared with what was uploaded."""
+    made; the inputs are compared with what was uploaded.  info: a dict that gets work_bytes, what kappa_shear_work_bytes reports."""
     import torch
     from mom6_amd import parallel
     from mom6_amd.dycore import Dycore
@@ -59,6 +63,8 @@ def _device(d, M, GV, P, opt, inp, fill=np.nan, ncalls=1, layout=None, pe=None, 
         else:
             P2 = P
         dy.kappa_shear_init(P2, R.case_eos(opt), inp["Rlay"] if layered else None)
+        if info is not None:
+            info["work_bytes"] = dy.kappa_shear_work_bytes()
         torch.cuda.synchronize()
         dy.comm_exchange_count(reset=True)
         for _ in range(ncalls):
@@ -139,6 +145,56 @@ def test_a_slot_is_reused_without_a_trace_of_its_previous_column(monkeypatch):
     d, M, GV, P, opt, inp, want, _ = _want("benchmark_small", 8, "shear")
     got, _ = _device(d, M, GV, P, opt, inp)
     _check(d, got, want, "shear: the default slots, poisoned")
+
+
+def _edge_torus():
+    from tests import ref_param as RP
+    ni, nj = RP.edge_torus_shape()
+    return dict(ni=ni, nj=nj)
+
+
+# (grid, layers, keyword arguments of the grid, work_columns, the slots that makes, (columns, whole passes, busy lanes of the last pass))
+LAUNCH_EDGES = {
+    # 1008 columns through 64 slots: lanes 0..47 walk 16 columns and lanes 48..63 walk 15, so the last sixteen lanes of the only
+    # wavefront have left the grid-stride loop while the others are still iterating
+    "island_64": ("island_basin", 4, {}, 64, 64, (1008, 15, 48)),
+    # work_columns = 65 rounds up to 128 slots (two wavefronts): 112 lanes walk 8 columns, the last 16 of the second wavefront 7
+    "island_65": ("island_basin", 4, {}, 65, 128, (1008, 7, 112)),
+    # the edge torus is (bx + 1) x (by + 1) = 65 x 5: 325 columns, no multiple of 64, rows of bx + 1; after five whole passes the
+    # last pass has five busy lanes (the shape gives no pass with a single busy lane) beside 59 that are done
+    "torus_64": ("torus", 3, _edge_torus, 64, 64, (325, 5, 5)),
+    # fewer columns than a wavefront: 35 columns in the default slots, which round up to 64: one wavefront, 29 lanes never busy
+    "bowl_7x5": ("benchmark_small", 4, dict(ni=7, nj=5), None, 64, (35, 0, 35)),
+    # 75 layers with reuse: 240 columns through 64 slots, 48 lanes walk 4 and 16 walk 3, at the deepest K stride of the workspace
+    "bowl_75": ("benchmark_small", 75, dict(ni=20, nj=12), 64, 64, (240, 3, 48)),
+}
+
+
+@pytest.mark.parametrize("poison", ("0", "1"))
+@pytest.mark.parametrize("edge", sorted(LAUNCH_EDGES))
+def test_launch_shape_edges(monkeypatch, edge, poison):
+    """The case `shear` at the launch shapes of LAUNCH_EDGES, on a workspace that starts as zeros and as NaN, whole arrays bit for
+    bit against the restatement (held to the compiled reference by tests/test_ref_parity_cpu.py) and, where a result of the
+    reference is recorded for the grid (island basin x 4, torus x 3), against that too.  The shape a name stands for is asserted
+    from the grid, the workspace reports the rounded slot count, and the restatement has mixing columns on the grid."""
+    from tests import ref_param as RP
+    grid, nk, kw, wc, slots, (ncol, whole, last) = LAUNCH_EDGES[edge]
+    kw = kw() if callable(kw) else kw
+    d, M, GV, P, opt, inp, want, counts = _want(grid, nk, "shear", **kw)
+    assert d.ni * d.nj == ncol == whole * slots + last and 0 < last < slots, (d.ni, d.nj)
+    assert (slots + 63) // 64 * 64 == slots and (wc is None or (wc + 63) // 64 * 64 == slots)
+    assert counts["pred_corr"] > 0 and counts["two_iterations"] > 0, counts
+    monkeypatch.setenv("MOM6X_POISON_WORK", poison)
+    info = {}
+    got, nex = _device(d, M, GV, P, opt, inp, work_columns=wc, info=info)
+    assert info["work_bytes"] == 51 * (nk + 1) * slots * 8, (info, slots)
+    assert nex == 0
+    _check(d, got, want, f"{edge}, poison {poison}")
+    cfg = ("kshear", "shear", grid, dict(kw, nk=nk))
+    if cfg in RP.golden_configs():
+        gold = RP.load_golden(*cfg, M, RP.golden_setup(*cfg)[5])
+        for n, b in gold.items():
+            _bits(np.ascontiguousarray(got[n][(Ellipsis,) + RP.dom(d)]), b, f"{edge}, poison {poison}: {n} against the recorded reference")
 
 
 def test_two_calls_in_a_row_are_one():

@@ -1,15 +1,16 @@
 """The python restatements under tests/ held to the reference's own compiled code (oracle/_ref/libref_param.so: MOM_EOS_Wright*.F90,
-MOM_EOS_linear.F90, MOM_intrinsic_functions.F90, MOM_opacity.F90 and MOM_energetic_PBL.F90 built where they lie against interface
-stand-ins, see oracle/Makefile and tests/ref_param.py).  The restatements were written from the same reading of the Fortran as the
+MOM_EOS_linear.F90, MOM_intrinsic_functions.F90, MOM_opacity.F90, MOM_energetic_PBL.F90 and MOM_kappa_shear.F90 with MOM_EOS.F90,
+built where they lie against interface stand-ins, see oracle/Makefile and tests/ref_param.py).  The restatements were written from the same reading of the Fortran as the
 kernels they check, so a misread line sits in both; these tests are what involves the reference's code itself.
 
 Classes.  EXACT: whole arrays bit for bit on the computational domain.  TOLERANCE: the sites whose value goes through an
 intrinsic that two builds may round differently (tanh in opac_diag, pow and log10 of smooth chlorophyll, exp, log and pow of the
 libm cases of ePBL), held to the project's bound of 1e-12 of each field's range.  No site had to move from the first class to
-the second (see CHANGELOG.md).
+the second (see CHANGELOG.md).  MOM_kappa_shear has no second class: its arithmetic is + - * / and sqrt, and every word is EXACT.
 
 Without oracle/_ref every test that runs a door skips; the comparison of the restatements with the recorded results
-(tests/golden/ref_opacity_*.npz, ref_epbl_*.npz) never skips."""
+(tests/golden/ref_opacity_*.npz, ref_epbl_*.npz, ref_kshear_*.npz) never skips."""
+import functools
 import json
 import os
 
@@ -20,8 +21,10 @@ from mom6_amd import abi
 from tests import bflux_ref as B
 from tests import epbl_ref as E
 from tests import helpers as H
+from tests import kappa_shear_ref as K
 from tests import opacity_ref as R
 from tests import ref_param as RP
+from tests.test_kappa_shear_cpu import CONFIGS as KSHEAR_GRIDS, REQUIRED as KSHEAR_REQUIRED, RESCALE_SETS, _DIM_OUT, rescaled
 
 G = abi.G
 BOUND = 1.0e-12      # the project's bound for a transcendental site (BOUND of tests/test_opacity_gpu.py), as a fraction of the range
@@ -325,6 +328,143 @@ def test_epbl_init_refusal_is_the_references():
     assert {n for n in E.CASES if E.reference_refuses(E.case(n, GV)[0])} == {"rh18_orig", "translay1"}
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# MOM_kappa_shear
+
+KSHEAR_RUNS = tuple((grid, nk, ()) for grid, nk in KSHEAR_GRIDS) + (("benchmark_small", 75, (("ni", 20), ("nj", 12))),)
+KSHEAR_QUIET = ("quiet",)            # the one case whose inputs do not shear: no column of it mixes, by design
+KSHEAR_OUT = RP.KSHEAR_CORE + K.DIAG_3D
+
+
+def _kshear_cases(nk):
+    return tuple(K.CASES) if nk != 75 else ("shear",)
+
+
+@functools.lru_cache(maxsize=None)
+def _kshear(grid, nk, kw, name):
+    """A case on a grid with every diagnostic asked for, and the restatement's result and counters: computed once (read only)."""
+    d, M = getattr(H, grid)(nk=nk, **dict(kw))[1:]
+    GV = abi.vgrid_default()
+    P, opt = K.case(name, GV)
+    opt = dict(opt, diag=K.DIAG_3D + K.DIAG_2D)
+    inp = K.case_inputs(d, M, GV, opt)
+    want, counts = K.run(d, M, GV, P, opt, inp)
+    return d, M, GV, P, opt, inp, want, counts
+
+
+def _compare_kshear(tag, d, want, got):
+    """kappa_io, tke_io, kv_io and the four 3-D diagnostics on the computational domain, bit for bit.  Not held here: KS_its,
+    which reaches no diagnostic of the reference (like OBL_its of ePBL) and stays compared with the restatement only."""
+    dm = (Ellipsis,) + RP.dom(d)
+    assert set(got) == set(want) - set(RP.KSHEAR_NOT_EXPOSED) == set(KSHEAR_OUT), (sorted(got), sorted(want))
+    for n in KSHEAR_OUT:
+        H.assert_bitwise(np.ascontiguousarray(got[n][dm]), np.ascontiguousarray(want[n][dm]), f"{tag}: {n}")
+
+
+@pytest.mark.parametrize("grid,nk,kw", KSHEAR_RUNS, ids=lambda v: "x".join(str(b) for _, b in v) if isinstance(v, tuple) else str(v))
+def test_kappa_shear_against_the_compiled_reference(grid, nk, kw):
+    """tests/kappa_shear_ref.py against Calculate_kappa_shear of the reference's own MOM_kappa_shear.F90, set up by its own
+    kappa_shear_init, EOS_init (MOM_EOS.F90: the unit conversion around the array call and the `scale` product, :781-829, are the
+    reference's text) and unit_scaling_init: every case of the table on the bowl at 1, 2, 3, 4 and 8 layers and on the island basin
+    at 4, and `shear` at 20 x 12 x 75.  kappa_io, tke_io, kv_io, N2_shear_in, S2_shear_in, N2_shear_mean and S2_shear_mean, whole
+    arrays on the computational domain, bit for bit; zero FATALs.
+
+    Outside the comparison: find_uv_at_h (MOM_diabatic_aux.F90:546-611, twenty lines): its module imports extractFluxes1d,
+    MOM_interpolate and the tracer flow control, out of reach of interface-only stand-ins, so the compiled routine is handed the
+    u_h, v_h that kappa_shear_ref.find_uv_at_h makes; those lines stay held only by tests/test_kappa_shear_cpu.py (rescaling, the
+    inserted massless layers) and by the device comparison.  KS_its reaches no diagnostic of the reference.
+
+    A comparison of columns that do not mix proves little: with an interior interface (more layers than the nkml that are
+    merged into one), every case whose inputs shear has columns
+    in the predictor-corrector (`quiet` is the one that is meant not to), and `shear` keeps the floors of
+    tests/test_kappa_shear_cpu.py: a quarter of the wet columns mix, a tenth take two or more outer iterations."""
+    for name in _kshear_cases(nk):
+        d, M, GV, P, opt, inp, want, counts = _kshear(grid, nk, kw, name)
+        if nk > P.nkml:               # an interior interface is left after the first nkml layers are merged into one (:261)
+            assert (counts["pred_corr"] > 0) == (name not in KSHEAR_QUIET), (grid, nk, name, counts["pred_corr"])
+        if name == "tie" and nk >= 2:   # the tie of N2 = MAX(0.0, -0.0) (:1492-1502) is reached: the reference answers -0.0
+            z = want["N2_init"][(Ellipsis,) + RP.dom(d)]
+            assert (np.signbit(z) & (z == 0.0)).any(), (grid, nk)
+        if name == "shear" and nk >= 2:
+            own = np.zeros(d.shape2(), bool); own[H.interior(d, "h")] = True
+            wet = own & (M[G["mask2dT"]] > 0.0)
+            mixed = (want["kappa_io"][:, wet] > 0.0).any(axis=0)
+            two = want["KS_its"][wet] >= 2.0
+            assert 4 * mixed.sum() >= wet.sum() and 10 * two.sum() >= wet.sum(), (grid, nk, int(mixed.sum()), int(two.sum()), int(wet.sum()))
+    _need_lib()
+    for name in _kshear_cases(nk):
+        d, M, GV, P, opt, inp, want, counts = _kshear(grid, nk, kw, name)
+        got, fatal = RP.Calculate_kappa_shear(d, M, GV, P, opt, inp)
+        assert fatal == 0, (grid, nk, name, fatal)
+        _compare_kshear(f"{grid}/{nk}/{name}", d, want, got)
+
+
+def test_kappa_shear_compared_set_reaches_every_required_arm():
+    """Over everything test_kappa_shear_against_the_compiled_reference compares, every arm of tests/test_kappa_shear_cpu.REQUIRED is
+    reached, from the restatement's counters alone (newton_pivot_K, :1853, stays unreached: no input that reaches it is known)."""
+    tot = K.new_counts()
+    for grid, nk, kw in KSHEAR_RUNS:
+        for name in _kshear_cases(nk):
+            for k, v in _kshear(grid, nk, kw, name)[7].items():
+                tot[k] += v
+    for k in KSHEAR_REQUIRED:
+        assert tot[k] > 0, (k, tot)
+    print("newton_pivot_K over the compared set:", tot["newton_pivot_K"])
+
+
+@pytest.mark.parametrize("name", ("layered", "shear"))
+def test_kappa_shear_rescaled_through_the_references_unit_scaling_init(name):
+    """Z, L, T, H and R rescaled by 2**11 one at a time and all at once with unequal powers (the sets of
+    tests/test_kappa_shear_cpu.py), set in the door: the *_RESCALE_POWERs go through the reference's own unit_scaling_init, the
+    parameters through the `scale=` of its kappa_shear_init, the equation of state through the factors its EOS_init takes from US.
+    The unscaled outputs are the unscaled run's bits, and the rescaled restatement equals the rescaled reference: the restatement's
+    placement of the US% and GV% factors is held to the compiled init and not to itself."""
+    _need_lib()
+    d, M, GV, P, opt, inp, want, counts = _kshear("island_basin", 4, (), name)
+    assert counts["pred_corr"] > 0
+    base, fatal = RP.Calculate_kappa_shear(d, M, GV, P, opt, inp)
+    assert fatal == 0
+    _compare_kshear(f"{name} unscaled", d, want, base)
+    dm = (Ellipsis,) + RP.dom(d)
+    for sc in RESCALE_SETS:
+        M2, GV2, P2, opt2, inp2, f = rescaled(name, sc, M, GV, P, opt, inp)
+        got, fatal = RP.Calculate_kappa_shear(d, M2, GV2, P2, opt2, inp2)
+        assert fatal == 0, (name, sc)
+        mine, _ = K.run(d, M2, GV2, P2, opt2, inp2)
+        _compare_kshear(f"{name} rescaled by Z, L, T, H, R = {sc}", d, mine, got)
+        for n in KSHEAR_OUT:
+            H.assert_bitwise(np.ascontiguousarray(got[n][dm] / f(_DIM_OUT[n])), np.ascontiguousarray(base[n][dm]),
+                             f"{name}: {n} of the reference, rescaled by {sc} and unscaled")
+
+
+def test_kappa_shear_init_refusals_against_the_references():
+    """kappa_shear_ref.init_check (the twin of what mom6x_kappa_shear_init rejects as invalid) against the compiled
+    kappa_shear_init: the reference has no FATAL of its own and accepts every value the device rejects (include/mom6x.h lists the
+    difference); what both take, both take; an equation of state the reference does not know is FATAL in its EOS_init."""
+    GV = abi.vgrid_default()
+    dflt = abi.kappa_shear_params_default
+    d, M = H.benchmark_small(nk=2)[1:]
+    _, opt = K.case("shear", GV)
+    inp = K.case_inputs(d, M, GV, opt)
+    init_only = dict(opt, dt=0.0)
+    rejected = (dict(max_KS_it=0), dict(max_RiNo_it=0), dict(RiNo_crit=0.0), dict(RiNo_crit=-0.25), dict(kappa_src_max_chg=1.0),
+                dict(nkml=0), dict(lambda_=0.0))
+    accepted = (dict(), dict(nkml=2), dict(kappa_src_max_chg=5.0), dict(RiNo_crit=0.3), dict(max_KS_it=1, max_RiNo_it=1))
+    for mods, bad in [(m, True) for m in rejected] + [(m, False) for m in accepted]:
+        P = dflt(GV, **mods)
+        if bad:
+            with pytest.raises(ValueError):
+                K.init_check(P, GV)
+        else:
+            K.init_check(P, GV)
+        if RP.lib() is not None:
+            got, fatal = RP.Calculate_kappa_shear(d, M, GV, P, init_only, inp)
+            assert fatal == 0, (mods, fatal)          # accepted, or rejected by the device alone: never the other way round
+    _need_lib()
+    got, fatal = RP.Calculate_kappa_shear(d, M, GV, dflt(GV), init_only, inp, table_extra=[("EQN_OF_STATE", "NO_SUCH_EOS")])
+    assert fatal >= 1 and got is None
+
+
 def test_zz_record_the_tolerance_class():
     """profiles/ref_parity_libm.json: the largest difference over range of every tolerance-class field seen by the tests above
     (MOM6X_RECORD_REF_PARITY names the file).  Runs last in the file; without the library there is nothing to record."""
@@ -348,6 +488,8 @@ def test_zz_record_the_tolerance_class():
 # recorded results
 
 def _restatement(kind, d, M, GV, P, opt, inp):
+    if kind == "kshear":
+        return K.run(d, M, GV, P, opt, inp)[0]
     if kind == "opacity":
         return R.run(d, M, GV, P, opt, inp)[0]
     return E.run(d, M, GV, P, opt, inp)[0]
@@ -357,8 +499,12 @@ def _against_golden(tag, kind, d, M, gold, out):
     """`out` (whole arrays) against the recorded computational domain, in the classes of the live comparisons."""
     dm = RP.dom(d)
     wet = (M[G["mask2dT"]] > 0.0)[dm]
-    names = set(out) - set(RP.EPBL_NOT_EXPOSED)
-    assert set(gold) == names, (sorted(gold), sorted(names))
+    names = set(out) - set(RP.EPBL_NOT_EXPOSED) - set(RP.KSHEAR_NOT_EXPOSED)
+    if kind == "kshear":                 # a file that would pass the size limit leaves out diagnostics, the last named first
+        left_out = sorted(names - set(gold))
+        assert set(RP.KSHEAR_CORE) <= set(gold) <= names and left_out == sorted(RP.KSHEAR_DROP_ORDER[:len(left_out)]), sorted(gold)
+    else:
+        assert set(gold) == names, (sorted(gold), sorted(names))
     for n in gold:
         a, b = out[n][(Ellipsis,) + dm], gold[n]
         if n in RP.EPBL_WET_ONLY:
@@ -381,10 +527,10 @@ def test_recorded_reference_is_what_the_library_gives():
     for kind, name, grid, kw in RP.golden_configs():
         d, M, GV, P, opt, inp = RP.golden_setup(kind, name, grid, kw)
         gold = RP.load_golden(kind, name, grid, kw, M, inp)
-        got, fatal = (RP.opacity if kind == "opacity" else RP.energetic_PBL)(d, M, GV, P, opt, inp)
+        got, fatal = dict(opacity=RP.opacity, epbl=RP.energetic_PBL, kshear=RP.Calculate_kappa_shear)[kind](d, M, GV, P, opt, inp)
         assert fatal == 0
         dm = (Ellipsis,) + RP.dom(d)
-        assert set(got) == set(gold)
+        assert set(got) == set(gold) if kind != "kshear" else set(gold) <= set(got)
         for n in gold:
             if n in RP.EPBL_WET_ONLY:
                 wet = (M[G["mask2dT"]] > 0.0)[RP.dom(d)]
