@@ -34,6 +34,7 @@ program check_abi
   type(mom6x_geothermal_params) :: geo
   type(mom6x_opacity_params) :: opa
   type(mom6x_kappa_shear_params) :: ksp
+  type(mom6x_neutral_diffusion_params) :: ndp
   integer :: nbad, rc
   nbad = 0
   call chk(0, int(c_sizeof(d)), "mom6x_dims")
@@ -67,6 +68,7 @@ program check_abi
   call chk(33, int(c_sizeof(geo)), "mom6x_geothermal_params")
   call chk(34, int(c_sizeof(opa)), "mom6x_opacity_params")
   call chk(35, int(c_sizeof(ksp)), "mom6x_kappa_shear_params")
+  call chk(36, int(c_sizeof(ndp)), "mom6x_neutral_diffusion_params")
   if (mom6x_abi_version() /= MOM6X_ABI_BUILT_FOR) then
     print '(a,i0,a,i0)', "ABI version: library ", mom6x_abi_version(), ", fortran/mom6x_c_api.F90 ", MOM6X_ABI_BUILT_FOR ; nbad = nbad + 1
   endif

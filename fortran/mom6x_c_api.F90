@@ -19,6 +19,9 @@ module mom6x_c_api
   public :: mom6x_geothermal_params, mom6x_geothermal_init, mom6x_geothermal_in_place
   public :: mom6x_opacity_params, mom6x_opacity_init, mom6x_set_pen_shortwave, mom6x_opacity_status
   public :: mom6x_kappa_shear_params, mom6x_kappa_shear_init, mom6x_Calculate_kappa_shear, mom6x_kappa_shear_work_bytes
+  public :: mom6x_neutral_diffusion_params, mom6x_neutral_diffusion_init, mom6x_neutral_diffusion_work_bytes
+  public :: mom6x_neutral_diffusion_calc_coeffs, mom6x_neutral_diffusion, mom6x_neutral_diffusion_coeffs
+  public :: mom6x_neutral_diffusion_status, mom6x_neutral_diffusion_tile, mom6x_tracer_hordiff_neutral
   public :: mom6x_energetic_PBL_params, mom6x_energetic_PBL_init, mom6x_energetic_PBL, mom6x_energetic_PBL_get_MLD, mom6x_ePBL_augment_Kd
   public :: mom6x_thickness_diffuse_params, mom6x_thickness_diffuse_init, mom6x_thickness_diffuse
   public :: mom6x_tracer_hor_diff_params, mom6x_tracer_hor_diff_init, mom6x_tracer_hordiff, mom6x_tracer_hordiff_tile
@@ -178,6 +181,12 @@ module mom6x_c_api
     integer(c_int) :: max_RiNo_it, max_KS_it, nkml, eliminate_massless, dKdQ_iteration_bug, all_layer_TKE_bug
     integer(c_int) :: restrictive_tolerance_check, KS_at_vertex, work_columns
   end type mom6x_kappa_shear_params
+  type, bind(C) :: mom6x_neutral_diffusion_params   !< what neutral_diffusion_init (MOM_neutral_diffusion.F90:134-345) leaves in neutral_diffusion_CS, with RECALC_NEUTRAL_SURF and the unit factors of the EOS type
+    integer(c_int) :: continuous_reconstruction
+    real(c_double) :: ref_pres
+    integer(c_int) :: interior_only, tapering, KhTh_use_vert_struct, use_unmasked_transport_bug, ndiff_answer_date, recalc_neutral_surf
+    real(c_double) :: RL2_T2_to_Pa, C_to_degC, S_to_ppt, kg_m3_to_R
+  end type mom6x_neutral_diffusion_params
 
   type, bind(C) :: mom6x_surface_fluxes   !< the members of `forcing` (MOM_forcing_type.F90:80-256) that applyBoundaryFluxesInOut touches: device planes, c_null_ptr where the reference's pointer is not associated
     type(c_ptr) :: sw, lw, latent, sens, evap, lprec, fprec, vprec, lrunoff, frunoff, lrunoff_glc, frunoff_glc, seaice_melt
@@ -597,6 +606,61 @@ module mom6x_c_api
       type(c_ptr), value :: ctx, u, v, h, T, S, p_surf
       real(c_double), value :: dt ; integer(c_int), value :: zero_mix
       type(c_ptr), value :: kappa_io, tke_io, kv_io, N2_init, S2_init, N2_mean, S2_mean, KS_its
+    end function
+    !> neutral_diffusion_init (MOM_neutral_diffusion.F90:134), continuous reconstruction: eos is c_loc(a mom6x_eos_params);
+    !! allocates every array of the calls below
+    integer(c_int) function mom6x_neutral_diffusion_init(ctx, p, eos) bind(C, name="mom6x_neutral_diffusion_init")
+      import :: c_ptr, c_int, mom6x_neutral_diffusion_params
+      type(c_ptr), value :: ctx ; type(mom6x_neutral_diffusion_params), intent(in) :: p ; type(c_ptr), value :: eos
+    end function
+    !> the bytes that mom6x_neutral_diffusion_init allocated
+    integer(c_long_long) function mom6x_neutral_diffusion_work_bytes(ctx) bind(C, name="mom6x_neutral_diffusion_work_bytes")
+      import :: c_ptr, c_long_long
+      type(c_ptr), value :: ctx
+    end function
+    !> neutral_diffusion_calc_coeffs (MOM_neutral_diffusion.F90:351): device pointers, p_surf may be c_null_ptr; h, T, S, p_surf
+    !! are read one point into the halo
+    integer(c_int) function mom6x_neutral_diffusion_calc_coeffs(ctx, h, T, S, p_surf) bind(C, name="mom6x_neutral_diffusion_calc_coeffs")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, h, T, S, p_surf
+    end function
+    !> neutral_diffusion (MOM_neutral_diffusion.F90:619); tracers, tendency, trans_x_2d, trans_y_2d: c_loc of host arrays of ntr
+    !! device pointers (the last three or their entries may be c_null_ptr); conc_underflow: c_loc of ntr host values or c_null_ptr;
+    !! Coef_x, Coef_y: nk + 1 planes, of which the first is read
+    integer(c_int) function mom6x_neutral_diffusion(ctx, h, Coef_x, Coef_y, dt, tracers, conc_underflow, ntr, tendency, trans_x_2d, &
+        trans_y_2d) bind(C, name="mom6x_neutral_diffusion")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, h, Coef_x, Coef_y, tracers, conc_underflow, tendency, trans_x_2d, trans_y_2d
+      real(c_double), value :: dt
+      integer(c_int), value :: ntr
+    end function
+    !> the module's resident uPoL, uPoR, uKoL, uKoR, uhEff (dir = 0) or the v set (dir = 1) as device pointers: Po and hEff are
+    !! real(c_double), Ko integer(c_short); planes [surface][j][i] laid out like a 2-D field
+    integer(c_int) function mom6x_neutral_diffusion_coeffs(ctx, dir, PoL, PoR, KoL, KoR, hEff) bind(C, name="mom6x_neutral_diffusion_coeffs")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx ; integer(c_int), value :: dir
+      type(c_ptr), intent(out) :: PoL, PoR, KoL, KoR, hEff
+    end function
+    !> how often each of the reference's stop sites was reached since init (klm1 or krm1 out of bounds, Ppos < Pneg, ppm_ave
+    !! dx < 0, dx > 1); synchronises
+    integer(c_int) function mom6x_neutral_diffusion_status(ctx, counts) bind(C, name="mom6x_neutral_diffusion_status")
+      import :: c_ptr, c_int, c_long_long
+      type(c_ptr), value :: ctx ; integer(c_long_long), intent(out) :: counts(4)
+    end function
+    integer(c_int) function mom6x_neutral_diffusion_tile(bx, by, i_first) bind(C, name="mom6x_neutral_diffusion_tile")
+      import :: c_int
+      integer(c_int), intent(out) :: bx, by, i_first
+    end function
+    !> the neutral branch of tracer_hordiff (MOM_tracer_hor_diff.F90:479-539), called in place of mom6x_tracer_hordiff (whose init
+    !! keeps use_neutral_diffusion = 0); T, S: tv%T, tv%S (they may be members of tracers), p_surf: tv%p_surf or c_null_ptr
+    integer(c_int) function mom6x_tracer_hordiff_neutral(ctx, h, dt, tracers, conc_underflow, ntr, L2u, SN_u, L2v, SN_v, Res_fn_h, &
+        Rd_dx_h, MEKE_Kh, T, S, p_surf, tendency, trans_x_2d, trans_y_2d, khdt_x_out, khdt_y_out, cfl_out, num_itts_out) &
+        bind(C, name="mom6x_tracer_hordiff_neutral")
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: ctx, h, tracers, conc_underflow, L2u, SN_u, L2v, SN_v, Res_fn_h, Rd_dx_h, MEKE_Kh, T, S, p_surf
+      type(c_ptr), value :: tendency, trans_x_2d, trans_y_2d, khdt_x_out, khdt_y_out, cfl_out, num_itts_out
+      real(c_double), value :: dt
+      integer(c_int), value :: ntr
     end function
     !> the wet points with negative chlorophyll since the last call (the reference's fatal error); synchronises
     integer(c_int) function mom6x_opacity_status(ctx, negative_chl) bind(C, name="mom6x_opacity_status")

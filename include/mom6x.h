@@ -360,7 +360,8 @@ int  mom6x_device_count(void);
  * 12 remapping_params, 13 regrid_zstar_params, 14 chksum_result, 15 sum_output_params, 16 energy_sums, 17 regrid_rho_params,
  * 18 set_visc_params, 19 thickness_diffuse_params, 20 tracer_hor_diff_params, 21 varmix_params,
  * 22 mixedlayer_restrat_params, 23 MEKE_params, 25 set_diffusivity_params, 27 diabatic_aux_params, 28 surface_fluxes, 30 energetic_PBL_params, 32 frazil_params,
- * 33 geothermal_params, 34 opacity_params, 35 kappa_shear_params; 24, 26, 29 and 31 are not assigned and return -1): lets ctypes /
+ * 33 geothermal_params, 34 opacity_params, 35 kappa_shear_params, 36 neutral_diffusion_params; 24, 26, 29 and 31 are not assigned and
+ * return -1): lets ctypes /
  * ISO_C_BINDING mirrors be checked at start-up.  */
 int  mom6x_struct_size(int which);
 
@@ -796,6 +797,19 @@ int mom6x_tracer_hordiff(mom6x_ctx *ctx, const double *h, double dt, double *con
                          double *khdt_y_out, double *cfl_out, int *num_itts_out);
 /* The extents of the iteration kernel's tile (columns, rows) and the number of tracers it carries per launch.                   */
 int mom6x_tracer_hordiff_tile(int *tx, int *ty, int *max_tracers);
+/* The neutral branch of tracer_hordiff (:479-539), an entry of its own: a host that uses neutral diffusion LEAVES
+ * use_neutral_diffusion = 0 (mom6x_tracer_hor_diff_init goes on refusing it) and calls this in place of mom6x_tracer_hordiff.  It
+ * needs mom6x_tracer_hor_diff_init and mom6x_neutral_diffusion_init.  khdt_x, khdt_y and the iteration count are formed exactly as
+ * in mom6x_tracer_hordiff (one code path); then the group pass of the registry (:483), neutral_diffusion_calc_coeffs with T, S (tv%T,
+ * tv%S, which may be members of `tracers`) and p_surf (tv%p_surf or NULL), Coef_x, Coef_y = I_numitts * khdt on nk + 1 planes
+ * (:494-507) and, per iteration, the group pass for itt > 1, calc_coeffs again under recalc_neutral_surf, and neutral_diffusion with
+ * I_numitts * dt (:525-539).  tendency, trans_x_2d, trans_y_2d: as in mom6x_neutral_diffusion; they hold the LAST iteration's values,
+ * as the reference's posted diagnostics do.  The other arguments are mom6x_tracer_hordiff's.                                      */
+int mom6x_tracer_hordiff_neutral(mom6x_ctx *ctx, const double *h, double dt, double *const *tracers, const double *conc_underflow,
+                                 int ntr, const double *L2u, const double *SN_u, const double *L2v, const double *SN_v,
+                                 const double *Res_fn_h, const double *Rd_dx_h, const double *MEKE_Kh, const double *T, const double *S,
+                                 const double *p_surf, double *const *tendency, double *const *trans_x_2d, double *const *trans_y_2d,
+                                 double *khdt_x_out, double *khdt_y_out, double *cfl_out, int *num_itts_out);
 
 /* ------------------------------------------------------------------------- */
 /* MOM_lateral_mixing_coeffs: calc_slope_functions                            */
@@ -1539,6 +1553,78 @@ long long mom6x_kappa_shear_work_bytes(mom6x_ctx *ctx);
 int mom6x_Calculate_kappa_shear(mom6x_ctx *ctx, const double *u, const double *v, const double *h, const double *T, const double *S,
                                 const double *p_surf, double dt, int zero_mix, double *kappa_io, double *tke_io, double *kv_io,
                                 double *N2_init, double *S2_init, double *N2_mean, double *S2_mean, double *KS_its);
+
+/* ------------------------------------------------------------------------- */
+/* MOM_neutral_diffusion: epineutral tracer mixing (USE_NEUTRAL_DIFFUSION), continuous reconstruction (NDIFF_CONTINUOUS = True) */
+/* What neutral_diffusion_init (src/tracer/MOM_neutral_diffusion.F90:134-345) leaves in neutral_diffusion_CS (:44-126), with
+ * RECALC_NEUTRAL_SURF of tracer_hor_diff_CS and the members of the EOS type that calculate_density_derivs reads
+ * (MOM_EOS.F90:809-827).  GV%g_Earth, H_to_RZ and H_subroundoff are the context's.  Logicals are ints.  The members marked "must
+ * be" are refused with MOM6X_EUNSUPPORTED and the parameter's name.  (struct 36)                                                 */
+typedef struct mom6x_neutral_diffusion_params {
+  int    continuous_reconstruction;  /* NDIFF_CONTINUOUS (T, :181): must be 1 (the discontinuous reconstruction is not on the device) */
+  double ref_pres;                   /* NDIFF_REF_PRES (-1, :187) [R L2 T-2]: negative: the local interface pressure (:493)           */
+  int    interior_only;              /* NDIFF_INTERIOR_ONLY (F, :191): must be 0                                                       */
+  int    tapering;                   /* NDIFF_TAPERING (F, :196): must be 0                                                            */
+  int    KhTh_use_vert_struct;       /* KHTR_USE_EBT_STRUCT or KHTR_USE_SQG_STRUCT (F, :201-208): must be 0                            */
+  int    use_unmasked_transport_bug; /* NDIFF_USE_UNMASKED_TRANSPORT_BUG (F, :209): must be 0                                          */
+  int    ndiff_answer_date;          /* NDIFF_ANSWER_DATE (20240101, :217): <= 20240330 the interleaved sum :897-907, later the four
+                                      * directional sums :909-922                                                                      */
+  int    recalc_neutral_surf;        /* RECALC_NEUTRAL_SURF (F, MOM_tracer_hor_diff.F90:1747): read by mom6x_tracer_hordiff_neutral
+                                      * alone, which has no other home for it                                                          */
+  double RL2_T2_to_Pa;               /* EOS%RL2_T2_to_Pa (1): the pressure handed to the equation of state, MOM_EOS.F90:813            */
+  double C_to_degC;                  /* EOS%C_to_degC (1): the temperature, MOM_EOS.F90:814, and dRdT :822                             */
+  double S_to_ppt;                   /* EOS%S_to_ppt (1): the salinity, MOM_EOS.F90:815, and dRdS :823                                 */
+  double kg_m3_to_R;                 /* EOS%kg_m3_to_R (1): the density derivatives, MOM_EOS.F90:820                                   */
+} mom6x_neutral_diffusion_params;
+/* neutral_diffusion_init :134: checks the members, keeps them with the equation of state and allocates every array the calls below
+ * use, so that none of them allocates: Pint, Tint, Sint, dRdT, dRdS of nk + 1 planes; per face direction PoL, PoR (doubles) and
+ * KoL, KoR (16-bit integers) on 2 nk + 2 surfaces and hEff on 2 nk + 1; the two flux arrays of 2 nk + 1 planes; Til, aL, aR and the
+ * accumulator of the update (4 nk + 1 planes); Coef_x, Coef_y of mom6x_tracer_hordiff_neutral (2 nk + 2 planes).  A refused or
+ * invalid call leaves no module behind, also where an earlier call had succeeded.  MOM6X_EUNSUPPORTED, naming the setting:
+ * NDIFF_CONTINUOUS = False, NDIFF_INTERIOR_ONLY, NDIFF_TAPERING, KHTR_USE_EBT_STRUCT / KHTR_USE_SQG_STRUCT,
+ * NDIFF_USE_UNMASKED_TRANSPORT_BUG, a non-Boussinesq context, a NULL equation of state (the module is only created with
+ * temperature and salinity, :134).  MOM6X_EINVAL: an unknown EQN_OF_STATE form, more than 32766 layers.                           */
+int mom6x_neutral_diffusion_init(mom6x_ctx *ctx, const mom6x_neutral_diffusion_params *p, const mom6x_eos_params *eos);
+/* The bytes that mom6x_neutral_diffusion_init allocated (0 before it). */
+long long mom6x_neutral_diffusion_work_bytes(mom6x_ctx *ctx);
+/* neutral_diffusion_calc_coeffs(G, GV, US, h, T, S, visc, CS, p_surf) :351-616, continuous arm, on the context's stream: no
+ * allocation, no host synchronisation, no halo exchange.  h, T, S: 3-D device arrays, p_surf: a plane or NULL; each is read on
+ * isc-1..iec+1 x jsc-1..jec+1 and nowhere else: the caller owes a halo of one.  Fills the module's interface state (Pint :436-445;
+ * Tint, Sint by interface_scalar :1091 with PLM_diff(.., 2, 1, ..) and ppm_edge; dRdT, dRdS by calculate_density_derivs of every
+ * form of mom6x_eos_form at Pint or ref_pres) and, at every u face I = isc-1..iec, j = jsc..jec and v face i = isc..iec,
+ * J = jsc-1..jec, the positions of find_neutral_surface_positions_continuous :1368-1573 (bl_kl = bl_kr = 1, bl_zl = bl_zr = 0 as the
+ * reference passes them, :543: the clamp :1541-1554 is the identity), hEff times 1 / (H_to_RZ g_Earth) (:592-597).  Dry faces
+ * hold Po = hEff = 0 and Ko = 1 (:524-533).  The reference's `stop` and FATAL sites -- klm1, krm1 out of bounds :1426-1428,
+ * Ppos < Pneg :1616 -- are unreachable with h >= 0; the device counts them (mom6x_neutral_diffusion_status), raises
+ * the context's numeric flag, which makes mom6x_ctx_sync return MOM6X_ENUMERIC, and goes on with the value clamped.               */
+int mom6x_neutral_diffusion_calc_coeffs(mom6x_ctx *ctx, const double *h, const double *T, const double *S, const double *p_surf);
+/* neutral_diffusion(G, GV, h, Coef_x, Coef_y, dt, Reg, US, CS) :619-1032 without vertical structure or tapering, on the context's
+ * stream: no allocation, no host synchronisation, no halo exchange -- the caller owes a halo of one on h and on every tracer.
+ * tracers: the registry, a HOST array of ntr 3-D device arrays, updated in place on the computational domain only, one after the
+ * other: neutral_surface_flux :2318-2496 (interface_scalar, ppm_left_right_edge_values :2562, ppm_ave :1181, the limiter :2457) at
+ * the wet faces, then the update :894-937 in the order of additions ndiff_answer_date selects, with the underflow :927 and
+ * :941-945.  conc_underflow: ntr HOST values or NULL.  Coef_x, Coef_y: device arrays of nk + 1 planes as the reference declares
+ * them; ONLY PLANE 1 IS READ in this configuration (KhTh_use_vert_struct = 0).  dt: the time step times I_numitts, read only for
+ * the diagnostics (Idt = 1 / dt).  tendency (3-D, the computational domain, 0 over land, :932), trans_x_2d (2-D, the u faces,
+ * :962-970) and trans_y_2d (2-D, the v faces, :991-999): NULL or HOST arrays of ntr nullable device outputs.
+ * MOM6X_EINVAL: a call before init or before the first calc_coeffs, a null array, dt <= 0 (whether or not a diagnostic is given).
+ * ppm_ave's dx outside [0, 1] (:1203, :1205) is counted like the sites of calc_coeffs.
+ * Not carried: dfxy_conc, dfxy_cont_2d, uhEff_2d, vhEff_2d (a host derives them from what is returned).                           */
+int mom6x_neutral_diffusion(mom6x_ctx *ctx, const double *h, const double *Coef_x, const double *Coef_y, double dt,
+                            double *const *tracers, const double *conc_underflow, int ntr, double *const *tendency,
+                            double *const *trans_x_2d, double *const *trans_y_2d);
+/* The module's resident coefficients, read only: dir 0 the u faces (uPoL, uPoR, uKoL, uKoR, uhEff), 1 the v faces.  Each is a stack
+ * of pitched planes [surface][j + joff][i + ioff] like a 2-D field of the context, the face (I, j) | (i, J) at the index of the cell
+ * it bounds to the east | north; Po: doubles, 2 nk + 2 planes; Ko: 16-bit integers (1-based layer indices), 2 nk + 2 planes; hEff:
+ * doubles, 2 nk + 1 planes.  Words outside the face ranges of calc_coeffs are not defined.  Any pointer argument may be NULL.      */
+int mom6x_neutral_diffusion_coeffs(mom6x_ctx *ctx, int dir, const double **PoL, const double **PoR, const short **KoL,
+                                   const short **KoR, const double **hEff);
+/* Waits for the context's stream and hands out how often each stop site was reached since init: counts[0] klm1 or krm1 out of bounds,
+ * [1] Ppos < Pneg, [2] ppm_ave dx < 0, [3] ppm_ave dx > 1.                                                                       */
+int mom6x_neutral_diffusion_status(mom6x_ctx *ctx, long long counts[4]);
+/* The work-group (lanes along i, rows) of the module's kernels and the i of their first lane, for tests that place a grid's edges
+ * where a launch extent rounds up to another block.                                                                              */
+int mom6x_neutral_diffusion_tile(int *bx, int *by, int *i_first);
 
 /* ------------------------------------------------------------------------- */
 /* MOM_dynamics_split_RK2                                                    */

@@ -673,6 +673,32 @@ def kappa_shear_params_default(GV=None, **kw):
     return p
 
 
+class NeutralDiffusionParams(C.Structure):
+    """mom6x_neutral_diffusion_params; what neutral_diffusion_init (MOM_neutral_diffusion.F90:134-345) leaves in
+    neutral_diffusion_CS, with RECALC_NEUTRAL_SURF of tracer_hor_diff_CS and the unit factors of the EOS type."""
+    _fields_ = [("continuous_reconstruction", C.c_int), ("ref_pres", C.c_double), ("interior_only", C.c_int), ("tapering", C.c_int),
+                ("KhTh_use_vert_struct", C.c_int), ("use_unmasked_transport_bug", C.c_int), ("ndiff_answer_date", C.c_int),
+                ("recalc_neutral_surf", C.c_int), ("RL2_T2_to_Pa", C.c_double), ("C_to_degC", C.c_double), ("S_to_ppt", C.c_double),
+                ("kg_m3_to_R", C.c_double)]
+
+
+NEUTRAL_DIFFUSION_MUST_BE_0 = ("interior_only", "tapering", "KhTh_use_vert_struct", "use_unmasked_transport_bug")
+
+
+def neutral_diffusion_params_default(**kw):
+    """neutral_diffusion_init (MOM_neutral_diffusion.F90:181-217) defaults, unscaled: NDIFF_CONTINUOUS = True, NDIFF_REF_PRES = -1
+    (the local interface pressure), NDIFF_ANSWER_DATE = 20240101 (:222: not yet DEFAULT_ANSWER_DATE), RECALC_NEUTRAL_SURF = False;
+    everything the device refuses is off."""
+    p = NeutralDiffusionParams()
+    p.continuous_reconstruction = 1; p.ref_pres = -1.0; p.ndiff_answer_date = 20240101; p.recalc_neutral_surf = 0
+    p.RL2_T2_to_Pa = 1.0; p.C_to_degC = 1.0; p.S_to_ppt = 1.0; p.kg_m3_to_R = 1.0
+    for n in NEUTRAL_DIFFUSION_MUST_BE_0:
+        setattr(p, n, 0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 class HorViscParams(C.Structure):
     """mom6x_hor_visc_params; hor_visc_CS (MOM_hor_visc.F90:36-259)."""
     _fields_ = [("Laplacian", C.c_int), ("biharmonic", C.c_int), ("Kh", C.c_double), ("Kh_bg_min", C.c_double),
@@ -949,6 +975,18 @@ def load_library(path=None):
         lib.mom6x_kappa_shear_work_bytes.argtypes = [vp]
         lib.mom6x_kappa_shear_work_bytes.restype = C.c_longlong
         lib.mom6x_Calculate_kappa_shear.argtypes = [vp] * 7 + [C.c_double, C.c_int] + [vp] * 8
+    if hasattr(lib, "mom6x_neutral_diffusion"):
+        vp = C.c_void_p
+        lib.mom6x_neutral_diffusion_init.argtypes = [vp, C.POINTER(NeutralDiffusionParams), C.POINTER(EOSParams)]
+        lib.mom6x_neutral_diffusion_work_bytes.argtypes = [vp]
+        lib.mom6x_neutral_diffusion_work_bytes.restype = C.c_longlong
+        lib.mom6x_neutral_diffusion_calc_coeffs.argtypes = [vp] * 5
+        lib.mom6x_neutral_diffusion.argtypes = [vp] * 4 + [C.c_double, vp, vp, C.c_int, vp, vp, vp]
+        lib.mom6x_neutral_diffusion_coeffs.argtypes = [vp, C.c_int] + [C.POINTER(vp)] * 5
+        lib.mom6x_neutral_diffusion_status.argtypes = [vp, C.POINTER(C.c_longlong)]
+        lib.mom6x_neutral_diffusion_tile.argtypes = [C.POINTER(C.c_int)] * 3
+        lib.mom6x_tracer_hordiff_neutral.argtypes = ([vp, vp, C.c_double, vp, vp, C.c_int] + [vp] * 7 + [vp] * 3 + [vp] * 3 + [vp] * 3 +
+                                                     [C.POINTER(C.c_int)])
     if path is None:
         _lib = lib
     return lib

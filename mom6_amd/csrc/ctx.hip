@@ -182,6 +182,7 @@ extern "C" int mom6x_struct_size(int which) {
     case 33: return (int)sizeof(mom6x_geothermal_params);
     case 34: return (int)sizeof(mom6x_opacity_params);
     case 35: return (int)sizeof(mom6x_kappa_shear_params);
+    case 36: return (int)sizeof(mom6x_neutral_diffusion_params);
     default: return -1;
   }
 }
@@ -265,6 +266,7 @@ extern "C" int mom6x_ctx_destroy(mom6x_ctx *c) {
   diabatic_TS_free(c);
   opacity_free(c);
   kappa_shear_free(c);
+  neutral_diffusion_free(c);
   comm_free(c);
   for (int m = 0; m < MOM6X_NSCR; m++) (void)hipFree(c->scr[m]);
   (void)hipFree(c->G); (void)hipFree(c->flag);
@@ -311,7 +313,11 @@ extern "C" int mom6x_ctx_sync(mom6x_ctx *c) {
   HIPCHK(hipMemcpy(&flag, c->flag, sizeof(int), hipMemcpyDeviceToHost));
   if (flag) {
     HIPCHK(hipMemset(c->flag, 0, sizeof(int)));
-    if (flag & MOM6X_FLAG_MEKE_EQUILIBRIUM)
+    if (flag & MOM6X_FLAG_NEUTRAL_DIFFUSION)
+      mom6x_set_error("device-side numeric error flag = %d (bit %d: neutral diffusion reached one of the reference's stop sites, "
+                      "MOM_neutral_diffusion.F90:1203, :1205, :1426, :1428, :1616, see mom6x_neutral_diffusion_status; other bits: NaN or "
+                      "negative thickness)", flag, MOM6X_FLAG_NEUTRAL_DIFFUSION);
+    else if (flag & MOM6X_FLAG_MEKE_EQUILIBRIUM)
       mom6x_set_error("device-side numeric error flag = %d (bit %d: MEKE_equilibrium found no bracket below 2e17 m2 s-2 or did not "
                       "converge in 200 bisections, MOM_MEKE.F90:1095, :1133; other bits: NaN or negative thickness)", flag,
                       MOM6X_FLAG_MEKE_EQUILIBRIUM);

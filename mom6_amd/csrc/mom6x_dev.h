@@ -75,6 +75,9 @@ __device__ __forceinline__ double dev_cuberoot(double x) {
 // a bit of the context's device-side error flag (mom6x_ctx::flag) with a message of its own in mom6x_ctx_sync: MEKE_equilibrium left a
 // column at one of the reference's two `stop`s (MOM_MEKE.F90:1095 the bracket, :1133 more than 200 bisections)
 #define MOM6X_FLAG_MEKE_EQUILIBRIUM 64
+// neutral_diffusion.hip: a face or a column reached one of the reference's `stop` / FATAL sites (MOM_neutral_diffusion.F90:1426, :1428
+// klm1, krm1 out of bounds; :1616 Ppos < Pneg; :1203, :1205 ppm_ave's dx outside [0, 1]); mom6x_neutral_diffusion_status has the counts
+#define MOM6X_FLAG_NEUTRAL_DIFFUSION 128
 
 // ---------------------------------------------------------------------------------------------
 // host-side error plumbing
@@ -102,7 +105,7 @@ enum Scr { SCR_q = 0, SCR_KE, SCR_absv, SCR_e, SCR_c1, SCR_t0, SCR_t1, SCR_t2, S
 // the module's parameter copy, its caller-owned pointers, the device arrays it allocates and an `init` flag where a setter may come
 // before the init call.  The context only owns them: a typed pointer each, null until the module is first touched.
 struct ContState; struct BTState; struct CorState; struct PgfState; struct VvState; struct HvState; struct RK2State; struct AleState;
-struct TAState; struct DiagState; struct SvState; struct TdState; struct ThdState; struct VmState; struct MleState; struct MekeState; struct SdState; struct DaState; struct EpblState; struct DtsState; struct OpState; struct KsState;
+struct TAState; struct DiagState; struct SvState; struct TdState; struct ThdState; struct VmState; struct MleState; struct MekeState; struct SdState; struct DaState; struct EpblState; struct DtsState; struct OpState; struct KsState; struct NdState;
 struct Comm;   // halo.hip: tile layout + RCCL communicator (null: single tile, wrap only)
 
 // u_bc_accel = (CAu + PFu) + diffu of the RK2 predictor (RK2.F90:565-572) formed by the pressure-force kernel that has just made
@@ -133,7 +136,7 @@ struct mom6x_ctx {
   long long n_exchanges, n_exchange_bytes;
   // the modules' states
   ContState *cont; BTState *bts; CorState *cor; PgfState *pgf; VvState *vv; HvState *hv; RK2State *rk2; AleState *ale;
-  TAState *ta; DiagState *diag; SvState *sv; TdState *td; ThdState *thd; VmState *vm; MleState *mle; MekeState *meke; SdState *sd; DaState *da; EpblState *epbl; DtsState *dts; OpState *op; KsState *ks; Comm *comm;
+  TAState *ta; DiagState *diag; SvState *sv; TdState *td; ThdState *thd; VmState *vm; MleState *mle; MekeState *meke; SdState *sd; DaState *da; EpblState *epbl; DtsState *dts; OpState *op; KsState *ks; NdState *nd; Comm *comm;
 };
 // Each frees every device pointer its struct owns, deletes the struct and nulls the context's pointer (a null pointer: nothing to
 // do).  mom6x_ctx_destroy calls them all; apart from them it frees only what mom6x_ctx_create allocated.
@@ -142,7 +145,7 @@ void PressureForce_free(mom6x_ctx *c);  void vertvisc_free(mom6x_ctx *c);       
 void rk2_state_free(mom6x_ctx *c);   void ALE_free(mom6x_ctx *c);               void ta_state_free(mom6x_ctx *c);
 void diag_sums_free(mom6x_ctx *c);   void set_visc_free(mom6x_ctx *c);          void thickness_diffuse_free(mom6x_ctx *c);
 void tracer_hor_diff_free(mom6x_ctx *c);  void varmix_free(mom6x_ctx *c);       void mixedlayer_restrat_free(mom6x_ctx *c);
-void MEKE_free(mom6x_ctx *c);  void set_diffusivity_free(mom6x_ctx *c);  void diabatic_aux_free(mom6x_ctx *c);  void energetic_PBL_free(mom6x_ctx *c);  void diabatic_TS_free(mom6x_ctx *c);  void opacity_free(mom6x_ctx *c);  void kappa_shear_free(mom6x_ctx *c);
+void MEKE_free(mom6x_ctx *c);  void set_diffusivity_free(mom6x_ctx *c);  void diabatic_aux_free(mom6x_ctx *c);  void energetic_PBL_free(mom6x_ctx *c);  void diabatic_TS_free(mom6x_ctx *c);  void opacity_free(mom6x_ctx *c);  void kappa_shear_free(mom6x_ctx *c);  void neutral_diffusion_free(mom6x_ctx *c);
 void comm_free(mom6x_ctx *c);
 // The widths of one group pass (create_group_pass(..., halo=)).  w: rows / columns of halo filled for its 3-D fields (0: the context's
 // halo); wf[0 .. nwf - 1]: the widths of single 3-D fields (0 entries and fields beyond nwf: w).  The default is what every pass but the
@@ -183,6 +186,10 @@ void tracer_advect_tile_steps(int *sx, int *sy);                   // tracer_adv
 // What one module asks of another (each lives in the file that owns the state).  xxx_ready: the module's init call has run
 bool continuity_ready(const mom6x_ctx *c);  bool barotropic_ready(const mom6x_ctx *c);  bool CoriolisAdv_ready(const mom6x_ctx *c);
 bool PressureForce_ready(const mom6x_ctx *c);  bool hor_visc_ready(const mom6x_ctx *c);
+// neutral_diffusion.hip, for tracer_hordiff's neutral branch (tracer_hor_diff.hip): the module is initialised; RECALC_NEUTRAL_SURF; the
+// module's Coef_x | Coef_y of nk + 1 planes each (the reference's locals of tracer_hordiff, MOM_tracer_hor_diff.F90:150-153)
+bool neutral_diffusion_ready(const mom6x_ctx *c);  bool neutral_diffusion_recalc(const mom6x_ctx *c);
+void neutral_diffusion_coef_arrays(const mom6x_ctx *c, double **Coef_x, double **Coef_y);
 bool vertvisc_ready(const mom6x_ctx *c);                           // vert_friction.hip: vertvisc_coef is on the device (mom6x_vertvisc_init)
 bool vertvisc_has_coef(const mom6x_ctx *c);                        // vert_friction.hip: there are coefficients to solve with (vertvisc_init or _set_coef)
 int continuity_stencil(const mom6x_ctx *c);                        // continuity.hip: 3, SIMPLE_2ND 2, UPWIND_1ST 1 (needs continuity_ready)

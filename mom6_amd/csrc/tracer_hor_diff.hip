@@ -3,6 +3,8 @@
 //   tracer_hordiff        <- MOM_tracer_hor_diff.F90:119-699 on its along-layer path: the face diffusivities and khdt_x, khdt_y
 //                            :237-357, the iteration count :371-390, the zeroing of df_x, df_y :392-402, the iteration :544-612
 //   tracer_hor_diff_init  <- :1630-1779
+//   tracer_hordiff_neutral <- the neutral branch :479-539, an entry of its own on the same state: khdt_x, khdt_y and the iteration
+//                            count come from the helper both entries call (thd_khdt_and_itts), the rest is neutral_diffusion.hip's
 //
 // The 2-D part is two small launches: k_thd_khdt (both face directions, blockIdx.z; MAX and MIN are fmax1 and fmin1 of
 // mom6x_dev.h, the reference compiler's) and, with CHECK_DIFFUSIVE_CFL, k_thd_cfl (the cell CFL and its maximum).  The iteration is
@@ -17,6 +19,7 @@
 #include "mom6x_dev.h"
 #include <cmath>
 #include <cfloat>
+#include <vector>
 
 constexpr int HD_TX = 240;     // columns of a work-group's tile (15 x 128 B: tiles start on cache lines); threads HD_TX and HD_TX + 1
                                // fetch the column west and east of the tile
@@ -287,19 +290,12 @@ extern "C" int mom6x_tracer_hor_diff_init(mom6x_ctx *c, const mom6x_tracer_hor_d
   return MOM6X_OK;
 }
 
-extern "C" int mom6x_tracer_hordiff(mom6x_ctx *c, const double *h, double dt, double *const *tracers, const double *conc_underflow,
-                                    int ntr, const double *L2u, const double *SN_u, const double *L2v, const double *SN_v,
-                                    const double *Res_fn_h, const double *Rd_dx_h, const double *MEKE_Kh, double *const *df_x,
-                                    double *const *df_y, double *khdt_x_out, double *khdt_y_out, double *cfl_out, int *num_itts_out) {
-  REQUIRE(c && c->thd, MOM6X_EINVAL, "MOM_tracer_hor_diff: tracer_hor_diff_init must be called before tracer_hordiff.");
-  ThdState *s = c->thd;
+// khdt_x, khdt_y :237-357 and the iteration count :371-390 of a call whose arguments are checked, for both entries
+struct ThdPlan { double *khx, *khy; int num_itts; double I_numitts, Idt; };
+static int thd_khdt_and_itts(mom6x_ctx *c, ThdState *s, double dt, const double *L2u, const double *SN_u, const double *L2v,
+                             const double *SN_v, const double *Res_fn_h, const double *Rd_dx_h, const double *MEKE_Kh, double *khdt_x_out,
+                             double *khdt_y_out, double *cfl_out, int *num_itts_out, ThdPlan *plan) {
   const mom6x_tracer_hor_diff_params &P = s->P;
-  REQUIRE(ntr >= 0, MOM6X_EINVAL, "tracer_hordiff: negative tracer count");
-  if (num_itts_out) *num_itts_out = 0;
-  if (ntr == 0 || (P.KhTr <= 0.0 && !P.use_variable_mixing)) return MOM6X_OK;   // :199
-  REQUIRE(h && tracers, MOM6X_EINVAL, "tracer_hordiff: null array");
-  for (int m = 0; m < ntr; m++) REQUIRE(tracers[m], MOM6X_EINVAL, "tracer_hordiff: null tracer array");
-  REQUIRE(dt > 0.0, MOM6X_EINVAL, "tracer_hordiff: dt must be positive");
   ThdK K;
   K.dt = dt; K.KhTr = P.KhTr; K.KhTr_Slope_Cff = P.KhTr_Slope_Cff; K.KhTr_min = P.KhTr_min; K.KhTr_max = P.KhTr_max;
   K.passivity_coeff = P.KhTr_passivity_coeff; K.passivity_min = P.KhTr_passivity_min; K.KhTr_fac = P.MEKE_KhTr_fac;
@@ -342,6 +338,30 @@ extern "C" int mom6x_tracer_hordiff(mom6x_ctx *c, const double *h, double dt, do
   }
   const double I_numitts = 1.0 / (double)num_itts, Idt = 1.0 / dt;
   if (num_itts_out) *num_itts_out = num_itts;
+  plan->khx = khx; plan->khy = khy; plan->num_itts = num_itts; plan->I_numitts = I_numitts; plan->Idt = Idt;
+  return MOM6X_OK;
+}
+
+extern "C" int mom6x_tracer_hordiff(mom6x_ctx *c, const double *h, double dt, double *const *tracers, const double *conc_underflow,
+                                    int ntr, const double *L2u, const double *SN_u, const double *L2v, const double *SN_v,
+                                    const double *Res_fn_h, const double *Rd_dx_h, const double *MEKE_Kh, double *const *df_x,
+                                    double *const *df_y, double *khdt_x_out, double *khdt_y_out, double *cfl_out, int *num_itts_out) {
+  REQUIRE(c && c->thd, MOM6X_EINVAL, "MOM_tracer_hor_diff: tracer_hor_diff_init must be called before tracer_hordiff.");
+  ThdState *s = c->thd;
+  const mom6x_tracer_hor_diff_params &P = s->P;
+  REQUIRE(ntr >= 0, MOM6X_EINVAL, "tracer_hordiff: negative tracer count");
+  if (num_itts_out) *num_itts_out = 0;
+  if (ntr == 0 || (P.KhTr <= 0.0 && !P.use_variable_mixing)) return MOM6X_OK;   // :199
+  REQUIRE(h && tracers, MOM6X_EINVAL, "tracer_hordiff: null array");
+  for (int m = 0; m < ntr; m++) REQUIRE(tracers[m], MOM6X_EINVAL, "tracer_hordiff: null tracer array");
+  REQUIRE(dt > 0.0, MOM6X_EINVAL, "tracer_hordiff: dt must be positive");
+  ThdPlan plan;
+  if (const int rc = thd_khdt_and_itts(c, s, dt, L2u, SN_u, L2v, SN_v, Res_fn_h, Rd_dx_h, MEKE_Kh, khdt_x_out, khdt_y_out, cfl_out, num_itts_out,
+                                       &plan)) return rc;
+  const Dm d = c->d;
+  double *khx = plan.khx, *khy = plan.khy;
+  const int num_itts = plan.num_itts;
+  const double I_numitts = plan.I_numitts, Idt = plan.Idt;
 
   // The kernel carries up to HD_MAXT tracers through one pass over h and the coefficients; a longer registry goes HD_MAXT at a
   // time, each group through all iterations: tracers do not interact, so every tracer gets the bits of one pass.
@@ -373,6 +393,66 @@ extern "C" int mom6x_tracer_hordiff(mom6x_ctx *c, const double *h, double dt, do
 #undef THD_M
 #undef THD
     }
+  }
+  HIPCHK(hipGetLastError());
+  REQUIRE(!c->halo_error, MOM6X_EHIP, mom6x_last_error());
+  return MOM6X_OK;
+}
+
+namespace {
+
+// Coef_x(I,j,K) = I_numitts * khdt_x(I,j) and Coef_y(i,J,K) = I_numitts * khdt_y(i,J) on all nk + 1 planes, :494-507
+__global__ void __launch_bounds__(256)
+k_thd_ndiff_coef(Dm d, double I_numitts, const double *__restrict__ khdt_x, const double *__restrict__ khdt_y, double *__restrict__ Coef_x,
+                 double *__restrict__ Coef_y) {
+  const FaceLane f = face_lane<0>(d);
+  if (!f.in) return;
+  const double coef = I_numitts * (f.dir ? khdt_y : khdt_x)[f.x];
+  double *Coef = f.dir ? Coef_y : Coef_x;
+  for (int K = 0; K <= d.nk; K++) Coef[f.x + (size_t)K * (size_t)d.slab] = coef;
+}
+
+}  // namespace
+
+// The neutral branch :479-539.  The registry's group pass is the context's, as in mom6x_tracer_hordiff.
+extern "C" int mom6x_tracer_hordiff_neutral(mom6x_ctx *c, const double *h, double dt, double *const *tracers, const double *conc_underflow,
+                                            int ntr, const double *L2u, const double *SN_u, const double *L2v, const double *SN_v,
+                                            const double *Res_fn_h, const double *Rd_dx_h, const double *MEKE_Kh, const double *T,
+                                            const double *S, const double *p_surf, double *const *tendency, double *const *trans_x_2d,
+                                            double *const *trans_y_2d, double *khdt_x_out, double *khdt_y_out, double *cfl_out,
+                                            int *num_itts_out) {
+  REQUIRE(c && c->thd, MOM6X_EINVAL, "MOM_tracer_hor_diff: tracer_hor_diff_init must be called before tracer_hordiff_neutral.");
+  REQUIRE(neutral_diffusion_ready(c), MOM6X_EINVAL, "tracer_hordiff_neutral: neutral_diffusion_init must be called first");
+  ThdState *s = c->thd;
+  const mom6x_tracer_hor_diff_params &P = s->P;
+  REQUIRE(ntr >= 0, MOM6X_EINVAL, "tracer_hordiff_neutral: negative tracer count");
+  if (num_itts_out) *num_itts_out = 0;
+  if (ntr == 0 || (P.KhTr <= 0.0 && !P.use_variable_mixing)) return MOM6X_OK;   // :199
+  REQUIRE(h && tracers && T && S, MOM6X_EINVAL, "tracer_hordiff_neutral: null array");
+  for (int m = 0; m < ntr; m++) REQUIRE(tracers[m], MOM6X_EINVAL, "tracer_hordiff_neutral: null tracer array");
+  REQUIRE(dt > 0.0, MOM6X_EINVAL, "tracer_hordiff_neutral: dt must be positive");
+  ThdPlan plan;
+  if (const int rc = thd_khdt_and_itts(c, s, dt, L2u, SN_u, L2v, SN_v, Res_fn_h, Rd_dx_h, MEKE_Kh, khdt_x_out, khdt_y_out, cfl_out, num_itts_out,
+                                       &plan)) return rc;
+  const Dm d = c->d;
+  std::vector<int> stg(ntr, 0), nks(ntr, d.nk);
+  c->halo_error = false;
+  halo_wrap(c, tracers, stg.data(), nks.data(), ntr);                            // do_group_pass(CS%pass_t) :483
+  if (const int rc = mom6x_neutral_diffusion_calc_coeffs(c, h, T, S, p_surf)) return rc;
+  double *Coef_x, *Coef_y;
+  neutral_diffusion_coef_arrays(c, &Coef_x, &Coef_y);
+  const dim3 b = blk2();
+  KLAUNCH(c, "k_thd_ndiff_coef", k_thd_ndiff_coef, grid3(d.ni + IAL, d.nj + 1, 2, b), b, d, plan.I_numitts, (const double *)plan.khx,
+          (const double *)plan.khy, Coef_x, Coef_y);
+  for (int itt = 0; itt < plan.num_itts; itt++) {
+    if (itt > 0) {
+      halo_wrap(c, tracers, stg.data(), nks.data(), ntr);                        // :528
+      if (neutral_diffusion_recalc(c)) {
+        if (const int rc = mom6x_neutral_diffusion_calc_coeffs(c, h, T, S, p_surf)) return rc;
+      }
+    }
+    if (const int rc = mom6x_neutral_diffusion(c, h, Coef_x, Coef_y, plan.I_numitts * dt, tracers, conc_underflow, ntr, tendency,
+                                               trans_x_2d, trans_y_2d)) return rc;
   }
   HIPCHK(hipGetLastError());
   REQUIRE(!c->halo_error, MOM6X_EHIP, mom6x_last_error());

@@ -325,6 +325,83 @@ class Dycore:
                                                       _ptr(khdt_x), _ptr(khdt_y), _ptr(CFL), C.byref(itts)))
         return itts.value
 
+    # -- MOM_neutral_diffusion ------------------------------------------------------------------
+    def neutral_diffusion_init(self, params, eos):
+        """neutral_diffusion_init (MOM_neutral_diffusion.F90:134) with abi.neutral_diffusion_params_default(...); eos:
+        tv%eqn_of_state.  Allocates every array of the calls below."""
+        self.neutral_diffusion_params = params
+        check(self.lib, self.lib.mom6x_neutral_diffusion_init(self.ctx, C.byref(params), C.byref(eos) if eos is not None else None))
+
+    def neutral_diffusion_work_bytes(self):
+        """The bytes that neutral_diffusion_init allocated."""
+        return int(self.lib.mom6x_neutral_diffusion_work_bytes(self.ctx))
+
+    def neutral_diffusion_calc_coeffs(self, h, T, S, p_surf=None):
+        """neutral_diffusion_calc_coeffs (MOM_neutral_diffusion.F90:351), continuous arm: h, T, S and p_surf are read one point
+        into the halo; no exchange."""
+        check(self.lib, self.lib.mom6x_neutral_diffusion_calc_coeffs(self.ctx, _ptr(h), _ptr(T), _ptr(S), _ptr(p_surf)))
+
+    def _per_tracer(self, fs, n):
+        if fs is None or n == 0:
+            return None
+        assert len(fs) == n
+        return (C.c_void_p * n)(*[(f.data_ptr() if f is not None else None) for f in fs])
+
+    def neutral_diffusion(self, h, Coef_x, Coef_y, dt, tracers, conc_underflow=None, tendency=None, trans_x_2d=None, trans_y_2d=None):
+        """neutral_diffusion (MOM_neutral_diffusion.F90:619): `tracers` is the registry as a list of 3-D fields, updated in place on
+        the computational domain; Coef_x, Coef_y have nk + 1 planes, of which the first is read; conc_underflow, tendency,
+        trans_x_2d, trans_y_2d are lists with one entry per tracer (entries of the last three may be None)."""
+        n = len(tracers)
+        ptrs = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in tracers])
+        uf = (C.c_double * n)(*conc_underflow) if conc_underflow is not None and n else None
+        check(self.lib, self.lib.mom6x_neutral_diffusion(self.ctx, _ptr(h), _ptr(Coef_x), _ptr(Coef_y), C.c_double(dt), ptrs, uf, n,
+                                                         self._per_tracer(tendency, n), self._per_tracer(trans_x_2d, n),
+                                                         self._per_tracer(trans_y_2d, n)))
+
+    NEUTRAL_DIFFUSION_COEFFS = ("PoL", "PoR", "KoL", "KoR", "hEff")
+
+    def neutral_diffusion_coeffs(self, dir):
+        """The module's resident coefficients of the u faces (dir 0) or the v faces (dir 1) as read-only torch views by the names of
+        NEUTRAL_DIFFUSION_COEFFS: PoL, PoR (float64, 2 nk + 2 planes), KoL, KoR (int16, 2 nk + 2 planes, 1-based layers), hEff
+        (float64, 2 nk + 1 planes); a plane is laid out like a 2-D field, a face at the index of the cell to its west | south."""
+        p = [C.c_void_p() for _ in range(5)]
+        check(self.lib, self.lib.mom6x_neutral_diffusion_coeffs(self.ctx, int(dir), *[C.byref(x) for x in p]))
+        ns = 2 * self.dims.nk + 2
+        out = {}
+        for n, x in zip(self.NEUTRAL_DIFFUSION_COEFFS, p):
+            shape = ((ns - 1) if n == "hEff" else ns,) + tuple(self.dims.shape2())
+            out[n] = _view(x.value, shape, self.device, "<i2" if n in ("KoL", "KoR") else "<f8")
+        return out
+
+    def neutral_diffusion_status(self):
+        """How often each of the reference's stop sites was reached since init (waits for the stream): klm1 or krm1 out of bounds,
+        Ppos < Pneg, ppm_ave dx < 0, ppm_ave dx > 1."""
+        counts = (C.c_longlong * 4)()
+        check(self.lib, self.lib.mom6x_neutral_diffusion_status(self.ctx, counts))
+        return tuple(int(x) for x in counts)
+
+    def neutral_diffusion_tile(self):
+        """(lanes along i, rows, i of the first lane) of the work-groups of the module's kernels."""
+        bx, by, i0 = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self.lib, self.lib.mom6x_neutral_diffusion_tile(C.byref(bx), C.byref(by), C.byref(i0)))
+        return bx.value, by.value, i0.value
+
+    def tracer_hordiff_neutral(self, h, dt, tracers, T, S, p_surf=None, MEKE_Kh=None, L2u=None, SN_u=None, L2v=None, SN_v=None,
+                               Res_fn_h=None, Rd_dx_h=None, conc_underflow=None, tendency=None, trans_x_2d=None, trans_y_2d=None,
+                               khdt_x=None, khdt_y=None, CFL=None):
+        """The neutral branch of tracer_hordiff (MOM_tracer_hor_diff.F90:479-539), called in place of tracer_hordiff by a host
+        that uses neutral diffusion (use_neutral_diffusion stays 0 in tracer_hor_diff_init): T, S are tv%T, tv%S (they may be
+        members of `tracers`), p_surf tv%p_surf.  Needs tracer_hor_diff_init and neutral_diffusion_init.  Returns num_itts."""
+        n = len(tracers)
+        ptrs = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in tracers])
+        uf = (C.c_double * n)(*conc_underflow) if conc_underflow is not None and n else None
+        itts = C.c_int(0)
+        check(self.lib, self.lib.mom6x_tracer_hordiff_neutral(
+            self.ctx, _ptr(h), C.c_double(dt), ptrs, uf, n, _ptr(L2u), _ptr(SN_u), _ptr(L2v), _ptr(SN_v), _ptr(Res_fn_h), _ptr(Rd_dx_h),
+            _ptr(MEKE_Kh), _ptr(T), _ptr(S), _ptr(p_surf), self._per_tracer(tendency, n), self._per_tracer(trans_x_2d, n),
+            self._per_tracer(trans_y_2d, n), _ptr(khdt_x), _ptr(khdt_y), _ptr(CFL), C.byref(itts)))
+        return itts.value
+
     def tracer_hordiff_tile(self):
         """(columns, rows, tracers per launch) of the iteration kernel's tile."""
         tx, ty, mt = C.c_int(0), C.c_int(0), C.c_int(0)
@@ -899,14 +976,14 @@ class Dycore:
                                                                 _ptr(sfc_flux), _ptr(btm_flux), C.c_int(int(convert_flux))))
 
 
-def _view(ptr, shape, device):
+def _view(ptr, shape, device, typestr="<f8"):
     """torch tensor aliasing device memory owned by the C library."""
     n = int(np.prod(shape))
 
     class _Holder:
         pass
     h = _Holder()
-    h.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (int(ptr), False), "version": 2}
+    h.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (int(ptr), False), "version": 2}
     return torch.as_tensor(h, device=device).view(shape)
 
 
