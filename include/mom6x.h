@@ -1583,7 +1583,13 @@ typedef struct mom6x_neutral_diffusion_params {
  * invalid call leaves no module behind, also where an earlier call had succeeded.  MOM6X_EUNSUPPORTED, naming the setting:
  * NDIFF_CONTINUOUS = False, NDIFF_INTERIOR_ONLY, NDIFF_TAPERING, KHTR_USE_EBT_STRUCT / KHTR_USE_SQG_STRUCT,
  * NDIFF_USE_UNMASKED_TRANSPORT_BUG, a non-Boussinesq context, a NULL equation of state (the module is only created with
- * temperature and salinity, :134).  MOM6X_EINVAL: an unknown EQN_OF_STATE form, more than 32766 layers.                           */
+ * temperature and salinity, :134).  MOM6X_EINVAL: an unknown EQN_OF_STATE form, more than 32766 layers.
+ * The reference's neutral_diffusion_init refuses none of these settings: the compiled init has no FATAL and no WARNING for
+ * NDIFF_CONTINUOUS = False (it goes on to set up MOM_remapping, :248-251), KHTR_USE_EBT_STRUCT / KHTR_USE_SQG_STRUCT (it allocates
+ * Coef_h, :306-308) or NDIFF_USE_UNMASKED_TRANSPORT_BUG; it does not even read NDIFF_TAPERING unless NDIFF_INTERIOR_ONLY is set
+ * (:195-200), so a lone NDIFF_TAPERING, which the device refuses, changes nothing there; and under NDIFF_INTERIOR_ONLY it is FATAL
+ * only where the diabatic driver holds neither KPP nor ePBL (:296-298).  The refusals above are the device's alone; only an unknown
+ * EQN_OF_STATE is FATAL there too (MOM_EOS.F90:1591).  tests/test_ref_parity_cpu.py holds this list to the compiled init.       */
 int mom6x_neutral_diffusion_init(mom6x_ctx *ctx, const mom6x_neutral_diffusion_params *p, const mom6x_eos_params *eos);
 /* The bytes that mom6x_neutral_diffusion_init allocated (0 before it). */
 long long mom6x_neutral_diffusion_work_bytes(mom6x_ctx *ctx);

@@ -1,8 +1,8 @@
 !> ORACLE SUPPORT (test infrastructure only): bind(C) doors into the reference's parameterization modules, compiled where
 !! they lie against the stand-ins of oracle/ref_standins.F90 into oracle/_ref/libref_param.so (see oracle/Makefile):
 !! MOM_EOS_Wright.F90, MOM_EOS_Wright_full.F90, MOM_EOS_Wright_red.F90, MOM_EOS_linear.F90, MOM_intrinsic_functions.F90,
-!! MOM_opacity.F90, MOM_energetic_PBL.F90 and MOM_kappa_shear.F90 (with the dispatcher MOM_EOS.F90 that it calls), with
-!! MOM_unit_scaling.F90 and MOM_string_functions.F90.
+!! MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90 and MOM_neutral_diffusion.F90 (with the dispatcher MOM_EOS.F90 that
+!! the last two call), with MOM_unit_scaling.F90 and MOM_string_functions.F90.
 !! tests/ref_param.py loads the library and holds the parameter-name maps; tests/test_ref_parity_cpu.py holds the python
 !! restatements under tests/ to these doors.  Nothing of the reference is copied here.
 !!
@@ -13,10 +13,11 @@
 !! m_to_H, H_to_MKS, HZ_T_to_m2_s).  Every door that runs a module returns the number of FATAL messages it met.
 module ref_param_shim
   use, intrinsic :: iso_c_binding
-  use MOM_error_handler, only : standin_fatal_count
+  use MOM_error_handler, only : standin_fatal_count, standin_never_count
   use MOM_file_parser, only : param_file_type, standin_clear_params, standin_set_real, standin_set_int, standin_set_char, &
                               standin_set_reals
   use MOM_diag_mediator, only : diag_ctrl, time_type, standin_clear_diags, standin_want_diag, standin_diag_size, standin_get_diag
+  use MOM_diag_mediator, only : axes_grp, register_diag_field
   use MOM_grid, only : ocean_grid_type
   use MOM_verticalGrid, only : verticalGrid_type
   use MOM_unit_scaling, only : unit_scale_type, unit_scaling_init, unit_scaling_end
@@ -34,6 +35,10 @@ module ref_param_shim
   use MOM_opacity, only : optics_type, opacity_CS, opacity_init, set_opacity, opacity_end, absorbRemainingSW, sumSWoverBands
   use MOM_energetic_PBL, only : energetic_PBL_CS, energetic_PBL_init, energetic_PBL, energetic_PBL_get_MLD, energetic_PBL_end
   use MOM_kappa_shear, only : Kappa_shear_CS, kappa_shear_init, Calculate_kappa_shear
+  use MOM_neutral_diffusion, only : neutral_diffusion_CS, neutral_diffusion_init, neutral_diffusion_calc_coeffs, neutral_diffusion, &
+                                    neutral_diffusion_end
+  use MOM_tracer_registry, only : tracer_registry_type
+  use MOM_diabatic_driver, only : diabatic_CS
   implicit none
 contains
   function fstr(s) result(f)
@@ -46,7 +51,7 @@ contains
 
   ! ---- the parameter table, the diagnostics asked for and the capture store ----
   subroutine ref_param_clear() bind(C, name="ref_param_clear")
-    call standin_clear_params() ; call standin_clear_diags() ; standin_fatal_count = 0
+    call standin_clear_params() ; call standin_clear_diags() ; standin_fatal_count = 0 ; standin_never_count = 0
   end subroutine
   subroutine ref_set_real(name, value) bind(C, name="ref_set_real")
     character(kind=c_char), intent(in) :: name(*) ; real(c_double), value :: value
@@ -352,5 +357,79 @@ contains
     if (associated(CS)) deallocate(CS)
     call unit_scaling_end(US)
     ref_Calculate_kappa_shear = standin_fatal_count
+  end function
+
+  !> Of the FATAL messages of the last door, those raised by a stand-in procedure that must never run (a path that leaves the
+  !! compiled files: NDIFF_CONTINUOUS false into MOM_remapping, NDIFF_INTERIOR_ONLY into MOM_diabatic_driver).
+  integer(c_int) function ref_standin_never_count() bind(C, name="ref_standin_never_count")
+    ref_standin_never_count = standin_never_count
+  end function
+
+  !> neutral_diffusion_init (MOM_neutral_diffusion.F90:138) and EOS_init through the table, then, `ncalls` times on the same control
+  !! structure, neutral_diffusion_calc_coeffs (:351) and neutral_diffusion (:619) over a registry of ntr tracers, on a whole tile.
+  !! h, T and S are [ncalls, nk, nj_mem, ni_mem] and p_surf (a C pointer, null: the argument is absent) [ncalls, nj_mem, ni_mem]:
+  !! round r computes its coefficients from slice r, so that an array left over from the round before would show.  Coef_x1 and
+  !! Coef_y1 are plane 1 of Coef_x and Coef_y; the other nk planes handed to the reference hold NaN.  tracers [ntr, nk, nj_mem,
+  !! ni_mem] are changed in place, every round going on from the one before.  masks = (mask2dT, mask2dCu, mask2dCv, IareaT); vgx =
+  !! (g_Earth, H_to_pa).  Tracer m's id_dfxy_cont, id_dfx_2d and id_dfy_2d are the ids of the names dfxy_cont_m, dfx_2d_m and
+  !! dfy_2d_m (m = 1 ..) where ref_want_diag has asked for them, else -1; id_dfxy_conc and id_dfxy_cont_2d stay -1.  What
+  !! post_data last copied (the last round's) is read back with ref_get_diag.  dt <= 0: the two inits only (for what they refuse).
+  !! The components of neutral_diffusion_CS are private and id_uhEff_2d, id_vhEff_2d are never registered by the reference:
+  !! PoL, PoR, KoL, KoR and hEff cannot be handed out.
+  integer(c_int) function ref_neutral_diffusion(ni_mem, nj_mem, idx, nk, vgr, vgx, masks, ncalls, h, T, S, p_surf, Coef_x1, Coef_y1, &
+        dt, ntr, tracers, conc_underflow) bind(C, name="ref_neutral_diffusion")
+    use, intrinsic :: ieee_arithmetic, only : ieee_value, ieee_quiet_nan
+    integer(c_int), value :: ni_mem, nj_mem, nk, ncalls, ntr ; integer(c_int), intent(in) :: idx(4)
+    real(c_double), intent(in) :: vgr(14), vgx(2), masks(ni_mem, nj_mem, 4)
+    real(c_double), intent(in), target, dimension(ni_mem, nj_mem, nk, ncalls) :: h, T, S
+    type(c_ptr), value :: p_surf
+    real(c_double), intent(in) :: Coef_x1(ni_mem, nj_mem), Coef_y1(ni_mem, nj_mem), conc_underflow(ntr) ; real(c_double), value :: dt
+    real(c_double), intent(inout), target :: tracers(ni_mem, nj_mem, nk, ntr)
+    type(ocean_grid_type) :: G ; type(verticalGrid_type) :: GV ; type(unit_scale_type), pointer :: US
+    type(param_file_type) :: pf ; type(diag_ctrl), target :: diag ; type(time_type), target :: Time
+    type(neutral_diffusion_CS), pointer :: CS ; type(EOS_type), target :: eqn ; type(vertvisc_type) :: visc
+    type(diabatic_CS), pointer :: diabatic_CSp ; type(tracer_registry_type), pointer :: Reg ; type(axes_grp) :: axes
+    real, allocatable :: Coef_x(:,:,:), Coef_y(:,:,:)
+    real, pointer :: p_ps(:,:,:)
+    character(len=16) :: tag
+    logical :: used
+    integer :: m, r
+    standin_fatal_count = 0 ; standin_never_count = 0
+    call setup(int(ni_mem), int(nj_mem), int(idx), int(nk), vgr, masks(:,:,1), c_null_ptr, pf, G, GV, US)
+    allocate(G%mask2dCu(ni_mem, nj_mem), G%mask2dCv(ni_mem, nj_mem), G%IareaT(ni_mem, nj_mem), G%Domain)
+    G%mask2dCu(:,:) = masks(:,:,2) ; G%mask2dCv(:,:) = masks(:,:,3) ; G%IareaT(:,:) = masks(:,:,4) ; G%ke = nk
+    GV%g_Earth = vgx(1) ; GV%H_to_pa = vgx(2) ; GV%semi_Boussinesq = .false.
+    call EOS_init(pf, eqn, US)
+    allocate(diabatic_CSp) ; CS => NULL()
+    used = neutral_diffusion_init(Time, G, GV, US, pf, diag, eqn, diabatic_CSp, CS)
+    if (.not.used) standin_fatal_count = standin_fatal_count + 1      ! USE_NEUTRAL_DIFFUSION is part of every table
+    if (standin_fatal_count == 0 .and. dt > 0.0) then
+      allocate(Reg) ; allocate(Reg%Tr(ntr)) ; Reg%ntr = ntr
+      do m = 1, ntr
+        Reg%Tr(m)%t => tracers(:,:,:,m) ; Reg%Tr(m)%conc_underflow = conc_underflow(m)
+        write(tag, '(i0)') m
+        Reg%Tr(m)%id_dfxy_cont = register_diag_field("ocean_model", "dfxy_cont_"//trim(tag), axes, Time)
+        Reg%Tr(m)%id_dfx_2d = register_diag_field("ocean_model", "dfx_2d_"//trim(tag), axes, Time)
+        Reg%Tr(m)%id_dfy_2d = register_diag_field("ocean_model", "dfy_2d_"//trim(tag), axes, Time)
+      enddo
+      allocate(Coef_x(ni_mem, nj_mem, nk+1), Coef_y(ni_mem, nj_mem, nk+1))
+      Coef_x(:,:,:) = ieee_value(dt, ieee_quiet_nan) ; Coef_y(:,:,:) = ieee_value(dt, ieee_quiet_nan)
+      Coef_x(:,:,1) = Coef_x1(:,:) ; Coef_y(:,:,1) = Coef_y1(:,:)
+      p_ps => NULL()
+      if (c_associated(p_surf)) call c_f_pointer(p_surf, p_ps, (/ int(ni_mem), int(nj_mem), int(ncalls) /))
+      do r = 1, ncalls
+        if (associated(p_ps)) then
+          call neutral_diffusion_calc_coeffs(G, GV, US, h(:,:,:,r), T(:,:,:,r), S(:,:,:,r), visc, CS, p_surf=p_ps(:,:,r))
+        else
+          call neutral_diffusion_calc_coeffs(G, GV, US, h(:,:,:,r), T(:,:,:,r), S(:,:,:,r), visc, CS)
+        endif
+        call neutral_diffusion(G, GV, h(:,:,:,r), Coef_x, Coef_y, dt, Reg, US, CS)
+      enddo
+      deallocate(Reg%Tr) ; deallocate(Reg)
+    endif
+    call neutral_diffusion_end(CS)
+    deallocate(diabatic_CSp) ; deallocate(G%Domain)
+    call unit_scaling_end(US)
+    ref_neutral_diffusion = standin_fatal_count
   end function
 end module ref_param_shim

@@ -1,6 +1,7 @@
 !> oracle/ref_standins.F90 -- ORACLE SUPPORT (test infrastructure only), not product and not reference text.
 !!
-!! The reference's parameterization modules (MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90) `use` framework modules
+!! The reference's parameterization modules (MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90,
+!! MOM_neutral_diffusion.F90) `use` framework modules
 !! that need FMS and netCDF.  oracle/Makefile compiles those files, and every framework file that does compile on its own (the
 !! equation-of-state dispatcher MOM_EOS.F90 with every module it uses among them), where they lie, against
 !! the interface-only stand-ins below.  The rule is that of tests/fortran_stubs/mom_stubs.F90: each module carries the name of the
@@ -16,18 +17,25 @@
 !!   * gsw_mod_toolbox (the TEOS-10 toolbox, a package the reference links to and does not hold) has the ten procedures that
 !!     MOM_EOS_TEOS10.F90 and MOM_TFreeze.F90 name, which answer NaN: with it those two files and MOM_EOS.F90 compile from their own
 !!     text.  No compared case selects TEOS10 or a TEOS10 freezing point, so none of the ten is ever called.
+!!   * a procedure that no compared path may reach (pass_var, the procedures of MOM_remapping, MOM_hor_bnd_diffusion,
+!!     MOM_CVMix_KPP and MOM_diabatic_driver, which MOM_neutral_diffusion.F90 names on its discontinuous, interior-only and
+!!     vertical-structure paths) calls standin_never: a FATAL, counted apart in standin_never_count.
 !! Stood in for: MOM_error_handler, MOM_coms, MOM_cpu_clock, MOM_time_manager, MOM_hor_index, MOM_domains, MOM_grid,
 !! MOM_verticalGrid, MOM_file_parser, MOM_io (stdout and stderr), gsw_mod_toolbox, MOM_variables, MOM_forcing_type,
-!! MOM_diag_mediator, MOM_debugging, MOM_interface_heights, MOM_wave_interface, MOM_stochastics.  MOM_EOS is no longer among them.
-!! The file is compiled twice: what needs neither a unit_scale_type nor an EOS_type before the reference's own
-!! MOM_unit_scaling.F90 and equation-of-state files, and MOM_variables (whose thermo_var_ptrs holds an EOS_type),
-!! MOM_interface_heights and MOM_wave_interface after them, with -DSTANDINS_AFTER_UNIT_SCALING.
+!! MOM_diag_mediator, MOM_debugging, MOM_interface_heights, MOM_wave_interface, MOM_stochastics, MOM_remapping,
+!! MOM_tracer_registry, MOM_hor_bnd_diffusion, MOM_CVMix_KPP, MOM_diabatic_driver.  MOM_EOS is no longer among them.
+!! The file is compiled three times: what needs neither a unit_scale_type nor an EOS_type before the reference's own
+!! MOM_unit_scaling.F90 and equation-of-state files; MOM_variables (whose thermo_var_ptrs holds an EOS_type),
+!! MOM_interface_heights, MOM_wave_interface and MOM_CVMix_KPP after them, with -DSTANDINS_AFTER_UNIT_SCALING; and
+!! MOM_diabatic_driver (whose extract_diabatic_member names an energetic_PBL_CS) after the reference's MOM_energetic_PBL.F90,
+!! with -DSTANDINS_AFTER_ENERGETIC_PBL as well.
 #ifndef STANDINS_AFTER_UNIT_SCALING
 
 module MOM_error_handler
   implicit none ; public
   integer, parameter :: NOTE = 0, WARNING = 1, FATAL = 2
   integer :: standin_fatal_count = 0     !< FATAL messages since the door last cleared it
+  integer :: standin_never_count = 0     !< of those, the ones a stand-in procedure that must never run has raised
   logical :: standin_print_warnings = .false.
 contains
   subroutine MOM_error(level, message, all_print)
@@ -45,6 +53,13 @@ contains
   logical function is_root_pe()
     is_root_pe = .true.
   end function is_root_pe
+  !> What a stand-in procedure that must never run calls: it counts as a FATAL, and is counted apart, so that a door can tell a
+  !! stop of the reference's own from a path that leads out of the compiled files.
+  subroutine standin_never(who)
+    character(len=*), intent(in) :: who
+    standin_never_count = standin_never_count + 1
+    call MOM_error(FATAL, "the stand-in "//trim(who)//" has been called: this path leaves the compiled reference files")
+  end subroutine standin_never
 end module MOM_error_handler
 
 module MOM_coms
@@ -104,10 +119,26 @@ module MOM_hor_index
 end module MOM_hor_index
 
 module MOM_domains
+  use MOM_error_handler, only : standin_never
   implicit none ; public
   type :: MOM_domain_type ; integer :: dummy = 0 ; end type MOM_domain_type
   type :: group_pass_type ; integer :: dummy = 0 ; end type group_pass_type
+  interface pass_var
+    module procedure pass_var_2d, pass_var_3d
+  end interface
 contains
+  !> Never reached: MOM_neutral_diffusion passes the boundary-layer depth (NDIFF_INTERIOR_ONLY) and Coef_h (KHTR_USE_EBT_STRUCT),
+  !! both of which the device refuses.
+  subroutine pass_var_2d(array, MOM_dom, sideflag, complete, position, halo, inner_halo, clock)
+    real, dimension(:,:), intent(inout) :: array ; type(MOM_domain_type), intent(inout) :: MOM_dom
+    integer, optional, intent(in) :: sideflag, position, halo, inner_halo, clock ; logical, optional, intent(in) :: complete
+    call standin_never("pass_var (2-D)")
+  end subroutine pass_var_2d
+  subroutine pass_var_3d(array, MOM_dom, sideflag, complete, position, halo, inner_halo, clock)
+    real, dimension(:,:,:), intent(inout) :: array ; type(MOM_domain_type), intent(inout) :: MOM_dom
+    integer, optional, intent(in) :: sideflag, position, halo, inner_halo, clock ; logical, optional, intent(in) :: complete
+    call standin_never("pass_var (3-D)")
+  end subroutine pass_var_3d
   subroutine create_group_pass(group, array, MOM_dom)
     type(group_pass_type), intent(inout) :: group ; real, dimension(:,:), intent(inout) :: array
     type(MOM_domain_type), intent(inout) :: MOM_dom
@@ -119,11 +150,13 @@ end module MOM_domains
 
 module MOM_grid
   use MOM_hor_index, only : hor_index_type
+  use MOM_domains, only : MOM_domain_type
   implicit none ; public
   type :: ocean_grid_type
     type(hor_index_type) :: HI
-    integer :: isc, iec, jsc, jec, isd, ied, jsd, jed, IscB, IecB, JscB, JecB, IsdB, IedB, JsdB, JedB
-    real, allocatable, dimension(:,:) :: mask2dT, CoriolisBu, geoLonT, geoLatT, Coriolis2Bu, mask2dCu, mask2dCv, mask2dBu
+    type(MOM_domain_type), pointer :: Domain => NULL()
+    integer :: isc, iec, jsc, jec, isd, ied, jsd, jed, IscB, IecB, JscB, JecB, IsdB, IedB, JsdB, JedB, ke
+    real, allocatable, dimension(:,:) :: mask2dT, CoriolisBu, geoLonT, geoLatT, Coriolis2Bu, mask2dCu, mask2dCv, mask2dBu, IareaT
   end type ocean_grid_type
 end module MOM_grid
 
@@ -134,7 +167,7 @@ module MOM_verticalGrid
     logical :: Boussinesq = .true., semi_Boussinesq = .false.
     real :: Rho0, g_Earth, g_Earth_Z_T2, Angstrom_H, Angstrom_Z, H_subroundoff, dZ_subroundoff
     real :: H_to_Z = 1., Z_to_H = 1., H_to_RZ, RZ_to_H, H_to_m = 1., m_to_H = 1., H_to_MKS = 1., HZ_T_to_m2_s = 1.
-    real :: m2_s_to_HZ_T = 1., HZ_T_to_MKS = 1.
+    real :: m2_s_to_HZ_T = 1., HZ_T_to_MKS = 1., H_to_pa = 1., kg_m2_to_H = 1.
     real, allocatable, dimension(:) :: Rlay
   end type verticalGrid_type
 end module MOM_verticalGrid
@@ -448,7 +481,88 @@ module MOM_stochastics
   end type stochastic_CS
 end module MOM_stochastics
 
-#else
+
+module MOM_remapping
+  use MOM_error_handler, only : standin_never
+  implicit none ; private
+  public :: remapping_CS, initialize_remapping, extract_member_remapping_CS, build_reconstructions_1d, average_value_ppoly
+  public :: remappingSchemesDoc, remappingDefaultScheme
+  type :: remapping_CS ; integer :: degree = 0 ; end type remapping_CS
+  character(len=*), parameter :: remappingSchemesDoc = "(MOM_remapping is stood in for: no scheme is known here)"
+  character(len=*), parameter :: remappingDefaultScheme = "STOOD_IN_FOR"
+contains
+  !> Never reached by a compared case: only the discontinuous reconstruction (NDIFF_CONTINUOUS false, which the device refuses)
+  !! sets up and uses a remapping control structure.
+  subroutine initialize_remapping(CS, remapping_scheme, boundary_extrapolation, check_reconstruction, check_remapping, &
+        force_bounds_in_subcell, force_bounds_in_target, better_force_bounds_in_target, offset_tgt_summation, &
+        om4_remap_via_sub_cells, answers_2018, answer_date, nk, h_neglect, h_neglect_edge)
+    type(remapping_CS), intent(inout) :: CS ; character(len=*), intent(in) :: remapping_scheme
+    logical, optional, intent(in) :: boundary_extrapolation, check_reconstruction, check_remapping, force_bounds_in_subcell, &
+                                     force_bounds_in_target, better_force_bounds_in_target, offset_tgt_summation, &
+                                     om4_remap_via_sub_cells, answers_2018
+    integer, optional, intent(in) :: answer_date, nk ; real, optional, intent(in) :: h_neglect, h_neglect_edge
+    call standin_never("initialize_remapping")
+  end subroutine initialize_remapping
+  subroutine extract_member_remapping_CS(CS, remapping_scheme, degree, boundary_extrapolation, check_reconstruction, &
+        check_remapping, force_bounds_in_subcell, force_bounds_in_target, better_force_bounds_in_target, offset_tgt_summation)
+    type(remapping_CS), intent(in) :: CS ; integer, optional, intent(out) :: remapping_scheme, degree
+    logical, optional, intent(out) :: boundary_extrapolation, check_reconstruction, check_remapping, force_bounds_in_subcell, &
+                                      force_bounds_in_target, better_force_bounds_in_target, offset_tgt_summation
+    if (present(remapping_scheme)) remapping_scheme = 0
+    if (present(degree)) degree = CS%degree
+    if (present(boundary_extrapolation)) boundary_extrapolation = .false.
+    if (present(check_reconstruction)) check_reconstruction = .false.
+    if (present(check_remapping)) check_remapping = .false.
+    if (present(force_bounds_in_subcell)) force_bounds_in_subcell = .false.
+    if (present(force_bounds_in_target)) force_bounds_in_target = .false.
+    if (present(better_force_bounds_in_target)) better_force_bounds_in_target = .false.
+    if (present(offset_tgt_summation)) offset_tgt_summation = .false.
+    call standin_never("extract_member_remapping_CS")
+  end subroutine extract_member_remapping_CS
+  subroutine build_reconstructions_1d(CS, n0, h0, u0, ppoly_r_coefs, ppoly_r_E, ppoly_r_S, iMethod, h_neglect, h_neglect_edge, &
+                                      PCM_cell, debug)
+    type(remapping_CS), intent(in) :: CS ; integer, intent(in) :: n0 ; real, dimension(n0), intent(in) :: h0, u0
+    real, dimension(:,:), intent(out) :: ppoly_r_coefs ; real, dimension(n0,2), intent(out) :: ppoly_r_E, ppoly_r_S
+    integer, intent(out) :: iMethod ; real, intent(in) :: h_neglect ; real, optional, intent(in) :: h_neglect_edge
+    logical, optional, intent(in) :: PCM_cell(n0), debug
+    ppoly_r_coefs(:,:) = 0.0 ; ppoly_r_E(:,:) = 0.0 ; ppoly_r_S(:,:) = 0.0 ; iMethod = 0
+    call standin_never("build_reconstructions_1d")
+  end subroutine build_reconstructions_1d
+  real function average_value_ppoly(n0, u0, ppoly0_E, ppoly0_coefs, method, i0, xa, xb)
+    integer, intent(in) :: n0, method, i0 ; real, intent(in) :: u0(n0), ppoly0_E(n0,2), ppoly0_coefs(:,:), xa, xb
+    average_value_ppoly = 0.0
+    call standin_never("average_value_ppoly")
+  end function average_value_ppoly
+end module MOM_remapping
+
+module MOM_tracer_registry
+  implicit none ; public
+  type :: tracer_type
+    real, dimension(:,:,:), pointer :: t => NULL()
+    real :: conc_underflow = 0.0
+    integer :: id_dfxy_conc = -1, id_dfxy_cont = -1, id_dfxy_cont_2d = -1, id_dfx_2d = -1, id_dfy_2d = -1
+  end type tracer_type
+  type :: tracer_registry_type
+    integer :: ntr = 0
+    type(tracer_type), allocatable :: Tr(:)
+  end type tracer_registry_type
+end module MOM_tracer_registry
+
+module MOM_hor_bnd_diffusion
+  use MOM_error_handler, only : standin_never
+  implicit none ; public
+  integer, parameter :: SURFACE = 1, BOTTOM = 2      ! (two distinct values: the stand-in tells nothing by them)
+contains
+  !> Never reached: only NDIFF_INTERIOR_ONLY and NDIFF_TAPERING, which the device refuses, look for the boundary layer's layers.
+  subroutine boundary_k_range(boundary, nk, h, hbl, k_top, zeta_top, k_bot, zeta_bot)
+    integer, intent(in) :: boundary, nk ; real, dimension(nk), intent(in) :: h ; real, intent(in) :: hbl
+    integer, intent(out) :: k_top, k_bot ; real, intent(out) :: zeta_top, zeta_bot
+    k_top = 1 ; k_bot = 1 ; zeta_top = 0.0 ; zeta_bot = 0.0
+    call standin_never("boundary_k_range")
+  end subroutine boundary_k_range
+end module MOM_hor_bnd_diffusion
+
+#elif !defined(STANDINS_AFTER_ENERGETIC_PBL)
 
 module MOM_variables
   use MOM_EOS, only : EOS_type
@@ -460,6 +574,7 @@ module MOM_variables
   end type thermo_var_ptrs
   type :: vertvisc_type
     real, allocatable, dimension(:,:) :: ustar_BBL, BBL_meanKE_loss, BBL_meanKE_loss_sqrtCd
+    real, pointer, dimension(:,:) :: h_ML => NULL()
   end type vertvisc_type
 end module MOM_variables
 
@@ -513,4 +628,39 @@ contains
     LA = 0.0
   end subroutine get_Langmuir_Number
 end module MOM_wave_interface
+
+module MOM_CVMix_KPP
+  use MOM_error_handler, only : standin_never
+  use MOM_grid, only : ocean_grid_type
+  use MOM_unit_scaling, only : unit_scale_type
+  implicit none ; public
+  type :: KPP_CS ; integer :: dummy = 0 ; end type KPP_CS
+contains
+  !> Never reached: MOM_neutral_diffusion imports the name and does not call it.
+  subroutine KPP_get_BLD(CS, BLD, G, US, m_to_BLD_units)
+    type(KPP_CS), pointer :: CS ; type(ocean_grid_type), intent(in) :: G ; type(unit_scale_type), intent(in) :: US
+    real, dimension(G%isd:G%ied,G%jsd:G%jed), intent(inout) :: BLD ; real, optional, intent(in) :: m_to_BLD_units
+    call standin_never("KPP_get_BLD")
+  end subroutine KPP_get_BLD
+end module MOM_CVMix_KPP
+
+#else
+
+module MOM_diabatic_driver
+  use MOM_error_handler, only : standin_never
+  use MOM_CVMix_KPP, only : KPP_CS
+  use MOM_energetic_PBL, only : energetic_PBL_CS
+  implicit none ; public
+  type :: diabatic_CS ; integer :: dummy = 0 ; end type diabatic_CS
+contains
+  !> Never reached by a compared case: neutral_diffusion_init asks for the boundary-layer schemes only with NDIFF_INTERIOR_ONLY,
+  !! which the device refuses.  Both pointers come back null.
+  subroutine extract_diabatic_member(CS, KPP_CSp, energetic_PBL_CSp)
+    type(diabatic_CS), target, intent(in) :: CS
+    type(KPP_CS), optional, pointer :: KPP_CSp ; type(energetic_PBL_CS), optional, pointer :: energetic_PBL_CSp
+    if (present(KPP_CSp)) KPP_CSp => NULL()
+    if (present(energetic_PBL_CSp)) energetic_PBL_CSp => NULL()
+    call standin_never("extract_diabatic_member")
+  end subroutine extract_diabatic_member
+end module MOM_diabatic_driver
 #endif

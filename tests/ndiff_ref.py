@@ -10,7 +10,8 @@ the pitched tile layout of include/mom6x.h ([k, j + joff, i + ioff]).  Density d
 (oracle/orc.py eos_density_derivs), one point at a time, inside calculate_density_derivs_1d's unit conversions
 (MOM_EOS.F90:809-827).  `counts` records how often each arm was taken.
 
-The Fortran module is not compiled into the oracle library, so tests/test_neutral_diffusion_cpu.py first holds this module to
+tests/test_ref_parity_cpu.py holds this module bit for bit to the reference's own compiled MOM_neutral_diffusion.F90 (tracers,
+tendencies and transports; the coefficient arrays are private to the compiled module), and tests/test_neutral_diffusion_cpu.py to
 facts that do not come from it."""
 import math
 
@@ -737,6 +738,8 @@ CASES = {
     "ties": (dict(), dict(kind="ties")),
     "massless": (dict(), dict(kind="massless")),
     "refp": (dict(ref_pres=2.0e7), dict(eos=abi.LINEAR)),
+    # (the linear equation of state's derivatives are constants: only under Wright's does it matter WHICH pressure they are taken at)
+    "refp_wright": (dict(ref_pres=2.0e7), dict()),
     "psurf": (dict(), dict(p_surf=True)),
     "new_order": (dict(ndiff_answer_date=20240401), dict()),
     "underflow": (dict(), dict(uf=(0.0, 1.9, 0.0))),

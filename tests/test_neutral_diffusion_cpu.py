@@ -1,6 +1,10 @@
 """What pins tests/ndiff_ref.py, the checker of mom6x_neutral_diffusion_calc_coeffs, mom6x_neutral_diffusion and
-mom6x_tracer_hordiff_neutral, without a GPU.  The restatement and the kernels come from one reading of MOM_neutral_diffusion.F90,
-and the Fortran module is not compiled into the oracle library, so the checks here stand on something else: the reference's
+mom6x_tracer_hordiff_neutral, without a GPU.  The restatement and the kernels come from one reading of MOM_neutral_diffusion.F90.
+That reading is held to the Fortran itself elsewhere: tests/test_ref_parity_cpu.py compares the restatement bit for bit with the
+reference's own compiled module (oracle/_ref/libref_param.so, where it is built) and with results recorded from it
+(tests/golden/ref_ndiff_*.npz, always), through the tracers, tendencies and transports; the coefficient arrays, which the compiled
+module keeps private, the neutral branch of tracer_hordiff (MOM_tracer_hor_diff.F90 is not compiled) and the discontinuous
+reconstruction stay outside that comparison.  The checks here need no compiled reference and stand on something else: the reference's
 dimensional test (Z, L, T, H, R, C and S each rescaled by 2**11 leave the unscaled bits), the transposed grid with the
 rotationally symmetric order of additions, a uniform tracer, the tracer content, invariants of the positions, the arms the case
 table reaches on the grids of the GPU tests, two floors on how much of the `slope` case really slopes and diffuses, and the struct
@@ -130,6 +134,29 @@ RESCALE_SETS = [tuple(2.0 ** 11 if n == m else 1.0 for n in range(7)) for m in r
                [(2.0 ** 11, 2.0 ** 5, 2.0 ** -7, 2.0 ** 9, 2.0 ** 3, 2.0 ** -4, 2.0 ** 6)]
 
 
+def rescaled(sc, d, M, GV, P, inp):
+    """A case with Z, L, T, H, R, C and S rescaled by the factors `sc`: (metrics, vertical grid, parameters, inputs, Coef_x and
+    Coef_y, dt, f), f giving the factor of a unit from its seven powers (tests/test_ref_parity_cpu.py rescales the compiled
+    reference the same way)."""
+    f = lambda pw: float(np.prod([s ** p for s, p in zip(sc, pw)]))                    # noqa: E731
+    L, T_ = sc[1], sc[2]
+    GV2 = abi.vgrid_default()
+    for n, pw in _DIM_GV.items():
+        setattr(GV2, n, getattr(GV, n) * f(pw))
+    P2 = abi.NeutralDiffusionParams.from_buffer_copy(P)
+    for n, pw in _DIM_P.items():
+        setattr(P2, n, getattr(P, n) * f(pw))
+    M2 = M.copy()
+    for n in abi.METRICS:
+        if n.startswith(("dx", "dy")): M2[G[n]] = M[G[n]] * L
+        elif n.startswith(("Idx", "Idy")): M2[G[n]] = M[G[n]] / L
+        elif n.startswith("area"): M2[G[n]] = M[G[n]] * L * L
+        elif n.startswith("Iarea"): M2[G[n]] = M[G[n]] / (L * L)
+    inp2 = {n: (a * f(_DIM_IN[n]) if n in _DIM_IN else a) for n, a in inp.items()}
+    coef = tuple(a * (L * L) for a in R.coef_planes(d, M))
+    return M2, GV2, P2, inp2, coef, R.DT * T_, f
+
+
 @pytest.mark.parametrize("name", ("slope", "refp", "psurf", "massless"))
 def test_dimensional_rescaling(name):
     """The reference's test.dim: Z, L, T, H, R, C and S rescaled by 2**11, one at a time and all at once with unequal powers.
@@ -138,23 +165,8 @@ def test_dimensional_rescaling(name):
     unscaled run's.  A unit factor in the wrong place (pa_to_H :382, the pressure handed to the equation of state, Idt) breaks it."""
     d, M, GV, P, opt, inp, want, _ = R.want("island_basin", 4, name)
     for sc in RESCALE_SETS:
-        f = lambda pw: float(np.prod([s ** p for s, p in zip(sc, pw)]))                    # noqa: E731
-        L, T_ = sc[1], sc[2]
-        GV2 = abi.vgrid_default()
-        for n, pw in _DIM_GV.items():
-            setattr(GV2, n, getattr(GV, n) * f(pw))
-        P2 = abi.NeutralDiffusionParams.from_buffer_copy(P)
-        for n, pw in _DIM_P.items():
-            setattr(P2, n, getattr(P, n) * f(pw))
-        M2 = M.copy()
-        for n in abi.METRICS:
-            if n.startswith(("dx", "dy")): M2[G[n]] = M[G[n]] * L
-            elif n.startswith(("Idx", "Idy")): M2[G[n]] = M[G[n]] / L
-            elif n.startswith("area"): M2[G[n]] = M[G[n]] * L * L
-            elif n.startswith("Iarea"): M2[G[n]] = M[G[n]] / (L * L)
-        inp2 = {n: (a * f(_DIM_IN[n]) if n in _DIM_IN else a) for n, a in inp.items()}
-        coef = tuple(a * (L * L) for a in R.coef_planes(d, M))
-        got, _ = R.run(d, M2, GV2, P2, opt, inp2, dt=R.DT * T_, coef=coef)
+        M2, GV2, P2, inp2, coef, dt2, f = rescaled(sc, d, M, GV, P, inp)
+        got, _ = R.run(d, M2, GV2, P2, opt, inp2, dt=dt2, coef=coef)
         for n in R.COEFFS:
             a = got[n] / f(_DIM_OUT["hEff"]) if n.endswith("hEff") else got[n]
             _bits(a, want[n], f"{name}: {n} rescaled by Z, L, T, H, R, C, S = {sc}")

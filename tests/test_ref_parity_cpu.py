@@ -1,15 +1,19 @@
 """The python restatements under tests/ held to the reference's own compiled code (oracle/_ref/libref_param.so: MOM_EOS_Wright*.F90,
-MOM_EOS_linear.F90, MOM_intrinsic_functions.F90, MOM_opacity.F90, MOM_energetic_PBL.F90 and MOM_kappa_shear.F90 with MOM_EOS.F90,
-built where they lie against interface stand-ins, see oracle/Makefile and tests/ref_param.py).  The restatements were written from the same reading of the Fortran as the
+MOM_EOS_linear.F90, MOM_intrinsic_functions.F90, MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90 and
+MOM_neutral_diffusion.F90 with MOM_EOS.F90, built where they lie against interface stand-ins, see oracle/Makefile and tests/ref_param.py).  The restatements were written from the same reading of the Fortran as the
 kernels they check, so a misread line sits in both; these tests are what involves the reference's code itself.
 
 Classes.  EXACT: whole arrays bit for bit on the computational domain.  TOLERANCE: the sites whose value goes through an
 intrinsic that two builds may round differently (tanh in opac_diag, pow and log10 of smooth chlorophyll, exp, log and pow of the
 libm cases of ePBL), held to the project's bound of 1e-12 of each field's range.  No site had to move from the first class to
 the second (see CHANGELOG.md).  MOM_kappa_shear has no second class: its arithmetic is + - * / and sqrt, and every word is EXACT.
+Nor has MOM_neutral_diffusion: + - * / and compares around Wright's and the linear equation of state.  Of it the compiled module
+hands out the tracers, their content tendencies and the two transports; its coefficient arrays (PoL, PoR, KoL, KoR, hEff) are
+private and are held through those and through two probing tracers.  Outside the comparison stay the neutral branch of
+tracer_hordiff (MOM_tracer_hor_diff.F90 is not compiled), the coefficient arrays themselves and the discontinuous reconstruction.
 
 Without oracle/_ref every test that runs a door skips; the comparison of the restatements with the recorded results
-(tests/golden/ref_opacity_*.npz, ref_epbl_*.npz, ref_kshear_*.npz) never skips."""
+(tests/golden/ref_opacity_*.npz, ref_epbl_*.npz, ref_kshear_*.npz, ref_ndiff_*.npz) never skips."""
 import functools
 import json
 import os
@@ -22,6 +26,7 @@ from tests import bflux_ref as B
 from tests import epbl_ref as E
 from tests import helpers as H
 from tests import kappa_shear_ref as K
+from tests import ndiff_ref as N
 from tests import opacity_ref as R
 from tests import ref_param as RP
 from tests.test_kappa_shear_cpu import CONFIGS as KSHEAR_GRIDS, REQUIRED as KSHEAR_REQUIRED, RESCALE_SETS, _DIM_OUT, rescaled
@@ -465,6 +470,244 @@ def test_kappa_shear_init_refusals_against_the_references():
     assert fatal >= 1 and got is None
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# MOM_neutral_diffusion
+
+NDIFF_RUNS = tuple((grid, nk, (), tuple(N.CASES)) for grid, nk in N.CONFIGS) + (
+    ("benchmark_small", 75, (("ni", 20), ("nj", 12)), ("slope",)),
+    ("torus", 3, tuple(zip(("ni", "nj"), RP.edge_torus_shape())), ("slope", "new_order")))
+NDIFF_PROBED = ("slope", "ties", "massless")
+# What the compiled neutral_diffusion_init does with each setting that mom6x_neutral_diffusion_init refuses (include/mom6x.h):
+# setting -> (members of the parameters, FATALs of the reference's own, calls of stood-in procedures, in words)
+NDIFF_REFUSALS = {
+    "NDIFF_CONTINUOUS": (dict(continuous_reconstruction=0), 0, 2,
+                         "accepts: no FATAL and no WARNING; goes on into initialize_remapping and extract_member_remapping_CS (:248-251)"),
+    "NDIFF_INTERIOR_ONLY": (dict(interior_only=1), 1, 2,
+                            "accepts the setting; asks the diabatic driver for KPP and ePBL (:294-295) and is FATAL where neither is there (:297)"),
+    "NDIFF_TAPERING": (dict(tapering=1), 0, 0, "ignores it: NDIFF_TAPERING is read only under NDIFF_INTERIOR_ONLY (:195-200)"),
+    "KHTR_USE_EBT_STRUCT": (dict(KhTh_use_vert_struct=1), 0, 0, "accepts: no FATAL and no WARNING (Coef_h is allocated, :306-308)"),
+    "NDIFF_USE_UNMASKED_TRANSPORT_BUG": (dict(use_unmasked_transport_bug=1), 0, 0, "accepts: no FATAL and no WARNING"),
+}
+
+
+def _compare_ndiff(tag, d, want, got, names=RP.NDIFF_OUT):
+    """The tracers and tendencies on the computational domain, trans_x_2d and trans_y_2d on their face ranges (the ranges of
+    tests/test_neutral_diffusion_gpu.py's _check), bit for bit.  Not held here: the ten coefficient arrays of
+    RP.NDIFF_NOT_EXPOSED, which the compiled module keeps private."""
+    rng = RP.ndiff_ranges(d)
+    assert set(got) == set(RP.NDIFF_OUT) and set(RP.NDIFF_NOT_EXPOSED) == set(N.COEFFS) <= set(want), (sorted(got), sorted(want))
+    for n in names:
+        assert len(got[n]) == len(want[n]), (tag, n)
+        for m, (a, b) in enumerate(zip(got[n], want[n])):
+            sl = (Ellipsis,) + rng[n]
+            assert np.isfinite(b[sl]).all(), (tag, n, m)
+            H.assert_bitwise(np.ascontiguousarray(a[sl]), np.ascontiguousarray(b[sl]), f"{tag}: {n}[{m}]")
+
+
+def _ndiff_tag(grid, nk, kw, name):
+    return "/".join([grid] + [str(v) for _, v in kw] + [str(nk), name])
+
+
+@functools.lru_cache(maxsize=None)
+def _ndiff_probed(name):
+    """A case on the island basin at 4 layers with a registry of T, S, the case's three tracers and two probes, and the
+    restatement's result and counters: computed once (read only)."""
+    d, M, GV, P, opt, inp = N.want("island_basin", 4, name)[:6]
+    nk = d.nk
+    rng = np.random.default_rng(23)
+    noise = 0.25 * rng.uniform(-1.0, 1.0, d.shape2())                       # the seeded column noise: below half a unit
+    index = np.stack([np.full(d.shape2(), k + 1.0) + noise for k in range(nk)])
+    zmid = np.cumsum(inp["h"], axis=0) - 0.5 * inp["h"]                       # (NaN where h is: beyond the first halo)
+    pmid = (GV.g_Earth * GV.H_to_RZ) * zmid
+    linear = (2.0 + rng.uniform(-1.0, 1.0, d.shape2())) + (1.0e-6 * (1.0 + rng.uniform(0.0, 1.0, d.shape2()))) * pmid
+    keep = np.isfinite(inp["h"][0])
+    inp = dict(inp, tracers=[inp["T"].copy(), inp["S"].copy()] + [t.copy() for t in inp["tracers"]] +
+               [np.where(keep, index, np.nan), np.where(keep, linear, np.nan)])
+    want, counts = N.run(d, M, GV, P, opt, inp)
+    return d, M, GV, P, opt, inp, want, counts
+
+
+def _ndiff_two_rounds():
+    """(d, M, GV, P, opt, first inputs, second inputs, the restatement's outputs after the second round, its counters): `slope`
+    on the island basin at 4 layers, then calc_coeffs from the thicknesses, T, S of `massless` and neutral_diffusion once more on
+    the tracers the first round left."""
+    d, M, GV, P, opt, inp, one, _ = N.want("island_basin", 4, "slope")
+    inp2 = N.want("island_basin", 4, "massless")[5]
+    counts = N.new_counts()
+    CS = N.calc_coeffs(d, M, GV, P, N.case_eos(opt), inp2["h"], inp2["T"], inp2["S"], None, counts=counts)
+    out = dict(tracers=[t.copy() for t in one["tracers"]], tendency=[np.full(d.shape3(), np.nan) for _ in range(3)],
+               trans_x_2d=[np.full(d.shape2(), np.nan) for _ in range(3)], trans_y_2d=[np.full(d.shape2(), np.nan) for _ in range(3)])
+    Cx, Cy = N.coef_planes(d, M)
+    N.neutral_diffusion(d, M, GV, P, CS, inp2["h"], Cx, Cy, N.DT, out["tracers"], None, out["tendency"], out["trans_x_2d"],
+                        out["trans_y_2d"], counts)
+    out.update({n: getattr(CS, n) for n in N.COEFFS})
+    return d, M, GV, P, opt, inp, inp2, out, counts
+
+
+def _ndiff_hordiff_rounds():
+    """Two iterations of the restatement's neutral branch of tracer_hordiff with RECALC_NEUTRAL_SURF on the bowl at 3 layers, T
+    and S outside the registry and no group pass (one closed tile has nothing to exchange): what it hands calc_coeffs and
+    neutral_diffusion in its two iterations is what the door's two rounds are handed.  Returns (d, M, GV, P, opt, inp, Coef_x and
+    Coef_y, dt of an iteration, the restatement's outputs, its counters)."""
+    from tests import hordiff_ref
+    d, M, GV, P, opt, inp = N.want("benchmark_small", 3, "slope")[:6]
+    Pthd = abi.tracer_hor_diff_params_default(KHTR=1.0, check_diffusive_CFL=1)
+    khx, khy = hordiff_ref.khdt_faces(d, M, Pthd, N.DT, {})
+    Pthd.KhTr = 1.5 / float(hordiff_ref.cell_cfl(d, M, khx, khy).max())
+    P2 = abi.NeutralDiffusionParams.from_buffer_copy(P); P2.recalc_neutral_surf = 1
+    out = dict(tracers=[t.copy() for t in inp["tracers"]], tendency=[np.full(d.shape3(), np.nan) for _ in range(3)],
+               trans_x_2d=[np.full(d.shape2(), np.nan) for _ in range(3)], trans_y_2d=[np.full(d.shape2(), np.nan) for _ in range(3)])
+    counts = N.new_counts()
+    rec = {}
+    n = N.tracer_hordiff_neutral(d, M, GV, Pthd, P2, N.case_eos(opt), inp["h"], N.DT, out["tracers"], inp["T"], inp["S"],
+                                 tendency=out["tendency"], trans_x_2d=out["trans_x_2d"], trans_y_2d=out["trans_y_2d"], counts=counts,
+                                 pass_fn=lambda a: None, record=rec)
+    assert n == 2 and rec["calc_coeffs"] == 2 and counts["recalc"] == 1 and counts["itt_gt1"] == 1
+    khx, khy = hordiff_ref.khdt_faces(d, M, Pthd, N.DT, {})
+    io, jo, ni, nj = d.ioff, d.joff, d.ni, d.nj
+    Cx = np.full(d.shape3(d.nk + 1), np.nan); Cy = np.full(d.shape3(d.nk + 1), np.nan)
+    Cx[0, jo:jo + nj, io - 1:io + ni] = 0.5 * khx; Cy[0, jo - 1:jo + nj, io:io + ni] = 0.5 * khy
+    out.update({c: getattr(rec["CS"], c) for c in N.COEFFS})
+    return d, M, GV, P2, opt, inp, (Cx, Cy), 0.5 * N.DT, out, counts
+
+
+@pytest.mark.parametrize("grid,nk,kw,cases", NDIFF_RUNS, ids=[_ndiff_tag(g, n, kw, "") for g, n, kw, _ in NDIFF_RUNS])
+def test_neutral_diffusion_against_the_compiled_reference(grid, nk, kw, cases):
+    """tests/ndiff_ref.py against neutral_diffusion_calc_coeffs and neutral_diffusion of the reference's own
+    MOM_neutral_diffusion.F90, set up by its own neutral_diffusion_init, EOS_init (the array form of calculate_density_derivs with
+    its unit conversions, MOM_EOS.F90:781-829, is the reference's text) and unit_scaling_init: every case of ndiff_ref.CASES on the
+    bowl at 1, 2, 3, 4 and 8 layers and on the island basin at 4, `slope` at 20 x 12 x 75, `slope` and `new_order` on the land-free
+    torus one cell larger than a work-group, from the NaN-beyond-the-first-halo inputs of ndiff_ref.want.  Every tracer and its
+    content tendency on the computational domain and both transports on their face ranges, bit for bit; zero FATALs.  All words
+    are of the EXACT class: the path is + - * / and compares with Wright's and the linear equation of state, and no site of it goes
+    through an intrinsic that two builds may round differently (x**2 at :1209 is x * x).
+
+    Outside the comparison: PoL, PoR, KoL, KoR and hEff themselves (private components of neutral_diffusion_CS; id_uhEff_2d and
+    id_vhEff_2d are registered nowhere), held through what they produce and by the probing registry below; the neutral branch of
+    tracer_hordiff (MOM_tracer_hor_diff.F90 is not compiled); the discontinuous reconstruction (MOM_remapping is stood in for)."""
+    _need_lib()
+    for name in cases:
+        d, M, GV, P, opt, inp, want, counts = N.want(grid, nk, name, **dict(kw))
+        got, fatal = RP.neutral_diffusion(d, M, GV, P, opt, inp)
+        assert fatal == 0, (grid, nk, name, fatal)
+        _compare_ndiff(_ndiff_tag(grid, nk, kw, name), d, want, got)
+
+
+@pytest.mark.parametrize("name", NDIFF_PROBED)
+def test_neutral_diffusion_with_a_probing_registry(name):
+    """`slope`, `ties` and `massless` once more on the island basin at 4 layers with a registry of seven: T, S, the case's three
+    tracers and two probes.  The probes stand in for the coefficient arrays the compiled reference hides: one equals its layer's
+    index plus a seeded noise per column of less than half a unit, so that a KoL or KoR taken one interface off moves its flux
+    by a whole unit; the other is linear in pressure within each column, so that its interface values and sublayer means follow
+    PoL and PoR.  Both must move for the comparison to mean anything, which is asserted from the restatement first."""
+    d, M, GV, P, opt, inp, want, counts = _ndiff_probed(name)
+    assert len(inp["tracers"]) == 7 and counts["flux_down"] > 0
+    own = (slice(None),) + H.interior(d, "h")
+    for m in (5, 6):
+        assert (want["tendency"][m][own] != 0.0).sum() > 0.1 * want["tendency"][m][own].size, (name, m)
+    _need_lib()
+    got, fatal = RP.neutral_diffusion(d, M, GV, P, opt, inp)
+    assert fatal == 0
+    _compare_ndiff(f"{name} with probes", d, want, got)
+
+
+@pytest.mark.parametrize("name", ("slope", "refp", "refp_wright"))
+def test_neutral_diffusion_rescaled_through_the_references_unit_scaling_init(name):
+    """`slope`, and `refp` and `refp_wright` (the reference pressure under the linear and under Wright's equation of state) with
+    a surface pressure, with Z, L, T, H, R, C and S rescaled by 2**11 one at a time and all at once
+    with unequal powers (the sets of tests/test_neutral_diffusion_cpu.py).  The *_RESCALE_POWERs go through the reference's own
+    unit_scaling_init, NDIFF_REF_PRES through the `scale=` of its neutral_diffusion_init and the equation of state through the
+    factors its EOS_init takes from US; the vertical grid's members (GV is a stand-in: MOM_verticalGrid.F90 is not compiled) are
+    the rescaled grid's.  After unscaling, every word is the unscaled door's, and the rescaled restatement equals the rescaled
+    reference: where the restatement puts its unit factors is held to the compiled module and not to itself."""
+    _need_lib()
+    from tests.test_neutral_diffusion_cpu import RESCALE_SETS, _DIM_OUT, rescaled
+    d, M, GV, P, opt, inp = N.want("island_basin", 4, name)[:6]
+    if name.startswith("refp"):
+        opt = dict(opt, p_surf=True)
+        inp = N.nan_halo(d, N.case_inputs(d, M, GV, opt))
+        assert "p_surf" in inp and P.ref_pres > 0.0
+    want, _ = N.run(d, M, GV, P, opt, inp)
+    base, fatal = RP.neutral_diffusion(d, M, GV, P, opt, inp)
+    assert fatal == 0
+    _compare_ndiff(f"{name} unscaled", d, want, base)
+    rng = RP.ndiff_ranges(d)
+    for sc in RESCALE_SETS:
+        M2, GV2, P2, inp2, coef, dt2, f = rescaled(sc, d, M, GV, P, inp)
+        powers = {u: -RP._power_of_two(s, u) for u, s in zip("ZLTHRCS", sc) if u != "H"}      # US%x_to_m = 1 / sc: the power is -11
+        got, fatal = RP.neutral_diffusion(d, M2, GV2, P2, opt, inp2, powers=powers, dt=dt2, coef=coef)
+        assert fatal == 0, (name, sc)
+        mine, _ = N.run(d, M2, GV2, P2, opt, inp2, dt=dt2, coef=coef)
+        _compare_ndiff(f"{name} rescaled by Z, L, T, H, R, C, S = {sc}", d, mine, got)
+        for n in RP.NDIFF_OUT:
+            for m, (a, b) in enumerate(zip(got[n], base[n])):
+                sl = (Ellipsis,) + rng[n]
+                H.assert_bitwise(np.ascontiguousarray(a[sl] / f(_DIM_OUT.get(n, (0,) * 7))), np.ascontiguousarray(b[sl]),
+                                 f"{name}: {n}[{m}] of the reference, rescaled by {sc} and unscaled")
+
+
+def test_neutral_diffusion_second_round_on_one_control_structure():
+    """calc_coeffs and neutral_diffusion twice on ONE neutral_diffusion_CS of the reference.  First `slope`, then coefficients
+    from the thicknesses, T and S of `massless` (layers of zero thickness where `slope` had none): a position, an index or an
+    effective thickness left over from the first round would show in the second round's tracers and transports.  Then the two
+    iterations the restatement's tracer_hordiff_neutral makes under RECALC_NEUTRAL_SURF (calc_coeffs again, neutral_diffusion
+    with half the coefficients and half the time step): its loop is not compared (MOM_tracer_hor_diff.F90 is not compiled), what
+    it calls twice is."""
+    d, M, GV, P, opt, inp, inp2, want, _ = _ndiff_two_rounds()
+    hd = _ndiff_hordiff_rounds()
+    _need_lib()
+    got, fatal = RP.neutral_diffusion(d, M, GV, P, opt, inp, ncalls=2, inp2=inp2)
+    assert fatal == 0
+    _compare_ndiff("slope, then massless on the same control structure", d, want, got)
+    d, M, GV, P, opt, inp, coef, dt, want, _ = hd
+    got, fatal = RP.neutral_diffusion(d, M, GV, P, opt, inp, ncalls=2, coef=coef, dt=dt)
+    assert fatal == 0
+    _compare_ndiff("two iterations of tracer_hordiff_neutral", d, want, got)
+
+
+def test_neutral_diffusion_init_refusals_against_the_references():
+    """Every setting mom6x_neutral_diffusion_init refuses (ndiff_ref.refused names it) against the compiled
+    neutral_diffusion_init: NDIFF_REFUSALS records what the reference does.  It has no FATAL and no WARNING for any of them: it
+    accepts the discontinuous reconstruction, the vertical structure and the unmasked-transport bug, ignores NDIFF_TAPERING
+    without NDIFF_INTERIOR_ONLY, and under NDIFF_INTERIOR_ONLY is FATAL only where the diabatic driver has neither KPP nor ePBL.
+    The refusals are the device's alone (include/mom6x.h lists the difference).  Calls of stood-in procedures (MOM_remapping,
+    MOM_diabatic_driver) are counted apart from the reference's own FATALs.  An unknown EQN_OF_STATE is FATAL in its EOS_init."""
+    GV = abi.vgrid_default()
+    eos = abi.eos_params_default()
+    assert N.refused(abi.neutral_diffusion_params_default(), GV, eos) is None
+    for word, (mods, own, standins, _) in NDIFF_REFUSALS.items():
+        assert N.refused(abi.neutral_diffusion_params_default(**mods), GV, eos) == word
+    assert set(sum((tuple(m) for m, _, _, _ in NDIFF_REFUSALS.values()), ())) == {"continuous_reconstruction"} | set(abi.NEUTRAL_DIFFUSION_MUST_BE_0)
+    _need_lib()
+    d, M, GV, P, opt, inp = N.want("benchmark_small", 2, "slope")[:6]
+    got, fatal = RP.neutral_diffusion(d, M, GV, P, opt, inp, dt=0.0)
+    assert fatal == 0 and got == {} and RP.standin_never_count() == 0
+    for word, (mods, own, standins, _) in NDIFF_REFUSALS.items():
+        got, fatal = RP.neutral_diffusion(d, M, GV, abi.neutral_diffusion_params_default(**mods), opt, inp, dt=0.0)
+        never = RP.standin_never_count()
+        assert (fatal - never, never) == (own, standins), (word, fatal, never)
+    got, fatal = RP.neutral_diffusion(d, M, GV, P, opt, inp, dt=0.0, table_extra=[("EQN_OF_STATE", "NO_SUCH_EOS")])
+    assert fatal >= 1 and got is None and RP.standin_never_count() == 0
+    got, fatal = RP.neutral_diffusion(d, M, GV, P, opt, inp, dt=0.0, table_extra=[("USE_NEUTRAL_DIFFUSION", False)])
+    assert fatal == 1 and got is None             # (the door counts an init that answers "not used")
+
+
+def test_neutral_diffusion_compared_set_reaches_every_required_arm():
+    """Over everything the door tests above compare -- NDIFF_RUNS, the probing registry, the second rounds -- every arm of
+    tests/test_neutral_diffusion_cpu.REQUIRED is reached, from the restatement's counters alone; `recalc` and `itt_gt1` by the two
+    iterations whose calls the second-round test compares."""
+    from tests.test_neutral_diffusion_cpu import NOT_REACHED, REQUIRED
+    tot = N.new_counts()
+    runs = [N.want(grid, nk, name, **dict(kw))[7] for grid, nk, kw, cases in NDIFF_RUNS for name in cases]
+    runs += [_ndiff_probed(name)[7] for name in NDIFF_PROBED] + [_ndiff_two_rounds()[8], _ndiff_hordiff_rounds()[9]]
+    for counts in runs:
+        for k, v in counts.items():
+            tot[k] += v
+    assert set(REQUIRED) | set(NOT_REACHED) == set(N.ARMS) and len(REQUIRED) == len(N.ARMS) - 4
+    for k in REQUIRED:
+        assert tot[k] > 0, (k, tot)
+
+
 def test_zz_record_the_tolerance_class():
     """profiles/ref_parity_libm.json: the largest difference over range of every tolerance-class field seen by the tests above
     (MOM6X_RECORD_REF_PARITY names the file).  Runs last in the file; without the library there is nothing to record."""
@@ -490,6 +733,8 @@ def test_zz_record_the_tolerance_class():
 def _restatement(kind, d, M, GV, P, opt, inp):
     if kind == "kshear":
         return K.run(d, M, GV, P, opt, inp)[0]
+    if kind == "ndiff":
+        return {n: a for n, a in N.run(d, M, GV, P, opt, inp)[0].items() if n in RP.NDIFF_OUT}
     if kind == "opacity":
         return R.run(d, M, GV, P, opt, inp)[0]
     return E.run(d, M, GV, P, opt, inp)[0]
@@ -497,6 +742,15 @@ def _restatement(kind, d, M, GV, P, opt, inp):
 
 def _against_golden(tag, kind, d, M, gold, out):
     """`out` (whole arrays) against the recorded computational domain, in the classes of the live comparisons."""
+    if kind == "ndiff":                  # lists of arrays, each on its own range; a file over the size limit leaves out diagnostics
+        left_out = sorted(set(out) - set(gold))
+        assert set(RP.NDIFF_CORE) <= set(gold) <= set(out) == set(RP.NDIFF_OUT), sorted(gold)
+        assert left_out == sorted(RP.NDIFF_DROP_ORDER[:len(left_out)]), sorted(gold)
+        for n in gold:
+            assert len(gold[n]) == len(out[n]), (tag, n)
+            for m, (a, b) in enumerate(zip(out[n], gold[n])):
+                H.assert_bitwise(np.ascontiguousarray(a[(Ellipsis,) + RP.ndiff_ranges(d)[n]]), np.ascontiguousarray(b), f"{tag}: {n}[{m}]")
+        return
     dm = RP.dom(d)
     wet = (M[G["mask2dT"]] > 0.0)[dm]
     names = set(out) - set(RP.EPBL_NOT_EXPOSED) - set(RP.KSHEAR_NOT_EXPOSED)
@@ -527,8 +781,11 @@ def test_recorded_reference_is_what_the_library_gives():
     for kind, name, grid, kw in RP.golden_configs():
         d, M, GV, P, opt, inp = RP.golden_setup(kind, name, grid, kw)
         gold = RP.load_golden(kind, name, grid, kw, M, inp)
-        got, fatal = dict(opacity=RP.opacity, epbl=RP.energetic_PBL, kshear=RP.Calculate_kappa_shear)[kind](d, M, GV, P, opt, inp)
+        got, fatal = RP.DOORS[kind](d, M, GV, P, opt, inp)
         assert fatal == 0
+        if kind == "ndiff":
+            _against_golden(name, kind, d, M, gold, got)
+            continue
         dm = (Ellipsis,) + RP.dom(d)
         assert set(got) == set(gold) if kind != "kshear" else set(gold) <= set(got)
         for n in gold:
@@ -537,5 +794,5 @@ def test_recorded_reference_is_what_the_library_gives():
                 H.assert_bitwise(got[n][dm][wet], gold[n][wet], f"{name}: {n}")
             else:
                 H.assert_bitwise(got[n][dm], gold[n], f"{name}: {n}")
-        largest = max(os.path.getsize(os.path.join(RP.GOLDEN, f)) for f in os.listdir(RP.GOLDEN) if f.startswith("ref_"))
-        assert largest <= 248 * 1024, largest
+    largest = max(os.path.getsize(os.path.join(RP.GOLDEN, f)) for f in os.listdir(RP.GOLDEN) if f.startswith("ref_"))
+    assert largest <= 248 * 1024, largest

@@ -1,6 +1,7 @@
-"""mom6x_set_pen_shortwave, mom6x_energetic_PBL and mom6x_Calculate_kappa_shear on the device against what the reference's own
-compiled MOM_opacity.F90, MOM_energetic_PBL.F90 and MOM_kappa_shear.F90 gave on the same seeded inputs: the recorded results
-tests/golden/ref_opacity_*.npz, ref_epbl_*.npz and ref_kshear_*.npz
+"""mom6x_set_pen_shortwave, mom6x_energetic_PBL, mom6x_Calculate_kappa_shear and mom6x_neutral_diffusion_calc_coeffs with
+mom6x_neutral_diffusion on the device against what the reference's own
+compiled MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90 and MOM_neutral_diffusion.F90 gave on the same seeded inputs:
+the recorded results tests/golden/ref_opacity_*.npz, ref_epbl_*.npz, ref_kshear_*.npz and ref_ndiff_*.npz
 (scripts/record_ref_parity.py wrote them from oracle/_ref/libref_param.so; tests/test_ref_parity_cpu.py holds the restatements
 and the live library to the same files).  Nothing here needs the compiled reference.
 
@@ -13,7 +14,15 @@ diagnostic of the reference and is not recorded.
 Kind kshear: shear, bugs, nkml2, layered, newton and tie on the basin with an island at 4 layers, shear and nkml2 on the bowl at 8, shear
 on the bowl at 2, shear and layered on the torus at 3.  The device is fed u and v (its own find_uv_at_h runs; the compiled routine
 was handed the restatement's u_h, v_h) with NaN halos; kappa_io, tke_io, kv_io and the four 3-D diagnostics bit for bit, there is
-no tolerance class; no halo exchange happens.  KS_its reaches no diagnostic of the reference and is not recorded."""
+no tolerance class; no halo exchange happens.  KS_its reaches no diagnostic of the reference and is not recorded.
+
+Kind ndiff: every case of ndiff_ref.CASES on the basin with an island at 4 layers, slope on the bowl at 1 and at 2, slope and massless on
+the bowl at 8, slope and new_order on the torus at 3, fed through _device of tests/test_neutral_diffusion_gpu.py (one init, one
+calc_coeffs and one neutral_diffusion call) with that file's NaN-beyond-the-first-halo inputs.  Every tracer and its content tendency
+on the computational domain, trans_x_2d and trans_y_2d on their face ranges, bit for bit: there is no tolerance class.  Every
+diagnostic starts as NaN and is still NaN outside its range, the tracers keep the NaN of their outer halos; no exchange happens and
+the status is (0, 0, 0, 0).  The coefficient arrays are private to the compiled module and are not recorded; the neutral branch of
+tracer_hordiff and the discontinuous reconstruction are outside what was compiled."""
 import numpy as np
 import pytest
 
@@ -56,6 +65,26 @@ def _compare(tag, kind, d, M, gold, got):
             H.assert_bitwise(a, np.ascontiguousarray(b), f"{tag}: {n}")
 
 
+def _ndiff(tag, d, M, GV, P, opt, inp, gold):
+    """The four outputs bit for bit on the ranges of test_neutral_diffusion_gpu._check; NaN outside them (the tracers: beyond the
+    first halo, where the inputs hold NaN); no exchange; status (0, 0, 0, 0) (asserted inside _device)."""
+    from tests.test_neutral_diffusion_gpu import _device
+    got, nex = _device(d, M, GV, P, opt, inp)
+    assert nex == 0
+    assert set(RP.NDIFF_CORE) <= set(gold) <= set(RP.NDIFF_OUT), sorted(gold)
+    rng = RP.ndiff_ranges(d)
+    ring = np.ones(d.shape2(), bool); ring[H.interior(d, "h", extra=1)] = False
+    for n in RP.NDIFF_OUT:
+        inside = np.zeros(d.shape2(), bool); inside[rng[n]] = True
+        for m, a in enumerate(got[n]):
+            assert np.isfinite(a[..., inside]).all(), (tag, n, m)
+            assert np.isnan(a[..., ring if n == "tracers" else ~inside]).all(), (tag, n, m)
+    for n, recorded in gold.items():
+        assert len(recorded) == len(got[n]) == len(inp["tracers"]), (tag, n)
+        for m, (a, b) in enumerate(zip(got[n], recorded)):
+            H.assert_bitwise(np.ascontiguousarray(a[(Ellipsis,) + rng[n]]), np.ascontiguousarray(b), f"{tag}: {n}[{m}]")
+
+
 @pytest.mark.parametrize("kind,name,grid,kw", RP.golden_configs(), ids=_ids())
 def test_device_against_the_recorded_reference(kind, name, grid, kw):
     d, M, GV, P, opt, inp = RP.golden_setup(kind, name, grid, kw)
@@ -66,6 +95,9 @@ def test_device_against_the_recorded_reference(kind, name, grid, kw):
         with _Dy(d, M, GV) as dy:
             got, neg = _device(dy, d, P, opt, inp)
         assert neg == 0
+    elif kind == "ndiff":
+        _ndiff(tag, d, M, GV, P, opt, inp, gold)
+        return
     elif kind == "kshear":
         from tests.test_kappa_shear_gpu import _device, _nan_halo
         got, nex = _device(d, M, GV, P, opt, _nan_halo(d, inp))
