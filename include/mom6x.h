@@ -705,7 +705,15 @@ int mom6x_set_viscous_BBL(mom6x_ctx *ctx, const double *u, const double *v, cons
 /* MOM_thickness_diffuse: thickness_diffuse                                    */
 /* thickness_diffuse_CS (src/parameterizations/lateral/MOM_thickness_diffuse.F90:41-128; thickness_diffuse_init :2175-2500):
  * the members thickness_diffuse (:134-630) and thickness_diffuse_full (:635-1671) read on a Boussinesq grid with the plain
- * (Gent-McWilliams) streamfunction.  The members marked "must be 0" are refused with MOM6X_EUNSUPPORTED.                  */
+ * (Gent-McWilliams) streamfunction.  The members marked "must be 0" are refused with MOM6X_EUNSUPPORTED.
+ * The reference's own thickness_diffuse_init (compiled, tests/test_ref_parity_cpu.py LATERAL_REFUSALS) stops on only one of
+ * them: USE_STANLEY_GM without STANLEY_COEFF >= 0 (:2334), and accepts it with one.  KH_ETA_CONST, KH_ETA_VEL_SCALE,
+ * DETANGLE_INTERFACES, USE_GME, KHTH_USE_FGNV_STREAMFUNCTION and USE_MEKE it accepts (the last two make VarMix_init ask for wave
+ * speeds); the device refuses them because their paths are not on the device.  use_variable_mixing is not a parameter of this
+ * init: it is VarMix%use_variable_mixing, which the reference's VarMix_init sets TRUE by default (INTERPOLATED_SQG_STRUCTURE with
+ * SQG_EXPO > 0 allocates the stored slopes, MOM_lateral_mixing_coeffs.F90:1699-1701, :2053); with KHTH_SLOPE_CFF = 0 and nothing
+ * else switched on that changes no arithmetic (:206-221), and the device takes stored slopes as arguments instead.  Both inits
+ * stop on KHTH > 0 with READ_KHTH (:2218), as the device does.                                                              */
 typedef struct mom6x_thickness_diffuse_params {
   int    thickness_diffuse;   /* THICKNESSDIFFUSE (F, :2207); F: mom6x_thickness_diffuse returns at once (:195)            */
   double Khth;                /* KHTH (0, :2210) [L2 T-1]; 0 without khth2d: returns at once (:196)                         */
@@ -818,6 +826,10 @@ int mom6x_tracer_hordiff_neutral(mom6x_ctx *ctx, const double *h, double dt, dou
  * calc_Eady_growth_rate_2D (:962-1112), calc_Visbeck_coeffs_old (:743-959, without open boundaries) and
  * calc_slope_functions_using_just_e (:1116-1275), on a Boussinesq grid.  The members marked "must be 0" are refused with
  * MOM6X_EUNSUPPORTED.                                                                                                      */
+/* Of the members marked "must be 0" the reference's own VarMix_init (compiled, tests/test_ref_parity_cpu.py LATERAL_REFUSALS)
+ * stops only on USE_STANLEY_ISO without STANLEY_COEFF >= 0 (:1621) and accepts it with one; DEBUG it accepts; open_bcs and
+ * non_Boussinesq are no parameters of it (the OBC pointer, GV%Boussinesq).  Both stop on USE_SIMPLER_EADY_GROWTH_RATE without
+ * USE_STORED_SLOPES (:1722).                                                                                                */
 typedef struct mom6x_varmix_params {
   int    calculate_Eady_growth_rate;   /* CS%calculate_Eady_growth_rate (:1604); 0: mom6x_calc_slope_functions writes nothing (:708) */
   int    use_stored_slopes;            /* USE_STORED_SLOPES (F, :1589)                                                              */

@@ -13,8 +13,10 @@
 // carries vint_SN and sum_dz of calc_Eady_growth_rate_2D along (the reference's summation order), so dzu, dzSxN and N2 only go to
 // memory when a diagnostic asks for them.  k_vm_eady_combine: the four-neighbour combination from the un-combined planes.
 // k_vm_visbeck: the sums of calc_Visbeck_coeffs_old, h4_u | h4_v formed from h as the walk goes.  k_vm_just_e: the third branch in
-// one launch, the neighbours' E_x | E_y recomputed from e.  MAX and MIN are fmax1 and fmin1 of mom6x_dev.h, the reference
-// compiler's.  The density gradients (isoneutral_grads) and the vert_fill_TS solve come from isopycnal_slopes_dev.h, which
+// one launch, the neighbours' E_x | E_y recomputed from e.  MAX and MIN are fmax1 and fmin1 of mom6x_dev.h, but the radicand of
+// dzSxN | dzSyN (MOM_isopycnal_slopes.F90:418, :602) is dmax: max(0.0, -0.0), which both vertical density differences being -0.0
+// make of it, the compiled reference answers with its second argument, and sqrt(-0.0) = -0.0 shows in the diagnostic (found by
+// tests/test_ref_parity_cpu.py with the case eady_tie).  The density gradients (isoneutral_grads) and the vert_fill_TS solve come from isopycnal_slopes_dev.h, which
 // thickness_diffuse.hip shares; the lane of a face from face_lane (mom6x_dev.h), the EOS form's kernel from EOS_FORM_DISPATCH.
 #include "mom6x_dev.h"
 #include "eos_dev.h"
@@ -123,7 +125,7 @@ k_vm_faces(Dm d, const double *__restrict__ G, VmK K, const double *__restrict__
     bool want_dzSN = dzs != nullptr;
     if constexpr (BR == 1) want_dzSN = true;
     if (want_dzSN) {
-      const double dzSN = sqrt(K.G_Rho0 * fmax1(0.0, (g.wtL * (g.dzaL * g.drdkL)) + (g.wtR * (g.dzaR * g.drdkR))) / (g.wtL + g.wtR)) * fabs(sl) * mask;
+      const double dzSN = sqrt(K.G_Rho0 * dmax(0.0, (g.wtL * (g.dzaL * g.drdkL)) + (g.wtR * (g.dzaR * g.drdkR))) / (g.wtL + g.wtR)) * fabs(sl) * mask;
       if (dzs) dzs[o + x] = dzSN;
       if constexpr (BR == 1) {                    // :1014-1041 | :1057-1085
         double dnew = sum_dz + dzu;

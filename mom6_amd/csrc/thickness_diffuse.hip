@@ -10,7 +10,9 @@
 // tridiagonal solve of vert_fill_TS (any layer count: the solve's c1 goes through a work array).  k_td_faces: one lane per face,
 // both directions in one launch (blockIdx.z), ONE bottom-up walk -- without the FGNV solver the two K = nz..2 loops of a face row
 // carry only uhtot -- that forms e from h as it climbs (find_eta's own order), h_avail pointwise, writes uhD | vhD and adds them
-// to uhtr | vhtr.  k_td_update: h.  MAX and MIN are fmax1 and fmin1 of mom6x_dev.h, the reference compiler's.  The density
+// to uhtr | vhtr.  k_td_update: h.  MAX and MIN are fmax1 and fmin1 of mom6x_dev.h, but the limiter of uhD | vhD (:1160-1161, :1479) is
+// dmax(dmin()): where no transport meets no available mass beyond the face, MAX(+0.0, -0.0), the compiled reference answers
+// with its second argument, -0.0, which shows in uhGM | vhGM (found by tests/test_ref_parity_cpu.py on every grid).  The density
 // gradients of MODE 1 (isoneutral_grads) and the vert_fill_TS solve come from isopycnal_slopes_dev.h, which
 // lateral_mixing_coeffs.hip shares; the lane of a face from face_lane (mom6x_dev.h), the EOS form's kernel from EOS_FORM_DISPATCH.
 #include "mom6x_dev.h"
@@ -143,7 +145,7 @@ k_td_faces(Dm d, const double *__restrict__ G, TdK K, const double *__restrict__
       Sfn_est = K.Z_to_H * Sfn_unlim;
     }
     const double Sfn_in_H = fmin1(fmax1(Sfn_est, -rsum[o + x]), rsum[o + y]);
-    const double D = fmax1(fmin1((Sfn_in_H - uhtot), haL_), -haR_);
+    const double D = dmax(dmin((Sfn_in_H - uhtot), haL_), -haR_);   // :1160-1161, :1479: a tie here shows (see the header)
     uhtot = uhtot + D;
     hD[o + x] = D;
     htr[o + x] = htr[o + x] + D * K.dt;

@@ -1,8 +1,9 @@
 !> ORACLE SUPPORT (test infrastructure only): bind(C) doors into the reference's parameterization modules, compiled where
 !! they lie against the stand-ins of oracle/ref_standins.F90 into oracle/_ref/libref_param.so (see oracle/Makefile):
 !! MOM_EOS_Wright.F90, MOM_EOS_Wright_full.F90, MOM_EOS_Wright_red.F90, MOM_EOS_linear.F90, MOM_intrinsic_functions.F90,
-!! MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90 and MOM_neutral_diffusion.F90 (with the dispatcher MOM_EOS.F90 that
-!! the last two call), with MOM_unit_scaling.F90 and MOM_string_functions.F90.
+!! MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90, MOM_neutral_diffusion.F90, MOM_isopycnal_slopes.F90,
+!! MOM_lateral_mixing_coeffs.F90 and MOM_thickness_diffuse.F90 (with the dispatcher MOM_EOS.F90 that the last five call and the
+!! find_eta and thickness_to_dz of MOM_interface_heights.F90), with MOM_unit_scaling.F90 and MOM_string_functions.F90.
 !! tests/ref_param.py loads the library and holds the parameter-name maps; tests/test_ref_parity_cpu.py holds the python
 !! restatements under tests/ to these doors.  Nothing of the reference is copied here.
 !!
@@ -38,6 +39,11 @@ module ref_param_shim
   use MOM_neutral_diffusion, only : neutral_diffusion_CS, neutral_diffusion_init, neutral_diffusion_calc_coeffs, neutral_diffusion, &
                                     neutral_diffusion_end
   use MOM_tracer_registry, only : tracer_registry_type
+  use MOM_variables, only : cont_diag_ptrs
+  use MOM_open_boundary, only : ocean_OBC_type
+  use MOM_MEKE_types, only : MEKE_type
+  use MOM_lateral_mixing_coeffs, only : VarMix_CS, VarMix_init, VarMix_end, calc_slope_functions
+  use MOM_thickness_diffuse, only : thickness_diffuse_CS, thickness_diffuse_init, thickness_diffuse, thickness_diffuse_end
   use MOM_diabatic_driver, only : diabatic_CS
   implicit none
 contains
@@ -431,5 +437,144 @@ contains
     deallocate(diabatic_CSp) ; deallocate(G%Domain)
     call unit_scaling_end(US)
     ref_neutral_diffusion = standin_fatal_count
+  end function
+
+  ! ---- the lateral modules: MOM_lateral_mixing_coeffs.F90 (with MOM_isopycnal_slopes.F90) and MOM_thickness_diffuse.F90 ----
+  !> The grid and vertical-grid members the lateral modules read beyond setup's.  metrics [18, nj_mem, ni_mem] holds, in this
+  !! order, mask2dT, mask2dCu, mask2dCv, IdxCu, IdyCu, IdxCv, IdyCv, dxCu, dyCu, dxCv, dyCv, dy_Cu, dx_Cv, areaT, IareaT, areaCu,
+  !! areaCv, bathyT; OBCmaskCu and OBCmaskCv are the face masks (no open boundaries).  vgx = (g_Earth, m2_s_to_HZ_T, H_to_kg_m2,
+  !! max_depth).  dxT, dyT, dxBu, dyBu and Coriolis2Bu, which only the resolution-function part of VarMix_init reads (with
+  !! USE_MEKE or a RESOLN_SCALED_ switch: tried for what the init refuses, never compared), are zero; dF_dx and dF_dy, which only
+  !! calc_QG_Leith_viscosity reads, stay unallocated.
+  subroutine setup_lateral(ni_mem, nj_mem, nk, vgx, metrics, Rlay, g_prime, G, GV)
+    integer, intent(in) :: ni_mem, nj_mem, nk ; real, intent(in) :: vgx(4), metrics(ni_mem, nj_mem, 18), Rlay(nk), g_prime(nk+1)
+    type(ocean_grid_type), intent(inout) :: G ; type(verticalGrid_type), intent(inout) :: GV
+    allocate(G%mask2dCu(ni_mem, nj_mem), G%mask2dCv(ni_mem, nj_mem), G%OBCmaskCu(ni_mem, nj_mem), G%OBCmaskCv(ni_mem, nj_mem), &
+             G%IdxCu(ni_mem, nj_mem), G%IdyCu(ni_mem, nj_mem), G%IdxCv(ni_mem, nj_mem), G%IdyCv(ni_mem, nj_mem), &
+             G%dxCu(ni_mem, nj_mem), G%dyCu(ni_mem, nj_mem), G%dxCv(ni_mem, nj_mem), G%dyCv(ni_mem, nj_mem), &
+             G%dy_Cu(ni_mem, nj_mem), G%dx_Cv(ni_mem, nj_mem), G%areaT(ni_mem, nj_mem), G%IareaT(ni_mem, nj_mem), &
+             G%areaCu(ni_mem, nj_mem), G%areaCv(ni_mem, nj_mem), G%bathyT(ni_mem, nj_mem), G%Domain, &
+             G%dxT(ni_mem, nj_mem), G%dyT(ni_mem, nj_mem), G%dxBu(ni_mem, nj_mem), G%dyBu(ni_mem, nj_mem), G%Coriolis2Bu(ni_mem, nj_mem))
+    G%dxT(:,:) = 0.0 ; G%dyT(:,:) = 0.0 ; G%dxBu(:,:) = 0.0 ; G%dyBu(:,:) = 0.0 ; G%Coriolis2Bu(:,:) = 0.0
+    G%mask2dCu(:,:) = metrics(:,:,2) ; G%mask2dCv(:,:) = metrics(:,:,3) ; G%OBCmaskCu(:,:) = metrics(:,:,2)
+    G%OBCmaskCv(:,:) = metrics(:,:,3) ; G%IdxCu(:,:) = metrics(:,:,4) ; G%IdyCu(:,:) = metrics(:,:,5)
+    G%IdxCv(:,:) = metrics(:,:,6) ; G%IdyCv(:,:) = metrics(:,:,7) ; G%dxCu(:,:) = metrics(:,:,8) ; G%dyCu(:,:) = metrics(:,:,9)
+    G%dxCv(:,:) = metrics(:,:,10) ; G%dyCv(:,:) = metrics(:,:,11) ; G%dy_Cu(:,:) = metrics(:,:,12) ; G%dx_Cv(:,:) = metrics(:,:,13)
+    G%areaT(:,:) = metrics(:,:,14) ; G%IareaT(:,:) = metrics(:,:,15) ; G%areaCu(:,:) = metrics(:,:,16)
+    G%areaCv(:,:) = metrics(:,:,17) ; G%bathyT(:,:) = metrics(:,:,18) ; G%Z_ref = 0.0 ; G%ke = nk
+    GV%g_Earth = vgx(1) ; GV%m2_s_to_HZ_T = vgx(2) ; GV%H_to_kg_m2 = vgx(3) ; GV%max_depth = vgx(4)
+    GV%semi_Boussinesq = .false. ; GV%nkml = 0 ; GV%nk_rho_varies = 0
+    allocate(GV%Rlay(nk), GV%g_prime(nk+1)) ; GV%Rlay(:) = Rlay(:) ; GV%g_prime(:) = g_prime(:)
+  end subroutine setup_lateral
+
+  !> unit_scaling_init, EOS_init (where T and S are given) and VarMix_init (MOM_lateral_mixing_coeffs.F90:1445) through the table,
+  !! then calc_slope_functions (:686) `ncalls` times on the same VarMix_CS, on a whole tile.  h is [ncalls, nk, nj_mem, ni_mem]
+  !! (round r reads slice r); T and S [nk, nj_mem, ni_mem] are C pointers, null together for "tv%eqn_of_state not associated" (the
+  !! layered arm, which reads GV%Rlay); p_surf [nj_mem, ni_mem] is a C pointer, null for "not associated".  The OBC pointer is
+  !! null.  Out come the public members CS%SN_u, CS%SN_v, CS%slope_x, CS%slope_y, CS%L2u, CS%L2v, each only where VarMix_init has
+  !! allocated it (has = 1, else 0 and the array is left as it came); the diagnostics asked for with ref_want_diag (N2_u, N2_v,
+  !! S2_u, S2_v, dzu_Visbeck, dzv_Visbeck, dzSxN, dzSyN, SN_u, SN_v, L2u, L2v) are read back with ref_get_diag.  No member of
+  !! VarMix_CS is set from here.  dt <= 0: the inits only.
+  integer(c_int) function ref_calc_slope_functions(ni_mem, nj_mem, idx, nk, vgr, vgx, metrics, Rlay, g_prime, ncalls, h, T, S, &
+        p_surf, dt, SN_u, SN_v, slope_x, slope_y, L2u, L2v, has) bind(C, name="ref_calc_slope_functions")
+    integer(c_int), value :: ni_mem, nj_mem, nk, ncalls ; integer(c_int), intent(in) :: idx(4)
+    real(c_double), intent(in) :: vgr(14), vgx(4), metrics(ni_mem, nj_mem, 18), Rlay(nk), g_prime(nk+1)
+    real(c_double), intent(inout) :: h(ni_mem, nj_mem, nk, ncalls) ; type(c_ptr), value :: T, S, p_surf ; real(c_double), value :: dt
+    real(c_double), intent(inout), dimension(ni_mem, nj_mem) :: SN_u, SN_v, L2u, L2v
+    real(c_double), intent(inout), dimension(ni_mem, nj_mem, nk+1) :: slope_x, slope_y
+    integer(c_int), intent(out) :: has(3)
+    type(ocean_grid_type) :: G ; type(verticalGrid_type) :: GV ; type(unit_scale_type), pointer :: US
+    type(param_file_type) :: pf ; type(diag_ctrl), target :: diag ; type(time_type), target :: Time
+    type(VarMix_CS) :: CS ; type(thermo_var_ptrs) :: tv ; type(EOS_type), target :: eqn ; type(ocean_OBC_type), pointer :: OBC
+    integer :: r
+    standin_fatal_count = 0 ; standin_never_count = 0 ; has(:) = 0
+    call setup(int(ni_mem), int(nj_mem), int(idx), int(nk), vgr, metrics(:,:,1), c_null_ptr, pf, G, GV, US)
+    call setup_lateral(int(ni_mem), int(nj_mem), int(nk), vgx, metrics, Rlay, g_prime, G, GV)
+    if (c_associated(T) .and. c_associated(S)) then
+      call c_f_pointer(T, tv%T, (/ int(ni_mem), int(nj_mem), int(nk) /))
+      call c_f_pointer(S, tv%S, (/ int(ni_mem), int(nj_mem), int(nk) /))
+      call EOS_init(pf, eqn, US) ; tv%eqn_of_state => eqn
+    endif
+    call plane(p_surf, int(ni_mem), int(nj_mem), tv%p_surf)
+    call VarMix_init(Time, G, GV, US, pf, diag, CS)
+    OBC => NULL()
+    if (standin_fatal_count == 0 .and. dt > 0.0) then
+      do r = 1, ncalls
+        call calc_slope_functions(h(:,:,:,r), tv, dt, G, GV, US, CS, OBC)
+      enddo
+      if (allocated(CS%SN_u)) then ; has(1) = 1 ; SN_u(:,:) = CS%SN_u(:,:) ; SN_v(:,:) = CS%SN_v(:,:) ; endif
+      if (allocated(CS%slope_x)) then ; has(2) = 1 ; slope_x(:,:,:) = CS%slope_x(:,:,:) ; slope_y(:,:,:) = CS%slope_y(:,:,:) ; endif
+    endif
+    if (allocated(CS%L2u)) then ; has(3) = 1 ; L2u(:,:) = CS%L2u(:,:) ; L2v(:,:) = CS%L2v(:,:) ; endif
+    call VarMix_end(CS)
+    deallocate(G%Domain)
+    call unit_scaling_end(US)
+    ref_calc_slope_functions = standin_fatal_count
+  end function
+
+  !> unit_scaling_init, EOS_init (where T and S are given), VarMix_init and thickness_diffuse_init (MOM_thickness_diffuse.F90:2170)
+  !! through the table, then thickness_diffuse (:134) `ncalls` times on the same control structures, on a whole tile; h, uhtr and
+  !! vhtr [nk, nj_mem, ni_mem] are changed in place, every round going on from the one before.  T, S, p_surf as in
+  !! ref_calc_slope_functions.  The stored slopes go the reference's way, through VarMix%slope_x and VarMix%slope_y with
+  !! VarMix%use_variable_mixing and VarMix%use_stored_slopes as VarMix_init sets them from USE_STORED_SLOPES (KHTH_SLOPE_CFF stays
+  !! 0, so use_VarMix is false, :211):
+  !!   mode 0: VarMix is as VarMix_init left it (no stored slopes unless the table asks for them, and then they are zero);
+  !!   mode 1: slope_x and slope_y [nk + 1, nj_mem, ni_mem] are copied into the public members VarMix%slope_x and VarMix%slope_y,
+  !!           which VarMix_init has allocated (the one member set from here: in the reference calc_slope_functions fills it);
+  !!   mode 2: the chain: every round first calls calc_slope_functions on the same VarMix_CS with the round's h, whose stored slopes
+  !!           thickness_diffuse then reads; slope_x, slope_y, SN_u and SN_v get the last round's.
+  !! uhGM and vhGM get CDp%uhGM and CDp%vhGM where thickness_diffuse_init has allocated them (it does where ref_want_diag has
+  !! asked for the diagnostics uhGM, vhGM: has = 1); the diagnostics asked for are read back with ref_get_diag.  MEKE is empty and
+  !! STOCH has skeb_use_gm false.  dt <= 0: the inits only.
+  integer(c_int) function ref_thickness_diffuse(ni_mem, nj_mem, idx, nk, vgr, vgx, metrics, Rlay, g_prime, ncalls, mode, h, uhtr, &
+        vhtr, T, S, p_surf, dt, slope_x, slope_y, SN_u, SN_v, uhGM, vhGM, has) bind(C, name="ref_thickness_diffuse")
+    integer(c_int), value :: ni_mem, nj_mem, nk, ncalls, mode ; integer(c_int), intent(in) :: idx(4)
+    real(c_double), intent(in) :: vgr(14), vgx(4), metrics(ni_mem, nj_mem, 18), Rlay(nk), g_prime(nk+1)
+    real(c_double), intent(inout), dimension(ni_mem, nj_mem, nk) :: h, uhtr, vhtr, uhGM, vhGM
+    type(c_ptr), value :: T, S, p_surf ; real(c_double), value :: dt
+    real(c_double), intent(inout), dimension(ni_mem, nj_mem, nk+1) :: slope_x, slope_y
+    real(c_double), intent(inout), dimension(ni_mem, nj_mem) :: SN_u, SN_v
+    integer(c_int), intent(out) :: has(2)
+    type(ocean_grid_type) :: G ; type(verticalGrid_type) :: GV ; type(unit_scale_type), pointer :: US
+    type(param_file_type) :: pf ; type(diag_ctrl), target :: diag ; type(time_type), target :: Time
+    type(VarMix_CS) :: VarMix ; type(thickness_diffuse_CS) :: CS ; type(thermo_var_ptrs) :: tv ; type(EOS_type), target :: eqn
+    type(ocean_OBC_type), pointer :: OBC ; type(MEKE_type) :: MEKE ; type(cont_diag_ptrs) :: CDp ; type(stochastic_CS) :: STOCH
+    integer :: r
+    standin_fatal_count = 0 ; standin_never_count = 0 ; has(:) = 0
+    call setup(int(ni_mem), int(nj_mem), int(idx), int(nk), vgr, metrics(:,:,1), c_null_ptr, pf, G, GV, US)
+    call setup_lateral(int(ni_mem), int(nj_mem), int(nk), vgx, metrics, Rlay, g_prime, G, GV)
+    if (c_associated(T) .and. c_associated(S)) then
+      call c_f_pointer(T, tv%T, (/ int(ni_mem), int(nj_mem), int(nk) /))
+      call c_f_pointer(S, tv%S, (/ int(ni_mem), int(nj_mem), int(nk) /))
+      call EOS_init(pf, eqn, US) ; tv%eqn_of_state => eqn
+    endif
+    call plane(p_surf, int(ni_mem), int(nj_mem), tv%p_surf)
+    call VarMix_init(Time, G, GV, US, pf, diag, VarMix)
+    call thickness_diffuse_init(Time, G, GV, US, pf, diag, CDp, CS)
+    OBC => NULL() ; STOCH%skeb_use_gm = .false.
+    if (mode == 1) then
+      if (allocated(VarMix%slope_x) .and. allocated(VarMix%slope_y)) then
+        VarMix%slope_x(:,:,:) = slope_x(:,:,:) ; VarMix%slope_y(:,:,:) = slope_y(:,:,:)
+      else
+        standin_fatal_count = standin_fatal_count + 1     ! the table of a stored-slopes case must set USE_STORED_SLOPES
+      endif
+    endif
+    if (standin_fatal_count == 0 .and. dt > 0.0) then
+      do r = 1, ncalls
+        if (mode == 2) call calc_slope_functions(h, tv, dt, G, GV, US, VarMix, OBC)
+        call thickness_diffuse(h, uhtr, vhtr, tv, dt, G, GV, US, MEKE, VarMix, CDp, CS, STOCH)
+      enddo
+      if (mode == 2) then
+        slope_x(:,:,:) = VarMix%slope_x(:,:,:) ; slope_y(:,:,:) = VarMix%slope_y(:,:,:)
+        SN_u(:,:) = VarMix%SN_u(:,:) ; SN_v(:,:) = VarMix%SN_v(:,:)
+      endif
+      if (associated(CDp%uhGM)) then ; has(1) = 1 ; uhGM(:,:,:) = CDp%uhGM(:,:,:) ; endif
+      if (associated(CDp%vhGM)) then ; has(2) = 1 ; vhGM(:,:,:) = CDp%vhGM(:,:,:) ; endif
+    endif
+    call thickness_diffuse_end(CS, CDp)
+    call VarMix_end(VarMix)
+    deallocate(G%Domain)
+    call unit_scaling_end(US)
+    ref_thickness_diffuse = standin_fatal_count
   end function
 end module ref_param_shim

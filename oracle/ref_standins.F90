@@ -1,7 +1,7 @@
 !> oracle/ref_standins.F90 -- ORACLE SUPPORT (test infrastructure only), not product and not reference text.
 !!
 !! The reference's parameterization modules (MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90,
-!! MOM_neutral_diffusion.F90) `use` framework modules
+!! MOM_neutral_diffusion.F90, MOM_isopycnal_slopes.F90, MOM_lateral_mixing_coeffs.F90, MOM_thickness_diffuse.F90) `use` framework modules
 !! that need FMS and netCDF.  oracle/Makefile compiles those files, and every framework file that does compile on its own (the
 !! equation-of-state dispatcher MOM_EOS.F90 with every module it uses among them), where they lie, against
 !! the interface-only stand-ins below.  The rule is that of tests/fortran_stubs/mom_stubs.F90: each module carries the name of the
@@ -19,14 +19,19 @@
 !!     text.  No compared case selects TEOS10 or a TEOS10 freezing point, so none of the ten is ever called.
 !!   * a procedure that no compared path may reach (pass_var, the procedures of MOM_remapping, MOM_hor_bnd_diffusion,
 !!     MOM_CVMix_KPP and MOM_diabatic_driver, which MOM_neutral_diffusion.F90 names on its discontinuous, interior-only and
-!!     vertical-structure paths) calls standin_never: a FATAL, counted apart in standin_never_count.
+!!     vertical-structure paths; pass_vector, MOM_read_data and the two procedures of MOM_wave_speed, which the lateral modules
+!!     name for calc_resoln_function, READ_KHTH and the resolution-function part of VarMix_init) calls standin_never: a FATAL,
+!!     counted apart in standin_never_count.
+!!   * MOM_open_boundary has the type, its members and the constants that MOM_isopycnal_slopes.F90 and
+!!     MOM_lateral_mixing_coeffs.F90 name, and no procedure: the doors leave the OBC pointer null.
 !! Stood in for: MOM_error_handler, MOM_coms, MOM_cpu_clock, MOM_time_manager, MOM_hor_index, MOM_domains, MOM_grid,
-!! MOM_verticalGrid, MOM_file_parser, MOM_io (stdout and stderr), gsw_mod_toolbox, MOM_variables, MOM_forcing_type,
-!! MOM_diag_mediator, MOM_debugging, MOM_interface_heights, MOM_wave_interface, MOM_stochastics, MOM_remapping,
-!! MOM_tracer_registry, MOM_hor_bnd_diffusion, MOM_CVMix_KPP, MOM_diabatic_driver.  MOM_EOS is no longer among them.
+!! MOM_verticalGrid, MOM_file_parser, MOM_io (stdout, stderr, MOM_read_data, slasher), gsw_mod_toolbox, MOM_variables,
+!! MOM_forcing_type, MOM_diag_mediator, MOM_debugging, MOM_wave_interface, MOM_stochastics, MOM_remapping, MOM_tracer_registry,
+!! MOM_hor_bnd_diffusion, MOM_open_boundary, MOM_wave_speed, MOM_CVMix_KPP, MOM_diabatic_driver.  MOM_EOS and
+!! MOM_interface_heights are no longer among them: the reference's own files are compiled.
 !! The file is compiled three times: what needs neither a unit_scale_type nor an EOS_type before the reference's own
 !! MOM_unit_scaling.F90 and equation-of-state files; MOM_variables (whose thermo_var_ptrs holds an EOS_type),
-!! MOM_interface_heights, MOM_wave_interface and MOM_CVMix_KPP after them, with -DSTANDINS_AFTER_UNIT_SCALING; and
+!! MOM_wave_speed, MOM_wave_interface and MOM_CVMix_KPP after them, with -DSTANDINS_AFTER_UNIT_SCALING; and
 !! MOM_diabatic_driver (whose extract_diabatic_member names an energetic_PBL_CS) after the reference's MOM_energetic_PBL.F90,
 !! with -DSTANDINS_AFTER_ENERGETIC_PBL as well.
 #ifndef STANDINS_AFTER_UNIT_SCALING
@@ -123,12 +128,28 @@ module MOM_domains
   implicit none ; public
   type :: MOM_domain_type ; integer :: dummy = 0 ; end type MOM_domain_type
   type :: group_pass_type ; integer :: dummy = 0 ; end type group_pass_type
+  integer, parameter :: CORNER = 1      ! (the stand-in tells nothing by it)
   interface pass_var
     module procedure pass_var_2d, pass_var_3d
   end interface
+  interface pass_vector
+    module procedure pass_vector_2d, pass_vector_3d
+  end interface
 contains
+  !> Never reached: MOM_lateral_mixing_coeffs.F90 and MOM_thickness_diffuse.F90 import the name and do not call it.
+  subroutine pass_vector_2d(u_cmpt, v_cmpt, MOM_dom, direction, stagger, complete, halo, clock)
+    real, dimension(:,:), intent(inout) :: u_cmpt, v_cmpt ; type(MOM_domain_type), intent(inout) :: MOM_dom
+    integer, optional, intent(in) :: direction, stagger, halo, clock ; logical, optional, intent(in) :: complete
+    call standin_never("pass_vector (2-D)")
+  end subroutine pass_vector_2d
+  subroutine pass_vector_3d(u_cmpt, v_cmpt, MOM_dom, direction, stagger, complete, halo, clock)
+    real, dimension(:,:,:), intent(inout) :: u_cmpt, v_cmpt ; type(MOM_domain_type), intent(inout) :: MOM_dom
+    integer, optional, intent(in) :: direction, stagger, halo, clock ; logical, optional, intent(in) :: complete
+    call standin_never("pass_vector (3-D)")
+  end subroutine pass_vector_3d
   !> Never reached: MOM_neutral_diffusion passes the boundary-layer depth (NDIFF_INTERIOR_ONLY) and Coef_h (KHTR_USE_EBT_STRUCT),
-  !! both of which the device refuses.
+  !! both of which the device refuses; calc_resoln_function and calc_sqg_struct (not compared) pass their structure functions, and
+  !! thickness_diffuse_init the khth2d plane it has read (READ_KHTH, left out of the comparison).
   subroutine pass_var_2d(array, MOM_dom, sideflag, complete, position, halo, inner_halo, clock)
     real, dimension(:,:), intent(inout) :: array ; type(MOM_domain_type), intent(inout) :: MOM_dom
     integer, optional, intent(in) :: sideflag, position, halo, inner_halo, clock ; logical, optional, intent(in) :: complete
@@ -139,6 +160,8 @@ contains
     integer, optional, intent(in) :: sideflag, position, halo, inner_halo, clock ; logical, optional, intent(in) :: complete
     call standin_never("pass_var (3-D)")
   end subroutine pass_var_3d
+  !> Bookkeeping only, as before.  do_group_pass is never reached: ePBL's group stays unused and calc_resoln_function, which
+  !! passes cg1, is not compared.
   subroutine create_group_pass(group, array, MOM_dom)
     type(group_pass_type), intent(inout) :: group ; real, dimension(:,:), intent(inout) :: array
     type(MOM_domain_type), intent(inout) :: MOM_dom
@@ -157,6 +180,9 @@ module MOM_grid
     type(MOM_domain_type), pointer :: Domain => NULL()
     integer :: isc, iec, jsc, jec, isd, ied, jsd, jed, IscB, IecB, JscB, JecB, IsdB, IedB, JsdB, JedB, ke
     real, allocatable, dimension(:,:) :: mask2dT, CoriolisBu, geoLonT, geoLatT, Coriolis2Bu, mask2dCu, mask2dCv, mask2dBu, IareaT
+    real, allocatable, dimension(:,:) :: OBCmaskCu, OBCmaskCv, areaT, areaCu, areaCv, bathyT, dF_dx, dF_dy
+    real, allocatable, dimension(:,:) :: dxT, dyT, dxCu, dyCu, dxCv, dyCv, dxBu, dyBu, IdxCu, IdyCu, IdxCv, IdyCv, dx_Cv, dy_Cu
+    real :: Z_ref = 0.0
   end type ocean_grid_type
 end module MOM_grid
 
@@ -167,8 +193,9 @@ module MOM_verticalGrid
     logical :: Boussinesq = .true., semi_Boussinesq = .false.
     real :: Rho0, g_Earth, g_Earth_Z_T2, Angstrom_H, Angstrom_Z, H_subroundoff, dZ_subroundoff
     real :: H_to_Z = 1., Z_to_H = 1., H_to_RZ, RZ_to_H, H_to_m = 1., m_to_H = 1., H_to_MKS = 1., HZ_T_to_m2_s = 1.
-    real :: m2_s_to_HZ_T = 1., HZ_T_to_MKS = 1., H_to_pa = 1., kg_m2_to_H = 1.
-    real, allocatable, dimension(:) :: Rlay
+    real :: m2_s_to_HZ_T = 1., HZ_T_to_MKS = 1., H_to_pa = 1., kg_m2_to_H = 1., H_to_kg_m2 = 1., max_depth = 0.
+    integer :: nk_rho_varies = 0
+    real, allocatable, dimension(:) :: Rlay, g_prime
   end type verticalGrid_type
 end module MOM_verticalGrid
 
@@ -308,7 +335,25 @@ end module MOM_file_parser
 
 module MOM_io
   use, intrinsic :: iso_fortran_env, only : stdout => output_unit, stderr => error_unit
+  use MOM_error_handler, only : standin_never
+  use MOM_domains, only : MOM_domain_type
   implicit none ; public
+contains
+  !> Never reached: only thickness_diffuse_init with READ_KHTH reads a file, and that case is left out of the comparison (the
+  !! plane it reads lands in a private member).  The data come back zero.
+  subroutine MOM_read_data(filename, fieldname, data, MOM_Domain, timelevel, position, scale)
+    character(len=*), intent(in) :: filename, fieldname ; real, dimension(:,:), intent(inout) :: data
+    type(MOM_domain_type), intent(in) :: MOM_Domain ; integer, optional, intent(in) :: timelevel, position
+    real, optional, intent(in) :: scale
+    data(:,:) = 0.0
+    call standin_never("MOM_read_data")
+  end subroutine MOM_read_data
+  !> The directory name with one slash at its end (a string helper: it reads nothing).
+  function slasher(dir)
+    character(len=*), intent(in) :: dir ; character(len=len(dir)+2) :: slasher
+    slasher = trim(dir)
+    if (len_trim(dir) > 0) then ; if (dir(len_trim(dir):len_trim(dir)) /= "/") slasher = trim(dir)//"/" ; endif
+  end function slasher
 end module MOM_io
 
 module gsw_mod_toolbox
@@ -365,10 +410,11 @@ module MOM_diag_mediator
   use MOM_time_manager, only : time_type
   implicit none ; private
   public :: time_type, diag_ctrl, axes_grp, register_diag_field, post_data, query_averaging_enabled, safe_alloc_ptr, safe_alloc_alloc
+  public :: diag_update_remap_grids
   public :: standin_clear_diags, standin_want_diag, standin_diag_size, standin_get_diag
   type :: axes_grp ; integer :: rank = 0 ; end type axes_grp
   type :: diag_ctrl
-    type(axes_grp) :: axesT1, axesTL, axesTi, axesBi
+    type(axes_grp) :: axesT1, axesTL, axesTi, axesBi, axesCu1, axesCv1, axesCuL, axesCvL, axesCui, axesCvi
   end type diag_ctrl
   integer, parameter :: NDMAX = 64
   type :: capture ; real, allocatable :: v(:) ; end type capture
@@ -412,11 +458,18 @@ contains
     n = min(size(out), size(store(m)%v)) ; out(1:n) = store(m)%v(1:n)
   end subroutine standin_get_diag
 
-  integer function register_diag_field(module_name, field_name, axes, init_time, long_name, units, conversion, cmor_long_name)
+  integer function register_diag_field(module_name, field_name, axes, init_time, long_name, units, conversion, cmor_long_name, &
+                                       cmor_field_name, cmor_standard_name, x_cell_method, y_cell_method, v_extensive)
     character(len=*), intent(in) :: module_name, field_name ; type(axes_grp), intent(in) :: axes ; type(time_type), intent(in) :: init_time
     character(len=*), optional, intent(in) :: long_name, units, cmor_long_name ; real, optional, intent(in) :: conversion
+    character(len=*), optional, intent(in) :: cmor_field_name, cmor_standard_name, x_cell_method, y_cell_method
+    logical, optional, intent(in) :: v_extensive
     register_diag_field = want_id(field_name)
   end function register_diag_field
+  !> Nothing to do: no diagnostic is remapped here.
+  subroutine diag_update_remap_grids(diag_cs)
+    type(diag_ctrl), intent(inout) :: diag_cs
+  end subroutine diag_update_remap_grids
   subroutine post_data_2d(diag_field_id, field, diag_cs)
     integer, intent(in) :: diag_field_id ; real, intent(in) :: field(:,:) ; type(diag_ctrl), intent(in) :: diag_cs
     if (diag_field_id < 1 .or. diag_field_id > NDMAX) return
@@ -454,7 +507,10 @@ end module MOM_diag_mediator
 module MOM_debugging
   use MOM_hor_index, only : hor_index_type
   implicit none ; private
-  public :: hchksum, Bchksum
+  public :: hchksum, Bchksum, uvchksum
+  interface uvchksum
+    module procedure uvchksum_2d, uvchksum_3d
+  end interface
   interface hchksum
     module procedure hchksum_2d, hchksum_3d
   end interface
@@ -470,14 +526,26 @@ contains
     real, intent(in) :: array(:,:,:) ; character(len=*), intent(in) :: mesg ; type(hor_index_type), intent(in) :: HI
     integer, optional, intent(in) :: haloshift ; real, optional, intent(in) :: unscale
   end subroutine hchksum_3d
+  subroutine uvchksum_2d(mesg, arrayU, arrayV, HI, haloshift, symmetric, omit_corners, unscale, logunit, scalar_pair)
+    character(len=*), intent(in) :: mesg ; real, intent(in) :: arrayU(:,:), arrayV(:,:) ; type(hor_index_type), intent(in) :: HI
+    integer, optional, intent(in) :: haloshift, logunit ; logical, optional, intent(in) :: symmetric, omit_corners, scalar_pair
+    real, optional, intent(in) :: unscale
+  end subroutine uvchksum_2d
+  subroutine uvchksum_3d(mesg, arrayU, arrayV, HI, haloshift, symmetric, omit_corners, unscale, logunit, scalar_pair)
+    character(len=*), intent(in) :: mesg ; real, intent(in) :: arrayU(:,:,:), arrayV(:,:,:) ; type(hor_index_type), intent(in) :: HI
+    integer, optional, intent(in) :: haloshift, logunit ; logical, optional, intent(in) :: symmetric, omit_corners, scalar_pair
+    real, optional, intent(in) :: unscale
+  end subroutine uvchksum_3d
 end module MOM_debugging
 
 module MOM_stochastics
   implicit none ; public
   type :: stochastic_CS
-    logical :: pert_epbl = .false.
+    logical :: pert_epbl = .false., skeb_use_gm = .false.
     integer :: id_epbl1_wts = -1, id_epbl2_wts = -1
+    real :: skeb_gm_coef = 0.0
     real, allocatable, dimension(:,:) :: epbl1_wts, epbl2_wts
+    real, allocatable, dimension(:,:,:) :: skeb_diss
   end type stochastic_CS
 end module MOM_stochastics
 
@@ -562,55 +630,74 @@ contains
   end subroutine boundary_k_range
 end module MOM_hor_bnd_diffusion
 
+!> Types and constants only: the device refuses open boundaries and the doors leave the OBC pointer null, so that no member is
+!! ever read.  The module has no procedure.
+module MOM_open_boundary
+  implicit none ; public
+  integer, parameter :: OBC_NONE = 0, OBC_DIRECTION_N = 100, OBC_DIRECTION_S = 200, OBC_DIRECTION_E = 300, OBC_DIRECTION_W = 400
+  type :: OBC_segment_type ; logical :: open = .false. ; end type OBC_segment_type
+  type :: ocean_OBC_type
+    logical :: open_u_BCs_exist_globally = .false., open_v_BCs_exist_globally = .false.
+    logical :: u_E_OBCs_on_PE = .false., u_W_OBCs_on_PE = .false., v_N_OBCs_on_PE = .false., v_S_OBCs_on_PE = .false.
+    integer :: Is_u_E_obc, Ie_u_E_obc, js_u_E_obc, je_u_E_obc, Is_u_W_obc, Ie_u_W_obc, js_u_W_obc, je_u_W_obc
+    integer :: is_v_N_obc, ie_v_N_obc, Js_v_N_obc, Je_v_N_obc, is_v_S_obc, ie_v_S_obc, Js_v_S_obc, Je_v_S_obc
+    integer, allocatable :: segnum_u(:,:), segnum_v(:,:)
+    type(OBC_segment_type), allocatable :: segment(:)
+  end type ocean_OBC_type
+end module MOM_open_boundary
+
 #elif !defined(STANDINS_AFTER_ENERGETIC_PBL)
 
 module MOM_variables
   use MOM_EOS, only : EOS_type
   implicit none ; public
   type :: thermo_var_ptrs
-    real, pointer, dimension(:,:,:) :: T => NULL(), S => NULL()
+    real, pointer, dimension(:,:,:) :: T => NULL(), S => NULL(), varT => NULL(), varS => NULL(), covarTS => NULL()
+    real, pointer, dimension(:,:) :: p_surf => NULL()
     type(EOS_type), pointer :: eqn_of_state => NULL()
+    real :: P_Ref = 0.0
     real, allocatable, dimension(:,:,:) :: SpV_avg
+    integer :: valid_SpV_halo = -1
   end type thermo_var_ptrs
+  type :: cont_diag_ptrs
+    real, pointer, dimension(:,:,:) :: uhGM => NULL(), vhGM => NULL()
+  end type cont_diag_ptrs
   type :: vertvisc_type
     real, allocatable, dimension(:,:) :: ustar_BBL, BBL_meanKE_loss, BBL_meanKE_loss_sqrtCd
     real, pointer, dimension(:,:) :: h_ML => NULL()
   end type vertvisc_type
 end module MOM_variables
 
-module MOM_interface_heights
+!> calc_resoln_function's wave speeds: not compared (the device has no calc_resoln_function), so both procedures count as FATAL.
+!! VarMix_init calls wave_speed_init only with a resolution function, MEKE, an EBT structure or the FGNV streamfunction.
+module MOM_wave_speed
+  use MOM_error_handler, only : standin_never
   use MOM_grid, only : ocean_grid_type
   use MOM_verticalGrid, only : verticalGrid_type
   use MOM_unit_scaling, only : unit_scale_type
   use MOM_variables, only : thermo_var_ptrs
-  implicit none ; private
-  public :: thickness_to_dz
-  interface thickness_to_dz
-    module procedure thickness_to_dz_jslice, thickness_to_dz_3d
-  end interface
+  implicit none ; public
+  type :: wave_speed_CS ; integer :: dummy = 0 ; end type wave_speed_CS
 contains
-  !> The j-slice form, Boussinesq only: dz = GV%H_to_Z * h.  The device refuses non-Boussinesq contexts, so the specific-volume
-  !! arm of the reference's routine cannot be reached by anything compared here and is not stood in for.
-  subroutine thickness_to_dz_jslice(h, tv, dz, j, G, GV, halo_size)
-    type(ocean_grid_type), intent(in) :: G ; type(verticalGrid_type), intent(in) :: GV
-    real, dimension(G%isd:G%ied,G%jsd:G%jed,GV%ke), intent(in) :: h ; type(thermo_var_ptrs), intent(in) :: tv
-    real, dimension(G%isd:G%ied,GV%ke), intent(inout) :: dz ; integer, intent(in) :: j ; integer, optional, intent(in) :: halo_size
-    integer :: i, k
-    do k = 1, GV%ke ; do i = G%isc, G%iec ; dz(i,k) = GV%H_to_Z * h(i,j,k) ; enddo ; enddo
-  end subroutine thickness_to_dz_jslice
-  !> The 3-D form, which only Calc_kappa_shear_vertex calls (compiled with its module, never run: the device refuses
-  !! VERTEX_SHEAR): the same body over the computational domain and halo_size points around it.
-  subroutine thickness_to_dz_3d(h, tv, dz, G, GV, US, halo_size)
+  subroutine wave_speed(h, tv, G, GV, US, cg1, CS, halo_size, use_ebt_mode, mono_N2_column_fraction, mono_N2_depth, modal_structure)
     type(ocean_grid_type), intent(in) :: G ; type(verticalGrid_type), intent(in) :: GV ; type(unit_scale_type), intent(in) :: US
     real, dimension(G%isd:G%ied,G%jsd:G%jed,GV%ke), intent(in) :: h ; type(thermo_var_ptrs), intent(in) :: tv
-    real, dimension(G%isd:G%ied,G%jsd:G%jed,GV%ke), intent(inout) :: dz ; integer, optional, intent(in) :: halo_size
-    integer :: i, j, k, halo
-    halo = 0 ; if (present(halo_size)) halo = max(halo_size, 0)
-    do k = 1, GV%ke ; do j = G%jsc-halo, G%jec+halo ; do i = G%isc-halo, G%iec+halo
-      dz(i,j,k) = GV%H_to_Z * h(i,j,k)
-    enddo ; enddo ; enddo
-  end subroutine thickness_to_dz_3d
-end module MOM_interface_heights
+    real, dimension(G%isd:G%ied,G%jsd:G%jed), intent(out) :: cg1 ; type(wave_speed_CS), intent(in) :: CS
+    integer, optional, intent(in) :: halo_size ; logical, optional, intent(in) :: use_ebt_mode
+    real, optional, intent(in) :: mono_N2_column_fraction, mono_N2_depth
+    real, dimension(G%isd:G%ied,G%jsd:G%jed,GV%ke), optional, intent(out) :: modal_structure
+    cg1(:,:) = 0.0 ; if (present(modal_structure)) modal_structure(:,:,:) = 0.0
+    call standin_never("wave_speed")
+  end subroutine wave_speed
+  subroutine wave_speed_init(CS, GV, use_ebt_mode, mono_N2_column_fraction, mono_N2_depth, remap_answers_2018, remap_answer_date, &
+                             better_speed_est, om4_remap_via_sub_cells, min_speed, wave_speed_tol, c1_thresh)
+    type(wave_speed_CS), intent(inout) :: CS ; type(verticalGrid_type), intent(in) :: GV
+    logical, optional, intent(in) :: use_ebt_mode, remap_answers_2018, better_speed_est, om4_remap_via_sub_cells
+    real, optional, intent(in) :: mono_N2_column_fraction, mono_N2_depth, min_speed, wave_speed_tol, c1_thresh
+    integer, optional, intent(in) :: remap_answer_date
+    call standin_never("wave_speed_init")
+  end subroutine wave_speed_init
+end module MOM_wave_speed
 
 module MOM_wave_interface
   use MOM_grid, only : ocean_grid_type

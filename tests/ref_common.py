@@ -22,6 +22,16 @@ def _min(a, b):
     return np.where(b < a, b, a)
 
 
+def _dmax(a, b):
+    """MAX(a, b) as the compiled reference evaluates it where a tie shows: b on a tie (dmax on the device)."""
+    return np.where(a > b, a, b)
+
+
+def _dmin(a, b):
+    """MIN(a, b) likewise: b on a tie (dmin on the device)."""
+    return np.where(a < b, a, b)
+
+
 def _faces(d, dir):
     """Row and column ranges of the faces (u: I = isc-1..iec, j = jsc..jec; v: i = isc..iec, J = jsc-1..jec) and the offset of
     the cell on the far side."""

@@ -1,8 +1,10 @@
 """The loader of oracle/_ref/libref_param.so -- the reference's own MOM_EOS_Wright*.F90, MOM_EOS_linear.F90,
-MOM_intrinsic_functions.F90, MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90 and MOM_neutral_diffusion.F90 (with
-MOM_EOS.F90) compiled where they
+MOM_intrinsic_functions.F90, MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90, MOM_neutral_diffusion.F90,
+MOM_isopycnal_slopes.F90, MOM_lateral_mixing_coeffs.F90 and MOM_thickness_diffuse.F90 (with MOM_EOS.F90 and
+MOM_interface_heights.F90) compiled where they
 lie against the interface stand-ins of oracle/ref_standins.F90, behind the bind(C) doors of oracle/ref_param_shim.F90 -- and the
-one place where the members of abi.OpacityParams, abi.EnergeticPBLParams, abi.KappaShearParams and abi.NeutralDiffusionParams are
+one place where the members of abi.OpacityParams, abi.EnergeticPBLParams, abi.KappaShearParams, abi.NeutralDiffusionParams,
+abi.VarMixParams and abi.ThicknessDiffuseParams are
 mapped to the names the reference reads with get_param.  Of MOM_neutral_diffusion the door hands out the tracers, their content
 tendencies and the two transports; the positions and effective thicknesses are private to the compiled module (see
 neutral_diffusion below).  Test infrastructure:
@@ -34,7 +36,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.ref_diag_size.restype = C.c_int
         for n in ("ref_opacity", "ref_energetic_PBL", "ref_absorbRemainingSW", "ref_sumSWoverBands", "ref_Calculate_kappa_shear",
-                  "ref_neutral_diffusion", "ref_standin_never_count"):
+                  "ref_neutral_diffusion", "ref_standin_never_count", "ref_calc_slope_functions", "ref_thickness_diffuse"):
             getattr(_lib, n).restype = C.c_int
     return _lib
 
@@ -552,6 +554,275 @@ def standin_never_count():
     return int(lib().ref_standin_never_count())
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# MOM_lateral_mixing_coeffs (with MOM_isopycnal_slopes) and MOM_thickness_diffuse
+
+# the grid planes the two modules read, in the order of setup_lateral (oracle/ref_param_shim.F90)
+LATERAL_METRICS = ("mask2dT", "mask2dCu", "mask2dCv", "IdxCu", "IdyCu", "IdxCv", "IdyCv", "dxCu", "dyCu", "dxCv", "dyCv", "dy_Cu", "dx_Cv",
+                   "areaT", "IareaT", "areaCu", "areaCv", "bathyT")
+LATERAL_EOS_NAMES = {abi.LINEAR: "LINEAR", abi.WRIGHT: "WRIGHT", abi.WRIGHT_FULL: "WRIGHT_FULL", abi.WRIGHT_REDUCED: "WRIGHT_REDUCED",
+                     abi.UNESCO: "UNESCO", abi.ROQUET_RHO: "ROQUET_RHO", abi.JACKETT06: "JACKETT_06", abi.ROQUET_SPV: "ROQUET_SPV"}
+# member of abi.VarMixParams -> (the name VarMix_init reads (MOM_lateral_mixing_coeffs.F90:1589-1758), kind, the unit of the member)
+VARMIX_PARAM_NAMES = {
+    "use_stored_slopes": ("USE_STORED_SLOPES", "bool", ""), "use_simpler_Eady_growth_rate": ("USE_SIMPLER_EADY_GROWTH_RATE", "bool", ""),
+    "full_depth_Eady_growth_rate": ("FULL_DEPTH_EADY_GROWTH_RATE", "bool", ""), "kappa_smooth": ("KD_SMOOTH", "real", "H Z T-1"),
+    "Visbeck_S_max": ("VISBECK_MAX_SLOPE", "real", "Z L-1"), "Visbeck_L_scale": ("VISBECK_L_SCALE", "real", "L"),
+    "Eady_GR_D_scale": ("EADY_GROWTH_RATE_D_SCALE", "real", "Z"), "cropping_distance": ("EADY_GROWTH_RATE_CROPPING_DISTANCE", "real", "Z"),
+    "VarMix_Ktop": ("VARMIX_KTOP", "int", ""), "h_min_N2": ("MIN_DZ_FOR_SLOPE_N2", "real", "H"),
+    "use_stanley_iso": ("USE_STANLEY_ISO", "bool", ""), "debug": ("DEBUG", "bool", ""),
+}
+# Not parameters of VarMix_init: calculate_Eady_growth_rate is `use_MEKE or KHTR_SLOPE_CFF > 0 or KHTH_SLOPE_CFF > 0` (:1604): the
+# table sets KHTR_SLOPE_CFF = 1 for it (KHTH_SLOPE_CFF stays 0: thickness_diffuse reads it too); VISBECK_MAX_SLOPE and
+# VISBECK_L_SCALE are read only then (:1688, :1753).  max_depth is GV%max_depth and Angstrom_Z GV%Angstrom_Z; H_to_Z, H_to_RZ,
+# Z_to_H_fill (GV%Z_to_H), g_Earth and Rho0 are GV's; Z_to_L and L_to_m come from the Z and L *_RESCALE_POWERs.  open_bcs is the
+# OBC pointer (null in the door) and non_Boussinesq GV%Boussinesq (true in the door).
+VARMIX_NOT_PARAMS = ("calculate_Eady_growth_rate", "max_depth", "H_to_Z", "Z_to_L", "L_to_m", "H_to_RZ", "Z_to_H_fill", "Angstrom_Z",
+                     "g_Earth", "Rho0", "open_bcs", "non_Boussinesq")
+# output of varmix_ref.run / the device -> where the reference has it: a public member of VarMix_CS, or the name of a diagnostic
+# that calc_slope_functions (:725-735) or calc_Visbeck_coeffs_old (:943-945) posts
+VARMIX_MEMBERS = ("SN_u", "SN_v", "slope_x", "slope_y")
+VARMIX_DIAG_NAMES = {"N2_u": "N2_u", "N2_v": "N2_v", "S2_u": "S2_u", "S2_v": "S2_v", "dzu": "dzu_Visbeck", "dzv": "dzv_Visbeck",
+                     "dzSxN": "dzSxN", "dzSyN": "dzSyN"}
+# dzu, dzv, dzSxN and dzSyN are locals of calc_slope_functions, but it posts them (:726-729, registered :1815-1826): nothing that
+# the device or the restatement hands out is hidden in the compiled module.
+VARMIX_NOT_EXPOSED = ()
+VARMIX_CORE = VARMIX_MEMBERS                        # in every file (slope_x, slope_y where the case stores slopes)
+VARMIX_DROP_ORDER = ("dzSyN", "dzSxN", "dzv", "dzu", "N2_v", "N2_u", "S2_v", "S2_u")   # left out of a file over the size limit, in this order
+# member of abi.ThicknessDiffuseParams -> (the name thickness_diffuse_init reads (MOM_thickness_diffuse.F90:2207-2404), kind, unit)
+THICKDIFF_PARAM_NAMES = {
+    "thickness_diffuse": ("THICKNESSDIFFUSE", "bool", ""), "Khth": ("KHTH", "real", "L2 T-1"), "read_khth": ("READ_KHTH", "bool", ""),
+    "Khth_Min": ("KHTH_MIN", "real", "L2 T-1"), "Khth_Max": ("KHTH_MAX", "real", "L2 T-1"), "max_Khth_CFL": ("KHTH_MAX_CFL", "real", ""),
+    "slope_max": ("KHTH_SLOPE_MAX", "real", "Z L-1"), "kappa_smooth": ("KD_SMOOTH", "real", "H Z T-1"),
+    "Kh_eta_bg": ("KH_ETA_CONST", "real", "L2 T-1"), "Kh_eta_vel": ("KH_ETA_VEL_SCALE", "real", "L T-1"),
+    "use_FGNV_streamfn": ("KHTH_USE_FGNV_STREAMFUNCTION", "bool", ""), "use_stanley_gm": ("USE_STANLEY_GM", "bool", ""),
+    "detangle_interfaces": ("DETANGLE_INTERFACES", "bool", ""), "use_GME": ("USE_GME", "bool", ""), "use_MEKE": ("USE_MEKE", "bool", ""),
+}
+# Not parameters of thickness_diffuse_init: Z_to_L (the Z and L powers), Z_to_H_fill (GV%Z_to_H), nkml (GV%nkml), open_bcs,
+# non_Boussinesq (GV%Boussinesq); use_variable_mixing is VarMix%use_variable_mixing, which VarMix_init sets; use_Kh_in_MEKE is
+# read only with USE_MEKE; GMwork is `the diagnostic GMwork is registered`; skeb_use_gm is STOCH%skeb_use_gm (false in the door).
+THICKDIFF_NOT_PARAMS = ("Z_to_L", "Z_to_H_fill", "nkml", "open_bcs", "non_Boussinesq", "use_variable_mixing", "use_Kh_in_MEKE", "GMwork",
+                        "skeb_use_gm")
+THICKDIFF_CORE = ("h", "uhtr", "vhtr")              # in every file
+THICKDIFF_DROP_ORDER = ("vhGM", "uhGM")             # left out of a file over the size limit, in this order (the chain: CHAIN_DROP_ORDER)
+THICKDIFF_OUT = THICKDIFF_CORE + ("uhGM", "vhGM")
+# READ_KHTH: thickness_diffuse_init reads the plane from a file (:2217-2237) into a private member and passes it through
+# pass_var: the khth2d case stays outside the comparison (the MOM_read_data stand-in counts as a path out of the compiled files).
+THICKDIFF_LEFT_OUT = ("khth2d",)
+UNITY = dict(T=1.0, L=1.0, H=1.0, Z=1.0, R=1.0)
+
+
+def lateral_units(GV, sc=None, max_depth=0.0):
+    """The *_RESCALE_POWERs, vgr, vgx and the to-MKS factors of a lateral case.  `sc` names the factors by which a quantity in
+    seconds, metres (horizontal), thickness units, metres (vertical) and kg m-3 is multiplied (the T, L, H, Z, R of
+    tests/test_thickness_diffuse_cpu.scaled): s_to_T, m_to_L, m_to_H, m_to_Z and kg_m3_to_R.  GV is checked against them."""
+    sc = dict(UNITY, **(sc or {}))
+    T_, L, Hs, Z, Rr = (sc[k] for k in "TLHZR")
+    powers = dict(Z=-_power_of_two(Z, "m_to_Z"), L=-_power_of_two(L, "m_to_L"), T=-_power_of_two(T_, "s_to_T"), R=-_power_of_two(Rr, "kg_m3_to_R"))
+    _power_of_two(Hs, "m_to_H")
+    assert GV.H_to_Z == Z / Hs and GV.Z_to_H == Hs / Z, "GV%H_to_Z is not what the factors give"
+    assert GV.H_to_RZ == (GV.Rho0 * Z) / Hs or GV.H_to_RZ == GV.Rho0 * (Z / Hs), "GV%H_to_RZ is not Rho0 * H_to_Z"
+    gv = np.array([GV.Rho0, GV.g_Earth * (Z / L) ** 2, GV.Angstrom_H, GV.H_to_Z * GV.Angstrom_H, GV.H_subroundoff, GV.dZ_subroundoff,
+                   GV.H_to_Z, GV.Z_to_H, GV.H_to_RZ, GV.RZ_to_H, 1.0 / Hs, Hs, 1.0 / Hs, T_ / (Hs * Z)])
+    gx = np.array([GV.g_Earth, Hs * Z / T_, (GV.Rho0 / Rr) / Hs, float(max_depth)])
+    to_mks = {"": 1.0, "H Z T-1": T_ / (Hs * Z), "Z L-1": L / Z, "L": 1.0 / L, "Z": 1.0 / Z, "H": 1.0 / Hs, "L2 T-1": T_ / (L * L),
+              "L T-1": T_ / L}
+    return powers, gv, gx, to_mks, sc
+
+
+def _entries(P, names, to_mks):
+    ent = []
+    for member, (name, kind, unit) in names.items():
+        v = getattr(P, member)
+        ent.append((name, float(v) * to_mks[unit] if kind == "real" else int(v) if kind == "int" else bool(v)))
+    return ent
+
+
+def _eos_entries(eos):
+    if eos is None:
+        return []
+    ent = [("EQN_OF_STATE", LATERAL_EOS_NAMES[eos.form])]
+    if eos.form == abi.LINEAR:
+        ent += [("RHO_T0_S0", float(eos.Rho_T0_S0)), ("DRHO_DT", float(eos.dRho_dT)), ("DRHO_DS", float(eos.dRho_dS)),
+                ("DRHO_DP", float(eos.dRho_dp))]
+    return ent
+
+
+def varmix_table(P, GV, eos=None, sc=None):
+    """The parameter table of a calc_slope_functions case: members in the model's units go back to the MKS values a parameter file
+    holds.  The unit factors among the members are checked against what unit_scaling_init and GV will give."""
+    powers, gv, gx, to_mks, sc = lateral_units(GV, sc, P.max_depth)
+    assert set(VARMIX_PARAM_NAMES) | set(VARMIX_NOT_PARAMS) == {n for n, _ in abi.VarMixParams._fields_}
+    assert (P.H_to_Z, P.H_to_RZ, P.Z_to_H_fill, P.g_Earth, P.Rho0) == (GV.H_to_Z, GV.H_to_RZ, GV.Z_to_H, GV.g_Earth, GV.Rho0), "not GV's"
+    assert P.Z_to_L == sc["L"] / sc["Z"] and P.L_to_m == 1.0 / sc["L"] and P.Angstrom_Z == GV.Angstrom_H * GV.H_to_Z, "not what US derives"
+    assert not P.open_bcs and not P.non_Boussinesq
+    ent = [("KHTR_SLOPE_CFF", 1.0 if P.calculate_Eady_growth_rate else 0.0), ("KHTH_SLOPE_CFF", 0.0)]
+    return ent + _entries(P, VARMIX_PARAM_NAMES, to_mks) + _eos_entries(eos), powers, gv, gx
+
+
+def thickdiff_table(P, GV, eos=None, sc=None, stored=False):
+    """The parameter table of a thickness_diffuse case; USE_STORED_SLOPES (read by VarMix_init) where the case hands slopes over."""
+    powers, gv, gx, to_mks, sc = lateral_units(GV, sc)
+    assert set(THICKDIFF_PARAM_NAMES) | set(THICKDIFF_NOT_PARAMS) == {n for n, _ in abi.ThicknessDiffuseParams._fields_}
+    assert P.Z_to_L == sc["L"] / sc["Z"] and P.Z_to_H_fill == GV.Z_to_H, "not what US and GV derive"
+    assert not (P.use_variable_mixing or P.use_Kh_in_MEKE or P.GMwork or P.skeb_use_gm or P.nkml or P.open_bcs or P.non_Boussinesq)
+    ent = [("KHTH_SLOPE_CFF", 0.0), ("KHTR_SLOPE_CFF", 0.0), ("USE_STORED_SLOPES", bool(stored))]
+    return ent + _entries(P, THICKDIFF_PARAM_NAMES, to_mks) + _eos_entries(eos), powers, gv, gx
+
+
+def _on_a_large_stack(fn, *args):
+    """fn(*args) on a thread with a 1 GiB stack: the lateral routines hold some twenty whole 3-D arrays as automatic variables, which
+    at 75 layers pass the 8 MiB a main thread usually has."""
+    import threading
+    box = []
+    old = threading.stack_size(1 << 30)
+    try:
+        t = threading.Thread(target=lambda: box.append(fn(*args)))
+        t.start(); t.join()
+    finally:
+        threading.stack_size(old)
+    return box[0]
+
+
+def _metrics(M):
+    return np.ascontiguousarray(np.stack([M[G[n]] for n in LATERAL_METRICS]), dtype=np.float64)
+
+
+def _layers(d, GV, Rlay, g_prime):
+    if Rlay is None:
+        Rlay, g_prime = abi.layer_densities(d.nk, Rho0=GV.Rho0, g_Earth=GV.g_Earth)
+    gp = np.zeros(d.nk + 1); gp[:d.nk] = g_prime          # GV%g_prime has nk + 1 entries; the last is never read
+    return _c(Rlay), gp
+
+
+def varmix_ranges(d, P, nk=None):
+    """name -> (k, j, i) slices of what calc_slope_functions writes of each output (the ranges of the reference's loops, halo = 1;
+    tests/test_ref_parity_cpu.py holds the restatement's written words to exactly these)."""
+    nz = d.nk if nk is None else nk
+    ni, nj = d.ni, d.nj
+    xs, ys = d.sl(-2, ni, -1, nj), d.sl(-1, ni, -2, nj)                 # calc_isoneutral_slopes with halo = 1 (:145, :255, :432)
+    ru, rv = d.sl(-1, ni - 1, 0, nj - 1), d.sl(0, ni - 1, -1, nj - 1)
+    allk, mid = slice(0, nz + 1), slice(1, nz)
+    out = {}
+    if not P.calculate_Eady_growth_rate:
+        return out
+    if P.use_stored_slopes:
+        out.update(slope_x=(mid,) + xs, slope_y=(mid,) + ys, N2_u=(allk,) + xs, N2_v=(allk,) + ys)
+    if P.use_simpler_Eady_growth_rate:
+        box = d.sl(-1, ni, -1, nj)
+        out.update(dzu=(allk,) + xs, dzv=(allk,) + ys, dzSxN=(allk,) + xs, dzSyN=(allk,) + ys, SN_u=box, SN_v=box)
+    elif P.use_stored_slopes:
+        out.update(SN_u=(slice(None), slice(None)), SN_v=(slice(None), slice(None)), S2_u=ru, S2_v=rv)
+    else:
+        out.update(SN_u=ru, SN_v=rv)
+    return out
+
+
+def thickdiff_ranges(d):
+    """name -> (j, i) slices of what thickness_diffuse writes: h on the computational domain, the fluxes on their faces."""
+    from tests import helpers as H
+    return dict(h=H.interior(d, "h"), uhtr=H.interior(d, "u"), vhtr=H.interior(d, "v"), uhGM=H.interior(d, "u"), vhGM=H.interior(d, "v"))
+
+
+def calc_slope_functions(d, M, GV, P, inp, dt, eos=None, give_ps=False, ncalls=1, inp2=None, sc=None, Rlay=None, g_prime=None,
+                         table_extra=(), diag=tuple(VARMIX_DIAG_NAMES)):
+    """unit_scaling_init, EOS_init and VarMix_init through the table, then calc_slope_functions `ncalls` times on the same VarMix_CS
+    (round r on the h of `inp2` where given, else of `inp` again), with the arguments of tests/varmix_ref.run.  Returns SN_u, SN_v,
+    slope_x, slope_y (the public members, where VarMix_init allocates them), L2u, L2v likewise, and every diagnostic of `diag`
+    that was posted, by the names of varmix_ref.outputs: whole arrays, which outside varmix_ranges hold whatever the reference
+    left; and the FATAL count.  dt <= 0: the inits only."""
+    L = lib()
+    ent, powers, gv, gx = varmix_table(P, GV, eos, sc)
+    _table(ent + list(table_extra), powers)
+    for n in diag:
+        L.ref_want_diag(VARMIX_DIAG_NAMES[n].encode())
+    ni_mem, nj_mem, idx = _tile(d)
+    Rl, gp = _layers(d, GV, Rlay, g_prime)
+    rounds = [inp] + [inp2 if inp2 is not None else inp] * (ncalls - 1)
+    h = np.ascontiguousarray(np.stack([r["h"] for r in rounds]), dtype=np.float64)
+    a = dict(T=_c(inp["T"]), S=_c(inp["S"])) if eos is not None else {}
+    if give_ps:
+        a["p_surf"] = _c(inp["p_surf"])
+    before = dict({n: x.copy() for n, x in a.items()}, h=h.copy())
+    o2 = {n: np.full(d.shape2(), np.nan) for n in ("SN_u", "SN_v", "L2u", "L2v")}
+    o3 = {n: np.full(d.shape3(d.nk + 1), np.nan) for n in ("slope_x", "slope_y")}
+    has = (C.c_int * 3)(0, 0, 0)
+    fatal = _on_a_large_stack(L.ref_calc_slope_functions, C.c_int(ni_mem), C.c_int(nj_mem), idx, C.c_int(d.nk), _p(gv), _p(gx), _p(_metrics(M)), _p(Rl), _p(gp),
+                                       C.c_int(ncalls), _p(h), _p(a.get("T")), _p(a.get("S")), _p(a.get("p_surf")), C.c_double(dt),
+                                       _p(o2["SN_u"]), _p(o2["SN_v"]), _p(o3["slope_x"]), _p(o3["slope_y"]), _p(o2["L2u"]), _p(o2["L2v"]), has)
+    if fatal:
+        return None, fatal
+    out = {}
+    if has[2]:
+        out.update(L2u=o2["L2u"], L2v=o2["L2v"])
+    if not dt > 0.0:
+        return out, fatal
+    assert np.array_equal(h, before["h"], equal_nan=True), "h is only read"
+    for n in a:
+        assert np.array_equal(a[n], before[n], equal_nan=True), n + " is only read"
+    if has[0]:
+        out.update(SN_u=o2["SN_u"], SN_v=o2["SN_v"])
+    if has[1]:
+        out.update(o3)
+    for n in diag:
+        name = VARMIX_DIAG_NAMES[n]
+        if L.ref_diag_size(name.encode()) > 0:
+            out[n] = _diag(name, d.shape2() if n in ("S2_u", "S2_v") else d.shape3(d.nk + 1))
+    return out, fatal
+
+
+def thickness_diffuse(d, M, GV, P, inp, dt, eos=None, give_ps=False, stored=False, ncalls=1, sc=None, chain=None, table_extra=(),
+                      diag=("uhGM", "vhGM"), Rlay=None, g_prime=None):
+    """unit_scaling_init, EOS_init, VarMix_init and thickness_diffuse_init through the table, then thickness_diffuse `ncalls` times on
+    the same control structures, with the arguments of tests/thickdiff_ref.run.  `stored`: inp["slope_x"], inp["slope_y"] are copied
+    into VarMix%slope_x, VarMix%slope_y (USE_STORED_SLOPES true).  `chain`, an abi.VarMixParams: every round first runs
+    calc_slope_functions on the same VarMix_CS, whose stored slopes thickness_diffuse reads; slope_x, slope_y, SN_u, SN_v come
+    back too.  Returns h, uhtr, vhtr; uhGM, vhGM (CDp's, allocated where the diagnostics of those names are asked for); uhGM_diag,
+    vhGM_diag (what the module posts); and the FATAL count.  dt <= 0: the inits only."""
+    L = lib()
+    assert not (stored and chain is not None)
+    if chain is not None:
+        ent, powers, gv, gx = varmix_table(chain, GV, eos, sc)
+        ent2, powers2, _, _ = thickdiff_table(P, GV, eos, sc, stored=bool(chain.use_stored_slopes))
+        assert powers == powers2 and chain.kappa_smooth == P.kappa_smooth and chain.use_stored_slopes, "one table serves both inits"
+        ent = [e for e in ent2 if e[0] not in dict(ent)] + ent
+    else:
+        ent, powers, gv, gx = thickdiff_table(P, GV, eos, sc, stored=stored)
+    _table(ent + list(table_extra), powers)
+    for n in diag:
+        L.ref_want_diag(n.encode())
+    ni_mem, nj_mem, idx = _tile(d)
+    Rl, gp = _layers(d, GV, Rlay, g_prime)
+    a = dict(T=_c(inp["T"]), S=_c(inp["S"])) if eos is not None else {}
+    if give_ps:
+        a["p_surf"] = _c(inp["p_surf"])
+    before = {n: x.copy() for n, x in a.items()}
+    io = {n: _c(inp[n]).copy() for n in THICKDIFF_CORE}
+    gm = {n: np.full(d.shape3(), np.nan) for n in ("uhGM", "vhGM")}
+    sl = {n: (_c(inp[n]).copy() if stored else np.full(d.shape3(d.nk + 1), np.nan)) for n in ("slope_x", "slope_y")}
+    sn = {n: np.full(d.shape2(), np.nan) for n in ("SN_u", "SN_v")}
+    has = (C.c_int * 2)(0, 0)
+    mode = 2 if chain is not None else 1 if stored else 0
+    fatal = _on_a_large_stack(L.ref_thickness_diffuse, C.c_int(ni_mem), C.c_int(nj_mem), idx, C.c_int(d.nk), _p(gv), _p(gx), _p(_metrics(M)), _p(Rl), _p(gp),
+                                    C.c_int(ncalls), C.c_int(mode), _p(io["h"]), _p(io["uhtr"]), _p(io["vhtr"]), _p(a.get("T")),
+                                    _p(a.get("S")), _p(a.get("p_surf")), C.c_double(dt), _p(sl["slope_x"]), _p(sl["slope_y"]),
+                                    _p(sn["SN_u"]), _p(sn["SN_v"]), _p(gm["uhGM"]), _p(gm["vhGM"]), has)
+    if fatal:
+        return None, fatal
+    if not dt > 0.0:
+        return {}, fatal
+    for n in a:
+        assert np.array_equal(a[n], before[n], equal_nan=True), n + " is only read"
+    out = dict(io)
+    for m, n in enumerate(("uhGM", "vhGM")):
+        if has[m]:
+            out[n] = gm[n]
+        if n in diag and L.ref_diag_size(n.encode()) > 0:
+            out[n + "_diag"] = _diag(n, d.shape3())
+    if chain is not None:
+        out.update(sl); out.update(sn)
+    return out, fatal
+
+
 def ndiff_ranges(d):
     """The ranges tests/test_neutral_diffusion_gpu.py's _check compares on, by output."""
     from tests import helpers as H
@@ -582,6 +853,42 @@ NDIFF_CORE = ("tracers",)                                          # in every fi
 NDIFF_DROP_ORDER = ("tendency", "trans_y_2d", "trans_x_2d")        # what a file that would pass the size limit leaves out, in this order
 
 
+# (case, EOS form or None, grid, keyword arguments) of calc_slope_functions: every case on the island basin at 4 layers (land, wet halo
+# corners, Angstrom bands), eady once per EOS form there (the dispatch); eady, visbeck and just_e on the bowl at 1, 2 and 8 layers
+# (no interior interface, exactly one; vert_fill_TS has separate first, middle and last steps; at one layer the reference's
+# vert_fill_TS would read layer 2, so the two cases with an equation of state are replaced by their layered twins); eady_diag and
+# visbeck_diag on the edge torus at 3
+_OTHER_FORMS = (abi.LINEAR, abi.WRIGHT_FULL, abi.WRIGHT_REDUCED, abi.UNESCO, abi.ROQUET_RHO, abi.JACKETT06, abi.ROQUET_SPV)
+GOLDEN_VARMIX = tuple((n, abi.WRIGHT, "island_basin", dict(nk=4)) for n in (
+    "eady", "eady_diag", "eady_nocrop", "eady_tie", "eady_noeos", "visbeck", "visbeck_diag", "visbeck_neg", "visbeck_noeos", "just_e", "just_e_full")) + tuple(
+    ("eady", f, "island_basin", dict(nk=4)) for f in _OTHER_FORMS) + tuple(
+    (n, abi.WRIGHT, "benchmark_small", dict(nk=nk)) for nk in (2, 8) for n in ("eady", "visbeck", "just_e")) + tuple(
+    (n, abi.WRIGHT, "benchmark_small", dict(nk=1)) for n in ("eady_noeos", "visbeck_noeos", "just_e")) + (
+    ("eady_diag", abi.WRIGHT, "torus", dict(nk=3)), ("visbeck_diag", abi.WRIGHT, "torus", dict(nk=3)))
+# likewise of thickness_diffuse: every case but khth2d (THICKDIFF_LEFT_OUT) on the island basin at 4, eos once per form; eos and
+# noeos on the bowl at 2 and 8, noeos at 1; eos and slopes_noeos on the edge torus at 3; and the chain (calc_slope_functions, whose
+# stored slopes thickness_diffuse reads on the same VarMix_CS) on the bowl at 8
+GOLDEN_THICKDIFF = tuple((n, abi.WRIGHT, "island_basin", dict(nk=4)) for n in (
+    "noeos", "eos", "psurf", "slopes_eos", "slopes_noeos", "kmax", "kmin", "large", "large_noeos", "kd0", "gm", "thin_top")) + tuple(
+    ("eos", f, "island_basin", dict(nk=4)) for f in _OTHER_FORMS) + tuple(
+    (n, abi.WRIGHT, "benchmark_small", dict(nk=nk)) for nk in (2, 8) for n in ("eos", "noeos")) + (
+    ("noeos", abi.WRIGHT, "benchmark_small", dict(nk=1)), ("eos", abi.WRIGHT, "torus", dict(nk=3)),
+    ("slopes_noeos", abi.WRIGHT, "torus", dict(nk=3)), ("chain", abi.WRIGHT, "benchmark_small", dict(nk=8)))
+CHAIN_OUT = THICKDIFF_CORE + VARMIX_MEMBERS          # what the chain case hands out; h, uhtr, vhtr (which both slopes feed) are in its file,
+CHAIN_DROP_ORDER = ("slope_y", "slope_x", "SN_v", "SN_u")   # of the intermediate planes a file over the size limit leaves out these, in this order
+CHAIN_DT = 3600.0
+
+
+def chain_params(GV):
+    """The two parameter sets of the chain case (test_chain_into_thickness_diffuse_and_tracer_hordiff of tests/test_varmix_gpu.py)."""
+    from tests import varmix_ref
+    return abi.varmix_params_default(GV, Visbeck_L_scale=3.0e4, **varmix_ref.VISB), abi.thickness_diffuse_params_default()
+
+
+def _form_tag(name, form):
+    return name if form == abi.WRIGHT else f"{name}-{LATERAL_EOS_NAMES[form].lower()}"
+
+
 def edge_torus_shape():
     bx, by, _ = abi.lane_launch_shape()
     return bx + 1, by + 1
@@ -602,6 +909,9 @@ def golden_configs():
         out.append(("kshear", name, grid, dict(kw, ni=ni, nj=nj) if grid == "torus" else dict(kw)))
     for name, grid, kw in GOLDEN_NDIFF:
         out.append(("ndiff", name, grid, dict(kw, ni=ni, nj=nj) if grid == "torus" else dict(kw)))
+    for kind, configs in (("varmix", GOLDEN_VARMIX), ("thickdiff", GOLDEN_THICKDIFF)):
+        for name, form, grid, kw in configs:
+            out.append((kind, _form_tag(name, form), grid, dict(kw, ni=ni, nj=nj) if grid == "torus" else dict(kw)))
     return out
 
 
@@ -619,6 +929,8 @@ def golden_setup(kind, name, grid, kw):
     if kind == "ndiff":       # the NaN-beyond-the-first-halo inputs of ndiff_ref.want, without running the restatement
         P, opt = ndiff_ref.case(name)
         return d, M, GV, P, opt, ndiff_ref.nan_halo(d, ndiff_ref.case_inputs(d, M, GV, opt, ntr=3))
+    if kind in ("varmix", "thickdiff"):
+        return (d, M, GV) + lateral_setup(kind, name, d, M, GV)
     if kind == "kshear":
         P, opt = kappa_shear_ref.case(name, GV)
         opt = dict(opt, diag=kappa_shear_ref.DIAG_3D + kappa_shear_ref.DIAG_2D)       # every diagnostic, whatever the case names
@@ -632,7 +944,75 @@ def golden_setup(kind, name, grid, kw):
     return d, M, GV, P, opt, inp
 
 
-DOORS = dict(opacity=opacity, epbl=energetic_PBL, kshear=Calculate_kappa_shear, ndiff=neutral_diffusion)     # kind -> its door
+def lateral_setup(kind, tag, d, M, GV):
+    """(P, opt, inp) of a recorded varmix or thickdiff configuration.  opt holds the arguments of the case (eos, give_ps, stored,
+    dt, chain); the inputs are NaN beyond what the reference reads (nan_beyond)."""
+    from tests import thickdiff_ref, varmix_ref
+    name, _, ftag = tag.partition("-")
+    form = {v.lower(): k for k, v in LATERAL_EOS_NAMES.items()}[ftag] if ftag else abi.WRIGHT
+    if kind == "varmix":
+        P, eos, ps, dg, dt, opts = varmix_ref.case(name, GV, form=form, nk=d.nk)
+        inp = varmix_ref.inputs(d, M, GV, **opts)
+        return P, dict(eos=eos, give_ps=ps, dt=dt), nan_beyond(d, inp, "varmix")
+    if name == "chain":
+        Pv, P = chain_params(GV)
+        inp = thickdiff_ref.inputs(d, M, GV)
+        return P, dict(eos=abi.eos_params_default(abi.WRIGHT), give_ps=False, stored=False, dt=CHAIN_DT, chain=Pv), nan_beyond(d, inp, "varmix")
+    P, eos, ps, stored, gm, dt, opts = thickdiff_ref.case(name, form=form)
+    inp = thickdiff_ref.inputs(d, M, GV, **opts)
+    return P, dict(eos=eos, give_ps=ps, stored=stored, dt=dt, chain=None), nan_beyond(d, inp, "thickdiff")
+
+
+def nan_beyond(d, inp, kind):
+    """The inputs with NaN where the reference's loops read nothing.  thickness_diffuse reads cells one beyond the computational
+    domain in x or in y (a plus shape, no halo corner) and stored slopes on their faces of the domain; calc_slope_functions the box
+    one beyond it (the four-face averages and calc_slope_functions_using_just_e read its corners) and a second cell in x or in y
+    (calc_isoneutral_slopes with halo = 1).  uhtr and vhtr are read on their faces of the domain."""
+    from tests import helpers as H
+    ni, nj = d.ni, d.nj
+    read = np.zeros(d.shape2(), bool)
+    if kind == "varmix":
+        for r in ((-2, ni + 1, -1, nj), (-1, ni, -2, nj + 1)):
+            read[d.sl(*r)] = True
+    else:
+        for r in ((-1, ni, 0, nj - 1), (0, ni - 1, -1, nj)):
+            read[d.sl(*r)] = True
+    out = {}
+    for n, a in inp.items():
+        if n in ("h", "T", "S", "p_surf", "khth2d"):
+            keep = read
+        else:
+            keep = np.zeros(d.shape2(), bool); keep[H.interior(d, "u" if n in ("uhtr", "slope_x") else "v")] = True
+        out[n] = np.ascontiguousarray(np.where(keep, a, np.nan))
+    return out
+
+
+def _varmix_door(d, M, GV, P, opt, inp):
+    """The recorded outputs of a varmix configuration, each cut to its range of varmix_ranges (L2u, L2v are not recorded)."""
+    got, fatal = calc_slope_functions(d, M, GV, P, inp, opt["dt"], eos=opt["eos"], give_ps=opt["give_ps"])
+    if fatal:
+        return None, fatal
+    rng = varmix_ranges(d, P)
+    return {n: np.ascontiguousarray(got[n][rng[n]]) for n in rng}, fatal
+
+
+def _thickdiff_door(d, M, GV, P, opt, inp):
+    """Likewise of a thickdiff configuration, each output on its range of thickdiff_ranges (the chain: CHAIN_OUT, the slopes and
+    SN_u, SN_v on theirs of varmix_ranges)."""
+    got, fatal = thickness_diffuse(d, M, GV, P, inp, opt["dt"], eos=opt["eos"], give_ps=opt["give_ps"], stored=opt["stored"],
+                                   chain=opt["chain"])
+    if fatal:
+        return None, fatal
+    rng = thickdiff_ranges(d)
+    if opt["chain"] is not None:
+        rng = dict({n: rng[n] for n in THICKDIFF_CORE}, **{n: varmix_ranges(d, opt["chain"])[n] for n in VARMIX_MEMBERS})
+        return {n: np.ascontiguousarray(got[n][(Ellipsis,) + rng[n]]) for n in CHAIN_OUT}, fatal
+    assert all(np.array_equal(got[n + "_diag"][(Ellipsis,) + rng[n]], got[n][(Ellipsis,) + rng[n]]) for n in ("uhGM", "vhGM"))
+    return {n: np.ascontiguousarray(got[n][(Ellipsis,) + rng[n]]) for n in THICKDIFF_OUT}, fatal
+
+
+DOORS = dict(opacity=opacity, epbl=energetic_PBL, kshear=Calculate_kappa_shear, ndiff=neutral_diffusion, varmix=_varmix_door,
+             thickdiff=_thickdiff_door)     # kind -> its door
 
 
 def sha256(a):
@@ -647,6 +1027,10 @@ def input_hashes(M, inp, kind=None):
         for n in ("mask2dT", "mask2dCu", "mask2dCv", "IareaT"):
             h[n] = sha256(M[G[n]])
         return h
+    if kind in ("varmix", "thickdiff"):
+        h = {n: sha256(a) for n, a in inp.items()}
+        h.update({n: sha256(M[G[n]]) for n in LATERAL_METRICS})
+        return h
     h = {n: sha256(a) for n, a in inp.items() if a is not None}
     h["mask2dT"] = sha256(M[G["mask2dT"]]); h["CoriolisBu"] = sha256(M[G["CoriolisBu"]])
     if kind == "kshear":
@@ -660,7 +1044,8 @@ def dom(d):
 
 
 def load_golden(kind, name, grid, kw, M, inp):
-    """The recorded outputs on the computational domain (kind ndiff: each on its range of ndiff_ranges), after the stored hashes of the inputs have been checked against the
+    """The recorded outputs on the computational domain (kind ndiff: each on its range of ndiff_ranges; varmix and thickdiff: each on
+    its range of varmix_ranges or thickdiff_ranges), after the stored hashes of the inputs have been checked against the
     regenerated ones."""
     path = os.path.join(GOLDEN, golden_name(kind, name, grid, kw) + ".npz")
     with np.load(path) as z:

@@ -1,6 +1,7 @@
 """The python restatements under tests/ held to the reference's own compiled code (oracle/_ref/libref_param.so: MOM_EOS_Wright*.F90,
-MOM_EOS_linear.F90, MOM_intrinsic_functions.F90, MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90 and
-MOM_neutral_diffusion.F90 with MOM_EOS.F90, built where they lie against interface stand-ins, see oracle/Makefile and tests/ref_param.py).  The restatements were written from the same reading of the Fortran as the
+MOM_EOS_linear.F90, MOM_intrinsic_functions.F90, MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90,
+MOM_neutral_diffusion.F90, MOM_isopycnal_slopes.F90, MOM_lateral_mixing_coeffs.F90 and MOM_thickness_diffuse.F90 with MOM_EOS.F90
+and MOM_interface_heights.F90, built where they lie against interface stand-ins, see oracle/Makefile and tests/ref_param.py).  The restatements were written from the same reading of the Fortran as the
 kernels they check, so a misread line sits in both; these tests are what involves the reference's code itself.
 
 Classes.  EXACT: whole arrays bit for bit on the computational domain.  TOLERANCE: the sites whose value goes through an
@@ -29,7 +30,11 @@ from tests import kappa_shear_ref as K
 from tests import ndiff_ref as N
 from tests import opacity_ref as R
 from tests import ref_param as RP
+from tests import thickdiff_ref as TD
+from tests import varmix_ref as V
 from tests.test_kappa_shear_cpu import CONFIGS as KSHEAR_GRIDS, REQUIRED as KSHEAR_REQUIRED, RESCALE_SETS, _DIM_OUT, rescaled
+from tests.test_thickness_diffuse_cpu import GRIDS as LAT_GRIDS, REQUIRED as TD_REQUIRED, SCALE_CASES as TD_SCALE_CASES, scaled as td_scaled
+from tests.test_varmix_cpu import REQUIRED as V_REQUIRED, SCALE_CASES as V_SCALE_CASES, scaled_varmix
 
 G = abi.G
 BOUND = 1.0e-12      # the project's bound for a transcendental site (BOUND of tests/test_opacity_gpu.py), as a fraction of the range
@@ -708,6 +713,368 @@ def test_neutral_diffusion_compared_set_reaches_every_required_arm():
         assert tot[k] > 0, (k, tot)
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# MOM_lateral_mixing_coeffs (with MOM_isopycnal_slopes and MOM_interface_heights) and MOM_thickness_diffuse
+
+NARROW = (("ni", 20), ("nj", 12))        # a narrowed bowl
+# every grid and layer count of tests/test_varmix_cpu.py, test_varmix_gpu.py and test_thickness_diffuse_gpu.py below 360 x 180:
+# (grid, nk, grid keywords, which cases): "all" is every entry of the case list, the eight equations of state included; "layers"
+# the cases of those files' test_layer_counts
+LATERAL_RUNS = tuple((grid, nk, (), "all") for grid in LAT_GRIDS for nk in (8, 75)) + (("benchmark_small", 6, (), "all"),) + tuple(
+    ("benchmark_small", nk, (), "layers") for nk in (1, 2, 3, 4, 52, 53, 76, 77, 120)) + tuple(
+    ("benchmark_small", nk, NARROW, "layers") for nk in (1, 2, 3, 75)) + (("island_basin", 4, (), "all"),)
+VARMIX_OUT = RP.VARMIX_MEMBERS + tuple(RP.VARMIX_DIAG_NAMES)
+
+
+def _lat_id(v):
+    return "x".join(str(b) for _, b in v) if isinstance(v, tuple) else str(v)
+
+
+def _lat_grid(grid, nk, kw):
+    return H.benchmark_small(nk=nk, **dict(kw))[1:] if kw else LAT_GRIDS[grid](nk)
+
+
+def _varmix_cases(nk, which):
+    if which == "all":
+        return tuple(V.case_list())
+    names = ("eady", "visbeck", "eady_noeos", "visbeck_noeos", "just_e") if nk > 1 else ("eady_noeos", "visbeck_noeos", "just_e")
+    return tuple((n, abi.WRIGHT if V.CASES[n][1] == "form" else None) for n in names + (("just_e_full",) if nk > 2 else ()))
+
+
+def _thick_cases(nk, which):
+    if which == "all":
+        return tuple((n, f) for n, c in TD.CASES.items() if n not in RP.THICKDIFF_LEFT_OUT
+                     for f in (V.FORMS if c[1] == "form" else (None,)))
+    return (("noeos", None), ("eos", abi.WRIGHT), ("large", None)) if nk > 1 else (("noeos", None),)
+
+
+@functools.lru_cache(maxsize=None)
+def _varmix(grid, nk, kw, name, form):
+    """A case on a grid with every diagnostic asked for, and the restatement's result and counters: computed once (read only)."""
+    from oracle import orc
+    orc.build()
+    d, M = _lat_grid(grid, nk, kw)
+    GV = abi.vgrid_default()
+    P, eos, ps, dg, dt, opts = V.case(name, GV, form=form, nk=nk)
+    if name == "just_e_full" and nk > 2:
+        P.VarMix_Ktop = max(P.VarMix_Ktop, 3)
+    inp = V.inputs(d, M, GV, **opts)
+    want, counts = V.run(d, M, GV, P, inp, dt, eos=eos, give_ps=ps, give_diag=True, orc=orc)
+    return d, M, GV, P, eos, ps, dt, inp, want, counts
+
+
+@functools.lru_cache(maxsize=None)
+def _thick(grid, nk, kw, name, form):
+    from oracle import orc
+    orc.build()
+    d, M = _lat_grid(grid, nk, kw)
+    GV = abi.vgrid_default()
+    P, eos, ps, stored, gm, dt, opts = TD.case(name, form=form or abi.WRIGHT)
+    inp = TD.inputs(d, M, GV, **opts)
+    want, counts = TD.run(d, M, GV, P, inp, dt, eos=eos, give_ps=ps, stored=stored, give_gm=True, orc=orc)
+    return d, M, GV, P, eos, ps, stored, dt, inp, want, counts
+
+
+def _written(d, P, want, tag):
+    """The restatement started every output as NaN: what it wrote is exactly the reference's ranges (RP.varmix_ranges)."""
+    rng = RP.varmix_ranges(d, P)
+    for n, a in want.items():
+        r = np.zeros(a.shape, bool)
+        if n in rng:
+            r[rng[n]] = True
+        assert np.array_equal(~np.isnan(a), r), f"{tag}: {n} is not written on its range"
+    return rng
+
+
+def _compare_varmix(tag, d, P, want, got, names=VARMIX_OUT):
+    """SN_u, SN_v, slope_x, slope_y (members of VarMix_CS) and N2_u, N2_v, S2_u, S2_v, dzu, dzv, dzSxN, dzSyN (what the module posts),
+    each on the range the reference writes, bit for bit; the reference hands out everything the restatement makes."""
+    rng = _written(d, P, want, tag)
+    assert set(rng) <= set(got), (tag, sorted(rng), sorted(got))
+    for n in names:
+        if n in rng:
+            H.assert_bitwise(np.ascontiguousarray(got[n][rng[n]]), np.ascontiguousarray(want[n][rng[n]]), f"{tag}: {n}")
+
+
+def _compare_thick(tag, d, want, got, names=RP.THICKDIFF_OUT):
+    """h, uhtr, vhtr, CDp%uhGM, CDp%vhGM and the posted uhGM, vhGM diagnostics on their ranges, bit for bit."""
+    rng = RP.thickdiff_ranges(d)
+    for n in names:
+        s = (Ellipsis,) + rng[n]
+        H.assert_bitwise(np.ascontiguousarray(got[n][s]), np.ascontiguousarray(want[n][s]), f"{tag}: {n}")
+        if n + "_diag" in got:
+            H.assert_bitwise(np.ascontiguousarray(got[n + "_diag"][s]), np.ascontiguousarray(want[n][s]), f"{tag}: posted {n}")
+    assert "uhGM_diag" in got and "vhGM_diag" in got, tag
+
+
+@pytest.mark.parametrize("grid,nk,kw,which", LATERAL_RUNS, ids=_lat_id)
+def test_calc_slope_functions_against_the_compiled_reference(grid, nk, kw, which):
+    """tests/varmix_ref.py against calc_slope_functions of the reference's own MOM_lateral_mixing_coeffs.F90 with
+    calc_isoneutral_slopes and vert_fill_TS of MOM_isopycnal_slopes.F90, find_eta of MOM_interface_heights.F90 and the array forms
+    of calculate_density_derivs of MOM_EOS.F90, set up by the reference's unit_scaling_init, EOS_init and VarMix_init: every entry
+    of the case list, the eight equations of state included, on the bowl, the island basin and the partially blocked faces at 8 and
+    75 layers and on the bowl at 6, and the layer-count cases on the bowl at 1, 2, 3, 4, 52, 53, 76, 77 and 120 layers and on a
+    narrowed bowl at 1, 2, 3 and 75.  Every output on the range the reference writes, bit for bit; zero FATALs and no call of a
+    stand-in that must never run.  There is no tolerance class: + - * / and sqrt only."""
+    for name, form in _varmix_cases(nk, which):
+        d, M, GV, P, eos, ps, dt, inp, want, counts = _varmix(grid, nk, kw, name, form)
+        rng = _written(d, P, want, f"{grid}/{nk}/{name}")
+        if name == "eady_tie" and nk >= 2 and not kw:
+            # the tie of the radicand of dzSxN (MOM_isopycnal_slopes.F90:418) is reached: MAX(0.0, -0.0), the reference answers -0.0
+            z = want["dzSxN"][rng["dzSxN"]][1:-1]
+            assert (np.signbit(z) & (z == 0.0)).any(), (grid, nk)
+    _need_lib()
+    for name, form in _varmix_cases(nk, which):
+        d, M, GV, P, eos, ps, dt, inp, want, counts = _varmix(grid, nk, kw, name, form)
+        got, fatal = RP.calc_slope_functions(d, M, GV, P, inp, dt, eos=eos, give_ps=ps)
+        assert fatal == 0 and RP.standin_never_count() == 0, (grid, nk, name, form, fatal)
+        _compare_varmix(f"{grid}/{nk}/{name}/{form}", d, P, want, got)
+
+
+@pytest.mark.parametrize("grid,nk,kw,which", LATERAL_RUNS, ids=_lat_id)
+def test_thickness_diffuse_against_the_compiled_reference(grid, nk, kw, which):
+    """tests/thickdiff_ref.py against thickness_diffuse and thickness_diffuse_full of the reference's own MOM_thickness_diffuse.F90,
+    set up by its thickness_diffuse_init and by VarMix_init, through which the stored slopes go: every case but khth2d (whose
+    plane the reference reads from a file into a private member), eos once per equation of state, on the grids and layer counts of
+    test_calc_slope_functions_against_the_compiled_reference.  h, uhtr, vhtr, CDp%uhGM, CDp%vhGM and the posted uhGM, vhGM on their
+    ranges, bit for bit."""
+    _need_lib()
+    for name, form in _thick_cases(nk, which):
+        d, M, GV, P, eos, ps, stored, dt, inp, want, counts = _thick(grid, nk, kw, name, form)
+        got, fatal = RP.thickness_diffuse(d, M, GV, P, inp, dt, eos=eos, give_ps=ps, stored=stored)
+        assert fatal == 0 and RP.standin_never_count() == 0, (grid, nk, name, form, fatal)
+        _compare_thick(f"{grid}/{nk}/{name}/{form}", d, want, got)
+        if name == "noeos" and grid != "partial_faces":
+            # the tie of the uhD limiter (:1160-1161) is reached: MAX(+0.0, -0.0), and the reference answers -0.0
+            z = want["uhGM"][(slice(1, None),) + RP.thickdiff_ranges(d)["uhGM"]]
+            assert nk == 1 or (np.signbit(z) & (z == 0.0)).any(), (grid, nk)
+
+
+@pytest.mark.parametrize("L_scale", [3.0e4, -0.25])
+def test_L2_planes_against_the_compiled_VarMix_init(L_scale):
+    """CS%L2u, CS%L2v of VarMix_init (:1759-1772) at the two signs of VISBECK_L_SCALE of test_L2_planes_of_the_init_call, on the
+    partially blocked faces and with L rescaled (L_to_m = 2), whole planes bit for bit."""
+    _need_lib()
+    d, M = LAT_GRIDS["partial_faces"](8)
+    GV = abi.vgrid_default()
+    M2, GV2, _, _, _, _ = td_scaled(d, M, GV, abi.thickness_diffuse_params_default(), {n: np.zeros(1) for n in (
+        "h", "T", "S", "p_surf", "khth2d", "uhtr", "vhtr", "slope_x", "slope_y")}, 900.0, "L", p=-1)
+    P = abi.varmix_params_default(GV2, Visbeck_L_scale=L_scale, L_to_m=2.0, Z_to_L=0.5)
+    want = V.varmix_L2(d, M2, P)
+    assert (want[0] != 0.0).any() and (L_scale > 0 or (want[0] == 0.0).any())
+    inp = V.inputs(d, M2, GV2)
+    got, fatal = RP.calc_slope_functions(d, M2, GV2, P, inp, 0.0, sc=dict(L=0.5))
+    assert fatal == 0 and RP.standin_never_count() == 0
+    for w, n in zip(want, ("L2u", "L2v")):
+        H.assert_bitwise(got[n], w, n)
+
+
+def _chain(kind):
+    """The chain of test_chain_into_thickness_diffuse_and_tracer_hordiff (kind visbeck) and its twin through
+    calc_Eady_growth_rate_2D: the two restatements, the first's slopes handed to the second."""
+    from oracle import orc
+    orc.build()
+    d, M = LAT_GRIDS["benchmark_small"](8)
+    GV = abi.vgrid_default()
+    eos = abi.eos_params_default(abi.WRIGHT)
+    inp = TD.inputs(d, M, GV)
+    Pv, Ptd = RP.chain_params(GV)
+    if kind == "eady":
+        Pv = abi.varmix_params_default(GV, **V.EADY)
+    w = dict(SN_u=np.full(d.shape2(), np.nan), SN_v=np.full(d.shape2(), np.nan), slope_x=np.zeros(d.shape3(d.nk + 1)),
+             slope_y=np.zeros(d.shape3(d.nk + 1)))
+    Rlay, gp = abi.layer_densities(d.nk)
+    rounds = []
+    h, uhtr, vhtr = inp["h"].copy(), inp["uhtr"].copy(), inp["vhtr"].copy()
+    for r in range(2):
+        V.calc_slope_functions(d, M, GV, Pv, h, RP.CHAIN_DT, w["SN_u"], w["SN_v"], T=inp["T"], S=inp["S"], eos=eos, Rlay=Rlay,
+                               g_prime=gp, slope_x=w["slope_x"], slope_y=w["slope_y"], orc=orc)
+        TD.thickness_diffuse(d, M, GV, Ptd, h, uhtr, vhtr, RP.CHAIN_DT, T=inp["T"], S=inp["S"], eos=eos, slope_x=w["slope_x"],
+                             slope_y=w["slope_y"], orc=orc)
+        rounds.append(dict({n: a.copy() for n, a in w.items()}, h=h.copy(), uhtr=uhtr.copy(), vhtr=vhtr.copy()))
+    return d, M, GV, Pv, Ptd, eos, inp, rounds
+
+
+@pytest.mark.parametrize("kind", ["visbeck", "eady"])
+def test_chain_of_the_two_on_one_VarMix_CS(kind):
+    """The reference's real path: one calc_slope_functions whose stored slopes one thickness_diffuse reads from the same VarMix_CS
+    (benchmark_small x 8, WRIGHT, dt = 3600), against the two restatements chained the same way; and two such rounds on the same
+    control structures, the second from the first's h.  h, uhtr, vhtr, the slopes and SN_u, SN_v of the last round, bit for bit."""
+    _need_lib()
+    d, M, GV, Pv, Ptd, eos, inp, rounds = _chain(kind)
+    rng = dict(RP.varmix_ranges(d, Pv), **{n: RP.thickdiff_ranges(d)[n] for n in RP.THICKDIFF_CORE})
+    assert not np.array_equal(rounds[0]["h"], rounds[1]["h"]) and not np.array_equal(rounds[0]["slope_x"][1:-1], rounds[1]["slope_x"][1:-1])
+    for ncalls in (1, 2):
+        got, fatal = RP.thickness_diffuse(d, M, GV, Ptd, inp, RP.CHAIN_DT, eos=eos, chain=Pv, ncalls=ncalls)
+        assert fatal == 0 and RP.standin_never_count() == 0
+        for n in RP.CHAIN_OUT:
+            s = rng[n] if n in RP.VARMIX_MEMBERS else (Ellipsis,) + rng[n]
+            H.assert_bitwise(np.ascontiguousarray(got[n][s]), np.ascontiguousarray(rounds[ncalls - 1][n][s]), f"chain {kind} x {ncalls}: {n}")
+
+
+def test_second_call_on_the_same_control_structures():
+    """State carried in a control structure would show in a second call: calc_slope_functions twice on one VarMix_CS, the second
+    on another h, gives what a fresh one gives on that h; thickness_diffuse twice on one thickness_diffuse_CS gives the restatement
+    applied twice."""
+    _need_lib()
+    from oracle import orc
+    for name in ("eady_diag", "visbeck_diag", "just_e"):
+        d, M, GV, P, eos, ps, dt, inp, want, counts = _varmix("island_basin", 4, (), name, None)
+        inp2 = dict(inp, h=np.ascontiguousarray(inp["h"][:, ::-1, :] * 1.03125))
+        want2, _ = V.run(d, M, GV, P, inp2, dt, eos=eos, give_ps=ps, give_diag=True, orc=orc)
+        got, fatal = RP.calc_slope_functions(d, M, GV, P, inp, dt, eos=eos, give_ps=ps, ncalls=2, inp2=inp2)
+        assert fatal == 0 and RP.standin_never_count() == 0
+        assert not np.array_equal(want2["SN_u"], want["SN_u"], equal_nan=True)
+        _compare_varmix(f"{name}, second call", d, P, want2, got)
+    for name in ("eos", "slopes_noeos", "gm"):
+        d, M, GV, P, eos, ps, stored, dt, inp, want, counts = _thick("island_basin", 4, (), name, abi.WRIGHT)
+        want2, _ = TD.run(d, M, GV, P, dict(inp, **{n: want[n] for n in RP.THICKDIFF_CORE}), dt, eos=eos, give_ps=ps, stored=stored,
+                          give_gm=True, orc=orc)
+        got, fatal = RP.thickness_diffuse(d, M, GV, P, inp, dt, eos=eos, give_ps=ps, stored=stored, ncalls=2)
+        assert fatal == 0 and RP.standin_never_count() == 0
+        assert not np.array_equal(want2["h"], want["h"])
+        _compare_thick(f"{name}, second call", d, want2, got)
+
+
+@pytest.mark.parametrize("name,dims", V_SCALE_CASES)
+def test_calc_slope_functions_rescaled_through_the_references_unit_scaling_init(name, dims):
+    """The cases and dimensions of tests/test_varmix_cpu.SCALE_CASES, each of T, L, H, Z, R rescaled by 2**11: the *_RESCALE_POWERs
+    go through the reference's own unit_scaling_init, the parameters through the `scale=` of its VarMix_init, H through GV.  The
+    rescaled restatement equals the rescaled reference, and the reference unscaled is the unscaled run, bit for bit."""
+    _need_lib()
+    from oracle import orc
+    d, M, GV, P, eos, ps, dt, inp, want, counts = _varmix("benchmark_small", 6, (), name, abi.WRIGHT if V.CASES[name][1] == "form" else None)
+    base, fatal = RP.calc_slope_functions(d, M, GV, P, inp, dt, eos=eos, give_ps=ps)
+    assert fatal == 0
+    _compare_varmix(f"{name} unscaled", d, P, want, base)
+    rng = RP.varmix_ranges(d, P)
+    for dim in dims:
+        M2, GV2, P2, in2, dt2, Rlay2, gp2, un = scaled_varmix(d, M, GV, P, inp, dt, dim)
+        P2.L_to_m = 1.0 / (2.0 ** 11 if dim == "L" else 1.0)       # (scaled_varmix leaves it: only VarMix_init's L2 planes read it)
+        mine, _ = V.run(d, M2, GV2, P2, in2, dt2, eos=eos, give_ps=ps, give_diag=True, orc=orc, Rlay=Rlay2, g_prime=gp2)
+        got, fatal = RP.calc_slope_functions(d, M2, GV2, P2, in2, dt2, eos=eos, give_ps=ps, sc={dim: 2.0 ** 11}, Rlay=Rlay2, g_prime=gp2)
+        assert fatal == 0 and RP.standin_never_count() == 0, (name, dim)
+        _compare_varmix(f"{name} rescaled in {dim}", d, P2, mine, got)
+        for n in rng:
+            H.assert_bitwise(np.ascontiguousarray(got[n][rng[n]] * un[n]), np.ascontiguousarray(base[n][rng[n]]),
+                             f"{name}: {n} of the reference, rescaled in {dim} and unscaled")
+
+
+@pytest.mark.parametrize("name,dims", [c for c in TD_SCALE_CASES if c[0] not in RP.THICKDIFF_LEFT_OUT])
+def test_thickness_diffuse_rescaled_through_the_references_unit_scaling_init(name, dims):
+    """Likewise the cases of tests/test_thickness_diffuse_cpu.SCALE_CASES (khth2d is outside the comparison)."""
+    _need_lib()
+    from oracle import orc
+    d, M, GV, P, eos, ps, stored, dt, inp, want, counts = _thick("benchmark_small", 6, (), name, abi.WRIGHT)
+    base, fatal = RP.thickness_diffuse(d, M, GV, P, inp, dt, eos=eos, give_ps=ps, stored=stored)
+    assert fatal == 0
+    _compare_thick(f"{name} unscaled", d, want, base)
+    rng = RP.thickdiff_ranges(d)
+    for dim in dims:
+        M2, GV2, P2, in2, dt2, un = td_scaled(d, M, GV, P, inp, dt, dim)
+        mine, _ = TD.run(d, M2, GV2, P2, in2, dt2, eos=eos, give_ps=ps, stored=stored, give_gm=True, orc=orc)
+        got, fatal = RP.thickness_diffuse(d, M2, GV2, P2, in2, dt2, eos=eos, give_ps=ps, stored=stored, sc={dim: 2.0 ** 11})
+        assert fatal == 0 and RP.standin_never_count() == 0, (name, dim)
+        _compare_thick(f"{name} rescaled in {dim}", d, mine, got)
+        for n in RP.THICKDIFF_OUT:
+            s = (Ellipsis,) + rng[n]
+            H.assert_bitwise(np.ascontiguousarray(got[n][s] * un[n]), np.ascontiguousarray(base[n][s]),
+                             f"{name}: {n} of the reference, rescaled in {dim} and unscaled")
+
+
+def _lateral_counts(configs=None):
+    """The restatements' branch counts over the live compared set (configs None) or over the recorded set."""
+    tv, tt = dict.fromkeys(V.BRANCHES, 0), dict.fromkeys(TD.BRANCHES, 0)
+    if configs is None:
+        runs_v = [_varmix(g, nk, kw, n, f)[9] for g, nk, kw, w in LATERAL_RUNS for n, f in _varmix_cases(nk, w)]
+        runs_t = [_thick(g, nk, kw, n, f)[10] for g, nk, kw, w in LATERAL_RUNS for n, f in _thick_cases(nk, w)]
+    else:
+        from oracle import orc
+        orc.build()
+        runs_v, runs_t = [], []
+        for kind, name, grid, kw in configs:
+            if kind not in ("varmix", "thickdiff"):
+                continue
+            d, M, GV, P, opt, inp = RP.golden_setup(kind, name, grid, kw)
+            (runs_v if kind == "varmix" else runs_t).append(_restatement(kind, d, M, GV, P, opt, inp, counts=True))
+    for tot, runs in ((tv, runs_v), (tt, runs_t)):
+        for c in runs:
+            for k, v in c.items():
+                tot[k] += v
+    return tv, tt
+
+
+def test_lateral_compared_set_reaches_every_required_arm():
+    """Over everything the two door tests above compare, every arm of REQUIRED of tests/test_varmix_cpu.py and of
+    tests/test_thickness_diffuse_cpu.py is reached, from the restatements' counters alone."""
+    tv, tt = _lateral_counts()
+    for k in V_REQUIRED:
+        assert tv[k] > 0, (k, tv)
+    for k in TD_REQUIRED:
+        assert tt[k] > 0, (k, tt)
+
+
+def test_lateral_recorded_set_reaches_every_required_arm():
+    """The recorded configurations (what the device is held to on the GPU) reach every one of those arms by themselves, KH_max and
+    the rest of the diffusivity clips included, so the GPU test's coverage is a checked fact.  Never skips."""
+    tv, tt = _lateral_counts(RP.golden_configs())
+    print("recorded set:", tv, tt)
+    for k in V_REQUIRED:
+        assert tv[k] > 0, (k, tv)
+    for k in TD_REQUIRED:
+        assert tt[k] > 0, (k, tt)
+
+
+# what the reference's inits do with each `must be 0` member that a parameter file can set: (FATALs of the reference's own, calls
+# of a stand-in that must never run).  include/mom6x.h states the result.
+LATERAL_REFUSALS = {
+    ("thickdiff", "use_FGNV_streamfn"): (0, 1),      # accepted; VarMix_init then wants wave speeds (wave_speed_init, :2003)
+    ("thickdiff", "use_stanley_gm"): (1, 0),         # FATAL without STANLEY_COEFF >= 0 (:2334) ...
+    ("thickdiff", "use_stanley_gm+coeff"): (0, 0),   # ... accepted with it
+    ("thickdiff", "detangle_interfaces"): (0, 0), ("thickdiff", "Kh_eta_bg"): (0, 0), ("thickdiff", "Kh_eta_vel"): (0, 0),
+    ("thickdiff", "use_GME"): (0, 0),
+    ("thickdiff", "use_MEKE"): (0, 1),               # accepted; VarMix_init then wants Rd/dx and with it wave speeds (:1602, :1955)
+    ("thickdiff", "read_khth+Khth"): (1, 2),         # FATAL: KHTH > 0 with READ_KHTH (:2218); the read and its pass_var leave the compiled files
+    ("varmix", "use_stanley_iso"): (1, 0),           # FATAL without STANLEY_COEFF >= 0 (:1621) ...
+    ("varmix", "use_stanley_iso+coeff"): (0, 0),     # ... accepted with it
+    ("varmix", "debug"): (0, 0),
+    ("varmix", "simpler_without_stored"): (1, 0),    # FATAL (:1722): the device refuses it too
+}
+
+
+def test_lateral_init_refusals_against_the_references():
+    """Which members of abi.THICKNESS_DIFFUSE_MUST_BE_0 and abi.VARMIX_MUST_BE_0 the reference's own inits stop on: only the two
+    Stanley switches without a coefficient (and KHTH > 0 with READ_KHTH, USE_SIMPLER_EADY_GROWTH_RATE without USE_STORED_SLOPES,
+    which the device refuses as well).  Everything else the device refuses the reference accepts.  The members that no parameter
+    sets (RP.THICKDIFF_NOT_PARAMS, RP.VARMIX_NOT_PARAMS: VarMix%use_variable_mixing, which VarMix_init sets TRUE by default, the OBC
+    pointer, GV%Boussinesq, GV%nkml, the GMwork diagnostic, STOCH) cannot be asked of an init."""
+    assert {k[1].split("+")[0] for k in LATERAL_REFUSALS if k[0] == "thickdiff"} | set(RP.THICKDIFF_NOT_PARAMS) >= set(abi.THICKNESS_DIFFUSE_MUST_BE_0)
+    assert {k[1].split("+")[0] for k in LATERAL_REFUSALS if k[0] == "varmix"} | set(RP.VARMIX_NOT_PARAMS) >= set(abi.VARMIX_MUST_BE_0)
+    _need_lib()
+    GV = abi.vgrid_default()
+    d, M = H.benchmark_small(nk=2)[1:]
+    inp = TD.inputs(d, M, GV)
+    for (kind, what), (own, never) in LATERAL_REFUSALS.items():
+        member, _, extra = what.partition("+")
+        tab = [("STANLEY_COEFF", 1.0)] if extra == "coeff" else []
+        if kind == "thickdiff":
+            P = abi.thickness_diffuse_params_default()
+            if what == "read_khth+Khth":
+                tab = [("READ_KHTH", True)]
+            else:
+                tab.append((RP.THICKDIFF_PARAM_NAMES[member][0], 1.0 if member.startswith("Kh_eta") else True))
+            got, fatal = RP.thickness_diffuse(d, M, GV, P, inp, 0.0, table_extra=tab)
+        else:
+            P = abi.varmix_params_default(GV)
+            if member == "simpler_without_stored":
+                tab = [("USE_SIMPLER_EADY_GROWTH_RATE", True)]
+            else:
+                tab.append((RP.VARMIX_PARAM_NAMES[member][0], True))
+            got, fatal = RP.calc_slope_functions(d, M, GV, P, inp, 0.0, table_extra=tab)
+        n = RP.standin_never_count()
+        assert (fatal - n, n) == (own, never), (kind, what, fatal, n)
+
+
 def test_zz_record_the_tolerance_class():
     """profiles/ref_parity_libm.json: the largest difference over range of every tolerance-class field seen by the tests above
     (MOM6X_RECORD_REF_PARITY names the file).  Runs last in the file; without the library there is nothing to record."""
@@ -730,7 +1097,9 @@ def test_zz_record_the_tolerance_class():
 # ------------------------------------------------------------------------------------------------------------------------------
 # recorded results
 
-def _restatement(kind, d, M, GV, P, opt, inp):
+def _restatement(kind, d, M, GV, P, opt, inp, counts=False):
+    if kind in ("varmix", "thickdiff"):
+        return _lateral_restatement(kind, d, M, GV, P, opt, inp, counts)
     if kind == "kshear":
         return K.run(d, M, GV, P, opt, inp)[0]
     if kind == "ndiff":
@@ -740,8 +1109,51 @@ def _restatement(kind, d, M, GV, P, opt, inp):
     return E.run(d, M, GV, P, opt, inp)[0]
 
 
+def _lateral_restatement(kind, d, M, GV, P, opt, inp, counts=False):
+    """The restatement on a recorded varmix or thickdiff configuration (NaN inputs beyond what the reference reads), every output
+    cut to its range as the recorder cuts the door's; or its branch counts."""
+    from oracle import orc
+    orc.build()
+    if kind == "varmix":
+        want, c = V.run(d, M, GV, P, inp, opt["dt"], eos=opt["eos"], give_ps=opt["give_ps"], give_diag=True, orc=orc)
+        rng = _written(d, P, want, "recorded")
+        return c if counts else {n: np.ascontiguousarray(want[n][rng[n]]) for n in rng}
+    rng = RP.thickdiff_ranges(d)
+    if opt["chain"] is None:
+        want, c = TD.run(d, M, GV, P, inp, opt["dt"], eos=opt["eos"], give_ps=opt["give_ps"], stored=opt["stored"], give_gm=True, orc=orc)
+        return c if counts else {n: np.ascontiguousarray(want[n][(Ellipsis,) + rng[n]]) for n in RP.THICKDIFF_OUT}
+    Pv = opt["chain"]
+    w = dict(SN_u=np.full(d.shape2(), np.nan), SN_v=np.full(d.shape2(), np.nan), slope_x=np.full(d.shape3(d.nk + 1), np.nan),
+             slope_y=np.full(d.shape3(d.nk + 1), np.nan))
+    Rlay, gp = abi.layer_densities(d.nk)
+    io = {n: inp[n].copy() for n in RP.THICKDIFF_CORE}
+    V.calc_slope_functions(d, M, GV, Pv, io["h"], opt["dt"], w["SN_u"], w["SN_v"], T=inp["T"], S=inp["S"], eos=opt["eos"], Rlay=Rlay,
+                           g_prime=gp, slope_x=w["slope_x"], slope_y=w["slope_y"], orc=orc)
+    c = TD.thickness_diffuse(d, M, GV, P, io["h"], io["uhtr"], io["vhtr"], opt["dt"], T=inp["T"], S=inp["S"], eos=opt["eos"],
+                             slope_x=w["slope_x"], slope_y=w["slope_y"], orc=orc)
+    rv = RP.varmix_ranges(d, Pv)
+    out = {n: np.ascontiguousarray(io[n][(Ellipsis,) + rng[n]]) for n in RP.THICKDIFF_CORE}
+    out.update({n: np.ascontiguousarray(w[n][rv[n]]) for n in RP.VARMIX_MEMBERS})
+    return c if counts else out
+
+
+def _lateral_golden_names(kind, name, gold, out):
+    """CORE <= recorded <= exposed, and what is left out is the head of the kind's drop order."""
+    core = set(RP.VARMIX_CORE if kind == "varmix" else RP.THICKDIFF_CORE) & set(out)
+    order = [n for n in (RP.CHAIN_DROP_ORDER if name == "chain" else RP.VARMIX_DROP_ORDER if kind == "varmix" else RP.THICKDIFF_DROP_ORDER)
+             if n in out]
+    left_out = sorted(set(out) - set(gold))
+    assert core <= set(gold) <= set(out) and left_out == sorted(order[:len(left_out)]), (sorted(gold), sorted(out))
+
+
 def _against_golden(tag, kind, d, M, gold, out):
     """`out` (whole arrays) against the recorded computational domain, in the classes of the live comparisons."""
+    if kind in ("varmix", "thickdiff"):      # both sides are cut to the ranges the reference writes; finite there, bit for bit
+        _lateral_golden_names(kind, tag.split("_")[2], gold, out)
+        for n in gold:
+            assert np.isfinite(out[n]).all(), (tag, n)
+            H.assert_bitwise(out[n], np.ascontiguousarray(gold[n]), f"{tag}: {n}")
+        return
     if kind == "ndiff":                  # lists of arrays, each on its own range; a file over the size limit leaves out diagnostics
         left_out = sorted(set(out) - set(gold))
         assert set(RP.NDIFF_CORE) <= set(gold) <= set(out) == set(RP.NDIFF_OUT), sorted(gold)
@@ -783,8 +1195,8 @@ def test_recorded_reference_is_what_the_library_gives():
         gold = RP.load_golden(kind, name, grid, kw, M, inp)
         got, fatal = RP.DOORS[kind](d, M, GV, P, opt, inp)
         assert fatal == 0
-        if kind == "ndiff":
-            _against_golden(name, kind, d, M, gold, got)
+        if kind in ("ndiff", "varmix", "thickdiff"):
+            _against_golden(RP.golden_name(kind, name, grid, kw), kind, d, M, gold, got)
             continue
         dm = (Ellipsis,) + RP.dom(d)
         assert set(got) == set(gold) if kind != "kshear" else set(gold) <= set(got)

@@ -1,7 +1,9 @@
-"""mom6x_set_pen_shortwave, mom6x_energetic_PBL, mom6x_Calculate_kappa_shear and mom6x_neutral_diffusion_calc_coeffs with
-mom6x_neutral_diffusion on the device against what the reference's own
-compiled MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90 and MOM_neutral_diffusion.F90 gave on the same seeded inputs:
-the recorded results tests/golden/ref_opacity_*.npz, ref_epbl_*.npz, ref_kshear_*.npz and ref_ndiff_*.npz
+"""mom6x_set_pen_shortwave, mom6x_energetic_PBL, mom6x_Calculate_kappa_shear, mom6x_neutral_diffusion_calc_coeffs with
+mom6x_neutral_diffusion, mom6x_calc_slope_functions and mom6x_thickness_diffuse on the device against what the reference's own
+compiled MOM_opacity.F90, MOM_energetic_PBL.F90, MOM_kappa_shear.F90, MOM_neutral_diffusion.F90, MOM_lateral_mixing_coeffs.F90 and
+MOM_thickness_diffuse.F90 gave on the same seeded inputs:
+the recorded results tests/golden/ref_opacity_*.npz, ref_epbl_*.npz, ref_kshear_*.npz, ref_ndiff_*.npz, ref_varmix_*.npz and
+ref_thickdiff_*.npz
 (scripts/record_ref_parity.py wrote them from oracle/_ref/libref_param.so; tests/test_ref_parity_cpu.py holds the restatements
 and the live library to the same files).  Nothing here needs the compiled reference.
 
@@ -22,7 +24,19 @@ calc_coeffs and one neutral_diffusion call) with that file's NaN-beyond-the-firs
 on the computational domain, trans_x_2d and trans_y_2d on their face ranges, bit for bit: there is no tolerance class.  Every
 diagnostic starts as NaN and is still NaN outside its range, the tracers keep the NaN of their outer halos; no exchange happens and
 the status is (0, 0, 0, 0).  The coefficient arrays are private to the compiled module and are not recorded; the neutral branch of
-tracer_hordiff and the discontinuous reconstruction are outside what was compiled."""
+tracer_hordiff and the discontinuous reconstruction are outside what was compiled.
+
+Kinds varmix and thickdiff (ref_param.GOLDEN_VARMIX, GOLDEN_THICKDIFF): mom6x_calc_slope_functions and mom6x_thickness_diffuse against
+the reference's own MOM_lateral_mixing_coeffs.F90 (with MOM_isopycnal_slopes.F90 and MOM_interface_heights.F90) and
+MOM_thickness_diffuse.F90: every case on the basin with an island at 4 layers (khth2d excepted, whose plane the reference reads from
+a file), eady and eos once per equation of state there; eady, visbeck, just_e and eos, noeos on the bowl at 1, 2 and 8 layers (at
+one layer their layered twins: the reference's vert_fill_TS reads layer 2); eady_diag, visbeck_diag and eos, slopes_noeos on the
+torus at 3; and the chain, one calc_slope_functions whose slopes one thickness_diffuse reads, on the bowl at 8.  Fed through
+_device of tests/test_varmix_gpu.py and tests/test_thickness_diffuse_gpu.py with inputs that are NaN beyond what the reference
+reads (ref_param.nan_beyond) and outputs that start as NaN: every output bit for bit on the range the reference writes
+(ref_param.varmix_ranges, thickdiff_ranges) and NaN, or for h, uhtr and vhtr the input's bits, outside it; no halo exchange; status
+0 (every call is checked).  There is no tolerance class.  tests/test_ref_parity_cpu.py asserts that these configurations by
+themselves reach every arm of REQUIRED of tests/test_varmix_cpu.py and tests/test_thickness_diffuse_cpu.py."""
 import numpy as np
 import pytest
 
@@ -85,6 +99,56 @@ def _ndiff(tag, d, M, GV, P, opt, inp, gold):
             H.assert_bitwise(np.ascontiguousarray(a[(Ellipsis,) + rng[n]]), np.ascontiguousarray(b), f"{tag}: {n}[{m}]")
 
 
+def _recorded(kind, name, gold, exposed):
+    """CORE <= recorded <= exposed: a file that would pass the size limit leaves out diagnostics, never a core array."""
+    core = set(RP.VARMIX_CORE if kind == "varmix" else RP.THICKDIFF_CORE) & set(exposed)
+    assert core <= set(gold) <= set(exposed), (sorted(gold), sorted(exposed))
+
+
+def _lateral(tag, kind, name, d, M, GV, P, opt, inp, gold):
+    from mom6_amd.dycore import Dycore
+    from tests import test_thickness_diffuse_gpu as TG, test_varmix_gpu as VG
+    dy = Dycore(d, M, GV)
+    try:
+        dy.comm_exchange_count(reset=True)
+        if kind == "varmix":
+            got = VG._device(d, M, GV, P, inp, opt["dt"], eos=opt["eos"], give_ps=opt["give_ps"], give_diag=True, dy=dy)
+            rng = RP.varmix_ranges(d, P)
+        elif opt["chain"] is None:
+            got = TG._device(d, M, GV, P, inp, opt["dt"], eos=opt["eos"], give_ps=opt["give_ps"], stored=opt["stored"], give_gm=True,
+                             dy=dy)
+            rng = {n: (slice(None),) + s for n, s in RP.thickdiff_ranges(d).items()}
+        else:
+            import torch
+            Pv = opt["chain"]
+            t = {n: dy.to_dev(inp[n]) for n in ("h", "uhtr", "vhtr", "T", "S")}
+            g = {n: dy.to_dev(np.full(d.shape2() if n.startswith("SN") else d.shape3(d.nk + 1), np.nan)) for n in RP.VARMIX_MEMBERS}
+            dy.varmix_init(Pv, opt["eos"], *abi.layer_densities(d.nk, Rho0=GV.Rho0, g_Earth=GV.g_Earth))
+            dy.thickness_diffuse_init(P, opt["eos"])
+            torch.cuda.synchronize()
+            dy.calc_slope_functions(t["h"], opt["dt"], g["SN_u"], g["SN_v"], T=t["T"], S=t["S"], slope_x=g["slope_x"], slope_y=g["slope_y"])
+            dy.thickness_diffuse(t["h"], t["uhtr"], t["vhtr"], opt["dt"], T=t["T"], S=t["S"], slope_x=g["slope_x"], slope_y=g["slope_y"])
+            dy.sync()
+            got = {n: a.cpu().numpy() for n, a in dict(g, h=t["h"], uhtr=t["uhtr"], vhtr=t["vhtr"]).items()}
+            rng = dict({n: (slice(None),) + RP.thickdiff_ranges(d)[n] for n in RP.THICKDIFF_CORE},
+                       **{n: RP.varmix_ranges(d, Pv)[n] for n in RP.VARMIX_MEMBERS})
+        assert dy.comm_exchange_count() == 0
+    finally:
+        dy.close()
+    _recorded(kind, name, gold, [n for n in got if n in rng])
+    for n, a in got.items():
+        inside = np.zeros(a.shape, bool)
+        if n in rng:
+            inside[rng[n]] = True
+        assert np.isfinite(a[inside]).all(), (tag, n)
+        if n in RP.THICKDIFF_CORE:           # changed in place: outside the range the input's bits, NaN included
+            H.assert_bitwise(a[~inside], inp[n][~inside], f"{tag}: {n} outside its range")
+        else:
+            assert np.isnan(a[~inside]).all(), (tag, n)
+    for n, b in gold.items():
+        H.assert_bitwise(np.ascontiguousarray(got[n][rng[n]]), np.ascontiguousarray(b), f"{tag}: {n}")
+
+
 @pytest.mark.parametrize("kind,name,grid,kw", RP.golden_configs(), ids=_ids())
 def test_device_against_the_recorded_reference(kind, name, grid, kw):
     d, M, GV, P, opt, inp = RP.golden_setup(kind, name, grid, kw)
@@ -97,6 +161,9 @@ def test_device_against_the_recorded_reference(kind, name, grid, kw):
         assert neg == 0
     elif kind == "ndiff":
         _ndiff(tag, d, M, GV, P, opt, inp, gold)
+        return
+    elif kind in ("varmix", "thickdiff"):
+        _lateral(tag, kind, name, d, M, GV, P, opt, inp, gold)
         return
     elif kind == "kshear":
         from tests.test_kappa_shear_gpu import _device, _nan_halo

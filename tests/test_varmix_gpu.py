@@ -69,7 +69,7 @@ def _both(grid, nk, name, form, tot=None, Ktop=None):
     return d, P, got
 
 
-GROUPS = {"eady": ("eady", "eady_diag", "eady_nocrop", "eady_noeos"),
+GROUPS = {"eady": ("eady", "eady_diag", "eady_nocrop", "eady_tie", "eady_noeos"),
           "visbeck": ("visbeck", "visbeck_diag", "visbeck_neg", "visbeck_noeos"),
           "just_e": ("just_e", "just_e_full")}
 GROUP_REQUIRED = {"eady": ("mag_grad2_zero", "Dscale_full", "Dscale_partial", "Dscale_zero", "crop_top_0", "crop_top_mid", "crop_top_1",

@@ -5,15 +5,19 @@ streamfunction, with find_eta (src/core/MOM_interface_heights.F90:91-97) and ver
 Fortran operation for operation (x**2 as x*x, nothing reordered) and vectorised over the faces of one direction with a loop
 over K.  Arrays are in the pitched tile layout of include/mom6x.h ([k, j + joff, i + ioff]).  Density derivatives come from the
 oracle's EOS only (oracle/orc.py eos_density_derivs), one point at a time.  MAX and MIN return their first argument on a tie,
-as the reference's compiler evaluates them, which decides the sign of a zero.  `counts` records how often each branch fired.
+which decides the sign of a zero, except in the limiter of uhD and vhD (:1160-1161, :1479), where the tie shows: with no
+transport and no available mass beyond the face, MAX(+0.0, -0.0), the compiled reference answers with its second argument, -0.0,
+in uhGM and vhGM.  `counts` records how often each branch fired.
 
-The Fortran routine itself cannot be compiled into oracle/_ref: the recipe under oracle/ is fixed and does not build it.  A
-restatement and a kernel written by one person can share a misreading, so tests/test_thickness_diffuse_cpu.py first holds this
-module to facts that do not come from it (closed forms, exact column sums, bounds, the quarter turn, unit scaling)."""
+tests/test_thickness_diffuse_cpu.py holds this module to facts that do not come from it (closed forms, exact column sums,
+bounds, the quarter turn, unit scaling); tests/test_ref_parity_cpu.py holds it bit for bit to the reference's own
+MOM_thickness_diffuse.F90, compiled into oracle/_ref/libref_param.so with MOM_lateral_mixing_coeffs.F90, MOM_isopycnal_slopes.F90
+and MOM_interface_heights.F90 (every case but khth2d, whose plane the reference reads from a file into a private member), and
+tests/golden/ref_thickdiff_*.npz hold the device to what that library gave."""
 import numpy as np
 
 from mom6_amd import abi
-from tests.ref_common import _derivs, _faces, _max, _min, find_eta, pressure_column, vert_fill_TS
+from tests.ref_common import _derivs, _dmax, _dmin, _faces, _max, _min, find_eta, pressure_column, vert_fill_TS
 
 G = abi.G
 BRANCHES = ("bottom_zero_pos", "bottom_zero_neg", "bottom_scale_pos", "bottom_scale_neg", "mag_grad2_zero", "rsum_clip_lo",
@@ -164,10 +168,10 @@ def thickness_diffuse(d, M, GV, P, h, uhtr, vhtr, dt, T=None, S=None, p_surf=Non
                 counts["rsum_clip_lo"] += int((-rL > Sfn_est).sum())
                 counts["rsum_clip_hi"] += int((rR < lo).sum())
                 Sfn_in_H = _min(lo, rR)
-                t = _min((Sfn_in_H - uhtot), haL_)                                      # :1160
+                t = _dmin((Sfn_in_H - uhtot), haL_)                                     # :1160-1161: second argument on a tie
                 counts["havail_clip_hi"] += int((haL_ < (Sfn_in_H - uhtot)).sum())
                 counts["havail_clip_lo"] += int((-haR_ > t).sum())
-                D = _max(t, -haR_)
+                D = _dmax(t, -haR_)                                                     # (MAX(+0.0, -0.0) is -0.0 in uhGM)
                 uhtot = uhtot + D                                                       # :1190
                 F(D3[k])[...] = D
             F(D3[0])[...] = -uhtot                                                      # :1534-1535
@@ -194,9 +198,11 @@ def thickness_diffuse(d, M, GV, P, h, uhtr, vhtr, dt, T=None, S=None, p_surf=Non
 # ------------------------------------------------------------------------------------------------------------------------------
 # Shared cases of tests/test_thickness_diffuse_cpu.py and tests/test_thickness_diffuse_gpu.py
 
-def inputs(d, M, GV, seed=5, uniform_patch=False):
+def inputs(d, M, GV, seed=5, uniform_patch=False, thin_top=False):
     """tests/setvisc_ref.inputs as they are (h with a band of Angstrom-thin bottom layers, T, S, p_surf) plus uhtr, vhtr, a
-    khth2d field and stored slopes; with `uniform_patch` T and S are uniform in a block of columns (mag_grad2 == 0)."""
+    khth2d field and stored slopes; with `uniform_patch` T and S are uniform in a block of columns (mag_grad2 == 0); with
+    `thin_top` the two top layers of a band of rows are Angstrom thin (no mass is available above their interfaces: the
+    h_avail_rsum clips of :1156 fire at a few layers, which otherwise takes 75)."""
     from mom6_amd import synth
     from tests import setvisc_ref
     b = setvisc_ref.inputs(d, M, GV, seed=seed)
@@ -206,6 +212,13 @@ def inputs(d, M, GV, seed=5, uniform_patch=False):
     out["khth2d"] = np.ascontiguousarray(600.0 * (1.0 + 0.5 * synth.smooth_field(d, seed + 402, ox=0.5, oy=0.5)))
     out["slope_x"] = np.ascontiguousarray(2.0e-3 * synth.smooth_field(d, seed + 403, nk=d.nk + 1, ox=1.0, oy=0.5))
     out["slope_y"] = np.ascontiguousarray(2.0e-3 * synth.smooth_field(d, seed + 404, nk=d.nk + 1, ox=0.5, oy=1.0))
+    if thin_top and d.nk > 3:
+        jl = np.arange(d.shape2()[0]) - d.joff + d.j_glob0
+        band = ((jl >= 3) & (jl <= 6))[:, None] & np.ones(d.pitch, bool)[None, :]
+        h = out["h"].copy()
+        for k in (0, 1):
+            h[k] = np.where(band, GV.Angstrom_H, h[k])
+        out["h"] = np.ascontiguousarray(h)
     if uniform_patch:
         il = np.arange(d.pitch) - d.ioff + d.i_glob0
         jl = np.arange(d.shape2()[0]) - d.joff + d.j_glob0
@@ -229,6 +242,7 @@ CASES = {
     "large_noeos": (dict(Khth=1.0e7), None, False, False, False, 3600.0, {}),
     "kd0": (dict(kappa_smooth=0.0), abi.WRIGHT, False, False, False, 900.0, dict(uniform_patch=True)),
     "gm": (dict(), abi.WRIGHT, False, False, True, 900.0, {}),
+    "thin_top": (dict(Khth=1.0e7), abi.WRIGHT, False, False, False, 3600.0, dict(thin_top=True)),
 }
 
 

@@ -6,16 +6,20 @@ calc_Eady_growth_rate_2D (:962-1112), calc_Visbeck_coeffs_old (:743-959) and cal
 of the L2u, L2v of VarMix_init (:1759-1772).  Written from the Fortran operation for operation (x**2 as x*x, x**4 as (x*x)*(x*x),
 nothing reordered), independent of the HIP, vectorised over the faces of one direction with a loop over K.  Arrays are in the
 pitched tile layout of include/mom6x.h ([k, j + joff, i + ioff]); local indices are zero based (isc = 0, iec = ni-1).  Density
-derivatives come from the oracle's EOS only, one point at a time.  MAX and MIN return their first argument on a tie.  These,
+derivatives come from the oracle's EOS only, one point at a time.  MAX and MIN return their first argument on a tie, except in the
+radicand of dzSxN and dzSyN (MOM_isopycnal_slopes.F90:418, :602), where the tie shows: MAX(0.0, -0.0) is -0.0 in the compiled
+reference, and so is its square root (the case eady_tie reaches it).  These,
 find_eta, the pressure column and vert_fill_TS come from tests/ref_common.py; the slope arithmetic is this module's own.
 `counts` records how often each branch fired.
 
-The Fortran routines cannot be compiled into oracle/_ref (the recipe under oracle/ is fixed and does not build them), so
-tests/test_varmix_cpu.py first holds this module to facts that do not come from it."""
+tests/test_varmix_cpu.py holds this module to facts that do not come from it; tests/test_ref_parity_cpu.py holds it bit for bit to
+the reference's own MOM_lateral_mixing_coeffs.F90, MOM_isopycnal_slopes.F90 and MOM_interface_heights.F90, compiled into
+oracle/_ref/libref_param.so (every case, slopes and every posted diagnostic), and tests/golden/ref_varmix_*.npz hold the device to
+what that library gave."""
 import numpy as np
 
 from mom6_amd import abi
-from tests.ref_common import _A, _derivs, _max, _min, find_eta, pressure_column, vert_fill_TS
+from tests.ref_common import _A, _derivs, _dmax, _max, _min, find_eta, pressure_column, vert_fill_TS
 
 G = abi.G
 BRANCHES = ("mag_grad2_zero", "kap_zero", "dzSN_clip", "N2_clipped", "S2max_applied", "S2max_idle", "Hu_le0", "Dscale_full",
@@ -110,7 +114,7 @@ def calc_isoneutral_slopes(d, M, GV, P, h, e, dt_kappa_smooth, out, T=None, S=No
                 arg = (wtL * (dzaL * drdkL)) + (wtR * (dzaR * drdkR))
                 if counts is not None:
                     counts["dzSN_clip"] += int((arg > 0.0).sum() < arg.size)
-                L(dzs[k])[...] = np.sqrt(G_Rho0 * _max(0.0, arg) / (wtL + wtR)) * np.abs(sl) * mask
+                L(dzs[k])[...] = np.sqrt(G_Rho0 * _dmax(0.0, arg) / (wtL + wtR)) * np.abs(sl) * mask   # (second argument on a tie)
 
 
 def calc_Eady_growth_rate_2D(d, M, GV, P, e, dzu, dzv, dzSxN, dzSyN, SN_u, SN_v, counts):
@@ -382,6 +386,9 @@ CASES = {
     "eady_diag": (dict(EADY, Eady_GR_D_scale=500.0, cropping_distance=50.0), abi.WRIGHT, True, True, 900.0, dict(thin_top=True)),
     "eady_nocrop": (dict(EADY, Eady_GR_D_scale=150.0, cropping_distance=-1.0, kappa_smooth=0.0), abi.WRIGHT, False, False, 900.0,
                     dict(uniform_patch=True)),
+    # T and S uniform in a patch and never smoothed under a linear equation of state with both coefficients negative: both vertical
+    # density differences are -0.0 there, and the radicand of dzSxN is MAX(0.0, -0.0)
+    "eady_tie": (dict(EADY, kappa_smooth=0.0), abi.LINEAR, False, True, 900.0, dict(uniform_patch=True, eos_mods=dict(dRho_dT=-0.25, dRho_dS=-0.75))),
     "eady_noeos": (dict(EADY, Eady_GR_D_scale=1000.0, cropping_distance=200.0), None, False, True, 900.0, dict(thin_top=True)),
     "visbeck": (dict(VISB), "form", False, False, 900.0, {}),
     "visbeck_diag": (dict(VISB, Visbeck_S_max=1.0e-3), abi.WRIGHT, True, True, 900.0, {}),
@@ -411,6 +418,9 @@ def case(name, GV, form=None, nk=None):
     if eos_form == "form":
         eos_form = form
     eos = abi.eos_params_default(eos_form) if eos_form is not None else None
+    opts = dict(opts)
+    for k, val in opts.pop("eos_mods", {}).items():
+        setattr(eos, k, val)
     return P, eos, give_ps, give_diag, dt, opts
 
 
